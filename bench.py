@@ -20,6 +20,10 @@ N > 1: one process per GPU.  `python bench.py --gpus N` with no WORLD_SIZE in th
   value = the band's symbols / max time, "scaling": "strong".
 
 Prints ONE JSON line (rank 0).  See DESIGN.md section 6 for the definitions of roofline / roofline_compute / cpu_baseline.
+A plain run measures the headline only (setup, prewarm + warmup, the --steps timed steps, the line); --full adds the other slicer specs,
+the other decimation, the secondary workload with its latency record, the CPU baseline, power / clock sampling and, with N > 1, the
+one-band passes.  --dump-outputs DIR writes the records of the last timed step as .npy files (inputs are seeded: the same arguments give
+the same records).
 """
 import argparse
 import json
@@ -83,6 +87,14 @@ def parse(argv=None):
     ap.add_argument("--no-other-specs", action="store_true", help="skip the short runs of the other slicer specs")
     ap.add_argument("--no-latency", action="store_true", help="skip the 20 ms-block real-time latency run (scripts/profile_round.sh: its small launches would dilute the per-kernel profile means)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the other slicer specs, the other decimation, the secondary workload and its "
+                         "real-time latency record, the CPU baseline, package power / clocks around the timed region and, with N > 1, the one-band "
+                         "passes behind the headline (the --no-* options above select among them).  Without it a run sets up, warms up, times "
+                         "--steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the records the last timed step drained, one float64 array per field, as DIR/records_<field>.npy "
+                         "(position as records_position_in_step: samples from the first sample of that step's push)")
     return ap.parse_args(argv)
 
 
@@ -196,6 +208,40 @@ def make_wideband_batch(torch, dev, nsamp, first_bin, n_channels, every, seed, b
     _WIDEBAND_CACHE.clear()
     _WIDEBAND_CACHE[key] = out
     return out
+
+
+# ----------------------------------------------------------------------------------------------------- --dump-outputs
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def record_arrays(recs, position_origin=0):
+    """The records of one drain (amps_recc_burst_t, sorted by channel and position) as {name: float64 array}, one per field, padding left
+    out: a field of shape S holds [n_records, *S]; the text fields (min, dialed) are their bytes; position becomes position_in_step, the
+    sample index counted from `position_origin`.  More than DUMP_LIMIT_BYTES in all: a fixed, seeded sample of the records, in their
+    order, whose indices are under `rows`."""
+    n = len(recs)
+    names = [f for f in recs.dtype.names if not f.startswith("_")]
+    per_record = sum(8 * max(1, int(np.prod(recs.dtype[f].shape)) * (recs.dtype[f].itemsize if recs.dtype[f].kind == "S" else 1)) for f in names)
+    out = {}
+    if n * per_record > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_LIMIT_BYTES // per_record - 1, replace=False))
+        recs = recs[rows]
+        out["rows"] = rows.astype(np.float64)
+    for f in names:
+        v = recs[f]
+        if v.dtype.kind == "S":
+            v = np.ascontiguousarray(v).view(np.uint8).reshape(len(recs), -1)
+        if f == "position":
+            out["position_in_step"] = v.astype(np.int64).astype(np.float64) - float(position_origin)
+        else:
+            out[f] = v.astype(np.float64)
+    return out
+
+
+def dump_records(d, recs, position_origin):
+    os.makedirs(d, exist_ok=True)
+    for k, v in record_arrays(recs, position_origin).items():
+        np.save(os.path.join(d, "records_%s.npy" % k), v)
 
 
 # ----------------------------------------------------------------------------------------------------- CPU baseline
@@ -469,13 +515,14 @@ def run_workload(name, a, torch, dev, dist, rank, world, local, slicer, steps, w
 
     # the metric is SUSTAINED throughput: the GPU's clocks take a few hundred ms of load to settle (kernel time falls
     # ~7 % over the first dozen launches), so the same step runs untimed for --prewarm-ms before the W warmup steps
-    short_poll = not light and steps < 4000 and not a.no_power_sample and not one_band
+    short_poll = a.full and not light and steps < 4000 and not a.no_power_sample and not one_band
     short_smi = SmiSampler(local, period=0.02) if (short_poll and rank == 0) else None
     if short_smi:
         short_smi.start()
     tp = time.perf_counter()
     lockstep = dist is not None and one_band                # a step holds a collective: every rank must run the SAME number of them
     go = torch.ones(1, device=dev, dtype=torch.int32) if lockstep else None
+    n_prewarm = 0
     while True:
         more = (time.perf_counter() - tp) * 1e3 < (100.0 if light else a.prewarm_ms)
         if lockstep:
@@ -488,6 +535,7 @@ def run_workload(name, a, torch, dev, dist, rank, world, local, slicer, steps, w
         if not more:
             break
         step()
+        n_prewarm += 1
     recs = None
     r.timing(reset=True)
     for _ in range(warmup):             # the per-kernel breakdown comes from these (all launches bracketed by HIP events)
@@ -516,7 +564,7 @@ def run_workload(name, a, torch, dev, dist, rank, world, local, slicer, steps, w
 
     barrier()
     sustained = steps >= 4000                             # a region of a couple of seconds: sampled while it runs
-    smi = SmiSampler(local) if (rank == 0 and not light and sustained and not a.no_power_sample) else None
+    smi = SmiSampler(local) if (a.full and rank == 0 and not light and sustained and not a.no_power_sample) else None
     if smi:
         smi.start()
     # A short region (the driver's --steps 20 is 9 ms) ends before one rocm-smi call returns.  The poller (`short_smi`, started in front
@@ -527,9 +575,11 @@ def run_workload(name, a, torch, dev, dist, rank, world, local, slicer, steps, w
     # runs the same number of untimed steps (whole-band modes only: no collective in them); rank 0 samples.
     t0 = time.perf_counter()
     nrec = 0
+    last = None
     if a.no_pipeline:
         for _ in range(steps):
-            nrec += len(step())
+            last = step()
+            nrec += len(last)
     else:
         # streaming form of the same K steps: the records of step i are collected (split drain) while step i+1 runs, so the
         # GPU does not idle for the ~60 us of host work between steps; every step's records are still drained inside the
@@ -539,11 +589,18 @@ def run_workload(name, a, torch, dev, dist, rank, world, local, slicer, steps, w
             if i:
                 nrec += len(r.drain_end(copy=False))
             r.drain_begin()
-        nrec += len(r.drain_end(copy=False))
+        last = r.drain_end(copy=False)
+        nrec += len(last)
     torch.cuda.synchronize()
     barrier()
     el = time.perf_counter() - t0
     el_own = el
+    # the last timed step's records, copied before any later drain reuses the handle's buffer; position made relative to the first
+    # sample (channel rate) of that step's push, which a clock-bounded prewarm would otherwise move from run to run
+    last_records = None
+    if a.dump_outputs and not light and last is not None:
+        pushes_before = n_prewarm + warmup + steps - 1
+        last_records = (np.array(last), pushes_before * NW // decim if wide else pushes_before * N)
     power = None
     tm_keep = None
     if smi:
@@ -600,7 +657,7 @@ def run_workload(name, a, torch, dev, dist, rank, world, local, slicer, steps, w
                         "rccl_library": i["library"] if i["nranks"] else None, "ms_per_step": round(el_own / steps * 1e3, 4), "kernel_ms": None}
         except capi.AmpsError:
             identity = {"rank": rank, "error": "amps_recc_rccl_info"}
-    if wide and abi_mode:
+    if wide and abi_mode and a.full:
         # outside the timed region: one more step whose records come back through the ABI's collective drain (amps_recc_drain_gather:
         # every rank's list merged at rank 0) -- the whole band's bursts in one place, counted on the record
         push()
@@ -701,6 +758,8 @@ def run_workload(name, a, torch, dev, dist, rank, world, local, slicer, steps, w
         res["identity"] = identity
     if coll is not None:
         res["collective"] = coll
+    if last_records is not None:
+        res["last_records"] = last_records
     return res, iq_base
 
 
@@ -792,6 +851,9 @@ def main(argv=None):
     a.decim = lib_decim if a.decim == "default" else int(a.decim)
     broken_group = False
     res, iq_base = run_workload(a.workload, a, torch, dev, dist, rank, world, local, a.slicer, a.steps, a.warmup)
+    last_records = res.pop("last_records", None)
+    if rank == 0 and last_records is not None:
+        dump_records(a.dump_outputs, *last_records)
     res["config"]["slicer_is_library_default"] = is_default
     if a.workload == "wideband832":
         res["config"]["decim_is_library_default"] = decim_is_default
@@ -806,7 +868,7 @@ def main(argv=None):
         "power": res.get("power"),
         "dist": a.dist,
     }
-    if world == 1 and not a.no_other_specs:
+    if a.full and world == 1 and not a.no_other_specs:
         # the same workload under the other slicer specs (short runs: kernel time + the decode check), so that what the default
         # (spec D) saves against the arctangent of spec A -- and what the cheaper specs B / C would save on top -- is on the record
         other = {}
@@ -815,7 +877,7 @@ def main(argv=None):
                 o, _ = run_workload(a.workload, a, torch, dev, None, 0, 1, local, sp, 20, 3, light=True)
                 other[SLICERS[sp]] = o
         out["other_slicer_specs"] = other
-    if world == 1 and a.workload == "wideband832" and not a.no_other_decim:
+    if a.full and world == 1 and a.workload == "wideband832" and not a.no_other_decim:
         # the same workload at the other decimation of the filter bank: the library default (D = 512, three samples per symbol: the most
         # sensitive form) and the 4/3 x oversampled bank (D = 768, two samples per symbol: 1.5 x fewer frames per input byte) side by side
         od = 768 if a.decim == 512 else 512
@@ -824,7 +886,7 @@ def main(argv=None):
         out["other_decim"] = {"wideband_decim": od, "value": o["value"], "unit": "Msym/s", "steps": o_steps, "ms_per_step": o["ms_per_step"], "config": o["config"],
                               "roofline": o["roofline"], "roofline_compute": o["roofline_compute"], "power": o.get("power"),
                               "sensitivity": DECIM_SENSITIVITY}
-    if world == 1 and a.secondary != "none" and a.secondary != a.workload:
+    if a.full and world == 1 and a.secondary != "none" and a.secondary != a.workload:
         sec_steps = min(a.steps, 2000)
         sec, sec_base = run_workload(a.secondary, a, torch, dev, None, 0, 1, local, a.slicer, sec_steps, a.warmup)
         out["secondary"] = {"value": sec["value"], "unit": "Msym/s", "steps": sec_steps, "ms_per_step": sec["ms_per_step"], "config": sec["config"],
@@ -848,7 +910,7 @@ def main(argv=None):
         out["process_group"] = {"backend": dist.get_backend(), "world_size": dist.get_world_size()}
         if res.get("collective"):
             out["collective"] = res["collective"]
-    if world > 1 and a.dist == "bands" and a.workload == "wideband832" and a.secondary != "none":
+    if a.full and world > 1 and a.dist == "bands" and a.workload == "wideband832" and a.secondary != "none":
         # What BASELINE configs[4] names beside the band-per-GPU headline: ONE band, its block distributed from rank 0 over xGMI inside
         # the timed region, every rank decoding its interleaved channel group.  Two short passes, so that one driver invocation per N
         # yields all curves: `secondary` = RCCL ncclBroadcast through torch.distributed; `secondary_abi` = scatter + all-gather issued by
@@ -892,7 +954,7 @@ def main(argv=None):
                 broken_group = True
         done.set()
         dog.cancel()
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         if iq_base is None:
             iq_base = make_batch(torch, torch.device("cpu"), 16, 1 << 18, 10, seed=1)[1]
         out["cpu_baseline"] = cpu_baseline(iq_base[:, :1 << 18], 10, a.cpu_seconds)

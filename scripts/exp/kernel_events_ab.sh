@@ -4,7 +4,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=gpurun_out/kernel_events_ab.txt; : > $OUT
 timeout 600 python -m pytest tests/test_gpu_timing_modes.py tests/test_gpu_errors.py -x -q 2>&1 | tail -2 >> $OUT
-C="--no-cpu-baseline --no-other-specs --no-latency --no-other-decim"
+C="--full --no-cpu-baseline --no-other-specs --no-latency --no-other-decim"
 line() { python - "$1" "$2" <<'PY' >> gpurun_out/kernel_events_ab.txt
 import json, sys
 try:

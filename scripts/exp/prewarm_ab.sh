@@ -2,7 +2,7 @@
 # EXPERIMENT (round 6): how long the untimed prewarm of the driver's 20-step form has to be for the timed region to sit in the settled power state
 cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=gpurun_out/prewarm_ab.txt; : > $OUT
-C="--no-cpu-baseline --no-other-specs --no-latency --no-other-decim --secondary none --steps 20 --warmup 5"
+C="--full --no-cpu-baseline --no-other-specs --no-latency --no-other-decim --secondary none --steps 20 --warmup 5"
 for rep in 1 2 3 4; do
 for pw in 400 1000 2000 4000; do
   python bench.py $C --prewarm-ms $pw > /tmp/l.json 2>/dev/null

@@ -69,3 +69,45 @@ def test_committed_bench_line_has_the_contract_fields():
             assert ev["consistent"] and ev["kernel_ms_plus_other_kernels"] <= 1.02 * ev["ms_per_step"], ev
         r = line["roofline"]
         assert abs(r["frac"] - r["algorithmic_bytes_per_launch"] / (r["kernel_ms"] * 1e-3) / 8e12) < 2e-3
+
+
+def test_plain_run_is_the_headline_only():
+    """a plain run measures the headline; whatever else the line used to carry is asked for with --full"""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+
+
+def _records(n):
+    import oracle
+    r = np.zeros(n, oracle.BURST_DTYPE)
+    r["channel"] = np.arange(n) % 832
+    r["position"] = (1 << 40) + 1000 * np.arange(n)
+    r["word_dec"][:, 2, 5] = 1
+    r["min"] = b"2125551212"
+    r["esn"] = 0xDEADBEEF
+    return r
+
+
+def test_dump_arrays_are_the_records_as_floats(tmp_path):
+    r = _records(5)
+    bench.dump_records(str(tmp_path), r, (1 << 40) + 500)
+    files = sorted(os.listdir(tmp_path))
+    assert "records_position_in_step.npy" in files and "records_position.npy" not in files
+    assert not any(f.startswith("records__pad") for f in files) and "records_rows.npy" not in files
+    arr = {f[len("records_"):-4]: np.load(os.path.join(tmp_path, f)) for f in files}
+    assert all(v.dtype == np.float64 and len(v) == 5 for v in arr.values())
+    assert arr["position_in_step"].tolist() == [-500.0, 500.0, 1500.0, 2500.0, 3500.0]
+    assert arr["word_dec"].shape == (5, 7, 36) and arr["word_dec"][:, 2, 5].tolist() == [1.0] * 5
+    assert bytes(arr["min"][0].astype(np.uint8)).rstrip(b"\0") == b"2125551212" and arr["esn"][0] == 0xDEADBEEF
+
+
+def test_dump_of_a_large_drain_is_a_fixed_sample(monkeypatch):
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 200 * 8 * 800)
+    r = _records(1000)
+    a, b = bench.record_arrays(r), bench.record_arrays(r.copy())
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_LIMIT_BYTES
+    rows = a["rows"].astype(np.int64)
+    assert 0 < len(rows) < 1000 and np.all(np.diff(rows) > 0) and np.array_equal(a["rows"], b["rows"])
+    assert np.array_equal(a["channel"], (rows % 832).astype(np.float64))
