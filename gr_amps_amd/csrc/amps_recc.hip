@@ -320,82 +320,76 @@ bool bits_kernel_is_front()   // AMPS_RECC_BITS_KERNEL=front: search the bit rin
     return v == 1;
 }
 
-// tiles in flight per wave beyond the one being processed; AMPS_RECC_DEPTH overrides for experiments.  Measured with the
-// non-temporal tile loads (832 x 2^18, ms): spec A 0.329 at depth 1 / 0.342 at depth 2 (its discriminator needs the registers:
-// depth 2 costs a wave per SIMD); specs B / C 0.298 / 0.286: with the arctangent gone the kernel only waits for HBM
-int front_depth(int slicer)
-{
-    static int env = -1;
-    if (env < 0) { const char *e = std::getenv("AMPS_RECC_DEPTH"); env = e ? std::atoi(e) : 0; if (env < 0 || env > 3) env = 0; }
-    if (env) return env;
-    // round 4: depth 2 is compiled for four waves per SIMD too (AMPS_FRONT_D2_BLOCKS = 4: a handful of prologue spills, none in the tile
-    // loop).  Same box, ms: spec A 0.3336 at depth 1 / 0.3343 at depth 2; D 0.3208 / 0.3174; B 0.3118 (three waves) -> 0.3038; C 0.3122 ->
-    // 0.3055.  The default spec keeps depth 1 -- 1 % slower and no scratch at all; the opt-in specs B and C take depth 2
-    return (slicer == AMPS_SLICER_ATAN_BOXCAR || slicer == AMPS_SLICER_EXACT) ? 1 : 2;
-}
 typedef void (*front_kernel_t)(FrontArgs);
-// the instantiation of the streaming kernel for (samples per symbol, slicer spec, tolerant sync, tiles in flight)
-template <int SPS, int SL> front_kernel_t front_kernel_of(bool tol, int depth)
+// The streaming kernel for one slicer spec.  Its tile depth (tiles in flight per wave beyond the one being processed) is part of
+// the choice: tolerant sync always takes depth 1, and without it specs A and D take depth 1, specs B and C depth 2.  Measured
+// with the non-temporal tile loads (832 x 2^18, ms): spec A 0.329 at depth 1 / 0.342 at depth 2 (its discriminator needs the
+// registers: depth 2 costs a wave per SIMD); specs B / C 0.298 / 0.286: with the arctangent gone the kernel only waits for HBM.
+// Round 4: depth 2 is compiled for four waves per SIMD too (a handful of prologue spills, none in the tile loop).  Same box, ms:
+// spec A 0.3336 at depth 1 / 0.3343 at depth 2; D 0.3208 / 0.3174; B 0.3118 (three waves) -> 0.3038; C 0.3122 -> 0.3055.  The
+// default spec keeps depth 1 -- 1 % slower and no scratch at all; the opt-in specs B and C take depth 2.
+template <int SPS, int SL> front_kernel_t front_kernel_of(bool tol)
 {
+    constexpr int DEPTH = (SL == AMPS_SLICER_ATAN_BOXCAR || SL == AMPS_SLICER_EXACT) ? 1 : 2;
     if (tol) return recc_front_kernel<SPS, 1, false, true, SL>;
-    if constexpr (SL == AMPS_SLICER_ATAN_BOXCAR) { if (depth == 3) return recc_front_kernel<SPS, 3, false, false, SL>; }
-    if (depth == 2) return recc_front_kernel<SPS, 2, false, false, SL>;
-    return recc_front_kernel<SPS, 1, false, false, SL>;
+    return recc_front_kernel<SPS, DEPTH, false, false, SL>;
 }
-template <int SPS> front_kernel_t front_kernel_for(int slicer, bool tol)
+template <int SPS> front_kernel_t front_kernel_of(int slicer, bool tol)
 {
-    const int depth = front_depth(slicer);
     switch (slicer) {
-    case AMPS_SLICER_PRODUCT: return front_kernel_of<SPS, AMPS_SLICER_PRODUCT>(tol, depth);
-    case AMPS_SLICER_SINE: return front_kernel_of<SPS, AMPS_SLICER_SINE>(tol, depth);
-    case AMPS_SLICER_EXACT: return front_kernel_of<SPS, AMPS_SLICER_EXACT>(tol, depth);
-    default: return front_kernel_of<SPS, AMPS_SLICER_ATAN_BOXCAR>(tol, depth);
+    case AMPS_SLICER_PRODUCT: return front_kernel_of<SPS, AMPS_SLICER_PRODUCT>(tol);
+    case AMPS_SLICER_SINE: return front_kernel_of<SPS, AMPS_SLICER_SINE>(tol);
+    case AMPS_SLICER_EXACT: return front_kernel_of<SPS, AMPS_SLICER_EXACT>(tol);
+    default: return front_kernel_of<SPS, AMPS_SLICER_ATAN_BOXCAR>(tol);
     }
 }
-template <int SPS> int front_blocks_per_cu(int slicer, bool tol)   // of the kernel launch_front<SPS> will pick
+// The streaming kernel for (samples per symbol, slicer spec, tolerant sync); nullptr for a rate it is not built for.  This switch
+// is the one table of the rates the streaming kernel supports.  sps = 2 is launchable but not supported (sps_supported): only the
+// unfused (two-kernel) form of the wideband seam at D = 768 reaches it, never a handle of the IQ seam.
+front_kernel_t front_kernel_for(uint32_t sps, int slicer, bool tol)
+{
+    switch (sps) {
+    case 2: return front_kernel_of<2>(slicer, tol);
+    case 3: return front_kernel_of<3>(slicer, tol);
+    case 4: return front_kernel_of<4>(slicer, tol);
+    case 5: return front_kernel_of<5>(slicer, tol);
+    case 6: return front_kernel_of<6>(slicer, tol);
+    case 8: return front_kernel_of<8>(slicer, tol);
+    case 10: return front_kernel_of<10>(slicer, tol);
+    case 12: return front_kernel_of<12>(slicer, tol);
+    default: return nullptr;
+    }
+}
+bool sps_supported(uint32_t sps) { return sps != 2 && front_kernel_for(sps, AMPS_SLICER_DEFAULT, false) != nullptr; }
+int front_blocks_per_cu_for(uint32_t sps, int slicer, bool tol)   // of the kernel dispatch_front will pick
 {
     int n = 0;
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, front_kernel_for<SPS>(slicer, tol), 256, 0);
-    return (e == hipSuccess && n > 0) ? n : 2;
+    const front_kernel_t k = front_kernel_for(sps, slicer, tol);
+    return (k && hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, 256, 0) == hipSuccess && n > 0) ? n : 2;
 }
-int front_blocks_per_cu_for(uint32_t sps, int slicer, bool tol)
-{
-    switch (sps) {
-    case 2: return front_blocks_per_cu<2>(slicer, tol);     // the two-kernel (unfused) form of the wideband seam at D = 768 only
-    case 3: return front_blocks_per_cu<3>(slicer, tol);
-    case 4: return front_blocks_per_cu<4>(slicer, tol);
-    case 5: return front_blocks_per_cu<5>(slicer, tol);
-    case 6: return front_blocks_per_cu<6>(slicer, tol);
-    case 8: return front_blocks_per_cu<8>(slicer, tol);
-    case 10: return front_blocks_per_cu<10>(slicer, tol);
-    case 12: return front_blocks_per_cu<12>(slicer, tol);
-    default: return 2;
-    }
-}
-template <int SPS> void launch_front(const FrontArgs &fa, dim3 grid, hipStream_t s, int slicer)
-{
-    hipLaunchKernelGGL(front_kernel_for<SPS>(slicer, fa.tol != 0), grid, dim3(256), 0, s, fa);
-}
-
-bool sps_supported(uint32_t sps)
-{
-    switch (sps) { case 3: case 4: case 5: case 6: case 8: case 10: case 12: return true; default: return false; }
-}
-
 int dispatch_front(uint32_t sps, const FrontArgs &fa, dim3 grid, hipStream_t s, int slicer)
 {
-    switch (sps) {
-    case 2: launch_front<2>(fa, grid, s, slicer); break;
-    case 3: launch_front<3>(fa, grid, s, slicer); break;
-    case 4: launch_front<4>(fa, grid, s, slicer); break;
-    case 5: launch_front<5>(fa, grid, s, slicer); break;
-    case 6: launch_front<6>(fa, grid, s, slicer); break;
-    case 8: launch_front<8>(fa, grid, s, slicer); break;
-    case 10: launch_front<10>(fa, grid, s, slicer); break;
-    case 12: launch_front<12>(fa, grid, s, slicer); break;
-    default: return -EINVAL;
-    }
+    const front_kernel_t k = front_kernel_for(sps, slicer, fa.tol != 0);
+    if (!k) return -EINVAL;
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, s, fa);
     return 0;
+}
+
+// The bit-domain search kernel for (samples per symbol, tolerant sync): run_bits_device launches it, and amps_recc_create sizes
+// max_waves_bits by its occupancy.  AMPS_RECC_BITS_KERNEL=front selects the bit-domain mode of the streaming kernel instead (an
+// independent implementation of the same search: the two must agree).
+front_kernel_t bits_kernel_for(uint32_t sps, bool tol)
+{
+    if (bits_kernel_is_front()) {
+        if (tol) return recc_front_kernel<3, 1, true, true>;
+        return recc_front_kernel<3, 1, true>;
+    }
+    if (sps == 2) {
+        if (tol) return recc_bits_kernel<2, true>;
+        return recc_bits_kernel<2, false>;
+    }
+    if (tol) return recc_bits_kernel<3, true>;
+    return recc_bits_kernel<3, false>;
 }
 
 // The streaming / bit-domain kernel of a push also does the push's housekeeping (thread 0): it clears the capture queue count,
@@ -424,6 +418,31 @@ static bool bits_search_is_separate()
 // the search stage inside the resolve kernel serves the many-channel form (no capture queue) at the wideband seam's two rates
 static bool search_in_resolve(const amps_recc *h) { return h->chz.enabled && !h->capq && !bits_kernel_is_front() && !bits_search_is_separate() && (h->sps == 2 || h->sps == 3); }
 
+typedef void (*resolve_kernel_t)(ResolveArgs);
+struct ResolveLaunch { resolve_kernel_t resolve; int threads; resolve_kernel_t capture; };
+// The resolve kernel (and its block size) and the capture kernel of the queue form for (a channel cut into more wave segments than
+// one batch compacts, trigger search in the resolve kernel, two samples per symbol, tolerant search).  Two samples per symbol (the
+// wideband seam at D = 768) have their own capture rule: a second instantiation of the kernels, so that the default ones carry
+// nothing of it.
+static ResolveLaunch resolve_kernels_for(bool wide, bool search, bool two, bool stol)
+{
+    const resolve_kernel_t capture = two ? recc_capture_kernel<true> : recc_capture_kernel<false>;
+    if (wide) {
+        if (two) return { recc_resolve_kernel<RESOLVE_THREADS_WIDE, RESOLVE_LDS_HITS_WIDE, true>, RESOLVE_THREADS_WIDE, capture };
+        return { recc_resolve_kernel<RESOLVE_THREADS_WIDE, RESOLVE_LDS_HITS_WIDE, false>, RESOLVE_THREADS_WIDE, capture };
+    }
+    if (search) {
+        if (two) {
+            if (stol) return { recc_resolve_kernel<RESOLVE_THREADS, RESOLVE_LDS_HITS, true, 2, true>, RESOLVE_THREADS, capture };
+            return { recc_resolve_kernel<RESOLVE_THREADS, RESOLVE_LDS_HITS, true, 2, false>, RESOLVE_THREADS, capture };
+        }
+        if (stol) return { recc_resolve_kernel<RESOLVE_THREADS, RESOLVE_LDS_HITS, false, 3, true>, RESOLVE_THREADS, capture };
+        return { recc_resolve_kernel<RESOLVE_THREADS, RESOLVE_LDS_HITS, false, 3, false>, RESOLVE_THREADS, capture };
+    }
+    if (two) return { recc_resolve_kernel<RESOLVE_THREADS, RESOLVE_LDS_HITS, true>, RESOLVE_THREADS, capture };
+    return { recc_resolve_kernel<RESOLVE_THREADS, RESOLVE_LDS_HITS, false>, RESOLVE_THREADS, capture };
+}
+
 static void launch_resolve(amps_recc *h, ResolveArgs &ra, hipStream_t s, bool search = false)
 {
     // capture + decode side of the kernel
@@ -446,30 +465,12 @@ static void launch_resolve(amps_recc *h, ResolveArgs &ra, hipStream_t s, bool se
     // that a change to either threshold cannot turn into a launch failure: a handle without a queue stays on the narrow kernel, whose
     // batches walk any number of segments.
     const bool wide = ra.tiles_per_channel / ra.span + 2 > (uint64_t)RESOLVE_THREADS && h->capq != nullptr;
-    // two samples per symbol (the wideband seam at D = 768) have their own capture rule: a second instantiation of the kernels, so that
-    // the default ones carry nothing of it
-    const bool two = h->sps == 2;
-    if (wide) {
-        if (two) hipLaunchKernelGGL((recc_resolve_kernel<RESOLVE_THREADS_WIDE, RESOLVE_LDS_HITS_WIDE, true>), dim3(h->C), dim3(RESOLVE_THREADS_WIDE), lds, s, ra);
-        else hipLaunchKernelGGL((recc_resolve_kernel<RESOLVE_THREADS_WIDE, RESOLVE_LDS_HITS_WIDE, false>), dim3(h->C), dim3(RESOLVE_THREADS_WIDE), lds, s, ra);
-    } else if (search) {
-        const dim3 g(h->C), b(RESOLVE_THREADS);
-        if (two) {
-            if (ra.search_tol) hipLaunchKernelGGL((recc_resolve_kernel<RESOLVE_THREADS, RESOLVE_LDS_HITS, true, 2, true>), g, b, lds, s, ra);
-            else hipLaunchKernelGGL((recc_resolve_kernel<RESOLVE_THREADS, RESOLVE_LDS_HITS, true, 2, false>), g, b, lds, s, ra);
-        } else {
-            if (ra.search_tol) hipLaunchKernelGGL((recc_resolve_kernel<RESOLVE_THREADS, RESOLVE_LDS_HITS, false, 3, true>), g, b, lds, s, ra);
-            else hipLaunchKernelGGL((recc_resolve_kernel<RESOLVE_THREADS, RESOLVE_LDS_HITS, false, 3, false>), g, b, lds, s, ra);
-        }
-    } else {
-        if (two) hipLaunchKernelGGL((recc_resolve_kernel<RESOLVE_THREADS, RESOLVE_LDS_HITS, true>), dim3(h->C), dim3(RESOLVE_THREADS), lds, s, ra);
-        else hipLaunchKernelGGL((recc_resolve_kernel<RESOLVE_THREADS, RESOLVE_LDS_HITS, false>), dim3(h->C), dim3(RESOLVE_THREADS), lds, s, ra);
-    }
+    const ResolveLaunch k = resolve_kernels_for(wide, search, h->sps == 2, ra.search_tol != 0);
+    hipLaunchKernelGGL(k.resolve, dim3(h->C), dim3(k.threads), lds, s, ra);
     if (h->capq) {
         const dim3 gq(std::min<uint32_t>(h->cfg.max_bursts, 2048u));
         const size_t ldsq = (size_t)resolve_cap_stride(ra.cap_words) * 8;
-        if (two) hipLaunchKernelGGL(recc_capture_kernel<true>, gq, dim3(64), ldsq, s, ra);
-        else hipLaunchKernelGGL(recc_capture_kernel<false>, gq, dim3(64), ldsq, s, ra);
+        hipLaunchKernelGGL(k.capture, gq, dim3(64), ldsq, s, ra);
     }
 #ifdef RESOLVE_TIMELINE
     if (const char *path = std::getenv("AMPS_RECC_RESOLVE_TIMELINE")) {   // the last launch's stamps, raw
@@ -670,19 +671,9 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, dev) != hipSuccess) { amps_recc_destroy(h); return -ENODEV; }
         h->max_waves = (uint32_t)prop.multiProcessorCount * 4u * (uint32_t)front_blocks_per_cu_for(h->sps, h->slicer, cfg->sync_tolerance != 0);   // exactly one resident round
-        if (const char *e = std::getenv("AMPS_RECC_MAX_WAVES")) { const long v = std::atol(e); if (v >= 4 && (uint32_t)v <= h->max_waves) h->max_waves = (uint32_t)v & ~3u; }   // experiments: fewer, longer wave streams (span geometry against the HBM channel interleave)
         {
             int nb = 0;
-            hipError_t e;
-            if (bits_kernel_is_front())
-                e = cfg->sync_tolerance ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, recc_front_kernel<3, 1, true, true>, 256, 0)
-                                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, recc_front_kernel<3, 1, true, false>, 256, 0);
-            else if (h->sps == 2)
-                e = cfg->sync_tolerance ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, recc_bits_kernel<2, true>, 256, 0)
-                                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, recc_bits_kernel<2, false>, 256, 0);
-            else
-                e = cfg->sync_tolerance ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, recc_bits_kernel<3, true>, 256, 0)
-                                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, recc_bits_kernel<3, false>, 256, 0);
+            const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, bits_kernel_for(h->sps, cfg->sync_tolerance != 0), 256, 0);
             if (e != hipSuccess || nb < 1) nb = 4;
             if (nb > 8) nb = 8;                                  // max_chunks below assumes at most 32 waves per CU
             h->max_waves_bits = (uint32_t)prop.multiProcessorCount * 4u * (uint32_t)nb;
@@ -910,17 +901,7 @@ int run_bits_device(amps_recc *h, uint32_t P)
     front_housekeeping_args(h, fa);
     {
         SpanGuard g(h, T_FRONT, P);
-        // the dedicated bit-domain kernel; AMPS_RECC_BITS_KERNEL=front selects the bit-domain mode of the streaming kernel
-        // instead (an independent implementation of the same search: the two must agree)
-        const dim3 grid((nwaves + 3) / 4);
-        if (bits_kernel_is_front()) {
-            if (fa.tol) hipLaunchKernelGGL((recc_front_kernel<3, 1, true, true>), grid, dim3(256), 0, s, fa);
-            else hipLaunchKernelGGL((recc_front_kernel<3, 1, true>), grid, dim3(256), 0, s, fa);
-        } else if (h->sps == 2) {
-            if (fa.tol) hipLaunchKernelGGL((recc_bits_kernel<2, true>), grid, dim3(256), 0, s, fa);
-            else hipLaunchKernelGGL((recc_bits_kernel<2, false>), grid, dim3(256), 0, s, fa);
-        } else if (fa.tol) hipLaunchKernelGGL((recc_bits_kernel<3, true>), grid, dim3(256), 0, s, fa);
-        else hipLaunchKernelGGL((recc_bits_kernel<3, false>), grid, dim3(256), 0, s, fa);
+        hipLaunchKernelGGL(bits_kernel_for(h->sps, fa.tol != 0), dim3((nwaves + 3) / 4), dim3(256), 0, s, fa);
     }
 #ifdef BITS_TIMELINE
     if (const char *path = std::getenv("AMPS_RECC_BITS_TIMELINE")) {

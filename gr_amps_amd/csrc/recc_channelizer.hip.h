@@ -100,13 +100,7 @@ typedef int chz_rsrc_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ chz_rsrc_t chz_make_rsrc(const void *base, uint64_t bytes)
 {
     const uint64_t a = (uint64_t)base;
-#ifdef CHZ_TIMING_NO_LOADS
-    // TIMING EXPERIMENT ONLY (profiles/r06/chz_no_loads.txt): every fast load falls outside the descriptor and returns zeros without touching
-    // memory -- WRONG results; what the kernel takes when its input stream costs nothing but the load instructions themselves
-    const uint32_t n = 64u; (void)bytes;
-#else
     const uint32_t n = bytes > 0xffffffffull ? 0xffffffffu : (uint32_t)bytes;
-#endif
     chz_rsrc_t r;
     r.x = __builtin_amdgcn_readfirstlane((int)(uint32_t)a);
     r.y = __builtin_amdgcn_readfirstlane((int)(uint32_t)((a >> 32) & 0xffffu));          // stride 0: a raw buffer, offsets and num_records in bytes
@@ -550,13 +544,7 @@ __device__ __forceinline__ void chz768_load1(cf2 (&ring)[4][CHZ768_R], const Chz
     if constexpr (FAST) {
         constexpr int CH = 3 * (4 * X + G) + K;                      // chunk of 256 samples behind the half-step's first sample
         const uint32_t voff = (uint32_t)t * (uint32_t)sizeof(float2);
-#ifdef CHZ_TIMING_CACHED_LOADS
-        // TIMING EXPERIMENT ONLY (profiles/r06/chz_no_loads.txt): every half-step reads the SAME 64 KB of its workgroup's range -- real (non-zero)
-        // data out of the L2, no HBM traffic; WRONG results
-        const uint32_t so = (soff & 0x7fffu) + 2048u * (uint32_t)(CH & ~1);
-#else
         const uint32_t so = soff + 2048u * (uint32_t)(CH & ~1);
-#endif
         // "+v": the new value is born in the ring's own register (see chz_load1_ring)
         if constexpr (CH & 1) asm volatile("buffer_load_dwordx2 %0, %1, %2, %3 offen offset:2048" : "+v"(ring[J][SLOT]) : "v"(voff), "s"(rsrc), "s"(so));
         else asm volatile("buffer_load_dwordx2 %0, %1, %2, %3 offen" : "+v"(ring[J][SLOT]) : "v"(voff), "s"(rsrc), "s"(so));
@@ -1021,11 +1009,9 @@ __global__ __launch_bounds__(768, 3) void chz12_kernel(ChzArgs a)
     // 1650): the FOLD ABOVE PASS 2 -- pass 3 + slicer 2, fold 1, pass 2 0 -- is 1.8-3.3 % faster under spec D at D = 768, 1.4-5 % under
     // B / C, 0.8-3.2 % at D = 512 (every triple with pass 2 lowest gains 2-3 %; profiles/r06/prio_ab.txt).  Spec A, whose pass-2 waves also
     // run pass 3, loses 4-8 % by it and keeps the old order, as does the unfused form.
-#ifndef CHZ_PRIO_SLICER
     constexpr bool FOLD_OVER_P2 = !IQ && SL != AMPS_SLICER_ATAN_BOXCAR;
-    constexpr int CHZ_PRIO_SLICER = 2, CHZ_PRIO_PASS2 = FOLD_OVER_P2 ? 0 : 1, CHZ_PRIO_FOLD = FOLD_OVER_P2 ? 1 : 0;
-#endif
-    if (role == 2) __builtin_amdgcn_s_setprio(CHZ_PRIO_SLICER); else if (role == 1) __builtin_amdgcn_s_setprio(CHZ_PRIO_PASS2); else __builtin_amdgcn_s_setprio(CHZ_PRIO_FOLD);
+    constexpr int PRIO_PASS2 = FOLD_OVER_P2 ? 0 : 1, PRIO_FOLD = FOLD_OVER_P2 ? 1 : 0;
+    if (role == 2) __builtin_amdgcn_s_setprio(2); else if (role == 1) __builtin_amdgcn_s_setprio(PRIO_PASS2); else __builtin_amdgcn_s_setprio(PRIO_FOLD);
     // The next launch's carry (the last L - D + 4 D samples and the leftover) is a ~80 KB copy: every workgroup moves its slice
     // here, a sample per thread of wave 0, instead of a kernel of its own behind this one (4.4 us + a launch gap per push).  Not
     // in the fold waves: their vmcnt windows count their own loads only.
@@ -1434,6 +1420,28 @@ inline int channelizer_create(ChannelizerState &z, const amps_recc_cfg_t &cfg, h
     return 0;
 }
 
+typedef void (*chz_kernel_t)(ChzArgs);
+// the filter-bank instantiation for (input samples per frame, fused slicer or channel-major IQ out, slicer spec)
+inline chz_kernel_t chz12_kernel_for(int D, bool fused, int slicer)
+{
+    if (D == CHZ_D768) {
+        if (!fused) return chz12_kernel<8, CHZ12_IQ, CHZ_D768>;
+        switch (slicer) {
+        case AMPS_SLICER_PRODUCT: return chz12_kernel<8, AMPS_SLICER_PRODUCT, CHZ_D768>;
+        case AMPS_SLICER_SINE: return chz12_kernel<8, AMPS_SLICER_SINE, CHZ_D768>;
+        case AMPS_SLICER_EXACT: return chz12_kernel<8, AMPS_SLICER_EXACT, CHZ_D768>;
+        default: return chz12_kernel<8, AMPS_SLICER_ATAN_BOXCAR, CHZ_D768>;
+        }
+    }
+    if (!fused) return chz12_kernel<8, CHZ12_IQ>;
+    switch (slicer) {
+    case AMPS_SLICER_PRODUCT: return chz12_kernel<8, AMPS_SLICER_PRODUCT>;
+    case AMPS_SLICER_SINE: return chz12_kernel<8, AMPS_SLICER_SINE>;
+    case AMPS_SLICER_EXACT: return chz12_kernel<8, AMPS_SLICER_EXACT>;
+    default: return chz12_kernel<8, AMPS_SLICER_ATAN_BOXCAR>;
+    }
+}
+
 // Channelise `nsamp` new wideband samples.
 //  fused = false: writes the channel-major block; *chan_iq / *ld / *nframes describe it (even number of frames).
 //  fused = true : runs discriminator + boxcar + slicer behind the FFT and writes only slicer bits into `gring`
@@ -1496,18 +1504,7 @@ inline int channelizer_run(ChannelizerState &z, const float2 *iq, size_t nsamp, 
         a.tl = tl_dev;
         a_tl_last = tl_dev;
 #endif
-        if (z.D == CHZ_D768) {
-            if (!fused) hipLaunchKernelGGL((chz12_kernel<8, CHZ12_IQ, CHZ_D768>), g12, b12, 0, s, a);
-            else if (slicer == AMPS_SLICER_PRODUCT) hipLaunchKernelGGL((chz12_kernel<8, AMPS_SLICER_PRODUCT, CHZ_D768>), g12, b12, 0, s, a);
-            else if (slicer == AMPS_SLICER_SINE) hipLaunchKernelGGL((chz12_kernel<8, AMPS_SLICER_SINE, CHZ_D768>), g12, b12, 0, s, a);
-            else if (slicer == AMPS_SLICER_EXACT) hipLaunchKernelGGL((chz12_kernel<8, AMPS_SLICER_EXACT, CHZ_D768>), g12, b12, 0, s, a);
-            else hipLaunchKernelGGL((chz12_kernel<8, AMPS_SLICER_ATAN_BOXCAR, CHZ_D768>), g12, b12, 0, s, a);
-        } else
-        if (!fused) hipLaunchKernelGGL((chz12_kernel<8, CHZ12_IQ>), g12, b12, 0, s, a);
-        else if (slicer == AMPS_SLICER_PRODUCT) hipLaunchKernelGGL((chz12_kernel<8, AMPS_SLICER_PRODUCT>), g12, b12, 0, s, a);
-        else if (slicer == AMPS_SLICER_SINE) hipLaunchKernelGGL((chz12_kernel<8, AMPS_SLICER_SINE>), g12, b12, 0, s, a);
-        else if (slicer == AMPS_SLICER_EXACT) hipLaunchKernelGGL((chz12_kernel<8, AMPS_SLICER_EXACT>), g12, b12, 0, s, a);
-        else hipLaunchKernelGGL((chz12_kernel<8, AMPS_SLICER_ATAN_BOXCAR>), g12, b12, 0, s, a);
+        hipLaunchKernelGGL(chz12_kernel_for(z.D, fused, slicer), g12, b12, 0, s, a);
     }
     if (after_main) after_main(after_ctx);                            // timing: the span ends behind the filter-bank kernel, before the carry copy
 #ifdef CHZ_TIMELINE

@@ -42,20 +42,11 @@
 
 namespace amps {
 
-#ifndef AMPS_FRONT_NT
-#define AMPS_FRONT_NT 1                        // the tiles are read exactly once: non-temporal loads (measured 832 x 2^18: spec C 0.364 -> 0.327 ms, spec A 0.373 -> 0.349)
-#endif
-#ifndef AMPS_FRONT_D2_BLOCKS
-#define AMPS_FRONT_D2_BLOCKS 4                 // workgroups per CU the depth-2 / depth-3 instantiations are compiled for (register budget 512 / blocks).
-                                               // Round 4: with the rare paths' lane addresses no longer hoisted, depth 2 fits 128 registers: four waves per SIMD AND two
-                                               // tiles in flight (832 x 2^18, same box: B 0.3118 -> 0.3038 ms, C 0.3122 -> 0.3055, D 0.3208 -> 0.3174)
-#endif
-#ifndef AMPS_FRONT_D3_BLOCKS
-#define AMPS_FRONT_D3_BLOCKS 3
-#endif
-#ifndef AMPS_FRONT_D1_BLOCKS
-#define AMPS_FRONT_D1_BLOCKS 4                 // depth 1: 125 registers as written; compiled for five (96 registers) the tile loop spills (round 6 probe, profiles/EXPERIMENTS.md)
-#endif
+// The streaming kernel is compiled for four workgroups per CU (128 registers) at both tile depths.  Depth 1 takes 125 registers as
+// written; compiled for five (96 registers) its tile loop spills (round 6 probe, profiles/EXPERIMENTS.md).  Round 4: with the rare
+// paths' lane addresses no longer hoisted, depth 2 fits 128 registers too: four waves per SIMD AND two tiles in flight (832 x 2^18,
+// same box: B 0.3118 -> 0.3038 ms, C 0.3122 -> 0.3055, D 0.3208 -> 0.3174)
+constexpr int FRONT_BLOCKS_PER_CU = 4;
 constexpr int TILE = AMPS_TILE_SAMPLES;      // 512 samples per wave tile
 constexpr int HALO = AMPS_HALO_SAMPLES;      // 1024 = 2 tiles of history per chunk / push
 constexpr int CARRY_CAP = HALO + 64;         // samples kept per channel between pushes
@@ -398,7 +389,7 @@ __host__ __device__ __forceinline__ uint32_t exact_slice_word2(uint32_t SX, uint
 // raw samples are staged in the wave's LDS buffer and each lane slices 8 consecutive samples with one v_pk_mul, one
 // v_sub and one v_alignbit each -- the kernel is then bound by its HBM reads alone.
 template <int SPS, int DEPTH, bool BITS = false, bool TOL = false, int SL = AMPS_SLICER_ATAN_BOXCAR>
-__global__ __launch_bounds__(256, DEPTH == 1 ? AMPS_FRONT_D1_BLOCKS : DEPTH == 2 ? AMPS_FRONT_D2_BLOCKS : AMPS_FRONT_D3_BLOCKS) void recc_front_kernel(FrontArgs a)
+__global__ __launch_bounds__(256, FRONT_BLOCKS_PER_CU) void recc_front_kernel(FrontArgs a)
 {
     constexpr bool EXACT = SL == AMPS_SLICER_EXACT;
     constexpr bool PROD = SL == AMPS_SLICER_PRODUCT || EXACT;          // specs B and D stage the tile's raw samples in LDS
@@ -484,12 +475,9 @@ __global__ __launch_bounds__(256, DEPTH == 1 ? AMPS_FRONT_D1_BLOCKS : DEPTH == 2
     auto load_tile = [&](float4 (&r)[4], int64_t s0) {
         if (s0 >= r_prev && s0 + TILE <= avail) {          // wave-uniform: entirely inside the new block
             const f4a8 *p = (const f4a8 *)(blk_lane + (s0 - r_prev));
+            // the tiles are read exactly once: non-temporal loads (measured 832 x 2^18: spec C 0.364 -> 0.327 ms, spec A 0.373 -> 0.349)
 #pragma unroll
-#if AMPS_FRONT_NT
             for (int q = 0; q < 4; q++) { f4a8 v = __builtin_nontemporal_load(p + 64 * q); r[q] = make_float4(v.x, v.y, v.z, v.w); }
-#else
-            for (int q = 0; q < 4; q++) { f4a8 v = p[64 * q]; r[q] = make_float4(v.x, v.y, v.z, v.w); }
-#endif
         } else {
             // (the lane's offset is made opaque here: otherwise its 64-bit sign extensions are hoisted out of the segment loop as
             // invariants of this rare path and, at 128 registers, spilled -- the kernel's only scratch traffic in rounds 2 and 3)
@@ -551,24 +539,12 @@ __global__ __launch_bounds__(256, DEPTH == 1 ? AMPS_FRONT_D1_BLOCKS : DEPTH == 2
         if (k + DEPTH < K) load_tile(nxt[DEPTH - 1], t0 + DEPTH * TILE);
         f2 *const xs = (f2 *)s_d;
         {
-#ifdef AMPS_FRONT_LDS_LINEAR_STORES_EXPERIMENT
-            // TIMING EXPERIMENT ONLY (profiles/r05/front_lds_conflicts.txt): the stores go to an unpadded, perfectly linear layout -- no
-            // bank conflict at all, and WRONG results (the reads keep the padded layout) -- to see what the real layout's 17 % of
-            // conflict cycles cost the kernel
-            f2 *const xw = xs + 2 * lane;
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                xw[XHIST + 128 * q] = (f2){ cur[q].x, cur[q].y };
-                xw[XHIST + 128 * q + 1] = (f2){ cur[q].z, cur[q].w };
-            }
-#else
             f2 *const xw = xs + 2 * lane + (lane >> 2);              // xidx(XHIST + 128 q + 2 lane + e) = const + this
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 xw[xidx(XHIST + 128 * q)] = (f2){ cur[q].x, cur[q].y };
                 xw[xidx(XHIST + 128 * q) + 1] = (f2){ cur[q].z, cur[q].w };
             }
-#endif
         }
         __builtin_amdgcn_wave_barrier();
         {

@@ -149,17 +149,14 @@ constexpr uint32_t DONE_GROUPS = 32;       // done_blocks[0] = top counter, [1 +
 // 4.4) but is not a guarantee of the memory model; release / acquire on the old counters would have
 // been: measured +15 us per launch (resolve + capture + decode 0.0317 -> 0.0468 ms at 416 bursts, profiles/r05/done_counters.txt),
 // because a release waits for the counting wave's 728-byte record stores to cross PCIe.  The packed count needs no ordering at all, so
-// the read-modify-writes stay RELAXED (AMPS_RESOLVE_DONE_ORDER: an acquire on them measured +2.5 us).  The status word is read
+// the read-modify-writes stay RELAXED (an acquire on them measured +2.5 us).  The status word is read
 // relaxed as well: the one bit that can be set inside the publishing launch -- 4, record list overflow -- is implied by the count the
 // host compares with max_bursts anyway (drain_end_impl), bit 2 (capture queue overflow) is set by the kernel in FRONT of the one that
 // publishes in the queue form, bit 1 by the search kernel in front of both: kernel boundaries order those.
 // AMPS_RECC_CHECK_HEADER (on in the test suite) still cross-checks the header against a copy of the device counters.
-#ifndef AMPS_RESOLVE_DONE_ORDER
-#define AMPS_RESOLVE_DONE_ORDER __ATOMIC_RELAXED
-#endif
 __device__ __forceinline__ unsigned long long count_done(unsigned long long *p, uint32_t done, unsigned long long reserved)
 {
-    return __hip_atomic_fetch_add(p, (reserved << 32) | done, AMPS_RESOLVE_DONE_ORDER, __HIP_MEMORY_SCOPE_AGENT);
+    return __hip_atomic_fetch_add(p, (reserved << 32) | done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 // the last workgroup of the launch: the list's running {count, status} to the device-side mirror and the host header
 __device__ __forceinline__ void publish_header(uint32_t *nrecords /* {slot allocator, status, published count} */, uint32_t *status,

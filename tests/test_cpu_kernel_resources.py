@@ -56,6 +56,14 @@ def test_streaming_kernel_budget(res):
             assert r["vgpr_spill"] <= spill_ok and r["scratch_bytes_per_lane"] <= 8 * spill_ok, (name, r)
 
 
+def test_streaming_kernel_variants(res):
+    # only what a handle can reach: eight rates x four slicer specs x {exact, tolerant sync}, each at the one tile depth its spec takes
+    # (1 for A / D and for tolerant sync, 2 for B / C), plus the bit-domain form with and without tolerant sync
+    hits = _one(res, "void amps::recc_front_kernel<")
+    assert len(hits) == 66, sorted(hits)
+    assert not [name for name in hits if name.split("<")[1].split(", ")[1] == "3"], sorted(hits)   # no depth-3 form
+
+
 def test_small_kernels_fit_many_per_cu(res):
     for name, r in list(_one(res, "void amps::recc_bits_kernel<3, false>").items()) + list(_one(res, "void amps::recc_bits_kernel<2, false>").items()):
         assert r["vgprs"] <= 168 and r["lds_bytes"] <= 8192 and r["scratch_bytes_per_lane"] == 0, (name, r)   # issue-bound: 3 waves per SIMD are enough
