@@ -111,6 +111,7 @@ EXPORTS = (
     "amps_recc_drain_bursts", "amps_recc_default_slicer", "amps_recc_default_wideband_decim", "amps_recc_debug_exact_slice",
     "amps_recc_rccl_unique_id", "amps_recc_rccl_init", "amps_recc_push_wideband_bcast", "amps_recc_drain_gather",
     "amps_recc_push_wideband_dist", "amps_recc_rccl_info", "amps_recc_rccl_abort", "amps_recc_rccl_set_timeout",
+    "amps_recc_debug_slicer_bits",
 )
 _NEW_IN_ABI4 = ("amps_recc_push_wideband_dist", "amps_recc_rccl_info", "amps_recc_rccl_abort", "amps_recc_rccl_set_timeout")
 DIST_BROADCAST, DIST_SCATTER_ALLGATHER = 0, 1
@@ -176,6 +177,8 @@ def load():
     L.amps_recc_get_timing.argtypes = [vp, C.POINTER(Timing), C.c_int]
     L.amps_recc_set_timing.argtypes = [vp, C.c_int]
     L.amps_recc_debug_channelize.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    if hasattr(L, "amps_recc_debug_slicer_bits"):
+        L.amps_recc_debug_slicer_bits.argtypes = [vp, C.c_uint64, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     L.amps_recc_reply_words.argtypes = [vp, C.POINTER(Reply)]
     L.amps_recc_set_xlate.argtypes = [vp, C.POINTER(XlateCfg)]
     L.amps_recc_push_raw.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int]
@@ -184,7 +187,7 @@ def load():
     L.amps_bch_decode_words.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, vp, vp]
     for name in EXPORTS:
         if name in ("amps_recc_default_slicer", "amps_recc_default_wideband_decim", "amps_recc_debug_exact_slice", "amps_recc_rccl_unique_id", "amps_recc_rccl_init",
-                    "amps_recc_push_wideband_bcast", "amps_recc_drain_gather") + _NEW_IN_ABI4 and not hasattr(L, name):
+                    "amps_recc_push_wideband_bcast", "amps_recc_drain_gather", "amps_recc_debug_slicer_bits") + _NEW_IN_ABI4 and not hasattr(L, name):
             continue
         if name not in ("amps_recc_strerror", "amps_recc_burst_size", "amps_recc_destroy"):   # every other entry point returns int
             getattr(L, name).restype = C.c_int
@@ -586,6 +589,21 @@ class Recc:
             raise AmpsError(rc, "amps_recc_debug_demod")
         p = (n // 64) * 64
         return d[:p], s[:p], g[:p]
+
+    def debug_slicer_bits(self, first, n):
+        """Test tap of the slicer bit ring: (bits uint8 [rows][n], produced) -- the bits of absolute samples [first, first + n) of
+        every ring row once the pushes so far have finished, and one past the last sample produced (amps_recc_debug_slicer_bits)."""
+        L = load()
+        rows, produced = C.c_uint32(0), C.c_uint64(0)
+        rc = L.amps_recc_debug_slicer_bits(self._h, 0, 0, None, 0, C.byref(rows), C.byref(produced))
+        if rc:
+            raise AmpsError(rc, "amps_recc_debug_slicer_bits")
+        out = np.zeros((rows.value, n), np.uint8)
+        if n:
+            rc = L.amps_recc_debug_slicer_bits(self._h, first, n, _hostptr(out), n, C.byref(rows), C.byref(produced))
+            if rc:
+                raise AmpsError(rc, "amps_recc_debug_slicer_bits")
+        return out, produced.value
 
     def set_timing(self, mode):
         """mode: "off" | "all" | "dominant" (only the streaming kernel of the seam in use is bracketed by HIP events) |

@@ -567,6 +567,7 @@ const char *amps_recc_strerror(int code)
     case ESTALE: return "the communicator died with collectives in flight: stream state and record lists are void until amps_recc_reset";
     case EREMOTEIO: return "another rank reported an error: no rank ran the collective";
     case ENODATA: return "end of stream: the root of the distributed push has no more samples";
+    case ERANGE: return "samples not produced yet, or no longer held by the slicer bit ring";
     default: return "unknown error";
     }
 }
@@ -1395,6 +1396,39 @@ int amps_recc_debug_channelize(amps_recc_t *h, const float *iq, size_t nsamp, in
         HIP_TRY(hipMemcpy2DAsync(out, out_ld * sizeof(float2), chan_iq, ld * sizeof(float2), nout * sizeof(float2), h->C,
                                  hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int amps_recc_debug_slicer_bits(amps_recc_t *h, uint64_t first, size_t n, uint8_t *out, size_t out_ld, uint32_t *rows, uint64_t *produced)
+{
+    if (!h || (n && (!out || out_ld < n))) return -EINVAL;
+    if (!h->gring) return -ENOSYS;
+    STALE_CHECK(h);
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = sync_stream(h, h->stream)) return rc;
+    // the slicers write ring words for [n_done, n_done + P) only, and n_done, origin and P are multiples of 64: after the wait the
+    // ring holds the last R = 64 ring_words samples produced, never anything before the origin
+    const uint64_t end = h->n_done, span = 64ull * h->ring_words;
+    const uint64_t lo = std::max<uint64_t>(h->origin, end > span ? end - span : 0);
+    if (rows) *rows = h->C;
+    if (produced) *produced = end;
+    if (n == 0) return 0;
+    if (first < lo || first > end || n > end - first) return -ERANGE;
+    const uint64_t w0 = first >> 6, nw = ((first + n - 1) >> 6) - w0 + 1;      // <= ring_words
+    const uint64_t s0 = w0 & (h->ring_words - 1), n1 = std::min<uint64_t>(nw, h->ring_words - s0);
+    std::vector<uint64_t> words((size_t)h->C * nw);
+    HIP_TRY(hipMemcpy2DAsync(words.data(), nw * 8, h->gring + s0, (size_t)h->ring_words * 8, n1 * 8, h->C, hipMemcpyDeviceToHost, h->stream));
+    if (nw > n1)                                                                 // the range wraps round the ring's end
+        HIP_TRY(hipMemcpy2DAsync(words.data() + n1, nw * 8, h->gring, (size_t)h->ring_words * 8, (nw - n1) * 8, h->C, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (size_t c = 0; c < h->C; c++) {
+        const uint64_t *w = words.data() + c * nw;
+        uint8_t *o = out + c * out_ld;
+        for (size_t i = 0; i < n; i++) {
+            const uint64_t s = first + i;
+            o[i] = (uint8_t)((w[(s >> 6) - w0] >> (s & 63)) & 1ull);
+        }
+    }
     return 0;
 }
 

@@ -303,6 +303,19 @@ int amps_recc_drain_bursts(amps_recc_t *h, amps_recc_burst_t *out, uint8_t *burs
 int amps_recc_debug_demod(amps_recc_t *h, const float *iq, size_t nsamp, int mem,
                           float *demod, float *soft, uint8_t *hard);
 
+/* test tap of the slicer bit ring: the bits of absolute samples [first, first + n) of every ring row, one byte (0 / 1) each,
+ * into host memory out[n_channels][out_ld], once the pushes enqueued so far have finished; *rows = the rows written (n_channels,
+ * or a channel-group handle's own channel count: row i = the i-th channel of its group in band order), *produced = one past the
+ * last sample the slicer has produced (set_origin counts).  Every seam that slices into the ring has one: IQ, translate and
+ * wideband (fused and AMPS_RECC_FLAG_UNFUSED_WIDEBAND).  The ring holds exactly the window
+ *     [max(origin, produced - R), produced),   R = the smallest power of two >= max_samples_per_push + sps * 3586 + 1024
+ * samples (3586 = AMPS_RECC_CAPTURE_SYMS + 2 * AMPS_RECC_TRIGGER_SYMS + 64).
+ * -ERANGE if any of the samples is not produced yet or no longer held by the ring; -ENOSYS on a handle without the ring (symbol
+ * seam only); -EINVAL for out == NULL or out_ld < n with n > 0 (rows / produced may be NULL).  n = 0 only reports rows and produced.
+ * Changes nothing: the next push behaves as if the call had not been made. */
+int amps_recc_debug_slicer_bits(amps_recc_t *h, uint64_t first, size_t n, uint8_t *out, size_t out_ld,
+                                uint32_t *rows, uint64_t *produced);
+
 /* ---- one band over the GPUs of a node (BASELINE configs[4]: "RCCL broadcast of wideband IQ over xGMI") ----
  * One process and one handle per GPU, every handle created with cfg.wideband_groups = N, wideband_group = its rank (the reference's
  * channels are independent -- per-instance state only, lib/recc_impl.h:31-43 -- so any split of them is exact).  Rank 0 (or any one
@@ -397,8 +410,8 @@ int amps_recc_rccl_info(amps_recc_t *h, amps_recc_rccl_info_t *info);
 /* test tap of slicer spec D's bit logic, evaluated ON THE HOST by the very functions the kernels inline (no device needed):
  *   form 0: the streaming kernel's 32-sample window, oldest sample at bit 0: in = {SX, ST, SC}; out[0] = the slicer bits, exact from bit
  *           `sps` on (sps = any supported samples-per-symbol);
- *   form 1: the filter bank's word, newest frame at bit 0, 3 frames per symbol: in = {SX, ST, SC, SX of the previous 32 frames, wp and wm
- *           of the previous call}; out = {slicer bits, wp, wm}.
+ *   form 1: the filter bank's word, newest frame at bit 0, sps = 3 or 2 frames per symbol (behind the D = 512 / D = 768 bank): in = {SX,
+ *           ST, SC, SX of the previous 32 frames, wp and wm of the previous call}; out = {slicer bits, wp, wm}.
  * 0, or -EINVAL. */
 int amps_recc_debug_exact_slice(int form, int sps, const uint32_t *in, uint32_t *out);
 

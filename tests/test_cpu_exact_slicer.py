@@ -32,7 +32,7 @@ def _boxcar_of_libm_atan2(x, sps):
     return cs[idx + 1] - cs[np.maximum(idx - sps + 1, 0)]
 
 
-@pytest.mark.parametrize("sps", [3, 4, 5, 6, 8, 10, 12])
+@pytest.mark.parametrize("sps", [2, 3, 4, 5, 6, 8, 10, 12])
 @pytest.mark.parametrize("snr,carrier", [(30.0, True), (10.0, True), (0.0, True), (0.0, False)])
 def test_exact_slicer_is_the_sign_of_the_libm_boxcar(sps, snr, carrier):
     n = 64 * 1500
@@ -54,7 +54,7 @@ def test_exact_slicer_is_the_sign_of_the_libm_boxcar(sps, snr, carrier):
         assert (fb.taps()[2][sps:] != want[sps:]).mean() > 0.01
 
 
-@pytest.mark.parametrize("sps", [3, 10])
+@pytest.mark.parametrize("sps", [2, 3, 10])
 def test_exact_slicer_equals_spec_a_away_from_zero(sps):
     """against the model's own spec A (binary32 arctangent polynomial, 4e-6 rad per step): same bit wherever |S_A| > 1e-4"""
     x = _fsk(64 * 2000, sps, 8.0, seed=7)
@@ -104,7 +104,7 @@ def _spec_d_bits(sx, st, sc, sps):
     return g, wp, wm
 
 
-@pytest.mark.parametrize("sps", [3, 4, 5, 6, 8, 10, 12])
+@pytest.mark.parametrize("sps", [2, 3, 4, 5, 6, 8, 10, 12])
 def test_streaming_kernels_window_logic_on_the_host(sps):
     import ctypes as C
     from gr_amps_amd import capi
@@ -127,8 +127,10 @@ def test_streaming_kernels_window_logic_on_the_host(sps):
     assert L.amps_recc_debug_exact_slice(0, 7, words, out) != 0          # unsupported samples per symbol
 
 
-def test_filter_bank_word_logic_on_the_host():
-    """the filter bank's form: newest frame at bit 0, the previous 32 frames in a second word, wrap words carried from call to call"""
+@pytest.mark.parametrize("fps", [2, 3])
+def test_filter_bank_word_logic_on_the_host(fps):
+    """the filter bank's form: newest frame at bit 0, the previous 32 frames in a second word, wrap words carried from call to call;
+    fps = frames per symbol: 3 behind the D = 512 bank (exact_slice_word3), 2 behind the D = 768 one (exact_slice_word2)"""
     import ctypes as C
     from gr_amps_amd import capi
     L = capi.load()
@@ -136,7 +138,7 @@ def test_filter_bank_word_logic_on_the_host():
     rng = np.random.default_rng(33)
     n = 32 * 40
     sx, st, sc = (rng.integers(0, 2, n) for _ in range(3))
-    g, wp, wm = _spec_d_bits(sx, st, sc, 3)
+    g, wp, wm = _spec_d_bits(sx, st, sc, fps)
 
     def word(b, w):       # frames [32 w, 32 w + 32), newest at bit 0
         return int(sum(int(b[32 * w + 31 - i]) << i for i in range(32))) if w >= 0 else 0
@@ -144,8 +146,8 @@ def test_filter_bank_word_logic_on_the_host():
     for w in range(n // 32):
         inp = (C.c_uint32 * 6)(word(sx, w), word(st, w), word(sc, w), prev[0], prev[1], prev[2])
         out = (C.c_uint32 * 3)()
-        assert L.amps_recc_debug_exact_slice(1, 3, inp, out) == 0
-        lo = 3 if w == 0 else 0
+        assert L.amps_recc_debug_exact_slice(1, fps, inp, out) == 0
+        lo = fps if w == 0 else 0
         got = np.array([(out[0] >> (31 - i)) & 1 for i in range(32)], np.uint8)
         assert np.array_equal(got[lo:], g[32 * w + lo:32 * w + 32]), w
         assert out[1] == word(wp, w) and out[2] == word(wm, w)

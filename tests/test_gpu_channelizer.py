@@ -198,3 +198,39 @@ def test_wideband_stream_origin(gpu, decim):
         g["position"] -= np.uint64(origin)
         outs.append(g)
     assert len(outs[0]) == len(bursts) and outs[0].tobytes() == outs[1].tobytes()
+
+
+def test_channelizer_per_bin_error_on_a_wrapped_band(gpu, decim):
+    """The IQ form against float64, bin by bin and frame by frame: |y32 - y64| <= c 2^-24 log2(1024) ||Y64(frame)||_2 -- the usual
+    FFT error bound taken per frame, so that a quiet channel beside a loud one is held to its own frame's energy rather than to the
+    block's loudest bin.  The band wraps past bin 1023; tones sit on its first and last bins (700, 507), on both sides of the wrap
+    (1023, 0) and just outside it (699, 508); the pushes are ragged and one of them launches >= 64 workgroups (carry in-kernel)."""
+    import slicerbound as sb
+    D = decim
+    first, C = 700, 832
+    rng = np.random.default_rng(23)
+    nfr = 4300
+    n = nfr * D + 123
+    t = np.arange(n)
+    x = 0.02 * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
+    for k, a in ((700, 1.0), (507, 0.8), (1023, 0.6), (0, 0.9), (699, 1.0), (508, 0.7)):
+        x += a * np.exp(2j * np.pi * (sw.bin_freq(k) + 3e3) * t / sw.FS_WIDE)
+    x = x.astype(np.complex64)
+    pieces = [3 * D + 11, 4100 * D + 500, 70 * D - 13, 2 * D + 1]           # 0-2 / 4100 (65 workgroups) / 68-72 / 0-4 frames, then the rest
+    pieces.append(n - sum(pieces))
+    with _handle(D, C, first, nfr + 8) as r:
+        parts, off = [], 0
+        for m in pieces:
+            parts.append(r.debug_channelize(x[off:off + m]))
+            off += m
+        got = np.concatenate(parts, axis=1)
+    assert parts[1].shape[1] > 63 * 64 and got.shape == (C, (n // D) & ~3 if D == 768 else (n // D) & ~1)
+    want = cz.channelize(x, P=8, D=D)[:, :got.shape[1]]                   # all 1024 bins, float64
+    norm = np.sqrt((np.abs(want) ** 2).sum(0))
+    rows = (first + np.arange(C)) % 1024
+    ratio = np.abs(got - want[rows]) / (sb.U32 * np.log2(1024) * norm)
+    print(f"\nD={D}: worst |y32 - y64| / (2^-24 log2(1024) ||Y64(frame)||) = {ratio.max():.3f}")
+    assert ratio.max() <= sb.FFT_C, (ratio.max(), np.unravel_index(np.argmax(ratio), ratio.shape))
+    # the edge tones are where the band says: full scale on its first / last rows and across the wrap
+    for k in (700, 507, 1023, 0):
+        assert np.abs(got[(k - first) % 1024, 100:]).mean() > 0.3, k
