@@ -3,6 +3,7 @@ AMPS band out (BASELINE configs[3]; replaces 832 x [freq_xlating_fir_filter_ccc 
 -> amps.recc -> amps.recc_decode] of grc/recctest.grc).  Needs an MI355X: the library has no CPU path.
 
     python examples/decode_wideband.py            # 12 mobiles on random channels, the stream pushed in ragged blocks
+    python examples/decode_wideband.py --sc16     # the same stream as a 16-bit converter delivers it: interleaved int16 I/Q, pushed as it is
 """
 import os
 import sys
@@ -18,6 +19,11 @@ rng = np.random.default_rng(7)
 plan = [(FIRST_BIN + int(c), int(rng.integers(4000, NSAMP - 3456 * 1536 - 4000))) for c in rng.choice(CHANNELS, 12, replace=False)]
 x, truth = sw.make_wideband(NSAMP, plan, seed=7, snr_db=20.0, sym_ppm=50.0)   # every mobile 50 ppm off the nominal bit clock
 
+SC16 = "--sc16" in sys.argv[1:]
+if SC16:                                          # full scale for the loudest sample, a power of two; no slicer decision depends on the scale
+    scale = 2.0 ** np.floor(np.log2(30000.0 / max(np.abs(x.real).max(), np.abs(x.imag).max())))
+    x = np.rint(np.stack([x.real, x.imag], axis=1) * scale).astype(np.int16)   # [n, 2]: 4 bytes per sample instead of 8
+
 try:
     rx = capi.Recc(n_channels=CHANNELS, max_samples=NSAMP // 512 + 72, max_bursts=256,
                    wideband={"channels": 1024, "first_channel": FIRST_BIN})     # decimation: the library default (768: 40 ksps per channel)
@@ -27,7 +33,7 @@ with rx:
     pos = 0
     while pos < NSAMP:                            # blocks of any size: what is left of a frame waits in the handle for the next push
         n = min(int(rng.integers(100_000, 3_000_000)), NSAMP - pos)
-        rx.push_wideband(x[pos:pos + n])
+        (rx.push_wideband_short if SC16 else rx.push_wideband)(x[pos:pos + n])
         pos += n
     recs = rx.drain()
 sent = {k - FIRST_BIN: v[1] for (k, _), v in truth.items()}

@@ -111,7 +111,7 @@ EXPORTS = (
     "amps_recc_drain_bursts", "amps_recc_default_slicer", "amps_recc_default_wideband_decim", "amps_recc_debug_exact_slice",
     "amps_recc_rccl_unique_id", "amps_recc_rccl_init", "amps_recc_push_wideband_bcast", "amps_recc_drain_gather",
     "amps_recc_push_wideband_dist", "amps_recc_rccl_info", "amps_recc_rccl_abort", "amps_recc_rccl_set_timeout",
-    "amps_recc_debug_slicer_bits",
+    "amps_recc_debug_slicer_bits", "amps_recc_push_wideband_short",
 )
 _NEW_IN_ABI4 = ("amps_recc_push_wideband_dist", "amps_recc_rccl_info", "amps_recc_rccl_abort", "amps_recc_rccl_set_timeout")
 DIST_BROADCAST, DIST_SCATTER_ALLGATHER = 0, 1
@@ -154,6 +154,8 @@ def load():
     L.amps_recc_decode_bursts.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, vp]
     L.amps_recc_push_iq.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int]
     L.amps_recc_push_wideband.argtypes = [vp, vp, C.c_size_t, C.c_int]
+    if hasattr(L, "amps_recc_push_wideband_short"):   # absent only from A/B builds of earlier revisions (AMPS_RECC_LIB)
+        L.amps_recc_push_wideband_short.argtypes = [vp, vp, C.c_size_t, C.c_int]
     if hasattr(L, "amps_recc_push_wideband_bcast"):   # absent only from A/B builds of earlier revisions (AMPS_RECC_LIB)
         L.amps_recc_rccl_unique_id.argtypes = [vp]
         L.amps_recc_rccl_init.argtypes = [vp, vp, C.c_int, C.c_int]
@@ -187,7 +189,8 @@ def load():
     L.amps_bch_decode_words.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, vp, vp]
     for name in EXPORTS:
         if name in ("amps_recc_default_slicer", "amps_recc_default_wideband_decim", "amps_recc_debug_exact_slice", "amps_recc_rccl_unique_id", "amps_recc_rccl_init",
-                    "amps_recc_push_wideband_bcast", "amps_recc_drain_gather", "amps_recc_debug_slicer_bits") + _NEW_IN_ABI4 and not hasattr(L, name):
+                    "amps_recc_push_wideband_bcast", "amps_recc_drain_gather", "amps_recc_debug_slicer_bits",
+                    "amps_recc_push_wideband_short") + _NEW_IN_ABI4 and not hasattr(L, name):
             continue
         if name not in ("amps_recc_strerror", "amps_recc_burst_size", "amps_recc_destroy"):   # every other entry point returns int
             getattr(L, name).restype = C.c_int
@@ -376,6 +379,31 @@ class Recc:
         rc = load().amps_recc_push_wideband(self._h, ptr, n, mem)
         if rc:
             raise AmpsError(rc, "amps_recc_push_wideband")
+
+    def push_wideband_short(self, iq):
+        """The wideband block as interleaved 16-bit I/Q (amps_recc_push_wideband_short): a numpy int16 array of shape [n, 2] or [2n], or
+        a torch int16 CUDA tensor of the same shapes (read in place, like push_wideband's device blocks).  Nothing else is taken: a
+        float array is a TypeError, not a silent cast."""
+        if isinstance(iq, np.ndarray):
+            if iq.dtype != np.int16:
+                raise TypeError("push_wideband_short takes int16 samples, not %s" % iq.dtype)
+            if not (iq.ndim == 1 or (iq.ndim == 2 and iq.shape[1] == 2)) or iq.size % 2:
+                raise TypeError("push_wideband_short takes shape [n, 2] or [2n], not %r" % (iq.shape,))
+            iq = np.ascontiguousarray(iq).reshape(-1)
+        elif hasattr(iq, "data_ptr") and hasattr(iq, "is_cuda"):
+            import torch
+            if iq.dtype != torch.int16 or not iq.is_cuda:
+                raise TypeError("push_wideband_short takes an int16 CUDA tensor, not %s on %s" % (iq.dtype, iq.device))
+            if not (iq.dim() == 1 or (iq.dim() == 2 and iq.shape[1] == 2)) or iq.numel() % 2:
+                raise TypeError("push_wideband_short takes shape [n, 2] or [2n], not %r" % (tuple(iq.shape),))
+            iq = iq.contiguous().reshape(-1)
+        else:
+            raise TypeError(type(iq))
+        n = iq.shape[0] // 2
+        ptr, mem, keep = _as_ptr(iq, self.sync_torch)
+        rc = load().amps_recc_push_wideband_short(self._h, ptr, n, mem)
+        if rc:
+            raise AmpsError(rc, "amps_recc_push_wideband_short")
 
     # ---- one band over the GPUs of a node: RCCL inside the C ABI (include/amps_recc.h, amps_recc_push_wideband_bcast)
     @staticmethod

@@ -923,9 +923,8 @@ int run_bits_device(amps_recc *h, uint32_t P)
     h->n_done += P;
     return 0;
 }
-} // namespace
-
-int amps_recc_push_wideband(amps_recc_t *h, const float *iq, size_t nsamp, int mem)
+// the wideband seam for either sample type of the block: fc32, or interleaved 16-bit I/Q (amps_recc_push_wideband_short)
+int push_wideband_block(amps_recc_t *h, const void *iq, size_t nsamp, int mem, bool sc16)
 {
     if (!h) return -EINVAL;
     STALE_CHECK(h);
@@ -943,13 +942,24 @@ int amps_recc_push_wideband(amps_recc_t *h, const float *iq, size_t nsamp, int m
     int rc;
     {
         SpanGuard g(h, T_CHANNELIZER, nsamp);
-        rc = channelizer_run(h->chz, (const float2 *)iq, nsamp, mem, h->stream, &chan_iq, &ld, &nout, fused, h->gring, h->ring_words, h->n_done, h->slicer,
-                             SpanGuard::end_cb, &g);
+        rc = channelizer_run(h->chz, iq, nsamp, mem, h->stream, &chan_iq, &ld, &nout, fused, h->gring, h->ring_words, h->n_done, h->slicer,
+                             SpanGuard::end_cb, &g, sc16);
     }
     if (rc) return rc;
     if (nout > h->cfg.max_samples_per_push) return -E2BIG;
     if (fused) return run_bits_device(h, nout);
     return run_iq_device(h, chan_iq, ld, nout);
+}
+} // namespace
+
+int amps_recc_push_wideband(amps_recc_t *h, const float *iq, size_t nsamp, int mem)
+{
+    return push_wideband_block(h, iq, nsamp, mem, false);
+}
+
+int amps_recc_push_wideband_short(amps_recc_t *h, const int16_t *iq, size_t nsamp, int mem)
+{
+    return push_wideband_block(h, iq, nsamp, mem, true);
 }
 
 int amps_recc_rccl_unique_id(uint8_t *id)

@@ -61,7 +61,7 @@ constexpr int CHZ_D = 512;           // input samples per frame of the default f
 constexpr int CHZ_D768 = 768;        // ... of the 4/3 x oversampled form (40 ksps per channel, 2 samples per symbol; round 6, section "D = 768" below)
 
 struct ChzArgs {
-    const float2 *block;     // new wideband samples of this push
+    const float2 *block;     // new wideband samples of this push (chz12_short_kernel: the same pointer holds chz_sc16 samples)
     const float2 *carry;     // samples [f_done*D + D - L, f_done*D + leftover) of the stream so far
     const float *taps;       // [L] prototype
     float2 *out;             // [C][ld] channel-major output of this push
@@ -90,6 +90,14 @@ struct ChzArgs {
 constexpr int CHZ_PRE = 4;   // frames of history the carry keeps beyond the filter's own L - D samples: what the exact half of a workgroup's pre-roll reaches back to
 
 typedef float cf2 __attribute__((ext_vector_type(2)));
+// A sample of the wideband block as the caller hands it over: fc32 (float2) or interleaved 16-bit I/Q ("sc16": I in the low half of
+// the dword).  The sc16 form is DEFINED as the fc32 form on the plainly converted block (amps_recc_push_wideband_short): every int16 is
+// exact in fp32, so both forms run the same fp32 operations on the same values.  Carry buffers stay fc32 whatever the block was.
+struct alignas(4) chz_sc16 { int16_t x, y; };
+template <typename T> struct chz_is_short { static constexpr bool value = false; };
+template <> struct chz_is_short<chz_sc16> { static constexpr bool value = true; };
+__device__ __forceinline__ cf2 chz_cvt(float2 s) { return (cf2){ s.x, s.y }; }
+__device__ __forceinline__ cf2 chz_cvt(chz_sc16 s) { return (cf2){ (float)s.x, (float)s.y }; }
 // Buffer resource (V#) of the fast loader (round 6).  The fold role's prefetch used `global_load_dwordx2 v, v_off, s[base:base+1]` with
 // a 64-bit scalar base per frame: clamp the frame index to the block, multiply, subtract, shift, add with carry -- nine scalar
 // instructions per frame and two more per chunk, ~65 per half-step in the wave whose instruction count IS the kernel's critical path
@@ -275,18 +283,27 @@ __device__ __forceinline__ void chz_p3(cf2 *A, const cf2 (&tw)[NT], int lane)
 // lies inside the new block (all but the first and last of a launch) is plain coalesced loads; the generic path walks
 // carry / block / zero padding.  The choice is made once per batch, so the common path has no branch between the four
 // folds (per-frame branches cost 8 %: they fence the scheduler).
-struct ChzIn {
-    const float2 *block, *carry;
+template <typename T = float2> struct ChzIn {
+    static constexpr bool SHORT = chz_is_short<T>::value;
+    const T *block;
+    const float2 *carry;
     int64_t hist, lead, carry_len, nsamp;
     uint32_t f_last;         // last launch-relative frame whose CHZ_D samples lie wholly inside the new block (FAST prefetch clamp)
     __device__ __forceinline__ cf2 generic(int64_t v) const
     {
         const int64_t ci = v + hist;
         if (ci < 0) return (cf2){ 0.f, 0.f };
+        if constexpr (SHORT) {
+            if (ci < carry_len) return chz_cvt(carry[ci]);
+            const int64_t bi = v - lead;
+            if (bi >= nsamp) return (cf2){ 0.f, 0.f };
+            return chz_cvt(block[bi]);
+        } else {
         float2 s;
         if (ci < carry_len) s = carry[ci];
         else { const int64_t bi = v - lead; if (bi >= nsamp) return (cf2){ 0.f, 0.f }; s = block[bi]; }
         return (cf2){ s.x, s.y };
+        }
     }
     // the same without a branch around the load: the edge paths fetch a batch of these and wait ONCE (round 6: sixteen -- at D = 768
     // nineteen -- generic loads of a workgroup's prologue each behind its own drain were that many HBM round trips in a row)
@@ -294,10 +311,21 @@ struct ChzIn {
     {
         const int64_t ci = v + hist, bi = v - lead;
         const bool in_carry = ci < carry_len, ok = ci >= 0 && (in_carry || bi < nsamp);
+        if constexpr (SHORT) {
+            // sc16 block: the two buffers differ in sample size -- two dword loads from whichever holds the sample (a block sample
+            // twice: no branch around a load, no more registers in flight than the fc32 form keeps); a block sample is converted here
+            typedef uint32_t __attribute__((may_alias)) raw_t;
+            const bool in_block = ok && !in_carry;
+            const char *p = in_block ? (const char *)(block + bi) : (const char *)(carry + (ok ? ci : 0));   // any valid address
+            const uint32_t d0 = *(const raw_t *)p, d1 = *(const raw_t *)(p + (in_block ? 0 : 4));
+            const cf2 b = { (float)(int16_t)(d0 & 0xffffu), (float)(int16_t)(d1 >> 16) };
+            return in_block ? b : ok ? (cf2){ __uint_as_float(d0), __uint_as_float(d1) } : (cf2){ 0.f, 0.f };
+        } else {
         const float2 *p = in_carry ? carry + ci : block + bi;
         p = ok ? p : carry;                                           // any valid address
         const float2 s = *p;
         return ok ? (cf2){ s.x, s.y } : (cf2){ 0.f, 0.f };
+        }
     }
     // all CHZ_BATCH frames starting at F lie inside the new block (wave-uniform)
     __device__ __forceinline__ bool batch_in_block(int64_t F) const
@@ -309,9 +337,8 @@ struct ChzIn {
     __device__ __forceinline__ void frame(int64_t F, int t, cf2 &s0, cf2 &s1) const
     {
         if constexpr (FAST) {
-            const float2 *p = block + (F * CHZ_D - lead) + t;
-            const float2 u = p[0], w = p[256];
-            s0 = (cf2){ u.x, u.y }; s1 = (cf2){ w.x, w.y };
+            const T *p = block + (F * CHZ_D - lead) + t;
+            s0 = chz_cvt(p[0]); s1 = chz_cvt(p[256]);
         } else {
             s0 = generic(F * CHZ_D + t); s1 = generic(F * CHZ_D + 256 + t);
         }
@@ -404,12 +431,19 @@ __device__ __forceinline__ void chz_fold2_ring(const cf2 (&ring)[4][P + 4], cons
 // cycles at the END of their step, when every other wave of the CU was already waiting at the barrier).
 // The generic path (carry, zero padding: first and last half-steps of a launch) uses ordinary loads and drains them before it
 // returns, so vmcnt(8) is right after either path.
-template <int P, int BASE, int ELEM, int G, bool FAST>
-__device__ __forceinline__ void chz_load1_ring(cf2 (&ring)[4][P + 4], const ChzIn &in, int64_t F, int t, chz_rsrc_t rsrc = chz_rsrc_t{}, uint32_t soff = 0u)
+template <int P, int BASE, int ELEM, int G, bool FAST, typename IN>
+__device__ __forceinline__ void chz_load1_ring(cf2 (&ring)[4][P + 4], const IN &in, int64_t F, int t, chz_rsrc_t rsrc = chz_rsrc_t{}, uint32_t soff = 0u)
 {
     constexpr int R = P + 4;
     constexpr int E = (BASE + ELEM + (G >> 1)) % R, J = 2 * (G & 1);
-    if constexpr (FAST) {
+    if constexpr (FAST && IN::SHORT) {
+        // sc16 block: the same two loads per frame, one dword each (a 256-sample chunk is 1 KB).  The packed sample is born in the low
+        // register of the slot's own pair -- the same tie -- and chz_ring_wait expands it in place once it has landed.
+        const uint32_t voff = (uint32_t)t * (uint32_t)sizeof(chz_sc16);
+        const uint32_t so = soff + (uint32_t)((2 * CHZ_BATCH + G) * CHZ_D * sizeof(chz_sc16));
+        asm volatile("buffer_load_dword %0, %1, %2, %3 offen" : "+v"(ring[J][E].x) : "v"(voff), "s"(rsrc), "s"(so));
+        asm volatile("buffer_load_dword %0, %1, %2, %3 offen offset:1024" : "+v"(ring[J + 1][E].x) : "v"(voff), "s"(rsrc), "s"(so));
+    } else if constexpr (FAST) {
         // Round 6: raw buffer loads against the workgroup's descriptor (chz_make_rsrc) -- `soff` = byte offset of the half-step in work,
         // the frame fetched here lies 2 * CHZ_BATCH + G frames behind its first sample; the hardware's range check stands in for the
         // clamp of rounds 3-5 (frame index against the last whole frame of the block, on the scalar unit since round 5), and the
@@ -436,8 +470,8 @@ __device__ __forceinline__ void chz_load1_ring(cf2 (&ring)[4][P + 4], const ChzI
     }
 }
 // the eight generic loads of a half-step as ONE batch: all of them in flight, one drain, then into their slots through the same ties
-template <int P, int BASE, int ELEM>
-__device__ __forceinline__ void chz_load_half_ring_generic(cf2 (&ring)[4][P + 4], const ChzIn &in, int64_t F, int t)
+template <int P, int BASE, int ELEM, typename IN>
+__device__ __forceinline__ void chz_load_half_ring_generic(cf2 (&ring)[4][P + 4], const IN &in, int64_t F, int t)
 {
     constexpr int R = P + 4;
     cf2 v[8];
@@ -451,8 +485,8 @@ __device__ __forceinline__ void chz_load_half_ring_generic(cf2 (&ring)[4][P + 4]
         asm volatile("v_mov_b64 %0, %1" : "+v"(ring[j + 1][e]) : "v"(v[2 * g + 1]));
     }
 }
-template <int P, int BASE, int ELEM, bool FAST>
-__device__ __forceinline__ void chz_load_half_ring(cf2 (&ring)[4][P + 4], const ChzIn &in, int64_t F, int t)
+template <int P, int BASE, int ELEM, bool FAST, typename IN>
+__device__ __forceinline__ void chz_load_half_ring(cf2 (&ring)[4][P + 4], const IN &in, int64_t F, int t)
 {
     if constexpr (!FAST) { chz_load_half_ring_generic<P, BASE, ELEM>(ring, in, F, t); return; }
     chz_load1_ring<P, BASE, ELEM, 0, FAST>(ring, in, F, t);
@@ -462,13 +496,29 @@ __device__ __forceinline__ void chz_load_half_ring(cf2 (&ring)[4][P + 4], const 
 }
 // before a fold: the samples of logical elements P and P+1 (loaded two half-steps ago) have arrived; the empty asm makes
 // every use of those registers depend on the wait
-template <int P, int BASE>
-__device__ __forceinline__ void chz_ring_wait(cf2 (&ring)[4][P + 4])
+// a packed sc16 sample that has landed in the low register of a ring slot -> the slot's cf2, in place: two conversions, no copy
+__device__ __forceinline__ void chz_expand_short(cf2 &e)
+{
+    asm volatile("v_cvt_f32_i32_sdwa %0, sext(%1) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1\n\t"
+                 "v_cvt_f32_i32_sdwa %1, sext(%1) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0" : "=v"(e.y), "+v"(e.x));
+}
+// SHORT (sc16 blocks), `expand`: the elements this wait covers were loaded by the fast loader, packed, and are expanded here, behind
+// the wait and before their first use (an element is read by eight taps).  `expand` is wave-uniform and false only in edge half-steps
+// and in the first two fast ones behind them, which still read what the generic loader left -- converted at the load.  Both arms of
+// the branch leave every register where it is: no slot with a load in flight is redefined in either.
+template <int P, int BASE, bool SHORT = false>
+__device__ __forceinline__ void chz_ring_wait(cf2 (&ring)[4][P + 4], bool expand = false)
 {
     constexpr int R = P + 4;
     asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     asm volatile("" : "+v"(ring[0][(BASE + P) % R]), "+v"(ring[1][(BASE + P) % R]), "+v"(ring[2][(BASE + P) % R]), "+v"(ring[3][(BASE + P) % R]),
                       "+v"(ring[0][(BASE + P + 1) % R]), "+v"(ring[1][(BASE + P + 1) % R]), "+v"(ring[2][(BASE + P + 1) % R]), "+v"(ring[3][(BASE + P + 1) % R]));
+    if constexpr (SHORT) {
+        if (__builtin_expect(expand, 1)) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) { chz_expand_short(ring[j][(BASE + P) % R]); chz_expand_short(ring[j][(BASE + P + 1) % R]); }
+        }
+    }
 }
 
 
@@ -535,13 +585,21 @@ __device__ __forceinline__ void chz768_fold2_ring(const cf2 (&ring)[4][CHZ768_R]
 // FAST: one raw buffer load (chz_make_rsrc).  `soff` = byte offset of the half-step in work inside the workgroup's descriptor; the
 // chunks a half-step fetches are the CONSECUTIVE 2 KB chunks 19 .. 30 behind its own first sample -- the stream is read in order --
 // so chunk c is soff + 2048 (c & ~1) with the odd ones on the 12-bit immediate.
-template <int BASE, int X, int G, int J, bool FAST>
-__device__ __forceinline__ void chz768_load1(cf2 (&ring)[4][CHZ768_R], const ChzIn &in, int64_t F0, int t, chz_rsrc_t rsrc = chz_rsrc_t{}, uint32_t soff = 0u)
+template <int BASE, int X, int G, int J, bool FAST, typename IN>
+__device__ __forceinline__ void chz768_load1(cf2 (&ring)[4][CHZ768_R], const IN &in, int64_t F0, int t, chz_rsrc_t rsrc = chz_rsrc_t{}, uint32_t soff = 0u)
 {
     constexpr int K = (J + G) & 3;
     static_assert(K != 3, "branch J receives nothing in frame G");
     constexpr int SLOT = (BASE + 7 + chz768_cnt(J, G) + 3 * X) % CHZ768_R;
-    if constexpr (FAST) {
+    if constexpr (FAST && IN::SHORT) {
+        // sc16 block: the chunks are 1 KB, chunk c at soff + 1024 (c & ~1), the odd ones on the immediate; one dword into the low
+        // register of the slot's own pair, expanded in place by chz768_ring_wait
+        constexpr int CH = 3 * (4 * X + G) + K;
+        const uint32_t voff = (uint32_t)t * (uint32_t)sizeof(chz_sc16);
+        const uint32_t so = soff + 1024u * (uint32_t)(CH & ~1);
+        if constexpr (CH & 1) asm volatile("buffer_load_dword %0, %1, %2, %3 offen offset:1024" : "+v"(ring[J][SLOT].x) : "v"(voff), "s"(rsrc), "s"(so));
+        else asm volatile("buffer_load_dword %0, %1, %2, %3 offen" : "+v"(ring[J][SLOT].x) : "v"(voff), "s"(rsrc), "s"(so));
+    } else if constexpr (FAST) {
         constexpr int CH = 3 * (4 * X + G) + K;                      // chunk of 256 samples behind the half-step's first sample
         const uint32_t voff = (uint32_t)t * (uint32_t)sizeof(float2);
         const uint32_t so = soff + 2048u * (uint32_t)(CH & ~1);
@@ -555,8 +613,8 @@ __device__ __forceinline__ void chz768_load1(cf2 (&ring)[4][CHZ768_R], const Chz
     }
 }
 // generic form in two halves, so that a batch of fetches shares one drain
-template <int X, int G, int J>
-__device__ __forceinline__ cf2 chz768_fetch(const ChzIn &in, int64_t F0, int t) { return in.generic_nb((F0 + 4 * X + G) * CHZ_D768 + 256 * ((J + G) & 3) + t); }
+template <int X, int G, int J, typename IN>
+__device__ __forceinline__ cf2 chz768_fetch(const IN &in, int64_t F0, int t) { return in.generic_nb((F0 + 4 * X + G) * CHZ_D768 + 256 * ((J + G) & 3) + t); }
 template <int BASE, int X, int G, int J>
 __device__ __forceinline__ void chz768_put(cf2 (&ring)[4][CHZ768_R], cf2 v)
 {
@@ -564,8 +622,8 @@ __device__ __forceinline__ void chz768_put(cf2 (&ring)[4][CHZ768_R], cf2 v)
     asm volatile("v_mov_b64 %0, %1" : "+v"(ring[J][SLOT]) : "v"(v));
 }
 // the twelve loads of an EDGE half-step (both lists below), one drain
-template <int BASE>
-__device__ __forceinline__ void chz768_loads_generic(cf2 (&ring)[4][CHZ768_R], const ChzIn &in, int64_t F0, int t)
+template <int BASE, typename IN>
+__device__ __forceinline__ void chz768_loads_generic(cf2 (&ring)[4][CHZ768_R], const IN &in, int64_t F0, int t)
 {
     cf2 v[12] = { chz768_fetch<1, 2, 3>(in, F0, t), chz768_fetch<1, 2, 0>(in, F0, t), chz768_fetch<1, 3, 1>(in, F0, t), chz768_fetch<1, 3, 2>(in, F0, t),
                   chz768_fetch<1, 3, 3>(in, F0, t), chz768_fetch<2, 0, 0>(in, F0, t), chz768_fetch<2, 0, 1>(in, F0, t), chz768_fetch<2, 0, 2>(in, F0, t),
@@ -577,7 +635,8 @@ __device__ __forceinline__ void chz768_loads_generic(cf2 (&ring)[4][CHZ768_R], c
 }
 // what the half-steps -2 and -1 would have left in flight when half-step 0 (first frame F0, BASE 0) begins: its own three samples per
 // branch (slots 8..10), the first of half-step 1 (slot 11) and -- branches 0..2, whose element 0 is dead already -- the second (slot 0)
-__device__ __forceinline__ void chz768_prime(cf2 (&ring)[4][CHZ768_R], const ChzIn &in, int64_t F0, int t)
+template <typename IN>
+__device__ __forceinline__ void chz768_prime(cf2 (&ring)[4][CHZ768_R], const IN &in, int64_t F0, int t)
 {
     cf2 a[12] = { chz768_fetch<0, 0, 0>(in, F0, t), chz768_fetch<0, 0, 1>(in, F0, t), chz768_fetch<0, 0, 2>(in, F0, t), chz768_fetch<0, 1, 3>(in, F0, t),
                   chz768_fetch<0, 1, 0>(in, F0, t), chz768_fetch<0, 1, 1>(in, F0, t), chz768_fetch<0, 2, 2>(in, F0, t), chz768_fetch<0, 2, 3>(in, F0, t),
@@ -593,15 +652,15 @@ __device__ __forceinline__ void chz768_prime(cf2 (&ring)[4][CHZ768_R], const Chz
     chz768_put<0, 1, 1, 0>(ring, b[4]); chz768_put<0, 1, 1, 1>(ring, b[5]); chz768_put<0, 1, 2, 2>(ring, b[6]);
 }
 // the six loads behind the first tap block of frames 0 / 1, and the six behind that of frames 2 / 3, in the order they are needed
-template <int BASE, bool FAST>
-__device__ __forceinline__ void chz768_loads_a(cf2 (&ring)[4][CHZ768_R], const ChzIn &in, int64_t F0, int t, chz_rsrc_t rs, uint32_t so)
+template <int BASE, bool FAST, typename IN>
+__device__ __forceinline__ void chz768_loads_a(cf2 (&ring)[4][CHZ768_R], const IN &in, int64_t F0, int t, chz_rsrc_t rs, uint32_t so)
 {
     chz768_load1<BASE, 1, 2, 3, FAST>(ring, in, F0, t, rs, so); chz768_load1<BASE, 1, 2, 0, FAST>(ring, in, F0, t, rs, so);
     chz768_load1<BASE, 1, 3, 1, FAST>(ring, in, F0, t, rs, so); chz768_load1<BASE, 1, 3, 2, FAST>(ring, in, F0, t, rs, so);
     chz768_load1<BASE, 1, 3, 3, FAST>(ring, in, F0, t, rs, so); chz768_load1<BASE, 2, 0, 0, FAST>(ring, in, F0, t, rs, so);
 }
-template <int BASE, bool FAST>
-__device__ __forceinline__ void chz768_loads_b(cf2 (&ring)[4][CHZ768_R], const ChzIn &in, int64_t F0, int t, chz_rsrc_t rs, uint32_t so)
+template <int BASE, bool FAST, typename IN>
+__device__ __forceinline__ void chz768_loads_b(cf2 (&ring)[4][CHZ768_R], const IN &in, int64_t F0, int t, chz_rsrc_t rs, uint32_t so)
 {
     chz768_load1<BASE, 2, 0, 1, FAST>(ring, in, F0, t, rs, so); chz768_load1<BASE, 2, 0, 2, FAST>(ring, in, F0, t, rs, so);
     chz768_load1<BASE, 2, 1, 3, FAST>(ring, in, F0, t, rs, so); chz768_load1<BASE, 2, 1, 0, FAST>(ring, in, F0, t, rs, so);
@@ -609,17 +668,37 @@ __device__ __forceinline__ void chz768_loads_b(cf2 (&ring)[4][CHZ768_R], const C
 }
 // in front of frames 0 / 1: element 8 of every branch and element 9 of branches 0, 1 have arrived (everything but the thirteen
 // youngest loads); in front of frames 2 / 3: element 9 of branches 2, 3 and element 10 of every branch (again thirteen)
-template <int BASE, int FA>
-__device__ __forceinline__ void chz768_ring_wait(cf2 (&ring)[4][CHZ768_R])
+// SHORT (sc16 blocks; chz_expand_short, see chz_ring_wait), `age` = fast half-steps run before this one (wave-uniform): a half-step
+// meets the packed elements of the one before it (element 9 of branch 3 and element 10 of every branch: the samples of frames 2 / 3)
+// and of the one before that (element 8 of every branch, element 9 of branches 0..2); whatever an edge half-step or the prologue
+// loaded arrived converted.  age < 0 in edge half-steps.
+template <int BASE, int FA, bool SHORT = false>
+__device__ __forceinline__ void chz768_ring_wait(cf2 (&ring)[4][CHZ768_R], int age = 0)
 {
     constexpr int R = CHZ768_R;
     asm volatile("s_waitcnt vmcnt(13)" ::: "memory");
-    if constexpr (FA == 0)
+    if constexpr (FA == 0) {
         asm volatile("" : "+v"(ring[0][(BASE + 8) % R]), "+v"(ring[1][(BASE + 8) % R]), "+v"(ring[2][(BASE + 8) % R]), "+v"(ring[3][(BASE + 8) % R]),
                           "+v"(ring[0][(BASE + 9) % R]), "+v"(ring[1][(BASE + 9) % R]));
-    else
+        if constexpr (SHORT) {
+            if (__builtin_expect(age >= 2, 1)) {
+#pragma unroll
+                for (int j = 0; j < 4; j++) chz_expand_short(ring[j][(BASE + 8) % R]);
+                chz_expand_short(ring[0][(BASE + 9) % R]); chz_expand_short(ring[1][(BASE + 9) % R]);
+            }
+        }
+    } else {
         asm volatile("" : "+v"(ring[2][(BASE + 9) % R]), "+v"(ring[3][(BASE + 9) % R]),
                           "+v"(ring[0][(BASE + 10) % R]), "+v"(ring[1][(BASE + 10) % R]), "+v"(ring[2][(BASE + 10) % R]), "+v"(ring[3][(BASE + 10) % R]));
+        if constexpr (SHORT) {
+            if (__builtin_expect(age >= 1, 1)) {
+                if (__builtin_expect(age >= 2, 1)) chz_expand_short(ring[2][(BASE + 9) % R]);
+                chz_expand_short(ring[3][(BASE + 9) % R]);
+#pragma unroll
+                for (int j = 0; j < 4; j++) chz_expand_short(ring[j][(BASE + 10) % R]);
+            }
+        }
+    }
 }
 
 // ---- the three-role pipeline ----
@@ -948,7 +1027,8 @@ constexpr int CHZ_TL_FIRST = 40;
 #endif
 
 // carry_out[k] = virtual sample (consumed - hist + k), k in [0, hist + leftover_new)
-__device__ __forceinline__ float2 chz_carry_sample(const float2 *block, const float2 *carry_in, uint32_t carry_len, uint32_t nsamp,
+template <typename T>
+__device__ __forceinline__ float2 chz_carry_sample(const T *block, const float2 *carry_in, uint32_t carry_len, uint32_t nsamp,
                                                    uint32_t hist, uint32_t consumed, uint32_t k)
 {
     const int64_t lead = (int64_t)carry_len - hist;
@@ -957,7 +1037,11 @@ __device__ __forceinline__ float2 chz_carry_sample(const float2 *block, const fl
     float2 s = make_float2(0.f, 0.f);
     if (ci >= 0) {
         if (ci < (int64_t)carry_len) s = carry_in[ci];
-        else { const int64_t bi = v - lead; if (bi < (int64_t)nsamp) s = block[bi]; }
+        else {
+            const int64_t bi = v - lead;
+            if constexpr (chz_is_short<T>::value) { if (bi < (int64_t)nsamp) { const cf2 c = chz_cvt(block[bi]); s = make_float2(c.x, c.y); } }
+            else { if (bi < (int64_t)nsamp) s = block[bi]; }
+        }
     }
     return s;
 }
@@ -969,323 +1053,38 @@ __global__ __launch_bounds__(256) void chz_carry_kernel(const float2 *block, con
     for (uint32_t k = blockIdx.x * 256 + threadIdx.x; k < out_len; k += gridDim.x * 256)
         carry_out[k] = chz_carry_sample(block, carry_in, carry_len, nsamp, hist, consumed, k);
 }
+// the same behind a push of 16-bit I/Q: the carry it leaves is fc32 like any other
+__global__ __launch_bounds__(256) void chz_carry_short_kernel(const chz_sc16 *block, const float2 *carry_in, float2 *carry_out,
+                                                               uint32_t carry_len, uint32_t nsamp, uint32_t hist, uint32_t consumed,
+                                                               uint32_t out_len)
+{
+    for (uint32_t k = blockIdx.x * 256 + threadIdx.x; k < out_len; k += gridDim.x * 256)
+        carry_out[k] = chz_carry_sample(block, carry_in, carry_len, nsamp, hist, consumed, k);
+}
+// sc16 -> fc32, a sample per thread: in front of the fc32 filter bank where the checking modes (unfused form, amps_recc_debug_channelize)
+// and the AMPS_RECC_SHORT_PREPASS experiment take a 16-bit block
+__global__ __launch_bounds__(256) void chz_short_to_float_kernel(const chz_sc16 *in, float2 *out, uint32_t n)
+{
+    for (uint32_t k = blockIdx.x * 256 + threadIdx.x; k < n; k += gridDim.x * 256) { const cf2 c = chz_cvt(in[k]); out[k] = make_float2(c.x, c.y); }
+}
 
+// The kernel's body is recc_chz12_body.hip.h, once per sample type of the block (see there for why it is text, not a function).
 template <int P, int MODE, int DEC = CHZ_D>
 __global__ __launch_bounds__(768, 3) void chz12_kernel(ChzArgs a)
 {
-    static_assert(DEC == CHZ_D || DEC == CHZ_D768, "input samples per frame");
-    constexpr int M = CHZ_M, D = DEC, NB = CHZ_BATCH;
-    constexpr int SPS = 1536 / DEC;                                   // frames per Manchester symbol (20 ksym/s at 30.72 Msps)
-    constexpr bool IQ = MODE == CHZ12_IQ;
-    constexpr int SL = IQ ? AMPS_SLICER_ATAN_BOXCAR : MODE;
-    __shared__ cf2 buf[CHZ_SLOTS * NB * CHZ_FB];
-    const int tid = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lane = tid & 63;
-    // Role of a wave.  The hardware arbitrates VALU issue between the waves of a SIMD by priority, then by age: the fold role is
-    // pure VALU and would starve the two roles that alternate LDS round trips with short VALU bursts -- their latency chains
-    // would then run AFTER the fold instead of beside it.  So the latency-bound roles get the oldest waves and a higher priority
-    // (measured, ms per GiB, spec C / A: fold in the oldest waves and no priorities 0.440 / 0.592; priorities alone 0.390 /
-    // 0.505; order alone 0.395 / 0.502; both 0.387 / 0.503; round 2's two-role kernel on the same box 0.387 / 0.532).
-    const int role = 2 - (wave >> 2);                                   // 0 fold (waves 8..11), 1 pass 2 (4..7), 2 pass 3 + slicer (0..3)
-    // (round 6, under the priorities below: the other wave orders of the three roles -- fold | pass 2 | slicer, fold | slicer | pass 2,
-    // slicer | fold | pass 2, pass 2 | slicer | fold -- are within 1 % of this one: profiles/r06/prio_ab.txt)
-    // Which role runs pass 3.  Behind the cheap slicers (specs B, C: 7 instructions per channel pair and frame) it shares the
-    // slicer's waves; spec A's arctangent makes the slicer the longest chain of a time step (46 instructions per pair and
-    // frame), so there pass 3 moves to the pass-2 waves (spec A 0.537 -> 0.517 ms, spec C 0.399 -> 0.414 if it moved too).
-    // Spec D keeps pass 3 beside its slicer like specs B / C: either placement 0.413-0.421 ms, and its second channel pair sliced by
-    // the pass-2 role's waves (which idle half a step) 0.425-0.428 against 0.420-0.428 -- the kernel is bound by VALU throughput, not
-    // by one role's chain (profiles/EXPERIMENTS.md, round 4).
-    constexpr bool P3_WITH_P2 = !IQ && SL == AMPS_SLICER_ATAN_BOXCAR;   // (handing one of the slicer's two channel pairs to the pass-2 role instead: 0.518 against 0.494)
-    const int wf = wave & 3;                                            // frame of a half-batch this wave transforms (roles 1, 2)
-    // Pass 3 produces the bins n = i (mod 64) from the points i + 64 r: a handle that decodes one channel group only needs the grp_w
-    // residues of its group, so the four frames of a half-batch pack into 4 grp_w lanes: virtual lane v = 64 wf + lane transforms
-    // residue i = grp_r grp_w + v % grp_w of frame v / grp_w (grp_w = 64: lane i of wave wf, frame wf, as ever)
-    const uint32_t p3_v = 64u * (uint32_t)wf + (uint32_t)lane;
-    const bool p3_on = p3_v < 4u * a.grp_w;
-    const int p3_f = (int)(p3_v / a.grp_w) & 3, p3_i = (int)(a.grp_r * a.grp_w + p3_v % a.grp_w);
-    // Priorities.  Rounds 3-5: pass 3 + slicer 2, pass 2 1, fold 0 (six other triples within the noise at D = 512 under specs A / C).  Round 6,
-    // with the fold the longest chain of a step at either decimation (chz_timeline: 2575 of 3445 cycles at D = 768, the pass-2 role idle for
-    // 1650): the FOLD ABOVE PASS 2 -- pass 3 + slicer 2, fold 1, pass 2 0 -- is 1.8-3.3 % faster under spec D at D = 768, 1.4-5 % under
-    // B / C, 0.8-3.2 % at D = 512 (every triple with pass 2 lowest gains 2-3 %; profiles/r06/prio_ab.txt).  Spec A, whose pass-2 waves also
-    // run pass 3, loses 4-8 % by it and keeps the old order, as does the unfused form.
-    constexpr bool FOLD_OVER_P2 = !IQ && SL != AMPS_SLICER_ATAN_BOXCAR;
-    constexpr int PRIO_PASS2 = FOLD_OVER_P2 ? 0 : 1, PRIO_FOLD = FOLD_OVER_P2 ? 1 : 0;
-    if (role == 2) __builtin_amdgcn_s_setprio(2); else if (role == 1) __builtin_amdgcn_s_setprio(PRIO_PASS2); else __builtin_amdgcn_s_setprio(PRIO_FOLD);
-    // The next launch's carry (the last L - D + 4 D samples and the leftover) is a ~80 KB copy: every workgroup moves its slice
-    // here, a sample per thread of wave 0, instead of a kernel of its own behind this one (4.4 us + a launch gap per push).  Not
-    // in the fold waves: their vmcnt windows count their own loads only.
-    if (a.carry_out && wave == 0) {
-        const uint32_t per = (a.carry_out_len + gridDim.x - 1) / gridDim.x;
-        const uint32_t k0 = blockIdx.x * per;
-        const uint32_t k1 = k0 + per < a.carry_out_len ? k0 + per : a.carry_out_len;
-        for (uint32_t k = k0 + (uint32_t)lane; k < k1; k += 64)
-            a.carry_out[k] = chz_carry_sample(a.block, a.carry, a.carry_len, a.nsamp, a.hist, a.consumed, k);
-    }
-    const int64_t f0 = (int64_t)blockIdx.x * a.frames_per_wg;   // multiple of 64
-    if (f0 >= (int64_t)a.nframes) return;
-    int64_t f1 = f0 + a.frames_per_wg; if (f1 > (int64_t)a.nframes) f1 = a.nframes;
-    // the slicer state of every bin is rebuilt by two pre-roll half-batches; the first may reach behind the carry (zeros): it
-    // only primes the delay lines for the second, which is exact (the carry holds L - D + 4 D samples)
-    const int64_t fs = IQ ? f0 : f0 - CHZ_PREROLL;
-    const int nh = (int)((f1 - fs + NB - 1) / NB);              // half-batches of this workgroup
-    CHZ_TL_DECL;
-    const int nsteps = nh + 3;                                    // time step i: fold h = i, pass 2 h = i - 1, pass 3 h = i - 2, slicer h = i - 3
-
-    if (role == 0) {
-        // ------------------------------------------------------------------ fold role
-        const int t = tid & 255;
-        const int64_t lead0 = (int64_t)a.carry_len - (int64_t)a.hist;
-        const int64_t fl = ((int64_t)a.nsamp - D + lead0) / D;              // floor for the non-negative values the FAST path sees
-        const ChzIn in{ a.block, a.carry, (int64_t)a.hist, lead0, (int64_t)a.carry_len, (int64_t)a.nsamp, (uint32_t)(fl < 0 ? 0 : fl) };
-        cf2 coef[4][P / 2];
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-#pragma unroll
-            for (int q = 0; q < P; q += 2) coef[j][q / 2] = (cf2){ a.taps[t + 256 * j + q * M], a.taps[t + 256 * j + (q + 1) * M] };
-        cf2 tw1[3];                                               // pass 2's input twiddles of this thread's outputs k1 = 1..3
-#pragma unroll
-        for (int k1 = 1; k1 < 4; k1++) tw1[k1 - 1] = chz_twiddle((t >> 4) * k1, 64);
-        if constexpr (DEC == CHZ_D768) {
-        // ---- D = 768 (section "D = 768" above): twelve ring slots per branch, three new samples per branch and half-step
-        cf2 ring[4][CHZ768_R];
-        {
-            const int64_t vend = fs * D;                          // multiple of M (fs is a multiple of four)
-#pragma unroll
-            for (int jb = 0; jb < 4; jb++) {
-                const int64_t vlast = vend - M + (t + 256 * jb);
-#pragma unroll
-                for (int q = 0; q < P; q++) ring[jb][q] = in.generic_nb(vlast - (int64_t)M * (P - 1 - q));
-            }
-        }
-        chz768_prime(ring, in, fs, t);
-        constexpr int PERIOD = 4;                                 // half-steps until the ring is back where it started (three slots per half-step, twelve slots)
-        // half-step h loads frames of the half-steps h + 1 (from its third frame on) and h + 2: the fast loader is right once the
-        // first frame of half-step h + 1 lies inside the new block
-        // (The unfused form -- a checking mode -- runs every half-step as an edge step at this decimation: with its epilogue's row
-        // addresses the kernel does not fit 168 registers, and what the compiler chose to spill were ring slots with a load in flight
-        // -- it stores the stale value and reloads it behind the wait; tests/test_cpu_inflight_loads.py scans for exactly that.  One
-        // drained batch of twelve loads per half-step is a third of the fast loader's speed, and the arithmetic is the same.)
-        int h_edge = 0;
-        if (IQ || in.nsamp < D) h_edge = nsteps;
-        else if ((fs + NB) * D < in.lead) {
-            const int64_t need = (in.lead + D - 1) / D - (fs + NB);
-            h_edge = (int)((need + NB - 1) / NB);
-            h_edge = (h_edge + PERIOD - 1) / PERIOD * PERIOD;
-            if (h_edge > nsteps) h_edge = nsteps;
-        }
-        // the workgroup's descriptor starts at the first sample of its first FAST half-step (a few frames in front of the block, at the
-        // most, for the workgroup that takes over from the carry: nothing down there is ever addressed); a range beyond 2^31 bytes -- a
-        // 50 GB push -- keeps the bounds-checked loader
-        const int64_t base_s = (fs + (int64_t)NB * h_edge) * D - in.lead;
-        if ((int64_t)(nsteps - h_edge + 3) * NB * D * (int64_t)sizeof(float2) >= (1ll << 31)) h_edge = nsteps;
-        const chz_rsrc_t rsrc = chz_make_rsrc(in.block + base_s, (uint64_t)(in.nsamp - base_s) * sizeof(float2));
-        __syncthreads();                                          // all roles start together
-        auto half_step = [&](auto basec, auto edgec, int h) {
-            constexpr int BASE = decltype(basec)::value;
-            constexpr bool EDGE = decltype(edgec)::value;
-            CHZ_STAMP(h, 0);
-            if (__builtin_expect(h < nh, 1)) {
-                const int64_t F = fs + (int64_t)NB * h;
-                cf2 *dst = buf + (h & (CHZ_SLOTS - 1)) * NB * CHZ_FB;
-                chz768_ring_wait<BASE, 0>(ring);
-                CHZ_STAMP(h, 1);
-                if constexpr (EDGE) {
-                    chz768_fold2_ring<P, BASE, 0>(ring, coef, tw1, dst, t, [] {});
-                    chz768_fold2_ring<P, BASE, 2>(ring, coef, tw1, dst, t, [] {});
-                    chz768_loads_generic<BASE>(ring, in, F, t);
-                } else {
-                    const uint32_t so = (uint32_t)(h - h_edge) * (uint32_t)(NB * D * sizeof(float2));   // this half-step inside the workgroup's descriptor
-                    chz768_fold2_ring<P, BASE, 0>(ring, coef, tw1, dst, t, [&] { chz768_loads_a<BASE, true>(ring, in, F, t, rsrc, so); });
-                    chz768_ring_wait<BASE, 2>(ring);
-                    chz768_fold2_ring<P, BASE, 2>(ring, coef, tw1, dst, t, [&] { chz768_loads_b<BASE, true>(ring, in, F, t, rsrc, so); });
-                }
-                CHZ_STAMP(h, 2);
-            }
-            CHZ_STAMP(h, 3);
-            __syncthreads();
-            CHZ_STAMP(h, 4);
-        };
-        auto run_steps = [&](auto edgec, int hb, int he) __attribute__((always_inline)) {        // half-steps [hb, he); hb is a multiple of the ring's period
-            for (int h = hb; h < he; h += PERIOD) {
-                half_step(std::integral_constant<int, 0>{}, edgec, h);
-                if (h + 1 >= he) break;
-                half_step(std::integral_constant<int, 3>{}, edgec, h + 1);
-                if (h + 2 >= he) break;
-                half_step(std::integral_constant<int, 6>{}, edgec, h + 2);
-                if (h + 3 >= he) break;
-                half_step(std::integral_constant<int, 9>{}, edgec, h + 3);
-            }
-        };
-        run_steps(std::true_type{}, 0, h_edge);
-        if constexpr (!IQ) run_steps(std::false_type{}, h_edge, nsteps);
-        } else {
-        cf2 ring[4][P + 4];                                       // delay lines + the inputs of this and the next half-step
-        {
-            const int64_t vend = fs * D;                          // multiple of M (fs is even)
-#pragma unroll
-            for (int jb = 0; jb < 4; jb++) {
-                const int64_t vlast = vend - M + (t + 256 * jb);
-#pragma unroll
-                for (int q = 0; q < P; q++) ring[jb][q] = in.generic_nb(vlast - (int64_t)M * (P - 1 - q));
-            }
-        }
-        chz_load_half_ring<P, 0, P, false>(ring, in, fs, t);
-        chz_load_half_ring<P, 0, P + 2, false>(ring, in, fs + NB, t);
-        constexpr int PERIOD = (P + 4) / 2;                       // half-steps until the ring is back where it started (6)
-        static_assert(PERIOD == 6, "the unrolled loop below is written for P = 8");
-        // half-step h loads the frames of half-step h + 2: the fast loader is right once those lie inside the new block
-        int h_edge = 0;
-        if (in.nsamp < D) h_edge = nsteps;
-        else if ((fs + 2 * NB) * D < in.lead) {
-            const int64_t need = (in.lead + D - 1) / D - (fs + 2 * NB);           // frames from the first loaded one to the first inside the block
-            h_edge = (int)((need + NB - 1) / NB);
-            h_edge = (h_edge + PERIOD - 1) / PERIOD * PERIOD;
-            if (h_edge > nsteps) h_edge = nsteps;
-        }
-        // the workgroup's descriptor (chz_make_rsrc) starts at the first sample of its first FAST half-step; a range beyond 2^31 bytes keeps the bounds-checked loader
-        const int64_t base_s = (fs + (int64_t)NB * h_edge) * D - in.lead;
-        if ((int64_t)(nsteps - h_edge + 3) * NB * D * (int64_t)sizeof(float2) >= (1ll << 31)) h_edge = nsteps;
-        const chz_rsrc_t rsrc = chz_make_rsrc(in.block + base_s, (uint64_t)(in.nsamp - base_s) * sizeof(float2));
-        __syncthreads();                                          // all roles start together 
-        // one half-step = four frames: fold them, then load the frames of the half-step after next into the two slots that
-        // just died.  A load has eight frames (~3 us) to arrive: with four frames of lead the fold waves were the critical path
-        // (4 waves x 8 loads x 512 B = 16 KB in flight per CU do not cover the HBM latency under load).
-        // One half-step = four frames.  EDGE half-steps (the head of a launch, where the inputs still come from the carry of the
-        // previous push, and pushes shorter than a frame) load with ordinary, bounds-checked loads BEHIND the fold and drain them
-        // at once; all others prefetch with untracked asm loads (chz_load1_ring) that go into the ring slots as they die, as early
-        // in the step as possible: the oldest slot of branches 0, 1 is not read at all in this half-step; the oldest of branches
-        // 2, 3 and the second-oldest of branches 0, 1 are last read by the first tap block of frames 0 / 1; the second-oldest of
-        // branches 2, 3 by the first tap block of frame 2.  A load then has almost two time steps to land and is issued beside the
-        // other roles' VALU work.  The two kinds never meet inside one loop body: a control-flow join behind an untracked load
-        // invites the compiler to copy a register whose load is still in flight (it did; tests/test_cpu_inflight_loads.py scans
-        // the assembly for that).
-        auto half_step = [&](auto basec, auto edgec, int h) {
-            constexpr int BASE = decltype(basec)::value;
-            constexpr bool EDGE = decltype(edgec)::value;
-            CHZ_STAMP(h, 0);
-            if (__builtin_expect(h < nh, 1)) {
-                const int64_t F = fs + (int64_t)NB * h;
-                cf2 *dst = buf + (h & (CHZ_SLOTS - 1)) * NB * CHZ_FB;
-                chz_ring_wait<P, BASE>(ring);
-                CHZ_STAMP(h, 1);
-                if constexpr (EDGE) {
-                    chz_fold2_ring<P, BASE, 0>(ring, coef, tw1, dst, t, [] {});
-                    chz_fold2_ring<P, BASE, 2>(ring, coef, tw1, dst, t, [] {});
-                    chz_load_half_ring<P, BASE, P + 4, false>(ring, in, F + 2 * NB, t);
-                } else {
-                    const uint32_t so = (uint32_t)(h - h_edge) * (uint32_t)(NB * D * sizeof(float2));   // this half-step inside the workgroup's descriptor
-                    chz_load1_ring<P, BASE, P + 4, 0, true>(ring, in, F + 2 * NB, t, rsrc, so);
-                    chz_fold2_ring<P, BASE, 0>(ring, coef, tw1, dst, t, [&] {
-                        chz_load1_ring<P, BASE, P + 4, 1, true>(ring, in, F + 2 * NB, t, rsrc, so);
-                        chz_load1_ring<P, BASE, P + 4, 2, true>(ring, in, F + 2 * NB, t, rsrc, so);
-                    });
-                    chz_fold2_ring<P, BASE, 2>(ring, coef, tw1, dst, t, [&] { chz_load1_ring<P, BASE, P + 4, 3, true>(ring, in, F + 2 * NB, t, rsrc, so); });
-                }
-                CHZ_STAMP(h, 2);
-            }
-            CHZ_STAMP(h, 3);
-            __syncthreads();
-            CHZ_STAMP(h, 4);
-        };
-        auto run_steps = [&](auto edgec, int hb, int he) __attribute__((always_inline)) {        // half-steps [hb, he); hb is a multiple of the ring's period
-            for (int h = hb; h < he; h += PERIOD) {
-                half_step(std::integral_constant<int, 0>{}, edgec, h);
-                if (h + 1 >= he) break;
-                half_step(std::integral_constant<int, 2>{}, edgec, h + 1);
-                if (h + 2 >= he) break;
-                half_step(std::integral_constant<int, 4>{}, edgec, h + 2);
-                if (h + 3 >= he) break;
-                half_step(std::integral_constant<int, 6>{}, edgec, h + 3);
-                if (h + 4 >= he) break;
-                half_step(std::integral_constant<int, 8>{}, edgec, h + 4);
-                if (h + 5 >= he) break;
-                half_step(std::integral_constant<int, 10>{}, edgec, h + 5);
-            }
-        };
-        run_steps(std::true_type{}, 0, h_edge);
-        run_steps(std::false_type{}, h_edge, nsteps);
-        }
-        CHZ_TL_FLUSH;
-    } else if (role == 1) {
-        // ------------------------------------------------------------------ pass-2 role (+ pass 3 when P3_WITH_P2)
-        cf2 tw3[P3_WITH_P2 ? 15 : 1];                             // twiddles of the second radix-16 pass: W_1024^{r lane}
-        if constexpr (P3_WITH_P2) {
-#pragma unroll
-            for (int r = 1; r < 16; r++) tw3[r - 1] = chz_twiddle(r * p3_i, 1024);
-        }
-        __syncthreads();                                          // all roles start together 
-        {
-            for (int i = 0; i < nh + 3; i++) {
-                const int h = i - 1, h3 = i - 2;
-                CHZ_STAMP(i, 0);
-                if (h >= 0 && h < nh) chz_p2(buf + ((h & (CHZ_SLOTS - 1)) * NB + wf) * CHZ_FB, lane);
-                CHZ_STAMP(i, 1);
-                if constexpr (P3_WITH_P2) { if (h3 >= 0 && h3 < nh && p3_on) chz_p3(buf + ((h3 & (CHZ_SLOTS - 1)) * NB + p3_f) * CHZ_FB, tw3, p3_i); }
-                CHZ_STAMP(i, 3);
-                __syncthreads();
-                CHZ_STAMP(i, 4);
-            }
-        }
-        CHZ_TL_FLUSH;
-    } else {
-        // ------------------------------------------------------------------ pass-3 + slicer role
-        cf2 tw3[P3_WITH_P2 ? 1 : 15];                             // twiddles of the second radix-16 pass: W_1024^{r lane}
-        if constexpr (!P3_WITH_P2) {
-#pragma unroll
-            for (int r = 1; r < 16; r++) tw3[r - 1] = chz_twiddle(r * p3_i, 1024);
-        }
-        ChzSlicer<SL, IQ, SPS> slicer;
-        slicer.init(a, wf, lane);
-        __syncthreads();                                          // all roles start together 
-        {
-            // time step i slices half-batch hs = i - 3 and transforms h3 = i - 2.  STEADY steps -- 2 <= hs <= nh - 2: real frames, not
-            // the range's last half-batch, h3 inside the range -- run without any of the rare-case tests (ChzSlicer::half<1 / 2>);
-            // a 32-frame word completes when hs = 1 (mod 8), i.e. in the last step of every group of eight that starts at i = 5
-            auto step = [&](auto kindc, auto parc, int i) __attribute__((always_inline)) {
-                constexpr int KIND = decltype(kindc)::value, PAR = decltype(parc)::value;   // PAR = i & 1
-                const int hs = i - 3, h3 = i - 2;
-                CHZ_STAMP(i, 0);
-                if (KIND != 0 || (hs >= 0 && hs < nh)) slicer.template half<KIND, PAR>(a, buf, fs, f0, f1, hs);
-                CHZ_STAMP(i, 1);
-                if constexpr (!P3_WITH_P2) { if ((KIND != 0 || (h3 >= 0 && h3 < nh)) && p3_on) chz_p3(buf + ((h3 & (CHZ_SLOTS - 1)) * NB + p3_f) * CHZ_FB, tw3, p3_i); }
-                CHZ_STAMP(i, 3);
-                __syncthreads();
-                CHZ_STAMP(i, 4);
-            };
-            constexpr int I_FIRST = IQ ? 3 + 2 : 5;               // first steady step (hs = 2); ODD, and a group is eight steps: the parities below
-            static_assert((I_FIRST & 1) == 1, "parity of the steady groups");
-            const int i_last = nh + 1;                            // last steady step (hs = nh - 2, h3 = nh - 1)
-            using K0 = std::integral_constant<int, 0>; using K1 = std::integral_constant<int, 1>; using K2 = std::integral_constant<int, 2>;
-            using P0 = std::integral_constant<int, 0>; using P1 = std::integral_constant<int, 1>;
-            // Every step's parity is a compile-time constant, the edge steps' too: a run-time parity at either end would keep BOTH
-            // frame buffers of the slicer alive across the whole steady loop (24 VGPRs: measured as spills in the word step, +10 %).
-            int i = 0;
-            static_assert(I_FIRST == 5, "the five edge steps in front of the steady groups are written out");
-            if (i < nsteps) { step(K0{}, P0{}, i); i++; }
-            if (i < nsteps) { step(K0{}, P1{}, i); i++; }
-            if (i < nsteps) { step(K0{}, P0{}, i); i++; }
-            if (i < nsteps) { step(K0{}, P1{}, i); i++; }
-            if (i < nsteps) { step(K0{}, P0{}, i); i++; }
-            while (i + 7 <= i_last) {
-                // seven plain steps and the one that completes a word; two steps per loop round so that the time step's parity -- which
-                // of the slicer's two frame buffers is written -- is a compile-time constant (all eight as straight-line code: 15
-                // spilled VGPRs)
-#pragma unroll 1
-                for (int k = 0; k < 6; k += 2) { step(K1{}, P1{}, i + k); step(K1{}, P0{}, i + k + 1); }
-                step(K1{}, P1{}, i + 6);
-                step(K2{}, P0{}, i + 7);
-                i += 8;
-            }
-            // (i is odd here -- I_FIRST + 8 n -- or the range was shorter than the five edge steps and nothing is left)
-            while (i < nsteps) {
-                step(K0{}, P1{}, i); i++;
-                if (i >= nsteps) break;
-                step(K0{}, P0{}, i); i++;
-            }
-        }
-        CHZ_TL_FLUSH;
-    }
+    using T = float2;
+#define CHZ12_BODY_SHORT 0
+#include "recc_chz12_body.hip.h"
+#undef CHZ12_BODY_SHORT
+}
+// the fused filter bank on a block of 16-bit I/Q, read in place (a.block points at chz_sc16): 4 bytes per sample from HBM
+template <int P, int MODE, int DEC = CHZ_D>
+__global__ __launch_bounds__(768, 3) void chz12_short_kernel(ChzArgs a)
+{
+    using T = chz_sc16;
+#define CHZ12_BODY_SHORT 1
+#include "recc_chz12_body.hip.h"
+#undef CHZ12_BODY_SHORT
 }
 
 struct ChannelizerState {
@@ -1305,8 +1104,11 @@ struct ChannelizerState {
     uint64_t frames_done = 0;
     float2 *out = nullptr;          // [C][ld]
     uint64_t ld = 0;
-    float2 *stage = nullptr;        // device staging for host-resident wideband input
-    size_t stage_samples = 0;
+    void *stage = nullptr;          // device staging for host-resident wideband input, as the caller's samples (fc32 or sc16)
+    size_t stage_bytes = 0;
+    float2 *cvt = nullptr;          // an sc16 block expanded to fc32: the checking modes and the pre-pass experiment only
+    size_t cvt_samples = 0;
+    bool short_prepass = false;     // AMPS_RECC_SHORT_PREPASS=1 at create: sc16 blocks go through chz_short_to_float_kernel + the fc32 kernel
     StageFence stage_fence;
 };
 
@@ -1360,7 +1162,7 @@ inline int channelizer_reset(ChannelizerState &z, hipStream_t s)
 inline void channelizer_destroy(ChannelizerState &z)
 {
     z.stage_fence.destroy();
-    void *bufs[] = { z.taps, z.carry[0], z.carry[1], z.out, z.stage, z.bin2row };
+    void *bufs[] = { z.taps, z.carry[0], z.carry[1], z.out, z.stage, z.cvt, z.bin2row };
     for (void *p : bufs) if (p) (void)hipFree(p);
     z = ChannelizerState();
 }
@@ -1415,15 +1217,34 @@ inline int channelizer_create(ChannelizerState &z, const amps_recc_cfg_t &cfg, h
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
             z.target_wgs = (uint32_t)prop.multiProcessorCount;
     }
+    { const char *e = std::getenv("AMPS_RECC_SHORT_PREPASS"); z.short_prepass = e && e[0] == '1'; }
     z.enabled = true;
     (void)s;
     return 0;
 }
 
 typedef void (*chz_kernel_t)(ChzArgs);
-// the filter-bank instantiation for (input samples per frame, fused slicer or channel-major IQ out, slicer spec)
-inline chz_kernel_t chz12_kernel_for(int D, bool fused, int slicer)
+// the filter-bank instantiation for (input samples per frame, fused slicer or channel-major IQ out, slicer spec, sample type of the
+// block: fc32, or sc16 read in place -- fused form only)
+inline chz_kernel_t chz12_kernel_for(int D, bool fused, int slicer, bool sc16 = false)
 {
+    if (sc16) {
+        if (!fused) return nullptr;
+        if (D == CHZ_D768) {
+            switch (slicer) {
+            case AMPS_SLICER_PRODUCT: return chz12_short_kernel<8, AMPS_SLICER_PRODUCT, CHZ_D768>;
+            case AMPS_SLICER_SINE: return chz12_short_kernel<8, AMPS_SLICER_SINE, CHZ_D768>;
+            case AMPS_SLICER_EXACT: return chz12_short_kernel<8, AMPS_SLICER_EXACT, CHZ_D768>;
+            default: return chz12_short_kernel<8, AMPS_SLICER_ATAN_BOXCAR, CHZ_D768>;
+            }
+        }
+        switch (slicer) {
+        case AMPS_SLICER_PRODUCT: return chz12_short_kernel<8, AMPS_SLICER_PRODUCT>;
+        case AMPS_SLICER_SINE: return chz12_short_kernel<8, AMPS_SLICER_SINE>;
+        case AMPS_SLICER_EXACT: return chz12_short_kernel<8, AMPS_SLICER_EXACT>;
+        default: return chz12_short_kernel<8, AMPS_SLICER_ATAN_BOXCAR>;
+        }
+    }
     if (D == CHZ_D768) {
         if (!fused) return chz12_kernel<8, CHZ12_IQ, CHZ_D768>;
         switch (slicer) {
@@ -1446,24 +1267,28 @@ inline chz_kernel_t chz12_kernel_for(int D, bool fused, int slicer)
 //  fused = false: writes the channel-major block; *chan_iq / *ld / *nframes describe it (even number of frames).
 //  fused = true : runs discriminator + boxcar + slicer behind the FFT and writes only slicer bits into `gring`
 //                 at absolute sample index n_done.. ; consumes a multiple of 64 frames.
-inline int channelizer_run(ChannelizerState &z, const float2 *iq, size_t nsamp, int mem, hipStream_t s,
+//  sc16 = true : `iq` is interleaved 16-bit I/Q (4 bytes per sample), else fc32.  The fused form reads it in place
+//                 (chz12_short_kernel); the unfused form and the pre-pass experiment expand it to fc32 first.
+inline int channelizer_run(ChannelizerState &z, const void *iq, size_t nsamp, int mem, hipStream_t s,
                            const float2 **chan_iq, uint64_t *ld, uint32_t *nframes_out,
                            bool fused = false, uint64_t *gring = nullptr, uint32_t ring_words = 0, uint64_t n_done = 0,
-                           int slicer = AMPS_SLICER_ATAN_BOXCAR, void (*after_main)(void *) = nullptr, void *after_ctx = nullptr)
+                           int slicer = AMPS_SLICER_ATAN_BOXCAR, void (*after_main)(void *) = nullptr, void *after_ctx = nullptr,
+                           bool sc16 = false)
 {
     if (!z.enabled) return -ENOSYS;
     if (!fused && z.groups > 1) return -ENOSYS;                   // channel groups exist in the fused form only
-    const float2 *d = iq;
+    const void *d = iq;
+    const size_t sample_bytes = sc16 ? sizeof(chz_sc16) : sizeof(float2);
     if (mem == AMPS_MEM_HOST) {
         if (int rc = z.stage_fence.wait()) return rc;             // the previous push may still be reading the staging buffer
-        if (z.stage_samples < nsamp) {
+        if (z.stage_bytes < sample_bytes * nsamp) {
             if (z.stage) (void)hipFree(z.stage);
-            z.stage = nullptr; z.stage_samples = 0;
-            if (hipMalloc((void **)&z.stage, sizeof(float2) * nsamp) != hipSuccess) return -ENOMEM;
-            z.stage_samples = nsamp;
+            z.stage = nullptr; z.stage_bytes = 0;
+            if (hipMalloc((void **)&z.stage, sample_bytes * nsamp) != hipSuccess) return -ENOMEM;
+            z.stage_bytes = sample_bytes * nsamp;
         }
         // synchronous: the caller may reuse its buffer as soon as the push returns (see amps_recc_push_iq)
-        if (hipMemcpy(z.stage, iq, sizeof(float2) * nsamp, hipMemcpyHostToDevice) != hipSuccess) return -EIO;
+        if (hipMemcpy(z.stage, iq, sample_bytes * nsamp, hipMemcpyHostToDevice) != hipSuccess) return -EIO;
         d = z.stage;
     }
     if (!fused && !z.out && hipMalloc((void **)&z.out, sizeof(float2) * (size_t)z.C * z.ld) != hipSuccess) return -ENOMEM;
@@ -1474,6 +1299,20 @@ inline int channelizer_run(ChannelizerState &z, const float2 *iq, size_t nsamp, 
     // frame phase 0 of 4 at D = 768), and in the fused form a multiple of 64 (whole words of the RECC bit ring); the rest waits in the carry
     const uint32_t nframes = (uint32_t)(avail / (uint32_t)z.D) & (fused ? ~63u : z.D == CHZ_D ? ~1u : ~3u);
     if (nframes > z.max_frames) return -E2BIG;
+    if (sc16 && (!fused || z.short_prepass)) {
+        // the block as fc32 in a buffer of its own, then everything as for an fc32 block.  Stream order keeps the buffer safe: the
+        // kernels of the previous push that read it run before this conversion
+        if (z.cvt_samples < nsamp) {
+            if (z.cvt) { if (hipStreamSynchronize(s) != hipSuccess) return -EIO; (void)hipFree(z.cvt); }
+            z.cvt = nullptr; z.cvt_samples = 0;
+            if (hipMalloc((void **)&z.cvt, sizeof(float2) * nsamp) != hipSuccess) return -ENOMEM;
+            z.cvt_samples = nsamp;
+        }
+        const uint32_t blocks = (uint32_t)std::min<size_t>((nsamp + 255) / 256, 65536);
+        hipLaunchKernelGGL(chz_short_to_float_kernel, dim3(blocks), dim3(256), 0, s, (const chz_sc16 *)d, z.cvt, (uint32_t)nsamp);
+        d = z.cvt;
+        sc16 = false;
+    }
 #ifdef CHZ_TIMELINE
     unsigned long long *a_tl_last = nullptr;
 #endif
@@ -1482,7 +1321,7 @@ inline int channelizer_run(ChannelizerState &z, const float2 *iq, size_t nsamp, 
     bool carry_in_kernel = false;
     if (nframes) {
         ChzArgs a{};
-        a.block = d; a.carry = z.carry[z.carry_cur]; a.taps = z.taps; a.out = z.out; a.ld = z.ld;
+        a.block = (const float2 *)d; a.carry = z.carry[z.carry_cur]; a.taps = z.taps; a.out = z.out; a.ld = z.ld;
         a.carry_len = z.carry_len; a.nsamp = (uint32_t)nsamp; a.nframes = nframes; a.hist = hist;
         // one resident round of 768-thread workgroups, one per CU; each refills its delay lines and re-runs eight pre-roll
         // frames when fused, so fewer, longer runs are cheaper
@@ -1504,7 +1343,7 @@ inline int channelizer_run(ChannelizerState &z, const float2 *iq, size_t nsamp, 
         a.tl = tl_dev;
         a_tl_last = tl_dev;
 #endif
-        hipLaunchKernelGGL(chz12_kernel_for(z.D, fused, slicer), g12, b12, 0, s, a);
+        hipLaunchKernelGGL(chz12_kernel_for(z.D, fused, slicer, sc16), g12, b12, 0, s, a);
     }
     if (after_main) after_main(after_ctx);                            // timing: the span ends behind the filter-bank kernel, before the carry copy
 #ifdef CHZ_TIMELINE
@@ -1514,9 +1353,12 @@ inline int channelizer_run(ChannelizerState &z, const float2 *iq, size_t nsamp, 
             if (FILE *f = std::fopen(path, "wb")) { std::fwrite(tl.data(), 8, tl.size(), f); std::fclose(f); }
     }
 #endif
-    if (!carry_in_kernel)
-        hipLaunchKernelGGL(chz_carry_kernel, dim3((hist + new_left + 255) / 256), dim3(256), 0, s, d, z.carry[z.carry_cur],
-                           z.carry[z.carry_cur ^ 1], z.carry_len, (uint32_t)nsamp, hist, consumed, hist + new_left);
+    if (!carry_in_kernel) {
+        if (sc16) hipLaunchKernelGGL(chz_carry_short_kernel, dim3((hist + new_left + 255) / 256), dim3(256), 0, s, (const chz_sc16 *)d, z.carry[z.carry_cur],
+                                     z.carry[z.carry_cur ^ 1], z.carry_len, (uint32_t)nsamp, hist, consumed, hist + new_left);
+        else hipLaunchKernelGGL(chz_carry_kernel, dim3((hist + new_left + 255) / 256), dim3(256), 0, s, (const float2 *)d, z.carry[z.carry_cur],
+                                z.carry[z.carry_cur ^ 1], z.carry_len, (uint32_t)nsamp, hist, consumed, hist + new_left);
+    }
     if (hipGetLastError() != hipSuccess) return -EIO;
     if (mem == AMPS_MEM_HOST) { if (int rc = z.stage_fence.arm(s)) return rc; }
     z.carry_cur ^= 1;

@@ -6,7 +6,9 @@
 //   recctest bank <file.u8>  [chunk] [C]  C channels in ONE gr::amps::recc_bank block: channel c = the symbol file delayed by 37 c symbols;
 //                                      every line is prefixed with the channel the burst came from
 //   recctest wide <file.fc32> [chunk] [slicer] [decim]  one 30.72 Msps wideband capture -> gr::amps::recc_wideband (832 channels from bin 96); every
-//                                      burst's lines are prefixed with its channel; decoded through the "bursts" port
+//                                      burst's lines are prefixed with its channel; decoded through the "bursts" port.  A file whose name ends
+//                                      in .sc16 (or a sixth argument `sc16`) is read as interleaved 16-bit I/Q and goes through the block's
+//                                      16-bit input
 //   recctest widerank <file.fc32> <chunk> <idfile> <nranks> <rank> [mode]   ONE rank of the same band over `nranks` processes (2, 4 or 8; one per GPU of a
 //                                      node): gr::amps::recc_wideband::make(832, 96, -1, nranks, rank) + set_rccl -- rank 0 owns the capture and the
 //                                      library distributes it (mode 0 = ncclBroadcast, 1 = scatter + all-gather); the other ranks' items only pace
@@ -117,7 +119,11 @@ int main(int argc, char **argv)
             const bool ranks = mode == "widerank";
             if (ranks && argc < 7) { std::fprintf(stderr, "usage: %s widerank <file> <chunk> <idfile> <nranks> <rank> [mode]\n", argv[0]); return 2; }
             const int nranks = ranks ? std::atoi(argv[5]) : 0, rank = ranks ? std::atoi(argv[6]) : 0;
-            auto src = ranks ? gr::amps::recc_wideband::make(832, 96, -1, nranks, rank) : gr::amps::recc_wideband::make(832, 96, argc > 4 ? std::atoi(argv[4]) : -1, 0, 0, argc > 5 ? std::atoi(argv[5]) : 0);
+            const std::string path = argv[2];
+            const bool sc16 = !ranks && ((path.size() > 5 && path.compare(path.size() - 5, 5, ".sc16") == 0) || (argc > 6 && std::string(argv[6]) == "sc16"));
+            const size_t item = sc16 ? 4 : 8;                         // bytes per wideband sample
+            auto src = ranks ? gr::amps::recc_wideband::make(832, 96, -1, nranks, rank)
+                             : gr::amps::recc_wideband::make(832, 96, argc > 4 ? std::atoi(argv[4]) : -1, 0, 0, argc > 5 ? std::atoi(argv[5]) : 0, sc16);
             if (ranks) {
                 // the control plane is the application's: here, a file
                 std::string id;
@@ -152,12 +158,13 @@ int main(int argc, char **argv)
             auto dm = std::make_shared<demux>();
             dm->dec = dec;
             gr::msg_connect(src, "bursts", dm, "bursts");
-            std::vector<char> tail((size_t)64 * 768 * 8, 0);          // silence: flushes the frames the fused form holds back (64 frames of at most 768 samples)
+            std::vector<char> tail((size_t)64 * 768 * item, 0);       // silence: flushes the frames the fused form holds back (64 frames of at most 768 samples)
+            data.resize(data.size() / item * item);
             data.insert(data.end(), tail.begin(), tail.end());
-            const size_t ns = data.size() / 8;
+            const size_t ns = data.size() / item;
             for (size_t off = 0; off < ns; off += (size_t)chunk) {
                 int n = (int)std::min<size_t>((size_t)chunk, ns - off);
-                gr_vector_const_void_star ins = { data.data() + 8 * off };
+                gr_vector_const_void_star ins = { data.data() + item * off };
                 if (src->work(n, ins, outs) != 0) return 1;
             }
             src->stop();                                              // as the scheduler does: the root announces its end of stream, the others join until they see it

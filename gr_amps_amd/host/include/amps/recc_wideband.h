@@ -22,7 +22,11 @@ public:
     //         process per GPU, every one fed the same stream) decodes interleaved channel group `group` only -- cfg.wideband_groups of
     //         include/amps_recc.h; channel numbers on the ports stay whole-band numbers.
     // decim: input samples per filter-bank frame, 512 (60 ksps per channel) or 768 (40 ksps); 0 = amps_recc_default_wideband_decim()
-    static sptr make(int n_channels = 832, int first_bin = 96, int slicer = -1, int groups = 0, int group = 0, int decim = 0);
+    // short_input: the input item is two shorts -- interleaved 16-bit I/Q, what a UHD source set to sc16 or an "interleaved short" file
+    //         source delivers -- instead of one gr_complex; the block pushes it as it is (amps_recc_push_wideband_short: 4 bytes per
+    //         sample to the device, no float copy on the host).  Scale does not matter to any slicer spec.  set_rccl is refused on such
+    //         a block: the distributed seam carries fc32.
+    static sptr make(int n_channels = 832, int first_bin = 96, int slicer = -1, int groups = 0, int group = 0, int decim = 0, bool short_input = false);
     // Let ONE rank own the stream: after this call (a collective over all `nranks` blocks; `id` = the 128 bytes one of them got from
     // rccl_unique_id(), carried between the processes by the application) work() distributes rank `root`'s input over xGMI with RCCL
     // inside amps_recc_push_wideband_dist (mode 0 = flat broadcast, 1 = scatter + all-gather: AMPS_RECC_DIST_*).  The other ranks'

@@ -20,11 +20,12 @@ class recc_wideband_impl : public recc_wideband {
     int d_root = 0, d_rank = 0, d_mode = AMPS_RECC_DIST_BROADCAST;
     unsigned long long d_stream_samples = 0, d_paced_items = 0;   // non-root ranks: samples the root has distributed / items this rank's pacing input has offered
     bool d_ended = false;                          // the root's end of stream has been sent (root) / seen (the others)
+    bool d_short = false;                          // items are two shorts (interleaved 16-bit I/Q, "sc16"): amps_recc_push_wideband_short
 
 public:
-    recc_wideband_impl(int C, int first_bin, int slicer, int groups, int group, int decim)
-        : gr::sync_block("recc_wideband", gr::io_signature::make(1, 1, 2 * sizeof(float)), gr::io_signature::make(0, 0, 0)), d_handle(nullptr),
-          d_recs(kMaxRecs), d_bursts((size_t)kMaxRecs * AMPS_RECC_CAPTURE_SYMS)
+    recc_wideband_impl(int C, int first_bin, int slicer, int groups, int group, int decim, bool short_input)
+        : gr::sync_block("recc_wideband", gr::io_signature::make(1, 1, short_input ? 2 * sizeof(short) : 2 * sizeof(float)), gr::io_signature::make(0, 0, 0)),
+          d_handle(nullptr), d_recs(kMaxRecs), d_bursts((size_t)kMaxRecs * AMPS_RECC_CAPTURE_SYMS), d_short(short_input)
     {
         amps_recc_cfg_t cfg = {};
         cfg.struct_size = sizeof(cfg);
@@ -50,6 +51,8 @@ public:
 
     void set_rccl(const std::string &id, int nranks, int rank, int root, int mode)
     {
+        // (the blocks RCCL carries are fc32: amps_recc_push_wideband_dist has no 16-bit form)
+        if (d_short) throw std::runtime_error("amps::recc_wideband: set_rccl is not available on a block with 16-bit input; distribute an fc32 stream");
         if (id.size() != AMPS_RECC_RCCL_ID_BYTES) throw std::runtime_error("amps::recc_wideband: the RCCL id is 128 bytes");
         if (mode != AMPS_RECC_DIST_BROADCAST && mode != AMPS_RECC_DIST_SCATTER_ALLGATHER) throw std::runtime_error("amps::recc_wideband: unknown distribution mode");
         int rc = amps_recc_rccl_init(d_handle, (const uint8_t *)id.data(), nranks, rank);
@@ -58,7 +61,7 @@ public:
     }
 
     // one block through the seam (alone, or as this rank's part of one collective) + its records out on the ports; false = stop the flow graph
-    bool push_and_publish(const float *in, size_t n)
+    bool push_and_publish(const void *in, size_t n)
     {
         int rc;
         size_t pushed = n;
@@ -67,9 +70,10 @@ public:
             // the root's n counts -- it travels in the header of the collective (the schedulers of the ranks' flow graphs do not agree on
             // noutput_items)
             const bool root = d_rank == d_root;
-            rc = amps_recc_push_wideband_dist(d_handle, root ? in : nullptr, root ? n : 0, AMPS_MEM_HOST, d_root, d_mode, &pushed);
+            rc = amps_recc_push_wideband_dist(d_handle, root ? (const float *)in : nullptr, root ? n : 0, AMPS_MEM_HOST, d_root, d_mode, &pushed);
             d_stream_samples += pushed;
-        } else rc = amps_recc_push_wideband(d_handle, in, n, AMPS_MEM_HOST);
+        } else if (d_short) rc = amps_recc_push_wideband_short(d_handle, (const int16_t *)in, n, AMPS_MEM_HOST);
+        else rc = amps_recc_push_wideband(d_handle, (const float *)in, n, AMPS_MEM_HOST);
         if (rc == -ENODATA) { d_ended = true; return false; }   // the root's stream has ended: a clean WORK_DONE, the communicator is left alone
         if (rc != 0) { std::fprintf(stderr, "amps::recc_wideband: %s\n", amps_recc_strerror(rc)); return leave(); }
         size_t nrec = 0;
@@ -106,7 +110,8 @@ public:
 
     int work(int noutput_items, gr_vector_const_void_star &input_items, gr_vector_void_star &)
     {
-        const float *in = (const float *)input_items[0];
+        const char *in = (const char *)input_items[0];
+        const size_t item = d_short ? 2 * sizeof(short) : 2 * sizeof(float);
         if (d_bcast && d_rank != d_root) {
             // A non-root rank: its items are pacing only.  The ranks stay in step by STREAM POSITION, not by call or item counts (which
             // the schedulers of different processes do not share): this rank joins collectives -- each of whatever size the root
@@ -121,7 +126,7 @@ public:
         while (done < noutput_items) {
             int n = noutput_items - done;
             if (n > kMaxPush) n = kMaxPush;
-            if (!push_and_publish(in + 2 * (size_t)done, (size_t)n)) return WORK_DONE;
+            if (!push_and_publish(in + item * (size_t)done, (size_t)n)) return WORK_DONE;
             done += n;
         }
         consume_each(noutput_items);
@@ -129,9 +134,9 @@ public:
     }
 };
 
-recc_wideband::sptr recc_wideband::make(int n_channels, int first_bin, int slicer, int groups, int group, int decim)
+recc_wideband::sptr recc_wideband::make(int n_channels, int first_bin, int slicer, int groups, int group, int decim, bool short_input)
 {
-    return gnuradio::get_initial_sptr(new recc_wideband_impl(n_channels, first_bin, slicer, groups, group, decim));
+    return gnuradio::get_initial_sptr(new recc_wideband_impl(n_channels, first_bin, slicer, groups, group, decim, short_input));
 }
 
 std::string recc_wideband::rccl_unique_id()

@@ -42,7 +42,8 @@ extern "C" {
 #define AMPS_RECC_ABI_VERSION 4   /* 2: amps_recc_cfg_t gained wideband_groups / wideband_group; 3: default slicer = spec D, captures track the bit
                                      clock unless AMPS_RECC_FLAG_FIXED_TIMING, amps_recc_rccl_* / _push_wideband_bcast / _drain_gather / _debug_exact_slice added;
                                      4: amps_recc_push_wideband_dist (scatter + all-gather), amps_recc_rccl_info / _abort / _set_timeout; rccl_init checks the
-                                     group split and allocates; every collective entry is bounded and carries a status word */
+                                     group split and allocates; every collective entry is bounded and carries a status word;
+                                     (still 4, one entry point added and nothing changed: amps_recc_push_wideband_short, 16-bit I/Q through the wideband seam) */
 
 /* protocol constants of the reference */
 #define AMPS_RECC_TRIGGER_SYMS 74   /* lib/recc_impl.cc:76-77: 37 bits x 2 Manchester symbols   */
@@ -238,6 +239,17 @@ int amps_recc_push_iq(amps_recc_t *h, const float *iq, size_t ld, size_t nsamp, 
 /* channelizer seam: one wideband interleaved fc32 stream (fs = M * 30 kHz) -> polyphase
  * channelizer -> the same fused path on every active channel.  nsamp wideband samples. */
 int amps_recc_push_wideband(amps_recc_t *h, const float *iq, size_t nsamp, int mem);
+
+/* like amps_recc_push_wideband, the block as interleaved 16-bit I/Q ("sc16": what converters, the wire formats of USRP-class devices
+ * and wideband capture files deliver): sample n = ((float)iq[2n], (float)iq[2n+1]).
+ * By definition this is amps_recc_push_wideband on the block converted with a plain int16 -> float conversion, no scaling (every
+ * int16 is exact in fp32 and a power-of-two scale changes no decision of any slicer spec): same stream, same carry, same records,
+ * same error codes (-EINVAL, -ENOSYS on a handle without the wideband seam, -E2BIG, -ESTALE), same ownership rules for host and
+ * device blocks, nsamp == 0 returns 0.  The two calls may be mixed freely on one handle, push by push.  A device block need only be
+ * 4-byte aligned (a slice that starts at an odd sample is legal).  The fused filter bank reads the 16-bit block in place, 4 bytes
+ * per sample from the host and from HBM; no fc32 copy of it exists (the checking form AMPS_RECC_FLAG_UNFUSED_WIDEBAND expands it first).
+ * Not offered in 16 bits: amps_recc_push_wideband_dist / _bcast (the blocks RCCL carries stay fc32) and the IQ and translate seams. */
+int amps_recc_push_wideband_short(amps_recc_t *h, const int16_t *iq, size_t nsamp, int mem);
 
 /* translate seam: the channel filter the reference's test flow graph wires in front of the
  * chain -- freq_xlating_fir_filter_ccc(decim, firdes.low_pass(gain, rate, cutoff, width), center, rate),
