@@ -24,6 +24,8 @@ FLAG_KEEP_BURSTS = 32
 FLAG_SLICER_ATAN = 64
 FLAG_SLICER_EXACT = 128
 FLAG_FIXED_TIMING = 256
+FLAG_CHANNEL_POWER = 512
+POWER_STRIDE = 256                       # AMPS_RECC_POWER_STRIDE: channel-rate samples between two power snapshots
 
 # slicer names accepted by Recc(slicer=...): numeric spec of include/amps_recc_numerics.h -> cfg flag
 _SLICER_FLAGS = {None: 0, "default": 0, "atan": FLAG_SLICER_ATAN, 0: FLAG_SLICER_ATAN, "A": FLAG_SLICER_ATAN,
@@ -112,7 +114,9 @@ EXPORTS = (
     "amps_recc_rccl_unique_id", "amps_recc_rccl_init", "amps_recc_push_wideband_bcast", "amps_recc_drain_gather",
     "amps_recc_push_wideband_dist", "amps_recc_rccl_info", "amps_recc_rccl_abort", "amps_recc_rccl_set_timeout",
     "amps_recc_debug_slicer_bits", "amps_recc_push_wideband_short",
+    "amps_recc_channel_power", "amps_recc_burst_power", "amps_recc_power_ring_snaps",
 )
+_POWER = ("amps_recc_channel_power", "amps_recc_burst_power", "amps_recc_power_ring_snaps")
 _NEW_IN_ABI4 = ("amps_recc_push_wideband_dist", "amps_recc_rccl_info", "amps_recc_rccl_abort", "amps_recc_rccl_set_timeout")
 DIST_BROADCAST, DIST_SCATTER_ALLGATHER = 0, 1
 DIST_MODES = {"broadcast": DIST_BROADCAST, "scatter_allgather": DIST_SCATTER_ALLGATHER, 0: 0, 1: 1}
@@ -181,6 +185,10 @@ def load():
     L.amps_recc_debug_channelize.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     if hasattr(L, "amps_recc_debug_slicer_bits"):
         L.amps_recc_debug_slicer_bits.argtypes = [vp, C.c_uint64, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    if hasattr(L, "amps_recc_channel_power"):         # absent only from A/B builds of earlier revisions (AMPS_RECC_LIB)
+        L.amps_recc_channel_power.argtypes = [vp, C.c_uint64, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+        L.amps_recc_burst_power.argtypes = [vp, vp, C.c_size_t, vp, vp]
+        L.amps_recc_power_ring_snaps.argtypes = [vp]
     L.amps_recc_reply_words.argtypes = [vp, C.POINTER(Reply)]
     L.amps_recc_set_xlate.argtypes = [vp, C.POINTER(XlateCfg)]
     L.amps_recc_push_raw.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int]
@@ -190,10 +198,10 @@ def load():
     for name in EXPORTS:
         if name in ("amps_recc_default_slicer", "amps_recc_default_wideband_decim", "amps_recc_debug_exact_slice", "amps_recc_rccl_unique_id", "amps_recc_rccl_init",
                     "amps_recc_push_wideband_bcast", "amps_recc_drain_gather", "amps_recc_debug_slicer_bits",
-                    "amps_recc_push_wideband_short") + _NEW_IN_ABI4 and not hasattr(L, name):
+                    "amps_recc_push_wideband_short") + _NEW_IN_ABI4 + _POWER and not hasattr(L, name):
             continue
         if name not in ("amps_recc_strerror", "amps_recc_burst_size", "amps_recc_destroy"):   # every other entry point returns int
-            getattr(L, name).restype = C.c_int
+            getattr(L, name).restype = C.c_uint32 if name == "amps_recc_power_ring_snaps" else C.c_int
     if L.amps_recc_burst_size() != BURST_DTYPE.itemsize:
         raise ImportError("amps_recc_burst_t layout mismatch between binding and library")
     _lib = L
@@ -227,7 +235,7 @@ class Recc:
 
     def __init__(self, n_channels=1, sps=None, max_samples=0, max_bursts=1024, device=-1, time_kernels=False,
                  stream=None, wideband=None, majority=False, unfused_wideband=False, sync_tolerance=0, slicer="default",
-                 sync_torch=True, keep_bursts=False, fixed_timing=False):
+                 sync_torch=True, keep_bursts=False, fixed_timing=False, channel_power=False):
         L = load()
         if isinstance(slicer, bool) or slicer not in _SLICER_FLAGS:        # a typo must not run a different numeric spec silently
             raise ValueError("slicer must be one of %r" % sorted(map(str, _SLICER_FLAGS)))
@@ -253,7 +261,8 @@ class Recc:
         cfg.flags = ((FLAG_TIME_KERNELS if time_kernels else 0) | (FLAG_MAJORITY if majority else 0)
                      | (FLAG_UNFUSED_WIDEBAND if unfused_wideband else 0)
                      | _SLICER_FLAGS[slicer]
-                     | (FLAG_KEEP_BURSTS if keep_bursts else 0) | (FLAG_FIXED_TIMING if fixed_timing else 0))
+                     | (FLAG_KEEP_BURSTS if keep_bursts else 0) | (FLAG_FIXED_TIMING if fixed_timing else 0)
+                     | (FLAG_CHANNEL_POWER if channel_power else 0))
         cfg.stream = stream
         cfg.sync_tolerance = sync_tolerance
         if wideband:
@@ -265,6 +274,7 @@ class Recc:
             cfg.wideband_group = wideband.get("group", 0)
         self.n_channels, self.sps, self.max_bursts, self.max_samples = n_channels, sps, max_bursts, max_samples
         self.decim = int(wideband["decim"]) if wideband else None
+        self._origin = 0
         self._h = C.c_void_p()
         rc = L.amps_recc_create(C.byref(self._h), C.byref(cfg))
         if rc != 0:
@@ -288,6 +298,7 @@ class Recc:
         rc = load().amps_recc_reset(self._h)
         if rc:
             raise AmpsError(rc, "amps_recc_reset")
+        self._origin = 0
 
     # ---- seam (i): recc::work ----
     def push_symbols(self, syms, n=None):
@@ -589,6 +600,7 @@ class Recc:
         rc = load().amps_recc_set_origin(self._h, first_sample)
         if rc:
             raise AmpsError(rc, "amps_recc_set_origin")
+        self._origin = int(first_sample)
 
     def drain_begin(self):
         """Close the current record list without waiting; pushes issued after this append to a second list."""
@@ -632,6 +644,42 @@ class Recc:
             if rc:
                 raise AmpsError(rc, "amps_recc_debug_slicer_bits")
         return out, produced.value
+
+    # ---- received power of the wideband seam (handles created with channel_power=True)
+    @property
+    def power_ring_snaps(self):
+        """snapshots the handle keeps per row (the slicer-bit ring's span / 256); 0 without channel_power"""
+        return int(load().amps_recc_power_ring_snaps(self._h))
+
+    def channel_power(self, first=None, n=None):
+        """(float32 [rows][n], first): P[row][first + i] = |filter-bank output|^2 of the frame at channel-rate sample 256 (first + i),
+        linear and unscaled, once the pushes so far have finished (amps_recc_channel_power).  Default: everything currently held;
+        `first` alone: from there to the newest snapshot."""
+        L = load()
+        rows, prod = C.c_uint32(0), C.c_uint64(0)
+        rc = L.amps_recc_channel_power(self._h, 0, 0, None, 0, C.byref(rows), C.byref(prod))
+        if rc:
+            raise AmpsError(rc, "amps_recc_channel_power")
+        if first is None:
+            first = max(-(-self._origin // POWER_STRIDE), prod.value - self.power_ring_snaps)      # the held window's first snapshot
+        if n is None:
+            n = max(0, prod.value - first)
+        out = np.zeros((rows.value, n), np.float32)
+        if n:
+            rc = L.amps_recc_channel_power(self._h, first, n, _hostptr(out), n, None, None)
+            if rc:
+                raise AmpsError(rc, "amps_recc_channel_power")
+        return out, int(first)
+
+    def burst_power(self, records):
+        """(mean float32 [n], count uint32 [n]) for records as drain() returns them: the mean power snapshot of each record's channel over
+        its capture and the number of snapshots averaged, (0.0, 0) where the ring no longer (or not yet) holds them (amps_recc_burst_power)"""
+        recs = np.ascontiguousarray(records, BURST_DTYPE).reshape(-1)
+        mean, cnt = np.zeros(recs.size, np.float32), np.zeros(recs.size, np.uint32)
+        rc = load().amps_recc_burst_power(self._h, _hostptr(recs), recs.size, _hostptr(mean), _hostptr(cnt))
+        if rc:
+            raise AmpsError(rc, "amps_recc_burst_power")
+        return mean, cnt
 
     def set_timing(self, mode):
         """mode: "off" | "all" | "dominant" (only the streaming kernel of the seam in use is bracketed by HIP events) |

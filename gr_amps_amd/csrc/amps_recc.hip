@@ -17,6 +17,7 @@
 #include "recc_resolve.hip.h"
 #include "recc_symbols.hip.h"
 #include "recc_channelizer.hip.h"
+#include "recc_power.hip.h"
 #include "recc_rccl.hip.h"
 #include "recc_xlate.hip.h"
 #include "recc_bits.hip.h"
@@ -91,6 +92,12 @@ struct amps_recc {
 
     // ---- channelizer seam ----
     ChannelizerState chz;
+
+    // ---- received power (AMPS_RECC_FLAG_CHANNEL_POWER; the ring itself is chz.pow_ring) ----
+    std::vector<int32_t> chan2row;            // whole-band channel number -> ring row, -1 for a channel this handle does not decode
+    amps::ChzBurstQuery *pq_dev = nullptr;    // amps_recc_burst_power scratch (grow-only)
+    uint2 *pq_out = nullptr;
+    size_t pq_cap = 0;
 
     // ---- translate seam (recctest.grc channel filter) ----
     XlateState xl;
@@ -294,6 +301,7 @@ int reset_state(amps_recc *h)
     h->r_prev = 0;
     int rc = channelizer_reset(h->chz, s);
     if (rc) return rc;
+    if (h->chz.pow_ring) HIP_TRY(hipMemsetAsync(h->chz.pow_ring, 0, sizeof(float) * (size_t)h->chz.pow_slots * h->C, s));   // n_done = 0: no snapshot is held
     rc = xlate_reset(h->xl, s);
     if (rc) return rc;
     rc = ref_reset(h->ref, s);
@@ -598,6 +606,8 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
         if (sl & (sl - 1)) return -EINVAL;                         // at most one slicer spec
     }
     if (cfg->n_channels >= (1u << (64 - CAPQ_POS_BITS))) return -EINVAL;
+    // received power exists where the fused filter bank runs: the snapshot kernel re-reads that launch's block and carry
+    if ((cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER) && (!cfg->wideband_channels || (cfg->flags & AMPS_RECC_FLAG_UNFUSED_WIDEBAND))) return -EINVAL;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return -ENODEV;
     int dev = cfg->device;
@@ -696,6 +706,12 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
     step("IQ seam buffers allocated");
     if (!rc && cfg->wideband_channels) rc = channelizer_create(h->chz, *cfg, h->stream);
     step("channelizer created");
+    if (!rc && (cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER)) {
+        h->chz.pow_slots = 64u * h->ring_words / AMPS_RECC_POWER_STRIDE;         // the bit ring's window, a power of two (ring_words >= 32)
+        rc = dev_alloc(&h->chz.pow_ring, (size_t)h->chz.pow_slots * C);
+        h->chan2row.assign(cfg->n_channels, -1);
+        for (size_t r = 0; r < h->chz.row2chan.size(); r++) h->chan2row[h->chz.row2chan[r]] = (int32_t)r;
+    }
     if (!rc) rc = reset_state(h);
     step("state reset");
     if (rc) { amps_recc_destroy(h); return rc; }
@@ -715,7 +731,7 @@ void amps_recc_destroy(amps_recc_t *h)
     void *bufs[] = { h->carry[0], h->carry[1], h->gring, h->det, h->detcount, h->next_allowed, h->pending,
                      h->done_blocks, h->capq, h->capq_count, h->nrecords_buf[0], h->nrecords_buf[1], h->stage_iq, h->symbuf, h->sym_len, h->sym_cur,
                      h->sym_stage, h->bursts_dev, h->burst_chan_dev, h->nbursts_dev, h->dec_out_dev, h->dec_in_dev,
-                     h->dec_chan_dev, h->dbg_d, h->dbg_S, h->bch_in, h->bch_out, h->bch_val, h->bch_err };
+                     h->dec_chan_dev, h->dbg_d, h->dbg_S, h->bch_in, h->bch_out, h->bch_val, h->bch_err, h->pq_dev, h->pq_out };
     for (void *p : bufs) if (p) (void)hipFree(p);
     for (int b = 0; b < 2; b++) if (h->rec_host_buf[b]) (void)hipHostFree(h->rec_host_buf[b]);
     for (int b = 0; b < 2; b++) if (h->bsym_host_buf[b]) (void)hipHostFree(h->bsym_host_buf[b]);
@@ -1441,6 +1457,75 @@ int amps_recc_debug_slicer_bits(amps_recc_t *h, uint64_t first, size_t n, uint8_
     }
     return 0;
 }
+
+// the snapshots the power ring holds once the stream is idle: [lo, hi), hi = one past the newest (snapshot j exists iff 256 j < n_done)
+static void power_window(const amps_recc *h, uint64_t *lo, uint64_t *hi)
+{
+    const uint64_t S = AMPS_RECC_POWER_STRIDE;
+    *hi = (h->n_done + S - 1) / S;
+    *lo = std::max<uint64_t>((h->origin + S - 1) / S, *hi > h->chz.pow_slots ? *hi - h->chz.pow_slots : 0);
+}
+
+int amps_recc_channel_power(amps_recc_t *h, uint64_t first_snap, size_t n, float *out, size_t out_ld, uint32_t *rows, uint64_t *produced_snaps)
+{
+    if (!h || (n && (!out || out_ld < n))) return -EINVAL;
+    if (!h->chz.pow_ring) return -ENOSYS;
+    STALE_CHECK(h);
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = sync_stream(h, h->stream)) return rc;
+    uint64_t lo, hi;
+    power_window(h, &lo, &hi);
+    if (rows) *rows = h->C;
+    if (produced_snaps) *produced_snaps = hi;
+    if (n == 0) return 0;
+    if (first_snap < lo || first_snap > hi || n > hi - first_snap) return -ERANGE;
+    // the ring is snapshot-major: n slots (two runs where the range wraps) to the host, transposed there
+    const uint32_t slots = h->chz.pow_slots;
+    const size_t C = h->C, s0 = (size_t)(first_snap & (slots - 1)), n1 = std::min<size_t>(n, slots - s0);
+    std::vector<float> snap(n * C);
+    HIP_TRY(hipMemcpyAsync(snap.data(), h->chz.pow_ring + s0 * C, sizeof(float) * n1 * C, hipMemcpyDeviceToHost, h->stream));
+    if (n > n1) HIP_TRY(hipMemcpyAsync(snap.data() + n1 * C, h->chz.pow_ring, sizeof(float) * (n - n1) * C, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (size_t c = 0; c < C; c++)
+        for (size_t i = 0; i < n; i++) out[c * out_ld + i] = snap[i * C + c];
+    return 0;
+}
+
+int amps_recc_burst_power(amps_recc_t *h, const amps_recc_burst_t *recs, size_t n, float *mean_power, uint32_t *n_snaps)
+{
+    if (!h || (n && (!recs || !mean_power || !n_snaps))) return -EINVAL;
+    if (!h->chz.pow_ring) return -ENOSYS;
+    STALE_CHECK(h);
+    if (n == 0) return 0;
+    if (n > 0xffffffffull) return -E2BIG;
+    std::vector<ChzBurstQuery> q(n);
+    for (size_t i = 0; i < n; i++) {
+        if (recs[i].channel >= h->chan2row.size() || h->chan2row[recs[i].channel] < 0) return -EINVAL;
+        q[i] = ChzBurstQuery{ recs[i].position, (uint32_t)h->chan2row[recs[i].channel], 0u };
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = sync_stream(h, h->stream)) return rc;            // the window is that of an idle stream; the copies below are synchronous
+    if (h->pq_cap < n) {
+        if (h->pq_dev) (void)hipFree(h->pq_dev);
+        if (h->pq_out) (void)hipFree(h->pq_out);
+        h->pq_dev = nullptr; h->pq_out = nullptr; h->pq_cap = 0;
+        if (dev_alloc(&h->pq_dev, n) || dev_alloc(&h->pq_out, n)) return -ENOMEM;
+        h->pq_cap = n;
+    }
+    uint64_t lo, hi;
+    power_window(h, &lo, &hi);
+    HIP_TRY(hipMemcpy(h->pq_dev, q.data(), sizeof(ChzBurstQuery) * n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(chz_power_gather_kernel, dim3((uint32_t)((n + 3) / 4)), dim3(256), 0, h->stream, h->chz.pow_ring, h->C, h->chz.pow_slots - 1, lo, hi,
+                       (uint32_t)AMPS_RECC_CAPTURE_SYMS * h->sps, h->pq_dev, (uint32_t)n, h->pq_out);
+    HIP_TRY(hipGetLastError());
+    std::vector<uint2> res(n);
+    HIP_TRY(hipMemcpyAsync(res.data(), h->pq_out, sizeof(uint2) * n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < n; i++) { std::memcpy(&mean_power[i], &res[i].x, sizeof(float)); n_snaps[i] = res[i].y; }
+    return 0;
+}
+
+uint32_t amps_recc_power_ring_snaps(const amps_recc_t *h) { return h && h->chz.pow_ring ? h->chz.pow_slots : 0u; }
 
 int amps_recc_set_origin(amps_recc_t *h, uint64_t first_sample)
 {

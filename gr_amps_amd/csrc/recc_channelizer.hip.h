@@ -1110,7 +1110,11 @@ struct ChannelizerState {
     size_t cvt_samples = 0;
     bool short_prepass = false;     // AMPS_RECC_SHORT_PREPASS=1 at create: sc16 blocks go through chz_short_to_float_kernel + the fc32 kernel
     StageFence stage_fence;
+    float *pow_ring = nullptr;      // AMPS_RECC_FLAG_CHANNEL_POWER: [pow_slots][C] power snapshots (recc_power.hip.h), else null
+    uint32_t pow_slots = 0;         // snapshots held per row: the bit ring's span / AMPS_RECC_POWER_STRIDE (a power of two)
 };
+// recc_power.hip.h: the snapshot frames of a fused filter-bank launch, from that launch's own arguments
+inline void chz_power_launch(const ChannelizerState &z, const ChzArgs &a, bool sc16, hipStream_t s);
 
 inline double bessel_i0(double x)
 {
@@ -1162,7 +1166,7 @@ inline int channelizer_reset(ChannelizerState &z, hipStream_t s)
 inline void channelizer_destroy(ChannelizerState &z)
 {
     z.stage_fence.destroy();
-    void *bufs[] = { z.taps, z.carry[0], z.carry[1], z.out, z.stage, z.cvt, z.bin2row };
+    void *bufs[] = { z.taps, z.carry[0], z.carry[1], z.out, z.stage, z.cvt, z.bin2row, z.pow_ring };
     for (void *p : bufs) if (p) (void)hipFree(p);
     z = ChannelizerState();
 }
@@ -1319,8 +1323,8 @@ inline int channelizer_run(ChannelizerState &z, const void *iq, size_t nsamp, in
     const uint32_t consumed = nframes * (uint32_t)z.D;                // virtual samples consumed (incl. leftover)
     const uint32_t new_left = (uint32_t)(avail - consumed);
     bool carry_in_kernel = false;
+    ChzArgs a{};
     if (nframes) {
-        ChzArgs a{};
         a.block = (const float2 *)d; a.carry = z.carry[z.carry_cur]; a.taps = z.taps; a.out = z.out; a.ld = z.ld;
         a.carry_len = z.carry_len; a.nsamp = (uint32_t)nsamp; a.nframes = nframes; a.hist = hist;
         // one resident round of 768-thread workgroups, one per CU; each refills its delay lines and re-runs eight pre-roll
@@ -1346,6 +1350,8 @@ inline int channelizer_run(ChannelizerState &z, const void *iq, size_t nsamp, in
         hipLaunchKernelGGL(chz12_kernel_for(z.D, fused, slicer, sc16), g12, b12, 0, s, a);
     }
     if (after_main) after_main(after_ctx);                            // timing: the span ends behind the filter-bank kernel, before the carry copy
+    // power snapshots (opt-in): behind the filter bank, from the block and the carry it read -- the carry buffers swap below
+    if (fused && z.pow_ring && nframes) chz_power_launch(z, a, sc16, s);
 #ifdef CHZ_TIMELINE
     if (const char *path = std::getenv("AMPS_RECC_CHZ_TIMELINE")) {       // the last launch's stamps, raw
         std::vector<unsigned long long> tl(12 * 8);

@@ -8,7 +8,9 @@
 //   recctest wide <file.fc32> [chunk] [slicer] [decim]  one 30.72 Msps wideband capture -> gr::amps::recc_wideband (832 channels from bin 96); every
 //                                      burst's lines are prefixed with its channel; decoded through the "bursts" port.  A file whose name ends
 //                                      in .sc16 (or a sixth argument `sc16`) is read as interleaved 16-bit I/Q and goes through the block's
-//                                      16-bit input
+//                                      16-bit input.  An argument `power` behind those (the seventh, or the eighth behind `sc16`) makes the block
+//                                      keep received power: every burst's lines are followed by `MSG power channel <c> <10 log10(mean power)> dB
+//                                      n=<snapshots>`; without it the output is what it always was
 //   recctest widerank <file.fc32> <chunk> <idfile> <nranks> <rank> [mode]   ONE rank of the same band over `nranks` processes (2, 4 or 8; one per GPU of a
 //                                      node): gr::amps::recc_wideband::make(832, 96, -1, nranks, rank) + set_rccl -- rank 0 owns the capture and the
 //                                      library distributes it (mode 0 = ncclBroadcast, 1 = scatter + all-gather); the other ranks' items only pace
@@ -24,6 +26,7 @@
 #include <amps/recc_bank.h>
 #include <amps/recc_fused.h>
 #include <amps/recc_wideband.h>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -122,8 +125,10 @@ int main(int argc, char **argv)
             const std::string path = argv[2];
             const bool sc16 = !ranks && ((path.size() > 5 && path.compare(path.size() - 5, 5, ".sc16") == 0) || (argc > 6 && std::string(argv[6]) == "sc16"));
             const size_t item = sc16 ? 4 : 8;                         // bytes per wideband sample
+            bool power = false;
+            for (int i = 6; !ranks && i < argc && i < 9; i++) power = power || std::string(argv[i]) == "power";
             auto src = ranks ? gr::amps::recc_wideband::make(832, 96, -1, nranks, rank)
-                             : gr::amps::recc_wideband::make(832, 96, argc > 4 ? std::atoi(argv[4]) : -1, 0, 0, argc > 5 ? std::atoi(argv[5]) : 0, sc16);
+                             : gr::amps::recc_wideband::make(832, 96, argc > 4 ? std::atoi(argv[4]) : -1, 0, 0, argc > 5 ? std::atoi(argv[5]) : 0, sc16, power);
             if (ranks) {
                 // the control plane is the application's: here, a file
                 std::string id;
@@ -152,12 +157,22 @@ int main(int argc, char **argv)
                         std::printf("MSG channel %ld\n", pmt::to_long(pmt::car(m)));
                         dec->dispatch("bursts", pmt::cdr(m));
                     });
+                    message_port_register_in(pmt::mp("power"));       // { float mean_power; uint32_t n_snaps; } (amps/recc_wideband.h)
+                    set_msg_handler(pmt::mp("power"), [](pmt::pmt_t m) {
+                        float p = 0.f;
+                        uint32_t n = 0;
+                        const uint8_t *b = (const uint8_t *)pmt::blob_data(pmt::cdr(m));
+                        std::memcpy(&p, b, 4);
+                        std::memcpy(&n, b + 4, 4);
+                        std::printf("MSG power channel %ld %.2f dB n=%u\n", pmt::to_long(pmt::car(m)), 10.0 * std::log10((double)p), (unsigned)n);
+                    });
                 }
                 int general_work(int n, gr_vector_int &, gr_vector_const_void_star &, gr_vector_void_star &) override { return n; }
             };
             auto dm = std::make_shared<demux>();
             dm->dec = dec;
             gr::msg_connect(src, "bursts", dm, "bursts");
+            if (power) gr::msg_connect(src, "power", dm, "power");
             std::vector<char> tail((size_t)64 * 768 * item, 0);       // silence: flushes the frames the fused form holds back (64 frames of at most 768 samples)
             data.resize(data.size() / item * item);
             data.insert(data.end(), tail.begin(), tail.end());

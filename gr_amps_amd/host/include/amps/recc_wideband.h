@@ -4,7 +4,13 @@
 // CHANNEL, the chain freq_xlating_fir_filter_ccc -> analog_quadrature_demod_cf -> digital_clock_recovery_mm_ff ->
 // digital_binary_slicer_fb -> amps_recc (grc/recctest.grc:889-937, 458, 846-874, 807, 310), 832 times over.
 // Message ports:  "bursts"  pmt::cons(from_long(channel), blob(3374)) -- cdr = what amps_recc publishes (lib/recc_impl.cc:126);
-//                 "records" pmt::cons(from_long(channel), blob(amps_recc_burst_t)) -- the burst already decoded.
+//                 "records" pmt::cons(from_long(channel), blob(amps_recc_burst_t)) -- the burst already decoded;
+//                 "power"   (blocks made with channel_power = true only) pmt::cons(from_long(channel), blob(8)) for every record, behind its
+//                           "records" message: the 8 bytes are { float mean_power; uint32_t n_snaps; } in host byte order, as
+//                           amps_recc_burst_power returns them -- the mean |filter-bank output|^2 of the record's channel over its capture
+//                           (linear, unscaled: 1.0 for a mobile at full scale of an fc32 stream, int16 units squared behind short_input) and
+//                           the number of power snapshots averaged (26 / 27 at decim 768, 39 / 40 at 512; 0 with power 0.0 if the handle no
+//                           longer held them).  The block drains after every push, so every record is covered.
 // channel 0 = FFT bin `first_bin` (centre first_bin x 30 kHz above the stream's centre, modulo the sample rate).
 #pragma once
 #include <amps/api.h>
@@ -26,7 +32,9 @@ public:
     //         source delivers -- instead of one gr_complex; the block pushes it as it is (amps_recc_push_wideband_short: 4 bytes per
     //         sample to the device, no float copy on the host).  Scale does not matter to any slicer spec.  set_rccl is refused on such
     //         a block: the distributed seam carries fc32.
-    static sptr make(int n_channels = 832, int first_bin = 96, int slicer = -1, int groups = 0, int group = 0, int decim = 0, bool short_input = false);
+    // channel_power: keep per-channel received power (AMPS_RECC_FLAG_CHANNEL_POWER) and publish every record's burst power on "power"
+    static sptr make(int n_channels = 832, int first_bin = 96, int slicer = -1, int groups = 0, int group = 0, int decim = 0, bool short_input = false,
+                     bool channel_power = false);
     // Let ONE rank own the stream: after this call (a collective over all `nranks` blocks; `id` = the 128 bytes one of them got from
     // rccl_unique_id(), carried between the processes by the application) work() distributes rank `root`'s input over xGMI with RCCL
     // inside amps_recc_push_wideband_dist (mode 0 = flat broadcast, 1 = scatter + all-gather: AMPS_RECC_DIST_*).  The other ranks'

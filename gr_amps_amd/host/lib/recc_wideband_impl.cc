@@ -21,11 +21,15 @@ class recc_wideband_impl : public recc_wideband {
     unsigned long long d_stream_samples = 0, d_paced_items = 0;   // non-root ranks: samples the root has distributed / items this rank's pacing input has offered
     bool d_ended = false;                          // the root's end of stream has been sent (root) / seen (the others)
     bool d_short = false;                          // items are two shorts (interleaved 16-bit I/Q, "sc16"): amps_recc_push_wideband_short
+    bool d_power = false;                          // AMPS_RECC_FLAG_CHANNEL_POWER: every record's burst power goes out on "power"
+    std::vector<float> d_pow;
+    std::vector<uint32_t> d_nsnap;
 
 public:
-    recc_wideband_impl(int C, int first_bin, int slicer, int groups, int group, int decim, bool short_input)
+    recc_wideband_impl(int C, int first_bin, int slicer, int groups, int group, int decim, bool short_input, bool channel_power)
         : gr::sync_block("recc_wideband", gr::io_signature::make(1, 1, short_input ? 2 * sizeof(short) : 2 * sizeof(float)), gr::io_signature::make(0, 0, 0)),
-          d_handle(nullptr), d_recs(kMaxRecs), d_bursts((size_t)kMaxRecs * AMPS_RECC_CAPTURE_SYMS), d_short(short_input)
+          d_handle(nullptr), d_recs(kMaxRecs), d_bursts((size_t)kMaxRecs * AMPS_RECC_CAPTURE_SYMS), d_short(short_input), d_power(channel_power),
+          d_pow(channel_power ? kMaxRecs : 0), d_nsnap(channel_power ? kMaxRecs : 0)
     {
         amps_recc_cfg_t cfg = {};
         cfg.struct_size = sizeof(cfg);
@@ -35,7 +39,8 @@ public:
         cfg.max_bursts = kMaxRecs;
         cfg.device = -1;
         cfg.flags = AMPS_RECC_FLAG_KEEP_BURSTS | (slicer == 0 ? AMPS_RECC_FLAG_SLICER_ATAN : slicer == 1 ? AMPS_RECC_FLAG_SLICER_PRODUCT
-                                                  : slicer == 2 ? AMPS_RECC_FLAG_SLICER_SINE : slicer == 3 ? AMPS_RECC_FLAG_SLICER_EXACT : 0u);
+                                                  : slicer == 2 ? AMPS_RECC_FLAG_SLICER_SINE : slicer == 3 ? AMPS_RECC_FLAG_SLICER_EXACT : 0u)
+                    | (channel_power ? AMPS_RECC_FLAG_CHANNEL_POWER : 0u);
         cfg.wideband_groups = (uint32_t)groups;
         cfg.wideband_group = (uint32_t)group;
         cfg.wideband_channels = 1024;
@@ -46,6 +51,7 @@ public:
         if (rc != 0) throw std::runtime_error(std::string("amps::recc_wideband: ") + amps_recc_strerror(rc));
         message_port_register_out(pmt::mp("bursts"));
         message_port_register_out(pmt::mp("records"));
+        if (d_power) message_port_register_out(pmt::mp("power"));
     }
     ~recc_wideband_impl() { amps_recc_destroy(d_handle); }
 
@@ -82,10 +88,20 @@ public:
         // next push -- a recoverable condition must not end the flow graph
         if (rc == -ENOSPC) std::fprintf(stderr, "amps::recc_wideband: %s (bursts dropped, continuing)\n", amps_recc_strerror(rc));
         else if (rc != 0) { std::fprintf(stderr, "amps::recc_wideband: %s\n", amps_recc_strerror(rc)); return leave(); }
+        // the push that found a record has just been drained: its capture is inside the power ring's window
+        if (d_power && nrec) {
+            rc = amps_recc_burst_power(d_handle, d_recs.data(), nrec, d_pow.data(), d_nsnap.data());
+            if (rc != 0) { std::fprintf(stderr, "amps::recc_wideband: burst power: %s\n", amps_recc_strerror(rc)); return leave(); }
+        }
         for (size_t i = 0; i < nrec; i++) {
             const pmt::pmt_t ch = pmt::from_long((long)d_recs[i].channel);
             message_port_pub(pmt::mp("bursts"), pmt::cons(ch, pmt::mp(d_bursts.data() + i * AMPS_RECC_CAPTURE_SYMS, AMPS_RECC_CAPTURE_SYMS)));
             message_port_pub(pmt::mp("records"), pmt::cons(ch, pmt::mp(&d_recs[i], sizeof(d_recs[i]))));
+            if (d_power) {
+                struct { float mean_power; uint32_t n_snaps; } p = { d_pow[i], d_nsnap[i] };
+                static_assert(sizeof(p) == 8, "payload of the power port");
+                message_port_pub(pmt::mp("power"), pmt::cons(ch, pmt::mp(&p, sizeof(p))));
+            }
         }
         return true;
     }
@@ -134,9 +150,9 @@ public:
     }
 };
 
-recc_wideband::sptr recc_wideband::make(int n_channels, int first_bin, int slicer, int groups, int group, int decim, bool short_input)
+recc_wideband::sptr recc_wideband::make(int n_channels, int first_bin, int slicer, int groups, int group, int decim, bool short_input, bool channel_power)
 {
-    return gnuradio::get_initial_sptr(new recc_wideband_impl(n_channels, first_bin, slicer, groups, group, decim, short_input));
+    return gnuradio::get_initial_sptr(new recc_wideband_impl(n_channels, first_bin, slicer, groups, group, decim, short_input, channel_power));
 }
 
 std::string recc_wideband::rccl_unique_id()

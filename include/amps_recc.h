@@ -43,7 +43,9 @@ extern "C" {
                                      clock unless AMPS_RECC_FLAG_FIXED_TIMING, amps_recc_rccl_* / _push_wideband_bcast / _drain_gather / _debug_exact_slice added;
                                      4: amps_recc_push_wideband_dist (scatter + all-gather), amps_recc_rccl_info / _abort / _set_timeout; rccl_init checks the
                                      group split and allocates; every collective entry is bounded and carries a status word;
-                                     (still 4, one entry point added and nothing changed: amps_recc_push_wideband_short, 16-bit I/Q through the wideband seam) */
+                                     (still 4, one entry point added and nothing changed: amps_recc_push_wideband_short, 16-bit I/Q through the wideband seam;
+                                     still 4, three entry points and a flag added and nothing changed: amps_recc_channel_power / _burst_power /
+                                     _power_ring_snaps behind AMPS_RECC_FLAG_CHANNEL_POWER) */
 
 /* protocol constants of the reference */
 #define AMPS_RECC_TRIGGER_SYMS 74   /* lib/recc_impl.cc:76-77: 37 bits x 2 Manchester symbols   */
@@ -79,6 +81,9 @@ extern "C" {
                                                gives (rounds 1-3).  Default: the capture tracks the mobile's bit clock, one sample per
                                                repeat at most, from where the mid-bit transitions fall -- the fast path's
                                                stand-in for clock_recovery_mm_ff's loop (grc/recctest.grc:846-874) */
+#define AMPS_RECC_FLAG_CHANNEL_POWER 0x200u /* wideband seam, fused form: keep per-channel received power (amps_recc_channel_power,
+                                               amps_recc_burst_power below).  Off by default; with it off nothing is allocated or launched for it.
+                                               With AMPS_RECC_FLAG_UNFUSED_WIDEBAND, or on a handle without wideband_channels: -EINVAL */
 #define AMPS_RECC_FLAG_MAJORITY     0x2u /* decode mode "majority" instead of "reference" (SURVEY.md 8f.2), see below */
 
 /* message classes, the branches of lib/recc_decode_impl.cc:108-168 */
@@ -327,6 +332,34 @@ int amps_recc_debug_demod(amps_recc_t *h, const float *iq, size_t nsamp, int mem
  * Changes nothing: the next push behaves as if the call had not been made. */
 int amps_recc_debug_slicer_bits(amps_recc_t *h, uint64_t first, size_t n, uint8_t *out, size_t out_ld,
                                 uint32_t *rows, uint64_t *produced);
+
+/* ---- received power of the wideband seam (handles created with AMPS_RECC_FLAG_CHANNEL_POWER; -ENOSYS on every other handle) ----
+ * A POWER SNAPSHOT is taken at every channel-rate sample index s with s % AMPS_RECC_POWER_STRIDE == 0, s in the numbering of
+ * amps_recc_debug_slicer_bits and of amps_recc_burst_t.position (absolute, amps_recc_set_origin counted: frame m of the stream is
+ * s = origin + m).  Snapshot j = s / 256 of row r is P[r][j] = |Y_k[m]|^2, Y_k[m] the filter-bank output of the row's FFT bin for that
+ * frame (prototype and decimation are the handle's; samples before the stream start are zeros): linear power, fp32, unscaled.  The
+ * prototype has unit DC gain, so an unmodulated carrier of amplitude a at a channel centre reads a^2; blocks pushed with
+ * amps_recc_push_wideband_short read in int16 units squared.  Snapshots depend on the stream only, never on how it was cut into pushes
+ * or on the sample type of a block; the fused form holds back up to 63 frames, and snapshot j exists once its frame has been consumed:
+ * 256 j < produced (the `produced` of amps_recc_debug_slicer_bits).  The handle keeps the last R / 256 snapshots of every row, R the
+ * span of the slicer-bit ring (see amps_recc_debug_slicer_bits): every record found by a push still has its whole capture inside the
+ * window when that push is drained.  amps_recc_reset empties the window.  Cost: one short kernel behind the filter bank per push that
+ * re-computes one frame in 256. */
+#define AMPS_RECC_POWER_STRIDE 256
+/* out[row][i] = P[row][first_snap + i], i < n, into host memory out[rows][out_ld], once the pushes enqueued so far have finished;
+ * *rows as amps_recc_debug_slicer_bits reports it, *produced_snaps = one past the newest snapshot (either may be NULL).  The held
+ * window is [max(ceil(origin / 256), produced_snaps - R / 256), produced_snaps): -ERANGE for anything outside it.  n = 0 only reports.
+ * -EINVAL for a null handle, or out == NULL / out_ld < n with n > 0; -ESTALE as the data seams.  Changes nothing. */
+int amps_recc_channel_power(amps_recc_t *h, uint64_t first_snap, size_t n, float *out, size_t out_ld,
+                            uint32_t *rows, uint64_t *produced_snaps);
+/* Burst power: for each of the n records (host array; only `channel` and `position` are read) the arithmetic mean of P[row(channel)][j]
+ * over all j with position <= 256 j <= position + AMPS_RECC_CAPTURE_SYMS * samples_per_symbol -- the capture -- into mean_power[i], and
+ * the number of those snapshots, floor(hi / 256) - ceil(lo / 256) + 1 (26 or 27 at D = 768, 39 or 40 at D = 512), into n_snaps[i].  If any
+ * of them is no longer held or not yet produced: n_snaps[i] = 0 and mean_power[i] = 0.0f, which is not an error.  `channel` is the
+ * whole-band channel number the records carry; one this handle does not decode: -EINVAL (as for a null handle or null arrays with n > 0). */
+int amps_recc_burst_power(amps_recc_t *h, const amps_recc_burst_t *recs, size_t n, float *mean_power, uint32_t *n_snaps);
+/* snapshots the handle keeps per row, R / 256; 0 on a handle without the flag (or a null handle) */
+uint32_t amps_recc_power_ring_snaps(const amps_recc_t *h);
 
 /* ---- one band over the GPUs of a node (BASELINE configs[4]: "RCCL broadcast of wideband IQ over xGMI") ----
  * One process and one handle per GPU, every handle created with cfg.wideband_groups = N, wideband_group = its rank (the reference's
