@@ -47,7 +47,50 @@ struct TimedSpan { hipEvent_t a, b; int tag; uint64_t samples; };
 
 } // namespace
 
-struct amps_recc {
+// Every device and mapped-host allocation of the handle's own seams, each behind its owner (recc_devmem.hip.h).  A part of the handle
+// of its own so that amps_recc_destroy can free all of it at its place in the teardown without naming a buffer: a buffer added here
+// cannot be left off a list.
+struct amps_recc_mem {
+    // ---- IQ seam ----
+    DevBuf<float2> carry[2];
+    DevBuf<uint64_t> gring;
+    DevBuf<uint64_t> det;
+    DevBuf<uint32_t> detcount;
+    DevBuf<uint64_t> next_allowed, pending;
+    DevBuf<unsigned long long> done_blocks;   // {resolve workgroups of the launch in flight that have finished, record slots they reserved}
+    DevBuf<uint64_t> capq;                    // queue form of the capture (few channels: resolve_uses_queue)
+    DevBuf<uint32_t> capq_count;
+    // two record lists: pushes append to the current one; drain_begin closes it (and switches), drain_end collects it
+    MappedBuf<amps_recc_burst_t> rec_buf[2];  // the capture kernel writes records here directly
+    MappedBuf<uint8_t> bsym_buf[2];           // AMPS_RECC_FLAG_KEEP_BURSTS: [max_bursts][PACKED_BURST_BYTES] (a bit per symbol; allocated for 3374 bytes each)
+    MappedBuf<uint32_t> hdr;                  // {nrecords, status} per record list: written by the capture kernel's last workgroup
+    DevBuf<uint32_t> nrecords_buf[2];         // [LIST_WORDS] per list
+    HostStage stage_iq;                       // host-resident IQ: [C][max_samples_per_push], allocated by the first host push
+
+    // ---- received power: amps_recc_burst_power scratch (grow-only) ----
+    DevBuf<amps::ChzBurstQuery> pq_dev;
+    DevBuf<uint2> pq_out;
+
+    // ---- symbol seam ----
+    DevBuf<uint8_t> symbuf;
+    DevBuf<uint32_t> sym_len;
+    DevBuf<int32_t> sym_cur;
+    DevBuf<uint8_t> sym_stage;        // [C][MAX_WORK_ITEMS]
+    DevBuf<uint8_t> bursts_dev;       // [max_bursts][3374]
+    DevBuf<uint32_t> burst_chan_dev;
+    DevBuf<uint32_t> nbursts_dev;
+    DevBuf<amps_recc_burst_t> dec_out_dev;   // decode_bursts staging (grow-only)
+    DevBuf<uint8_t> dec_in_dev;
+    DevBuf<uint32_t> dec_chan_dev;
+
+    // ---- amps_bch_* scratch (grow-only; no allocation per call) ----
+    DevBuf<uint8_t> bch_in, bch_out, bch_val, bch_err;
+
+    // ---- debug taps (amps_recc_debug_demod) ----
+    DevBuf<float> dbg_d, dbg_S;
+};
+
+struct amps_recc : amps_recc_mem {
     amps_recc_cfg_t cfg{};
     int device = 0;
     hipStream_t stream = nullptr;
@@ -55,7 +98,6 @@ struct amps_recc {
     uint32_t C = 0, sps = 0;
 
     // ---- IQ seam ----
-    float2 *carry[2] = { nullptr, nullptr };
     int carry_cur = 0;
     uint64_t n_done = 0;
     uint64_t origin = 0;              // absolute index of the stream's first sample (amps_recc_set_origin)
@@ -63,60 +105,28 @@ struct amps_recc {
     RcclState rccl;                         // one band over several GPUs: amps_recc_rccl_init / amps_recc_push_wideband_bcast
     uint32_t r_prev = 0;
     bool origin_locked = false;       // a push has happened since the last reset
-    uint64_t *gring = nullptr;
     uint32_t ring_words = 0;
-    uint32_t max_waves = 0, max_chunks = 0, det_cap = 0;   // front-launch geometry bounds (see run_iq_device)
+    uint32_t max_waves = 0, max_chunks = 0, det_cap = 0;   // front-launch geometry bounds (see front_geometry)
     uint32_t max_waves_bits = 0;                           // the same for the bit-domain kernel (more waves fit: 72 VGPRs, 2 KB LDS)
-    uint64_t *det = nullptr;
-    uint32_t *detcount = nullptr;
-    uint64_t *next_allowed = nullptr, *pending = nullptr;
-    unsigned long long *done_blocks = nullptr;    // {resolve workgroups of the launch in flight that have finished, record slots they reserved}
-    uint64_t *capq = nullptr;                     // queue form of the capture (few channels: resolve_uses_queue)
-    uint32_t *capq_count = nullptr;
-    amps_recc_burst_t *records = nullptr;
+    amps_recc_burst_t *records = nullptr;     // the current record list (select_record_list): its device-side records, count and status
     uint32_t *nrecords = nullptr;
     uint32_t *status = nullptr;
-    amps_recc_burst_t *rec_host = nullptr;   // mapped pinned host memory: the capture kernel writes records here directly
-    uint32_t *hdr_host = nullptr, *hdr_dev = nullptr;   // mapped pinned {nrecords, status} per record list: written by the capture kernel's last workgroup
     bool list_clean[2] = { true, true };      // the device-side {nrecords, status} of the list are zero (or a launch that zeroes them is enqueued)
-    // two record lists: pushes append to the current one; drain_begin closes it (and switches), drain_end collects it
-    amps_recc_burst_t *rec_host_buf[2] = { nullptr, nullptr }, *records_buf[2] = { nullptr, nullptr };
-    uint8_t *bsym_host_buf[2] = { nullptr, nullptr }, *bsym_dev_buf[2] = { nullptr, nullptr };   // AMPS_RECC_FLAG_KEEP_BURSTS: [max_bursts][PACKED_BURST_BYTES] (a bit per symbol; allocated for 3374 bytes each), mapped pinned
-    uint32_t *nrecords_buf[2] = { nullptr, nullptr }, *status_buf[2] = { nullptr, nullptr };
     int cur_buf = 0, open_buf = -1;
     bool open_untouched = false;      // no push has been enqueued since drain_begin: the open list's device counters are still there (header cross-check)
     hipEvent_t drain_event = nullptr;
-    float2 *stage_iq = nullptr;       // device staging for host-resident IQ
-    size_t stage_iq_samples = 0;
-    StageFence stage_iq_fence;
 
     // ---- channelizer seam ----
     ChannelizerState chz;
 
     // ---- received power (AMPS_RECC_FLAG_CHANNEL_POWER; the ring itself is chz.pow_ring) ----
     std::vector<int32_t> chan2row;            // whole-band channel number -> ring row, -1 for a channel this handle does not decode
-    amps::ChzBurstQuery *pq_dev = nullptr;    // amps_recc_burst_power scratch (grow-only)
-    uint2 *pq_out = nullptr;
-    size_t pq_cap = 0;
 
     // ---- translate seam (recctest.grc channel filter) ----
     XlateState xl;
 
     // ---- reference-timing seam (G2 -> G3 -> G4 as the flow graph wires them; created on first use) ----
     RefState ref;
-
-    // ---- symbol seam ----
-    uint8_t *symbuf = nullptr;
-    uint32_t *sym_len = nullptr;
-    int32_t *sym_cur = nullptr;
-    uint8_t *sym_stage = nullptr;     // [C][MAX_WORK_ITEMS]
-    uint8_t *bursts_dev = nullptr;    // [max_bursts][3374]
-    uint32_t *burst_chan_dev = nullptr;
-    uint32_t *nbursts_dev = nullptr;
-    amps_recc_burst_t *dec_out_dev = nullptr; // decode_bursts output staging
-    size_t dec_out_cap = 0;
-    uint8_t *dec_in_dev = nullptr;
-    uint32_t *dec_chan_dev = nullptr;
 
     // ---- timing ----
     bool timing = false;
@@ -127,13 +137,6 @@ struct amps_recc {
     double ms[T_COUNT] = { 0 };
     uint32_t launches_front = 0, launches_chz = 0;
     uint64_t samples_front = 0;
-
-    // ---- amps_bch_* scratch (grow-only; no allocation per call) ----
-    uint8_t *bch_in = nullptr, *bch_out = nullptr, *bch_val = nullptr, *bch_err = nullptr;
-    size_t bch_in_cap = 0, bch_out_cap = 0, bch_n_cap = 0;
-
-    // ---- debug taps (amps_recc_debug_demod) ----
-    float *dbg_d = nullptr, *dbg_S = nullptr;
 };
 
 namespace {
@@ -168,14 +171,6 @@ inline void expand_packed_burst(uint8_t *dst, const uint8_t *src)
     constexpr int FULL = AMPS_RECC_CAPTURE_SYMS / 8;                                                                             // 421 whole bytes of bits
     for (int k = 0; k < FULL; k++) std::memcpy(dst + 8 * k, &lut[src[k]], 8);
     for (int i = 8 * FULL; i < AMPS_RECC_CAPTURE_SYMS; i++) dst[i] = (uint8_t)((src[i >> 3] >> (i & 7)) & 1u);                    // the last six symbols
-}
-
-template <typename T> int dev_alloc(T **p, size_t n)
-{
-    if (n == 0) n = 1;
-    hipError_t e = hipMalloc((void **)p, n * sizeof(T));
-    if (e != hipSuccess) { *p = nullptr; return -ENOMEM; }
-    return 0;
 }
 
 struct SpanGuard {   // records a pair of events around a launch when timing is on
@@ -261,8 +256,8 @@ int sync_event(amps_recc *h, hipEvent_t e)
 void select_record_list(amps_recc *h, int b)
 {
     h->cur_buf = b;
-    h->records = h->records_buf[b]; h->rec_host = h->rec_host_buf[b];
-    h->nrecords = h->nrecords_buf[b]; h->status = h->status_buf[b];
+    h->records = h->rec_buf[b].dev();
+    h->nrecords = h->nrecords_buf[b].get(); h->status = h->nrecords + 1;   // {nrecords, status} of a list are adjacent: one 8-byte copy / memset serves both
 }
 
 constexpr int HDR_STRIDE = 16;      // dwords between the two lists' host headers (one 64-byte line each: the CPU clears one while the GPU may write the other)
@@ -274,26 +269,26 @@ int reset_state(amps_recc *h)
 {
     hipStream_t s = h->stream;
     if (h->carry[0]) {
-        HIP_TRY(hipMemsetAsync(h->carry[0], 0, sizeof(float2) * (size_t)h->C * CARRY_CAP, s));
-        HIP_TRY(hipMemsetAsync(h->carry[1], 0, sizeof(float2) * (size_t)h->C * CARRY_CAP, s));
-        HIP_TRY(hipMemsetAsync(h->gring, 0xff, sizeof(uint64_t) * (size_t)h->C * h->ring_words, s));
-        HIP_TRY(hipMemsetAsync(h->detcount, 0, sizeof(uint32_t) * (size_t)h->C * h->max_chunks, s));
-        HIP_TRY(hipMemsetAsync(h->next_allowed, 0, sizeof(uint64_t) * h->C, s));
-        HIP_TRY(hipMemsetAsync(h->pending, 0xff, sizeof(uint64_t) * h->C, s));
-        HIP_TRY(hipMemsetAsync(h->done_blocks, 0, (1 + DONE_GROUPS) * sizeof(unsigned long long), s));
-        if (h->capq_count) HIP_TRY(hipMemsetAsync(h->capq_count, 0, sizeof(uint32_t), s));
+        HIP_TRY(hipMemsetAsync(h->carry[0].get(), 0, sizeof(float2) * (size_t)h->C * CARRY_CAP, s));
+        HIP_TRY(hipMemsetAsync(h->carry[1].get(), 0, sizeof(float2) * (size_t)h->C * CARRY_CAP, s));
+        HIP_TRY(hipMemsetAsync(h->gring.get(), 0xff, sizeof(uint64_t) * (size_t)h->C * h->ring_words, s));
+        HIP_TRY(hipMemsetAsync(h->detcount.get(), 0, sizeof(uint32_t) * (size_t)h->C * h->max_chunks, s));
+        HIP_TRY(hipMemsetAsync(h->next_allowed.get(), 0, sizeof(uint64_t) * h->C, s));
+        HIP_TRY(hipMemsetAsync(h->pending.get(), 0xff, sizeof(uint64_t) * h->C, s));
+        HIP_TRY(hipMemsetAsync(h->done_blocks.get(), 0, (1 + DONE_GROUPS) * sizeof(unsigned long long), s));
+        if (h->capq_count) HIP_TRY(hipMemsetAsync(h->capq_count.get(), 0, sizeof(uint32_t), s));
     }
     for (int b = 0; b < 2; b++) {
-        HIP_TRY(hipMemsetAsync(h->nrecords_buf[b], 0, LIST_WORDS * sizeof(uint32_t), s));
+        HIP_TRY(hipMemsetAsync(h->nrecords_buf[b].get(), 0, LIST_WORDS * sizeof(uint32_t), s));
         h->list_clean[b] = true;
     }
-    std::memset(h->hdr_host, 0, 2 * HDR_STRIDE * sizeof(uint32_t));
+    std::memset(h->hdr.host(), 0, 2 * HDR_STRIDE * sizeof(uint32_t));
     h->open_buf = -1;
     select_record_list(h, 0);
-    HIP_TRY(hipMemsetAsync(h->symbuf, 0, (size_t)h->C * AMPS_RECC_SYMBUF, s));
-    HIP_TRY(hipMemsetAsync(h->sym_len, 0, sizeof(uint32_t) * h->C, s));
-    HIP_TRY(hipMemsetAsync(h->sym_cur, 0xff, sizeof(int32_t) * h->C, s));
-    HIP_TRY(hipMemsetAsync(h->nbursts_dev, 0, sizeof(uint32_t), s));
+    HIP_TRY(hipMemsetAsync(h->symbuf.get(), 0, (size_t)h->C * AMPS_RECC_SYMBUF, s));
+    HIP_TRY(hipMemsetAsync(h->sym_len.get(), 0, sizeof(uint32_t) * h->C, s));
+    HIP_TRY(hipMemsetAsync(h->sym_cur.get(), 0xff, sizeof(int32_t) * h->C, s));
+    HIP_TRY(hipMemsetAsync(h->nbursts_dev.get(), 0, sizeof(uint32_t), s));
     h->carry_cur = 0;
     h->n_done = 0;
     h->origin = 0;
@@ -301,7 +296,7 @@ int reset_state(amps_recc *h)
     h->r_prev = 0;
     int rc = channelizer_reset(h->chz, s);
     if (rc) return rc;
-    if (h->chz.pow_ring) HIP_TRY(hipMemsetAsync(h->chz.pow_ring, 0, sizeof(float) * (size_t)h->chz.pow_slots * h->C, s));   // n_done = 0: no snapshot is held
+    if (h->chz.pow_ring) HIP_TRY(hipMemsetAsync(h->chz.pow_ring.get(), 0, sizeof(float) * (size_t)h->chz.pow_slots * h->C, s));   // n_done = 0: no snapshot is held
     rc = xlate_reset(h->xl, s);
     if (rc) return rc;
     rc = ref_reset(h->ref, s);
@@ -407,9 +402,9 @@ front_kernel_t bits_kernel_for(uint32_t sps, bool tol)
 void front_housekeeping_args(amps_recc *h, FrontArgs &fa)
 {
     h->open_untouched = false;              // this launch may clear the counters of the list a split drain has open
-    fa.zero1 = h->capq_count;               // null in the fused form
+    fa.zero1 = h->capq_count.get();               // null in the fused form
     const int idle = h->cur_buf ^ 1;
-    fa.zero2 = h->list_clean[idle] ? nullptr : h->nrecords_buf[idle];
+    fa.zero2 = h->list_clean[idle] ? nullptr : h->nrecords_buf[idle].get();
     h->list_clean[idle] = true;
     h->list_clean[h->cur_buf] = false;      // the capture kernel of this push may append to the current list
 }
@@ -454,25 +449,25 @@ static ResolveLaunch resolve_kernels_for(bool wide, bool search, bool two, bool 
 static void launch_resolve(amps_recc *h, ResolveArgs &ra, hipStream_t s, bool search = false)
 {
     // capture + decode side of the kernel
-    ra.gring = h->gring; ra.ring_mask = h->ring_words - 1; ra.ring_words = h->ring_words; ra.cap_words = resolve_cap_words(h->sps);
+    ra.gring = h->gring.get(); ra.ring_mask = h->ring_words - 1; ra.ring_words = h->ring_words; ra.cap_words = resolve_cap_words(h->sps);
     ra.records = h->records; ra.nrecords = h->nrecords; ra.rec_cap = h->cfg.max_bursts; ra.status = h->status;
     ra.majority = (h->cfg.flags & AMPS_RECC_FLAG_MAJORITY) ? 1u : 0u;
     ra.track = (h->cfg.flags & AMPS_RECC_FLAG_FIXED_TIMING) ? 0u : 1u;
-    ra.burst_syms = h->bsym_dev_buf[h->cur_buf];
-    ra.done_blocks = h->done_blocks; ra.hdr_host = h->hdr_dev + HDR_STRIDE * h->cur_buf;
-    ra.capq = h->capq; ra.capq_count = h->capq_count; ra.capq_cap = h->cfg.max_bursts;
+    ra.burst_syms = h->bsym_buf[h->cur_buf].dev();
+    ra.done_blocks = h->done_blocks.get(); ra.hdr_host = h->hdr.dev() + HDR_STRIDE * h->cur_buf;
+    ra.capq = h->capq.get(); ra.capq_count = h->capq_count.get(); ra.capq_cap = h->cfg.max_bursts;
     const size_t lds = h->capq ? 0 : resolve_dyn_lds(h->sps);
 #ifdef RESOLVE_TIMELINE
-    static unsigned long long *tl_dev = nullptr;
-    if (!tl_dev) (void)hipMalloc((void **)&tl_dev, (size_t)24 * 8 * 4096);
-    if (tl_dev && h->C <= 4096) { (void)hipMemsetAsync(tl_dev, 0, (size_t)24 * 8 * h->C, s); ra.tl = tl_dev; }
+    static DevBuf<unsigned long long> &tl_dev = *new DevBuf<unsigned long long>();   // kept for the life of the process
+    if (!tl_dev) (void)tl_dev.alloc((size_t)24 * 4096);
+    if (tl_dev && h->C <= 4096) { (void)hipMemsetAsync(tl_dev.get(), 0, (size_t)24 * 8 * h->C, s); ra.tl = tl_dev.get(); }
 #endif
     // The wide instantiation (a channel cut into more wave segments than 256 lanes compact in one batch) exists for handles with few
     // channels, which always take the queue form: its 36.9 KB of static LDS next to the fused capture form's dynamic LDS is a
     // combination max_chunks never produces for 64 channels or more (Tc / span + 2 <= max_waves / C + 4 <= 131 there).  Held here, so
     // that a change to either threshold cannot turn into a launch failure: a handle without a queue stays on the narrow kernel, whose
     // batches walk any number of segments.
-    const bool wide = ra.tiles_per_channel / ra.span + 2 > (uint64_t)RESOLVE_THREADS && h->capq != nullptr;
+    const bool wide = ra.tiles_per_channel / ra.span + 2 > (uint64_t)RESOLVE_THREADS && h->capq;
     const ResolveLaunch k = resolve_kernels_for(wide, search, h->sps == 2, ra.search_tol != 0);
     hipLaunchKernelGGL(k.resolve, dim3(h->C), dim3(k.threads), lds, s, ra);
     if (h->capq) {
@@ -489,6 +484,27 @@ static void launch_resolve(amps_recc *h, ResolveArgs &ra, hipStream_t s, bool se
 #endif
 }
 
+// Geometry of the persistent front launch over P samples of each of C channels: Tc tiles per channel, cut into `nwaves` equal
+// spans of the flattened (channel, tile) space -- one resident round of at most max_waves waves, a span never under MIN_SPAN tiles.
+struct FrontGeom { uint32_t Tc, span, nwaves; };
+FrontGeom front_geometry(uint32_t C, uint32_t P, uint32_t max_waves)
+{
+    const uint32_t Tc = (P + TILE - 1) / TILE;
+    const uint64_t G = (uint64_t)C * Tc;
+    uint32_t nwaves = (uint32_t)std::min<uint64_t>(max_waves, (G + MIN_SPAN - 1) / MIN_SPAN);
+    if (nwaves == 0) nwaves = 1;
+    return { Tc, (uint32_t)((G + nwaves - 1) / nwaves), nwaves };
+}
+// the part of the resolve kernel's arguments that every push fills the same way (launch_resolve adds the capture + decode side)
+ResolveArgs resolve_args(const amps_recc *h, const FrontGeom &g, uint32_t P)
+{
+    ResolveArgs ra{};
+    ra.det = h->det.get(); ra.detcount = h->detcount.get(); ra.max_chunks = h->max_chunks; ra.det_cap = h->det_cap;
+    ra.tiles_per_channel = g.Tc; ra.span = g.span; ra.sps = h->sps; ra.n_proc = h->n_done + P;
+    ra.next_allowed = h->next_allowed.get(); ra.pending = h->pending.get();
+    return ra;
+}
+
 int run_iq_device(amps_recc *h, const float2 *iq, uint64_t ld, uint32_t nsamp)
 {
     h->origin_locked = true;
@@ -496,24 +512,20 @@ int run_iq_device(amps_recc *h, const float2 *iq, uint64_t ld, uint32_t nsamp)
     hipStream_t s = h->stream;
     const uint32_t avail = h->r_prev + nsamp;
     const uint32_t P = (avail / 64) * 64, r_new = avail - P;
-    // geometry of the persistent front launch
-    const uint32_t Tc = (P + TILE - 1) / TILE;
-    const uint64_t G = (uint64_t)h->C * Tc;
-    uint32_t nwaves = (uint32_t)std::min<uint64_t>(h->max_waves, (G + MIN_SPAN - 1) / MIN_SPAN);
-    if (nwaves == 0) nwaves = 1;
-    const uint32_t span = (uint32_t)((G + nwaves - 1) / nwaves);
+    const FrontGeom geom = front_geometry(h->C, P, h->max_waves);
+    const uint32_t Tc = geom.Tc, span = geom.span, nwaves = geom.nwaves;
     if (P && (uint64_t)(Tc + span - 1) / span + 1 > h->max_chunks) return -E2BIG;
     if (P) {
         FrontArgs fa{};
-        fa.block = iq; fa.carry = h->carry[h->carry_cur]; fa.ld = ld;
+        fa.block = iq; fa.carry = h->carry[h->carry_cur].get(); fa.ld = ld;
         fa.r_prev = h->r_prev; fa.avail = avail; fa.P = P; fa.tiles_per_channel = Tc; fa.n_channels = h->C; fa.span = span;
-        fa.n_done = h->n_done; fa.gring = h->gring; fa.ring_mask = h->ring_words - 1; fa.ring_words = h->ring_words;
-        fa.det = h->det; fa.detcount = h->detcount; fa.max_chunks = h->max_chunks; fa.det_cap = h->det_cap;
+        fa.n_done = h->n_done; fa.gring = h->gring.get(); fa.ring_mask = h->ring_words - 1; fa.ring_words = h->ring_words;
+        fa.det = h->det.get(); fa.detcount = h->detcount.get(); fa.max_chunks = h->max_chunks; fa.det_cap = h->det_cap;
         fa.tol = h->cfg.sync_tolerance;
         fa.force_ones = ((h->slicer == AMPS_SLICER_PRODUCT || h->slicer == AMPS_SLICER_EXACT) && h->n_done == h->origin) ? h->sps : 0u;   // specs B, D: no partner yet
-        fa.status = h->status; fa.dbg_d = h->dbg_d; fa.dbg_S = h->dbg_S; fa.dbg_channel = 0;
+        fa.status = h->status; fa.dbg_d = h->dbg_d.get(); fa.dbg_S = h->dbg_S.get(); fa.dbg_channel = 0;
         front_housekeeping_args(h, fa);
-        fa.carry_out = h->carry[h->carry_cur ^ 1]; fa.carry_n = HALO + r_new;     // the next push's carry is written by the streaming kernel itself
+        fa.carry_out = h->carry[h->carry_cur ^ 1].get(); fa.carry_n = HALO + r_new;     // the next push's carry is written by the streaming kernel itself
         SpanGuard g(h, T_FRONT, P);
         if (debug_sync_enabled())
             std::fprintf(stderr, "amps_recc[debug]: front waves=%u span=%u Tc=%u C=%u P=%u avail=%u r_prev=%u ld=%llu n_done=%llu ring_words=%u max_chunks=%u det_cap=%u\n",
@@ -524,17 +536,14 @@ int run_iq_device(amps_recc *h, const float2 *iq, uint64_t ld, uint32_t nsamp)
     if (int rc = debug_sync(h, "front")) return rc;
     if (!P) {                                              // a push too short for a 64-sample word only moves the carry
         CarryArgs ca{};
-        ca.block = iq; ca.carry_in = h->carry[h->carry_cur]; ca.carry_out = h->carry[h->carry_cur ^ 1];
+        ca.block = iq; ca.carry_in = h->carry[h->carry_cur].get(); ca.carry_out = h->carry[h->carry_cur ^ 1].get();
         ca.ld = ld; ca.r_prev = h->r_prev; ca.avail = avail; ca.P = P; ca.r_new = r_new;
         SpanGuard g(h, T_CARRY);
         hipLaunchKernelGGL(recc_carry_kernel, dim3((HALO + r_new + 255) / 256, h->C), dim3(256), 0, s, ca);
     }
     if (int rc = debug_sync(h, "carry")) return rc;
     if (P) {
-        ResolveArgs ra{};
-        ra.det = h->det; ra.detcount = h->detcount; ra.max_chunks = h->max_chunks; ra.det_cap = h->det_cap;
-        ra.tiles_per_channel = Tc; ra.span = span; ra.sps = h->sps; ra.n_proc = h->n_done + P;
-        ra.next_allowed = h->next_allowed; ra.pending = h->pending;
+        ResolveArgs ra = resolve_args(h, geom, P);
         {
             SpanGuard g(h, T_RESOLVE);
             launch_resolve(h, ra, s);
@@ -647,29 +656,21 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
     const size_t C = h->C;
     step("stream created");
     // results + symbol seam (always present)
-    for (int b = 0; b < 2; b++) {   // {nrecords, status} of a list are adjacent: one 8-byte copy / memset serves both
-        rc |= dev_alloc(&h->nrecords_buf[b], LIST_WORDS);
-        h->status_buf[b] = h->nrecords_buf[b] ? h->nrecords_buf[b] + 1 : nullptr;
-    }
-    rc |= dev_alloc(&h->symbuf, C * AMPS_RECC_SYMBUF);
-    rc |= dev_alloc(&h->sym_len, C);
-    rc |= dev_alloc(&h->sym_cur, C);
-    rc |= dev_alloc(&h->sym_stage, C * (size_t)(AMPS_RECC_MAX_WORK_ITEMS + 1));
-    rc |= dev_alloc(&h->bursts_dev, (size_t)cfg->max_bursts * AMPS_RECC_CAPTURE_SYMS);
-    rc |= dev_alloc(&h->burst_chan_dev, cfg->max_bursts);
-    rc |= dev_alloc(&h->nbursts_dev, 1);
+    for (int b = 0; b < 2; b++) rc |= h->nrecords_buf[b].alloc(LIST_WORDS);
+    rc |= h->symbuf.alloc(C * AMPS_RECC_SYMBUF);
+    rc |= h->sym_len.alloc(C);
+    rc |= h->sym_cur.alloc(C);
+    rc |= h->sym_stage.alloc(C * (size_t)(AMPS_RECC_MAX_WORK_ITEMS + 1));
+    rc |= h->bursts_dev.alloc((size_t)cfg->max_bursts * AMPS_RECC_CAPTURE_SYMS);
+    rc |= h->burst_chan_dev.alloc(cfg->max_bursts);
+    rc |= h->nbursts_dev.alloc(1);
     step("symbol seam buffers allocated");
     // result records live in mapped, pinned host memory (zero copy: PACKED_RECORD_BYTES = 216 per burst over PCIe while the
     // kernels run, expanded to the ABI's 728 by drain_end_impl); h->records is the device-side view of the same allocation
-    for (int b = 0; b < 2; b++)
-        if (hipHostMalloc((void **)&h->rec_host_buf[b], sizeof(amps_recc_burst_t) * (size_t)cfg->max_bursts, hipHostMallocMapped) != hipSuccess ||
-            hipHostGetDevicePointer((void **)&h->records_buf[b], h->rec_host_buf[b], 0) != hipSuccess) rc |= -ENOMEM;
+    for (int b = 0; b < 2; b++) rc |= h->rec_buf[b].alloc(cfg->max_bursts);
     if (cfg->flags & AMPS_RECC_FLAG_KEEP_BURSTS)
-        for (int b = 0; b < 2; b++)
-            if (hipHostMalloc((void **)&h->bsym_host_buf[b], (size_t)cfg->max_bursts * AMPS_RECC_CAPTURE_SYMS, hipHostMallocMapped) != hipSuccess ||
-                hipHostGetDevicePointer((void **)&h->bsym_dev_buf[b], h->bsym_host_buf[b], 0) != hipSuccess) rc |= -ENOMEM;
-    if (hipHostMalloc((void **)&h->hdr_host, 2 * HDR_STRIDE * sizeof(uint32_t), hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&h->hdr_dev, h->hdr_host, 0) != hipSuccess) rc |= -ENOMEM;
+        for (int b = 0; b < 2; b++) rc |= h->bsym_buf[b].alloc((size_t)cfg->max_bursts * AMPS_RECC_CAPTURE_SYMS);
+    rc |= h->hdr.alloc(2 * HDR_STRIDE);
     if (hipEventCreateWithFlags(&h->drain_event, hipEventDisableTiming) != hipSuccess) rc |= -ENOMEM;
     if (!rc) select_record_list(h, 0);
     step("pinned record lists mapped");
@@ -693,22 +694,22 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
         const uint64_t max_span = std::max<uint64_t>(MIN_SPAN, (C * max_tiles + h->max_waves - 1) / h->max_waves);
         h->max_chunks = (uint32_t)(prop.multiProcessorCount * 32u / C + 3);   // bound for any occupancy
         h->det_cap = (uint32_t)(max_span * TILE / ((uint64_t)AMPS_RECC_TRIGGER_SYMS * h->sps) + 4);
-        rc |= dev_alloc(&h->carry[0], C * CARRY_CAP);
-        rc |= dev_alloc(&h->carry[1], C * CARRY_CAP);
-        rc |= dev_alloc(&h->gring, C * h->ring_words);
-        rc |= dev_alloc(&h->det, C * h->max_chunks * h->det_cap);
-        rc |= dev_alloc(&h->detcount, C * h->max_chunks);
-        rc |= dev_alloc(&h->next_allowed, C);
-        rc |= dev_alloc(&h->pending, C);
-        rc |= dev_alloc(&h->done_blocks, 1 + DONE_GROUPS);
-        if (resolve_uses_queue((uint32_t)C)) { rc |= dev_alloc(&h->capq, cfg->max_bursts); rc |= dev_alloc(&h->capq_count, 1); }
+        rc |= h->carry[0].alloc(C * CARRY_CAP);
+        rc |= h->carry[1].alloc(C * CARRY_CAP);
+        rc |= h->gring.alloc(C * h->ring_words);
+        rc |= h->det.alloc(C * h->max_chunks * h->det_cap);
+        rc |= h->detcount.alloc(C * h->max_chunks);
+        rc |= h->next_allowed.alloc(C);
+        rc |= h->pending.alloc(C);
+        rc |= h->done_blocks.alloc(1 + DONE_GROUPS);
+        if (resolve_uses_queue((uint32_t)C)) { rc |= h->capq.alloc(cfg->max_bursts); rc |= h->capq_count.alloc(1); }
     }
     step("IQ seam buffers allocated");
     if (!rc && cfg->wideband_channels) rc = channelizer_create(h->chz, *cfg, h->stream);
     step("channelizer created");
     if (!rc && (cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER)) {
         h->chz.pow_slots = 64u * h->ring_words / AMPS_RECC_POWER_STRIDE;         // the bit ring's window, a power of two (ring_words >= 32)
-        rc = dev_alloc(&h->chz.pow_ring, (size_t)h->chz.pow_slots * C);
+        rc = h->chz.pow_ring.alloc((size_t)h->chz.pow_slots * C);
         h->chan2row.assign(cfg->n_channels, -1);
         for (size_t r = 0; r < h->chz.row2chan.size(); r++) h->chan2row[h->chz.row2chan[r]] = (int32_t)r;
     }
@@ -725,19 +726,11 @@ void amps_recc_destroy(amps_recc_t *h)
     (void)hipSetDevice(h->device);
     if (h->stream) { (void)sync_stream(h, h->stream); (void)hipStreamSynchronize(h->stream); }   // bounded first: a dead peer must not hang the destructor
     collect_spans(h);
-    h->stage_iq_fence.destroy();
     for (hipEvent_t e : h->event_pool) (void)hipEventDestroy(e);
     h->event_pool.clear();
-    void *bufs[] = { h->carry[0], h->carry[1], h->gring, h->det, h->detcount, h->next_allowed, h->pending,
-                     h->done_blocks, h->capq, h->capq_count, h->nrecords_buf[0], h->nrecords_buf[1], h->stage_iq, h->symbuf, h->sym_len, h->sym_cur,
-                     h->sym_stage, h->bursts_dev, h->burst_chan_dev, h->nbursts_dev, h->dec_out_dev, h->dec_in_dev,
-                     h->dec_chan_dev, h->dbg_d, h->dbg_S, h->bch_in, h->bch_out, h->bch_val, h->bch_err, h->pq_dev, h->pq_out };
-    for (void *p : bufs) if (p) (void)hipFree(p);
-    for (int b = 0; b < 2; b++) if (h->rec_host_buf[b]) (void)hipHostFree(h->rec_host_buf[b]);
-    for (int b = 0; b < 2; b++) if (h->bsym_host_buf[b]) (void)hipHostFree(h->bsym_host_buf[b]);
     if (h->drain_event) (void)hipEventDestroy(h->drain_event);
-    if (h->hdr_host) (void)hipHostFree(h->hdr_host);
     rccl_destroy(h->rccl);
+    static_cast<amps_recc_mem &>(*h) = amps_recc_mem();      // every buffer of the handle's own seams; then the other seams' states
     channelizer_destroy(h->chz);
     xlate_destroy(h->xl);
     ref_destroy(h->ref);
@@ -753,7 +746,7 @@ int amps_recc_reset(amps_recc_t *h)
     HIP_TRY(hipStreamSynchronize(h->stream));
     collect_spans(h);
     h->rccl.stale = false;                    // a fresh stream: whatever an aborted collective left behind is gone
-    if (h->open_buf >= 0) { volatile uint32_t *hdr = h->hdr_host + HDR_STRIDE * h->open_buf; hdr[0] = 0u; hdr[1] = 0u; h->open_buf = -1; }
+    if (h->open_buf >= 0) { volatile uint32_t *hdr = h->hdr.host() + HDR_STRIDE * h->open_buf; hdr[0] = 0u; hdr[1] = 0u; h->open_buf = -1; }
     return reset_state(h);
 }
 
@@ -772,13 +765,13 @@ int amps_recc_push_symbols(amps_recc_t *h, const uint8_t *syms, size_t ld, int n
     uint64_t dld = ld;
     if (mem == AMPS_MEM_HOST) {
         dld = AMPS_RECC_MAX_WORK_ITEMS + 1;
-        HIP_TRY(hipMemcpy2DAsync(h->sym_stage, dld, syms, ld, (size_t)n, h->C, hipMemcpyHostToDevice, s));
-        dsyms = h->sym_stage;
+        HIP_TRY(hipMemcpy2DAsync(h->sym_stage.get(), dld, syms, ld, (size_t)n, h->C, hipMemcpyHostToDevice, s));
+        dsyms = h->sym_stage.get();
     }
-    HIP_TRY(hipMemsetAsync(h->nbursts_dev, 0, sizeof(uint32_t), s));
+    HIP_TRY(hipMemsetAsync(h->nbursts_dev.get(), 0, sizeof(uint32_t), s));
     SymbolsArgs a{};
-    a.syms = dsyms; a.ld = dld; a.n = n; a.symbuf = h->symbuf; a.len = h->sym_len; a.curstart = h->sym_cur;
-    a.bursts = h->bursts_dev; a.burst_chan = h->burst_chan_dev; a.nbursts = h->nbursts_dev;
+    a.syms = dsyms; a.ld = dld; a.n = n; a.symbuf = h->symbuf.get(); a.len = h->sym_len.get(); a.curstart = h->sym_cur.get();
+    a.bursts = h->bursts_dev.get(); a.burst_chan = h->burst_chan_dev.get(); a.nbursts = h->nbursts_dev.get();
     a.cap = h->cfg.max_bursts; a.status = h->status;
     {
         SpanGuard g(h, T_SYMBOLS);
@@ -786,7 +779,7 @@ int amps_recc_push_symbols(amps_recc_t *h, const uint8_t *syms, size_t ld, int n
     }
     HIP_TRY(hipGetLastError());
     uint32_t nb = 0;
-    HIP_TRY(hipMemcpyAsync(&nb, h->nbursts_dev, sizeof(nb), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&nb, h->nbursts_dev.get(), sizeof(nb), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     collect_spans(h);
     int rc = 0;
@@ -794,8 +787,8 @@ int amps_recc_push_symbols(amps_recc_t *h, const uint8_t *syms, size_t ld, int n
     if (nb == 0) return rc;
     std::vector<uint32_t> chan(nb);
     std::vector<uint8_t> data((size_t)nb * AMPS_RECC_CAPTURE_SYMS);
-    HIP_TRY(hipMemcpy(chan.data(), h->burst_chan_dev, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(data.data(), h->bursts_dev, data.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(chan.data(), h->burst_chan_dev.get(), sizeof(uint32_t) * nb, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(data.data(), h->bursts_dev.get(), data.size(), hipMemcpyDeviceToHost));
     std::vector<uint32_t> order(nb);
     for (uint32_t i = 0; i < nb; i++) order[i] = i;
     std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return chan[x] < chan[y]; });
@@ -816,33 +809,25 @@ int amps_recc_decode_bursts(amps_recc_t *h, const uint8_t *bursts, size_t nburst
     if (nbursts == 0) return 0;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    if (nbursts > h->dec_out_cap) {
-        if (h->dec_out_dev) (void)hipFree(h->dec_out_dev);
-        if (h->dec_in_dev) (void)hipFree(h->dec_in_dev);
-        if (h->dec_chan_dev) (void)hipFree(h->dec_chan_dev);
-        h->dec_out_dev = nullptr; h->dec_in_dev = nullptr; h->dec_chan_dev = nullptr; h->dec_out_cap = 0;
-        if (dev_alloc(&h->dec_out_dev, nbursts) || dev_alloc(&h->dec_in_dev, nbursts * AMPS_RECC_CAPTURE_SYMS) ||
-            dev_alloc(&h->dec_chan_dev, nbursts)) return -ENOMEM;
-        h->dec_out_cap = nbursts;
-    }
+    if (h->dec_out_dev.reserve(nbursts) || h->dec_in_dev.reserve(nbursts * AMPS_RECC_CAPTURE_SYMS) || h->dec_chan_dev.reserve(nbursts)) return -ENOMEM;
     const uint8_t *din = bursts;
     if (mem == AMPS_MEM_HOST) {
-        HIP_TRY(hipMemcpyAsync(h->dec_in_dev, bursts, nbursts * AMPS_RECC_CAPTURE_SYMS, hipMemcpyHostToDevice, s));
-        din = h->dec_in_dev;
+        HIP_TRY(hipMemcpyAsync(h->dec_in_dev.get(), bursts, nbursts * AMPS_RECC_CAPTURE_SYMS, hipMemcpyHostToDevice, s));
+        din = h->dec_in_dev.get();
     }
     const uint32_t *dchan = nullptr;
     if (burst_channel) {
-        HIP_TRY(hipMemcpyAsync(h->dec_chan_dev, burst_channel, nbursts * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        dchan = h->dec_chan_dev;
+        HIP_TRY(hipMemcpyAsync(h->dec_chan_dev.get(), burst_channel, nbursts * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        dchan = h->dec_chan_dev.get();
     }
     {
         SpanGuard g(h, T_DECODE);
         uint32_t grid = (uint32_t)std::min<size_t>(nbursts, 4096);
-        hipLaunchKernelGGL(recc_decode_bursts_kernel, dim3(grid), dim3(64), 0, s, din, dchan, (uint32_t)nbursts, h->dec_out_dev,
+        hipLaunchKernelGGL(recc_decode_bursts_kernel, dim3(grid), dim3(64), 0, s, din, dchan, (uint32_t)nbursts, h->dec_out_dev.get(),
                            (h->cfg.flags & AMPS_RECC_FLAG_MAJORITY) ? 1u : 0u);
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, h->dec_out_dev, nbursts * sizeof(amps_recc_burst_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out, h->dec_out_dev.get(), nbursts * sizeof(amps_recc_burst_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     collect_spans(h);
     return 0;
@@ -861,23 +846,10 @@ int amps_recc_push_iq(amps_recc_t *h, const float *iq, size_t ld, size_t nsamp, 
     const float2 *d = (const float2 *)iq;
     uint64_t dld = ld;
     if (mem == AMPS_MEM_HOST) {
-        if (int rc = h->stage_iq_fence.wait()) return rc;         // the previous push may still be reading the staging buffer
-        if (h->stage_iq_samples < (size_t)h->C * h->cfg.max_samples_per_push) {
-            if (h->stage_iq) (void)hipFree(h->stage_iq);
-            h->stage_iq = nullptr; h->stage_iq_samples = 0;
-            if (dev_alloc(&h->stage_iq, (size_t)h->C * h->cfg.max_samples_per_push)) return -ENOMEM;
-            h->stage_iq_samples = (size_t)h->C * h->cfg.max_samples_per_push;
-        }
-        dld = nsamp;
-        // synchronous on purpose: an async copy from pageable memory can return before the source has been read (the
-        // fuzzer caught blocks freed right after the call being copied late); the fence above has already made sure
-        // nobody is reading the staging buffer, and the kernels below are enqueued after the copy has completed
-        HIP_TRY(hipMemcpy2D(h->stage_iq, dld * sizeof(float2), iq, ld * sizeof(float2), nsamp * sizeof(float2),
-                            h->C, hipMemcpyHostToDevice));
-        d = h->stage_iq;
+        if (int rc = h->stage_iq.stage(d, ld, nsamp, h->C, (size_t)h->C * h->cfg.max_samples_per_push, &d, &dld)) return rc;
     }
     int rc = run_iq_device(h, d, dld, (uint32_t)nsamp);
-    if (!rc && mem == AMPS_MEM_HOST) rc = h->stage_iq_fence.arm(h->stream);
+    if (!rc && mem == AMPS_MEM_HOST) rc = h->stage_iq.arm(h->stream);
     return rc;
 }
 
@@ -887,19 +859,14 @@ int run_bits_device(amps_recc *h, uint32_t P)
 {
     if (P == 0) return 0;
     hipStream_t s = h->stream;
-    const uint32_t Tc = (P + TILE - 1) / TILE;
-    const uint64_t G = (uint64_t)h->C * Tc;
-    uint32_t nwaves = (uint32_t)std::min<uint64_t>(h->max_waves_bits, (G + MIN_SPAN - 1) / MIN_SPAN);
-    if (nwaves == 0) nwaves = 1;
-    const uint32_t span = (uint32_t)((G + nwaves - 1) / nwaves);
+    const FrontGeom geom = front_geometry(h->C, P, h->max_waves_bits);
+    const uint32_t Tc = geom.Tc, span = geom.span, nwaves = geom.nwaves;
     if (search_in_resolve(h)) {
         // round 6: ONE launch -- every channel's workgroup searches its own slicer bits (a quarter of the push per wave, hits in LDS),
         // then resolves, captures and decodes them as ever; the launch's housekeeping goes with it
         FrontArgs hk{};
         front_housekeeping_args(h, hk);
-        ResolveArgs ra{};
-        ra.tiles_per_channel = Tc; ra.span = span; ra.sps = h->sps; ra.n_proc = h->n_done + P;
-        ra.next_allowed = h->next_allowed; ra.pending = h->pending;
+        ResolveArgs ra = resolve_args(h, geom, P);      // (det and detcount go unread: this form keeps its hits in LDS)
         ra.search_P = P; ra.search_tol = h->cfg.sync_tolerance; ra.zero1 = hk.zero1; ra.zero2 = hk.zero2;
         {
             SpanGuard g(h, T_RESOLVE);
@@ -912,8 +879,8 @@ int run_bits_device(amps_recc *h, uint32_t P)
     if ((uint64_t)(Tc + span - 1) / span + 1 > h->max_chunks) return -E2BIG;
     FrontArgs fa{};
     fa.r_prev = 0; fa.avail = P; fa.P = P; fa.tiles_per_channel = Tc; fa.n_channels = h->C; fa.span = span;
-    fa.n_done = h->n_done; fa.gring = h->gring; fa.ring_mask = h->ring_words - 1; fa.ring_words = h->ring_words;
-    fa.det = h->det; fa.detcount = h->detcount; fa.max_chunks = h->max_chunks; fa.det_cap = h->det_cap; fa.status = h->status;
+    fa.n_done = h->n_done; fa.gring = h->gring.get(); fa.ring_mask = h->ring_words - 1; fa.ring_words = h->ring_words;
+    fa.det = h->det.get(); fa.detcount = h->detcount.get(); fa.max_chunks = h->max_chunks; fa.det_cap = h->det_cap; fa.status = h->status;
     fa.tol = h->cfg.sync_tolerance;
     front_housekeeping_args(h, fa);
     {
@@ -927,10 +894,7 @@ int run_bits_device(amps_recc *h, uint32_t P)
             if (FILE *f = std::fopen(path, "wb")) { unsigned long long nw = nwaves; std::fwrite(&nw, 8, 1, f); std::fwrite(tl.data(), 8, tl.size(), f); std::fclose(f); }
     }
 #endif
-    ResolveArgs ra{};
-    ra.det = h->det; ra.detcount = h->detcount; ra.max_chunks = h->max_chunks; ra.det_cap = h->det_cap;
-    ra.tiles_per_channel = Tc; ra.span = span; ra.sps = h->sps; ra.n_proc = h->n_done + P;
-    ra.next_allowed = h->next_allowed; ra.pending = h->pending;
+    ResolveArgs ra = resolve_args(h, geom, P);
     {
         SpanGuard g(h, T_RESOLVE);
         launch_resolve(h, ra, s);
@@ -958,8 +922,11 @@ int push_wideband_block(amps_recc_t *h, const void *iq, size_t nsamp, int mem, b
     int rc;
     {
         SpanGuard g(h, T_CHANNELIZER, nsamp);
-        rc = channelizer_run(h->chz, iq, nsamp, mem, h->stream, &chan_iq, &ld, &nout, fused, h->gring, h->ring_words, h->n_done, h->slicer,
-                             SpanGuard::end_cb, &g, sc16);
+        ChzRunIn in;
+        in.iq = iq; in.nsamp = nsamp; in.mem = mem; in.sc16 = sc16; in.fused = fused;
+        in.gring = h->gring.get(); in.ring_words = h->ring_words; in.n_done = h->n_done; in.slicer = h->slicer;
+        in.after_main = SpanGuard::end_cb; in.after_ctx = &g;
+        rc = channelizer_run(h->chz, in, h->stream, &chan_iq, &ld, &nout);
     }
     if (rc) return rc;
     if (nout > h->cfg.max_samples_per_push) return -E2BIG;
@@ -1196,16 +1163,13 @@ int amps_recc_refchain_symbols(amps_recc_t *h, const float *iq, size_t ld, size_
     if (sym_ld < h->ref.sym_cap && sym_ld < nsamp / 9 + 16) return -EINVAL;
     const float2 *d = (const float2 *)iq;
     uint64_t dld = ld;
-    if (mem == AMPS_MEM_HOST && nsamp) {
-        if (!h->ref.stage && dev_alloc(&h->ref.stage, (size_t)h->C * h->cfg.max_samples_per_push)) return -ENOMEM;
-        dld = nsamp;
-        HIP_TRY(hipMemcpy2D(h->ref.stage, dld * sizeof(float2), iq, ld * sizeof(float2), nsamp * sizeof(float2), h->C, hipMemcpyHostToDevice));
-        d = h->ref.stage;
+    if (mem == AMPS_MEM_HOST && nsamp) {   // (never armed: the call ends with the stream idle)
+        if (int rc = h->ref.stage.stage(d, ld, nsamp, h->C, (size_t)h->C * h->cfg.max_samples_per_push, &d, &dld)) return rc;
     }
     if (int rc = ref_run(h->ref, d, dld, (uint32_t)nsamp, s)) return rc;
-    HIP_TRY(hipMemcpyAsync(nsym_out, h->ref.nsym, sizeof(uint32_t) * h->C, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(nsym_out, h->ref.nsym.get(), sizeof(uint32_t) * h->C, hipMemcpyDeviceToHost, s));
     const size_t w = std::min<size_t>(sym_ld, h->ref.sym_cap);
-    HIP_TRY(hipMemcpy2DAsync(symbols_out, sym_ld, h->ref.syms, h->ref.sym_cap, w, h->C, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpy2DAsync(symbols_out, sym_ld, h->ref.syms.get(), h->ref.sym_cap, w, h->C, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return 0;
 }
@@ -1251,7 +1215,7 @@ int amps_recc_drain_begin(amps_recc_t *h)
     h->open_untouched = true;
     select_record_list(h, b ^ 1);           // later pushes append to the other list
     if (!h->list_clean[b ^ 1]) {            // drained twice with no push in between: nobody has cleared it yet
-        HIP_TRY(hipMemsetAsync(h->nrecords_buf[b ^ 1], 0, LIST_WORDS * sizeof(uint32_t), s));
+        HIP_TRY(hipMemsetAsync(h->nrecords_buf[b ^ 1].get(), 0, LIST_WORDS * sizeof(uint32_t), s));
         h->list_clean[b ^ 1] = true;
     }
     return 0;
@@ -1277,7 +1241,7 @@ static int drain_end_impl(amps_recc_t *h, amps_recc_burst_t *out, uint8_t *burst
     *nout = 0;
     if (h->open_buf < 0) return -EINVAL;
     const int b = h->open_buf;
-    volatile uint32_t *hdr = h->hdr_host + HDR_STRIDE * b;
+    volatile uint32_t *hdr = h->hdr.host() + HDR_STRIDE * b;
     // an error below still CLOSES the split drain (and empties the list's header): a handle must not answer -EBUSY for ever
     // because one drain failed
     auto fail = [&](int rc) { hdr[0] = 0u; hdr[1] = 0u; h->open_buf = -1; return rc; };
@@ -1289,7 +1253,7 @@ static int drain_end_impl(amps_recc_t *h, amps_recc_burst_t *out, uint8_t *burst
     const uint32_t st = hdr[1];
     if (check_header_enabled() && h->open_untouched) {
         uint32_t dev[2] = { 0u, 0u };
-        if (hipMemcpy(dev, h->nrecords_buf[b], sizeof(dev), hipMemcpyDeviceToHost) != hipSuccess) return fail(-EIO);
+        if (hipMemcpy(dev, h->nrecords_buf[b].get(), sizeof(dev), hipMemcpyDeviceToHost) != hipSuccess) return fail(-EIO);
         if (dev[0] != n || dev[1] != st) {
             std::fprintf(stderr, "amps_recc: published list header {%u, %u} differs from the device counters {%u, %u}\n", n, st, dev[0], dev[1]);
             return fail(-EIO);
@@ -1306,7 +1270,7 @@ static int drain_end_impl(amps_recc_t *h, amps_recc_burst_t *out, uint8_t *burst
         struct Key { uint64_t k; uint32_t i; };
         std::vector<Key> keys(n);
         // (packed: PACKED_RECORD_BYTES each, the bit arrays as bits -- recc_decode.hip.h; channel and position sit in the first 16 bytes)
-        const uint8_t *r = (const uint8_t *)h->rec_host_buf[b];
+        const uint8_t *r = (const uint8_t *)h->rec_buf[b].host();
         for (uint32_t i = 0; i < n; i++) {
             uint32_t ch; uint64_t pos;
             std::memcpy(&ch, r + (size_t)i * PACKED_RECORD_BYTES + offsetof(amps_recc_burst_t, channel), 4);
@@ -1318,9 +1282,9 @@ static int drain_end_impl(amps_recc_t *h, amps_recc_burst_t *out, uint8_t *burst
         if (out) for (size_t i = 0; i < k; i++) expand_packed_record(&out[i], r + (size_t)keys[i].i * PACKED_RECORD_BYTES);
         if (out && h->chz.enabled && h->chz.groups > 1)               // rows of a channel group -> channel numbers of the band selection
             for (size_t i = 0; i < k; i++) out[i].channel = out[i].channel < h->chz.row2chan.size() ? h->chz.row2chan[out[i].channel] : out[i].channel;
-        if (bursts_out && h->bsym_host_buf[b])
+        if (bursts_out && h->bsym_buf[b])
             for (size_t i = 0; i < k; i++)
-                expand_packed_burst(bursts_out + i * AMPS_RECC_CAPTURE_SYMS, h->bsym_host_buf[b] + (size_t)keys[i].i * PACKED_BURST_BYTES);
+                expand_packed_burst(bursts_out + i * AMPS_RECC_CAPTURE_SYMS, h->bsym_buf[b].host() + (size_t)keys[i].i * PACKED_BURST_BYTES);
         *nout = k;
         if (n > cap) rc = -ENOSPC;
     }
@@ -1371,7 +1335,7 @@ int amps_recc_debug_demod(amps_recc_t *h, const float *iq, size_t nsamp, int mem
     int rc = amps_recc_reset(h);
     if (rc) return rc;
     const size_t P = (nsamp / 64) * 64;
-    if (dev_alloc(&h->dbg_d, nsamp) || dev_alloc(&h->dbg_S, nsamp)) return -ENOMEM;
+    if (h->dbg_d.alloc(nsamp) || h->dbg_S.alloc(nsamp)) { h->dbg_d.reset(); h->dbg_S.reset(); return -ENOMEM; }   // no tap may outlive the call
     // channel 0 only: replicate the single stream on every channel row is not needed, rows other than 0 read garbage-free zeros
     std::vector<float> zeros;
     const float *src = iq;
@@ -1388,17 +1352,16 @@ int amps_recc_debug_demod(amps_recc_t *h, const float *iq, size_t nsamp, int mem
         if (hipStreamSynchronize(h->stream) != hipSuccess) rc = -EIO;
     }
     if (!rc && P) {
-        if (demod && hipMemcpy(demod, h->dbg_d, P * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) rc = -EIO;
-        if (soft && hipMemcpy(soft, h->dbg_S, P * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) rc = -EIO;
+        if (demod && hipMemcpy(demod, h->dbg_d.get(), P * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) rc = -EIO;
+        if (soft && hipMemcpy(soft, h->dbg_S.get(), P * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) rc = -EIO;
         if (hard) {
             std::vector<uint64_t> ring(h->ring_words);
-            if (hipMemcpy(ring.data(), h->gring, sizeof(uint64_t) * h->ring_words, hipMemcpyDeviceToHost) != hipSuccess) rc = -EIO;
+            if (hipMemcpy(ring.data(), h->gring.get(), sizeof(uint64_t) * h->ring_words, hipMemcpyDeviceToHost) != hipSuccess) rc = -EIO;
             for (size_t i = 0; i < P; i++) hard[i] = (uint8_t)((ring[(i >> 6) & (h->ring_words - 1)] >> (i & 63)) & 1ull);
         }
     }
 done:
-    (void)hipFree(h->dbg_d); (void)hipFree(h->dbg_S);
-    h->dbg_d = nullptr; h->dbg_S = nullptr;
+    h->dbg_d.reset(); h->dbg_S.reset();
     {
         int rc2 = amps_recc_reset(h);
         if (!rc) rc = rc2;
@@ -1414,7 +1377,9 @@ int amps_recc_debug_channelize(amps_recc_t *h, const float *iq, size_t nsamp, in
     const float2 *chan_iq = nullptr;
     uint64_t ld = 0;
     uint32_t nout = 0;
-    int rc = channelizer_run(h->chz, (const float2 *)iq, nsamp, mem, h->stream, &chan_iq, &ld, &nout);
+    ChzRunIn in;                                             // the unfused form on fc32: the channel-major block is the output
+    in.iq = iq; in.nsamp = nsamp; in.mem = mem;
+    int rc = channelizer_run(h->chz, in, h->stream, &chan_iq, &ld, &nout);
     if (rc) return rc;
     *nframes = nout;
     if (nout > out_ld) return -E2BIG;
@@ -1443,9 +1408,9 @@ int amps_recc_debug_slicer_bits(amps_recc_t *h, uint64_t first, size_t n, uint8_
     const uint64_t w0 = first >> 6, nw = ((first + n - 1) >> 6) - w0 + 1;      // <= ring_words
     const uint64_t s0 = w0 & (h->ring_words - 1), n1 = std::min<uint64_t>(nw, h->ring_words - s0);
     std::vector<uint64_t> words((size_t)h->C * nw);
-    HIP_TRY(hipMemcpy2DAsync(words.data(), nw * 8, h->gring + s0, (size_t)h->ring_words * 8, n1 * 8, h->C, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpy2DAsync(words.data(), nw * 8, h->gring.get() + s0, (size_t)h->ring_words * 8, n1 * 8, h->C, hipMemcpyDeviceToHost, h->stream));
     if (nw > n1)                                                                 // the range wraps round the ring's end
-        HIP_TRY(hipMemcpy2DAsync(words.data() + n1, nw * 8, h->gring, (size_t)h->ring_words * 8, (nw - n1) * 8, h->C, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpy2DAsync(words.data() + n1, nw * 8, h->gring.get(), (size_t)h->ring_words * 8, (nw - n1) * 8, h->C, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     for (size_t c = 0; c < h->C; c++) {
         const uint64_t *w = words.data() + c * nw;
@@ -1483,8 +1448,8 @@ int amps_recc_channel_power(amps_recc_t *h, uint64_t first_snap, size_t n, float
     const uint32_t slots = h->chz.pow_slots;
     const size_t C = h->C, s0 = (size_t)(first_snap & (slots - 1)), n1 = std::min<size_t>(n, slots - s0);
     std::vector<float> snap(n * C);
-    HIP_TRY(hipMemcpyAsync(snap.data(), h->chz.pow_ring + s0 * C, sizeof(float) * n1 * C, hipMemcpyDeviceToHost, h->stream));
-    if (n > n1) HIP_TRY(hipMemcpyAsync(snap.data() + n1 * C, h->chz.pow_ring, sizeof(float) * (n - n1) * C, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(snap.data(), h->chz.pow_ring.get() + s0 * C, sizeof(float) * n1 * C, hipMemcpyDeviceToHost, h->stream));
+    if (n > n1) HIP_TRY(hipMemcpyAsync(snap.data() + n1 * C, h->chz.pow_ring.get(), sizeof(float) * (n - n1) * C, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     for (size_t c = 0; c < C; c++)
         for (size_t i = 0; i < n; i++) out[c * out_ld + i] = snap[i * C + c];
@@ -1505,21 +1470,15 @@ int amps_recc_burst_power(amps_recc_t *h, const amps_recc_burst_t *recs, size_t 
     }
     HIP_TRY(hipSetDevice(h->device));
     if (int rc = sync_stream(h, h->stream)) return rc;            // the window is that of an idle stream; the copies below are synchronous
-    if (h->pq_cap < n) {
-        if (h->pq_dev) (void)hipFree(h->pq_dev);
-        if (h->pq_out) (void)hipFree(h->pq_out);
-        h->pq_dev = nullptr; h->pq_out = nullptr; h->pq_cap = 0;
-        if (dev_alloc(&h->pq_dev, n) || dev_alloc(&h->pq_out, n)) return -ENOMEM;
-        h->pq_cap = n;
-    }
+    if (h->pq_dev.reserve(n) || h->pq_out.reserve(n)) return -ENOMEM;
     uint64_t lo, hi;
     power_window(h, &lo, &hi);
-    HIP_TRY(hipMemcpy(h->pq_dev, q.data(), sizeof(ChzBurstQuery) * n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(chz_power_gather_kernel, dim3((uint32_t)((n + 3) / 4)), dim3(256), 0, h->stream, h->chz.pow_ring, h->C, h->chz.pow_slots - 1, lo, hi,
-                       (uint32_t)AMPS_RECC_CAPTURE_SYMS * h->sps, h->pq_dev, (uint32_t)n, h->pq_out);
+    HIP_TRY(hipMemcpy(h->pq_dev.get(), q.data(), sizeof(ChzBurstQuery) * n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(chz_power_gather_kernel, dim3((uint32_t)((n + 3) / 4)), dim3(256), 0, h->stream, h->chz.pow_ring.get(), h->C, h->chz.pow_slots - 1, lo, hi,
+                       (uint32_t)AMPS_RECC_CAPTURE_SYMS * h->sps, h->pq_dev.get(), (uint32_t)n, h->pq_out.get());
     HIP_TRY(hipGetLastError());
     std::vector<uint2> res(n);
-    HIP_TRY(hipMemcpyAsync(res.data(), h->pq_out, sizeof(uint2) * n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(res.data(), h->pq_out.get(), sizeof(uint2) * n, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     for (size_t i = 0; i < n; i++) { std::memcpy(&mean_power[i], &res[i].x, sizeof(float)); n_snaps[i] = res[i].y; }
     return 0;
@@ -1579,22 +1538,17 @@ int amps_recc_get_timing(amps_recc_t *h, amps_recc_timing_t *t, int reset)
 
 // ---- BCH(63,51) shortened: batch encode / decode on the device
 // scratch buffers live in the handle and only ever grow: a call costs one launch, its copies and one synchronise
-static int bch_grow(uint8_t **p, size_t *cap, size_t need)
+static int bch_grow(DevBuf<uint8_t> &b, size_t need)
 {
-    if (need <= *cap) return 0;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; *cap = 0;
-    size_t want = need < 4096 ? 4096 : need + need / 2;
-    if (hipMalloc((void **)p, want) != hipSuccess) return -ENOMEM;
-    *cap = want;
-    return 0;
+    if (need <= b.capacity()) return 0;
+    return b.reserve(need < 4096 ? 4096 : need + need / 2);
 }
 static int bch_stage_in(amps_recc_t *h, const uint8_t *in, size_t nin, int mem, const uint8_t **din)
 {
     if (mem == AMPS_MEM_DEVICE) { *din = in; return 0; }
-    if (int rc = bch_grow(&h->bch_in, &h->bch_in_cap, nin)) return rc;
-    if (hipMemcpyAsync(h->bch_in, in, nin, hipMemcpyHostToDevice, h->stream) != hipSuccess) return -EIO;
-    *din = h->bch_in;
+    if (int rc = bch_grow(h->bch_in, nin)) return rc;
+    if (hipMemcpyAsync(h->bch_in.get(), in, nin, hipMemcpyHostToDevice, h->stream) != hipSuccess) return -EIO;
+    *din = h->bch_in.get();
     return 0;
 }
 
@@ -1606,10 +1560,10 @@ int amps_bch_encode_words(amps_recc_t *h, const uint8_t *msg, size_t nwords, int
     const uint8_t *din = nullptr;
     if (int rc = bch_stage_in(h, msg, nwords * k, mem, &din)) return rc;
     const size_t nout = nwords * (size_t)(k + 12);
-    if (int rc = bch_grow(&h->bch_out, &h->bch_out_cap, nout)) return rc;
+    if (int rc = bch_grow(h->bch_out, nout)) return rc;
     hipLaunchKernelGGL(bch_encode_words_kernel, dim3((unsigned)std::min<size_t>((nwords + 255) / 256, 4096)), dim3(256), 0, h->stream,
-                       din, (uint32_t)nwords, k, h->bch_out);
-    HIP_TRY(hipMemcpyAsync(codewords, h->bch_out, nout, hipMemcpyDeviceToHost, h->stream));
+                       din, (uint32_t)nwords, k, h->bch_out.get());
+    HIP_TRY(hipMemcpyAsync(codewords, h->bch_out.get(), nout, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return 0;
 }
@@ -1621,17 +1575,13 @@ int amps_bch_decode_words(amps_recc_t *h, const uint8_t *codewords, size_t nword
     HIP_TRY(hipSetDevice(h->device));
     const uint8_t *din = nullptr;
     if (int rc = bch_stage_in(h, codewords, nwords * (size_t)(k + 12), mem, &din)) return rc;
-    if (int rc = bch_grow(&h->bch_out, &h->bch_out_cap, nwords * (size_t)k)) return rc;
-    if (nwords > h->bch_n_cap) {
-        size_t c1 = h->bch_n_cap, c2 = h->bch_n_cap;
-        if (bch_grow(&h->bch_val, &c1, nwords) || bch_grow(&h->bch_err, &c2, nwords)) { h->bch_n_cap = 0; return -ENOMEM; }
-        h->bch_n_cap = std::min(c1, c2);
-    }
+    if (int rc = bch_grow(h->bch_out, nwords * (size_t)k)) return rc;
+    if (bch_grow(h->bch_val, nwords) || bch_grow(h->bch_err, nwords)) return -ENOMEM;
     hipLaunchKernelGGL(bch_decode_words_kernel, dim3((unsigned)std::min<size_t>((nwords + 255) / 256, 4096)), dim3(256), 0, h->stream,
-                       din, (uint32_t)nwords, k, h->bch_out, h->bch_val, h->bch_err);
-    HIP_TRY(hipMemcpyAsync(msg, h->bch_out, nwords * k, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(valid, h->bch_val, nwords, hipMemcpyDeviceToHost, h->stream));
-    if (nerrors) HIP_TRY(hipMemcpyAsync(nerrors, h->bch_err, nwords, hipMemcpyDeviceToHost, h->stream));
+                       din, (uint32_t)nwords, k, h->bch_out.get(), h->bch_val.get(), h->bch_err.get());
+    HIP_TRY(hipMemcpyAsync(msg, h->bch_out.get(), nwords * k, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(valid, h->bch_val.get(), nwords, hipMemcpyDeviceToHost, h->stream));
+    if (nerrors) HIP_TRY(hipMemcpyAsync(nerrors, h->bch_err.get(), nwords, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return 0;
 }

@@ -30,31 +30,9 @@
 #include <vector>
 #include "amps_recc.h"
 #include "amps_recc_numerics.h"
+#include "recc_devmem.hip.h"
 
 namespace amps {
-
-// Guard of a device staging buffer for host-resident input.  Copies from pageable host memory are neither ordered after
-// earlier kernels of a non-blocking stream nor guaranteed to have read their source when an Async call returns, so
-// back-to-back pushes without a drain in between corrupted samples (found by scripts/fuzz_parity.py: intermittent wrong
-// slicer bits).  Host pushes therefore: wait() until the previous push's kernels have released the staging buffer,
-// copy synchronously, enqueue the kernels, arm().
-struct StageFence {
-    hipEvent_t ev = nullptr;
-    bool armed = false;
-    int wait()
-    {
-        if (armed) { if (hipEventSynchronize(ev) != hipSuccess) return -EIO; armed = false; }
-        return 0;
-    }
-    int arm(hipStream_t s)
-    {
-        if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return -ENOMEM;
-        if (hipEventRecord(ev, s) != hipSuccess) return -EIO;
-        armed = true;
-        return 0;
-    }
-    void destroy() { if (ev) (void)hipEventDestroy(ev); ev = nullptr; armed = false; }
-};
 
 constexpr int CHZ_M = 1024;          // branches = FFT size
 constexpr int CHZ_D = 512;           // input samples per frame of the default form (2x oversampled: 60 ksps per channel, 3 samples per symbol)
@@ -1093,24 +1071,21 @@ struct ChannelizerState {
     int D = CHZ_D;                  // input samples per frame: 512 (3 samples per symbol) or 768 (2)
     uint32_t C = 0, first_bin = 0;  // rows this handle decodes (= the band's channels, or one group of them), FFT bin of the band's channel 0
     uint32_t groups = 1, group = 0; // cfg.wideband_groups / wideband_group
-    uint16_t *bin2row = nullptr;    // device [M]
+    DevBuf<uint16_t> bin2row;       // device [M]
     std::vector<uint32_t> row2chan; // row -> channel number within the band selection (what the records carry)
     uint32_t max_frames = 0;        // per push
     uint32_t target_wgs = 256;      // resident workgroups of the filter-bank kernel (one 768-thread workgroup per CU)
-    float *taps = nullptr;          // [L]
-    float2 *carry[2] = { nullptr, nullptr };
+    DevBuf<float> taps;             // [L]
+    DevBuf<float2> carry[2];
     int carry_cur = 0;
     uint32_t carry_len = 0;         // L - D + leftover
     uint64_t frames_done = 0;
-    float2 *out = nullptr;          // [C][ld]
+    DevBuf<float2> out;             // [C][ld]
     uint64_t ld = 0;
-    void *stage = nullptr;          // device staging for host-resident wideband input, as the caller's samples (fc32 or sc16)
-    size_t stage_bytes = 0;
-    float2 *cvt = nullptr;          // an sc16 block expanded to fc32: the checking modes and the pre-pass experiment only
-    size_t cvt_samples = 0;
+    HostStage stage;                // host-resident wideband input as the caller's samples (fc32 or sc16), sized in bytes: the largest block so far
+    DevBuf<float2> cvt;             // an sc16 block expanded to fc32: the checking modes and the pre-pass experiment only
     bool short_prepass = false;     // AMPS_RECC_SHORT_PREPASS=1 at create: sc16 blocks go through chz_short_to_float_kernel + the fc32 kernel
-    StageFence stage_fence;
-    float *pow_ring = nullptr;      // AMPS_RECC_FLAG_CHANNEL_POWER: [pow_slots][C] power snapshots (recc_power.hip.h), else null
+    DevBuf<float> pow_ring;         // AMPS_RECC_FLAG_CHANNEL_POWER: [pow_slots][C] power snapshots (recc_power.hip.h), else null
     uint32_t pow_slots = 0;         // snapshots held per row: the bit ring's span / AMPS_RECC_POWER_STRIDE (a power of two)
 };
 // recc_power.hip.h: the snapshot frames of a fused filter-bank launch, from that launch's own arguments
@@ -1155,21 +1130,15 @@ inline int channelizer_reset(ChannelizerState &z, hipStream_t s)
 {
     if (!z.enabled) return 0;
     const size_t cap = chz_carry_cap(z.P, z.D);
-    if (hipMemsetAsync(z.carry[0], 0, sizeof(float2) * cap, s) != hipSuccess) return -EIO;
-    if (hipMemsetAsync(z.carry[1], 0, sizeof(float2) * cap, s) != hipSuccess) return -EIO;
+    if (hipMemsetAsync(z.carry[0].get(), 0, sizeof(float2) * cap, s) != hipSuccess) return -EIO;
+    if (hipMemsetAsync(z.carry[1].get(), 0, sizeof(float2) * cap, s) != hipSuccess) return -EIO;
     z.carry_cur = 0;
     z.carry_len = chz_hist(z.P, z.D);                // all-zero history, no leftover
     z.frames_done = 0;
     return 0;
 }
 
-inline void channelizer_destroy(ChannelizerState &z)
-{
-    z.stage_fence.destroy();
-    void *bufs[] = { z.taps, z.carry[0], z.carry[1], z.out, z.stage, z.cvt, z.bin2row, z.pow_ring };
-    for (void *p : bufs) if (p) (void)hipFree(p);
-    z = ChannelizerState();
-}
+inline void channelizer_destroy(ChannelizerState &z) { z = ChannelizerState(); }
 
 // bins and rows of a handle: row i = the i-th channel (in band order) of the band selection [first, first + n) that belongs to the
 // handle's group -- all of them without groups.  Returns the row count, or a negative errno for an invalid split.
@@ -1203,16 +1172,15 @@ inline int channelizer_create(ChannelizerState &z, const amps_recc_cfg_t &cfg, h
     if (rows < 1) return rows < 0 ? rows : -EINVAL;
     z.P = P; z.D = (int)cfg.wideband_decim; z.C = (uint32_t)rows; z.first_bin = cfg.wideband_first_channel;
     z.groups = cfg.wideband_groups > 1 ? cfg.wideband_groups : 1u; z.group = cfg.wideband_group;
-    if (hipMalloc((void **)&z.bin2row, sizeof(uint16_t) * CHZ_M) != hipSuccess) return -ENOMEM;
-    if (hipMemcpy(z.bin2row, b2r.data(), sizeof(uint16_t) * CHZ_M, hipMemcpyHostToDevice) != hipSuccess) return -EIO;
+    if (z.bin2row.alloc(CHZ_M)) return -ENOMEM;
+    if (hipMemcpy(z.bin2row.get(), b2r.data(), sizeof(uint16_t) * CHZ_M, hipMemcpyHostToDevice) != hipSuccess) return -EIO;
     z.max_frames = cfg.max_samples_per_push;
     z.ld = ((uint64_t)z.max_frames + 7) & ~7ull;
     const size_t L = (size_t)P * CHZ_M;
     std::vector<float> h = chz_design_taps(P, z.D);
-    if (hipMalloc((void **)&z.taps, sizeof(float) * L) != hipSuccess) return -ENOMEM;
-    if (hipMemcpy(z.taps, h.data(), sizeof(float) * L, hipMemcpyHostToDevice) != hipSuccess) return -EIO;
-    if (hipMalloc((void **)&z.carry[0], sizeof(float2) * chz_carry_cap(P, z.D)) != hipSuccess) return -ENOMEM;
-    if (hipMalloc((void **)&z.carry[1], sizeof(float2) * chz_carry_cap(P, z.D)) != hipSuccess) return -ENOMEM;
+    if (z.taps.alloc(L)) return -ENOMEM;
+    if (hipMemcpy(z.taps.get(), h.data(), sizeof(float) * L, hipMemcpyHostToDevice) != hipSuccess) return -EIO;
+    if (z.carry[0].alloc(chz_carry_cap(P, z.D)) || z.carry[1].alloc(chz_carry_cap(P, z.D))) return -ENOMEM;
     // z.out (the channel-major block, C x ld x 8 B: 1.7 GB for a full band at 2^18 frames per push) is allocated by the first
     // unfused / debug run: the fused form never touches it
     {
@@ -1230,72 +1198,62 @@ inline int channelizer_create(ChannelizerState &z, const amps_recc_cfg_t &cfg, h
 typedef void (*chz_kernel_t)(ChzArgs);
 // the filter-bank instantiation for (input samples per frame, fused slicer or channel-major IQ out, slicer spec, sample type of the
 // block: fc32, or sc16 read in place -- fused form only)
-inline chz_kernel_t chz12_kernel_for(int D, bool fused, int slicer, bool sc16 = false)
+template <int DEC, bool SHORT, int MODE> chz_kernel_t chz12_kernel_of()
 {
-    if (sc16) {
-        if (!fused) return nullptr;
-        if (D == CHZ_D768) {
-            switch (slicer) {
-            case AMPS_SLICER_PRODUCT: return chz12_short_kernel<8, AMPS_SLICER_PRODUCT, CHZ_D768>;
-            case AMPS_SLICER_SINE: return chz12_short_kernel<8, AMPS_SLICER_SINE, CHZ_D768>;
-            case AMPS_SLICER_EXACT: return chz12_short_kernel<8, AMPS_SLICER_EXACT, CHZ_D768>;
-            default: return chz12_short_kernel<8, AMPS_SLICER_ATAN_BOXCAR, CHZ_D768>;
-            }
-        }
-        switch (slicer) {
-        case AMPS_SLICER_PRODUCT: return chz12_short_kernel<8, AMPS_SLICER_PRODUCT>;
-        case AMPS_SLICER_SINE: return chz12_short_kernel<8, AMPS_SLICER_SINE>;
-        case AMPS_SLICER_EXACT: return chz12_short_kernel<8, AMPS_SLICER_EXACT>;
-        default: return chz12_short_kernel<8, AMPS_SLICER_ATAN_BOXCAR>;
-        }
-    }
-    if (D == CHZ_D768) {
-        if (!fused) return chz12_kernel<8, CHZ12_IQ, CHZ_D768>;
-        switch (slicer) {
-        case AMPS_SLICER_PRODUCT: return chz12_kernel<8, AMPS_SLICER_PRODUCT, CHZ_D768>;
-        case AMPS_SLICER_SINE: return chz12_kernel<8, AMPS_SLICER_SINE, CHZ_D768>;
-        case AMPS_SLICER_EXACT: return chz12_kernel<8, AMPS_SLICER_EXACT, CHZ_D768>;
-        default: return chz12_kernel<8, AMPS_SLICER_ATAN_BOXCAR, CHZ_D768>;
-        }
-    }
-    if (!fused) return chz12_kernel<8, CHZ12_IQ>;
+    if constexpr (SHORT) return chz12_short_kernel<8, MODE, DEC>;
+    else return chz12_kernel<8, MODE, DEC>;
+}
+template <int DEC, bool SHORT> chz_kernel_t chz12_kernel_of(int slicer)
+{
     switch (slicer) {
-    case AMPS_SLICER_PRODUCT: return chz12_kernel<8, AMPS_SLICER_PRODUCT>;
-    case AMPS_SLICER_SINE: return chz12_kernel<8, AMPS_SLICER_SINE>;
-    case AMPS_SLICER_EXACT: return chz12_kernel<8, AMPS_SLICER_EXACT>;
-    default: return chz12_kernel<8, AMPS_SLICER_ATAN_BOXCAR>;
+    case AMPS_SLICER_PRODUCT: return chz12_kernel_of<DEC, SHORT, AMPS_SLICER_PRODUCT>();
+    case AMPS_SLICER_SINE: return chz12_kernel_of<DEC, SHORT, AMPS_SLICER_SINE>();
+    case AMPS_SLICER_EXACT: return chz12_kernel_of<DEC, SHORT, AMPS_SLICER_EXACT>();
+    default: return chz12_kernel_of<DEC, SHORT, AMPS_SLICER_ATAN_BOXCAR>();
     }
 }
-
-// Channelise `nsamp` new wideband samples.
-//  fused = false: writes the channel-major block; *chan_iq / *ld / *nframes describe it (even number of frames).
-//  fused = true : runs discriminator + boxcar + slicer behind the FFT and writes only slicer bits into `gring`
-//                 at absolute sample index n_done.. ; consumes a multiple of 64 frames.
-//  sc16 = true : `iq` is interleaved 16-bit I/Q (4 bytes per sample), else fc32.  The fused form reads it in place
-//                 (chz12_short_kernel); the unfused form and the pre-pass experiment expand it to fc32 first.
-inline int channelizer_run(ChannelizerState &z, const void *iq, size_t nsamp, int mem, hipStream_t s,
-                           const float2 **chan_iq, uint64_t *ld, uint32_t *nframes_out,
-                           bool fused = false, uint64_t *gring = nullptr, uint32_t ring_words = 0, uint64_t n_done = 0,
-                           int slicer = AMPS_SLICER_ATAN_BOXCAR, void (*after_main)(void *) = nullptr, void *after_ctx = nullptr,
-                           bool sc16 = false)
+inline chz_kernel_t chz12_kernel_for(int D, bool fused, int slicer, bool sc16 = false)
 {
+    if (!fused) {
+        if (sc16) return nullptr;
+        return D == CHZ_D768 ? chz12_kernel_of<CHZ_D768, false, CHZ12_IQ>() : chz12_kernel_of<CHZ_D, false, CHZ12_IQ>();
+    }
+    if (D == CHZ_D768) return sc16 ? chz12_kernel_of<CHZ_D768, true>(slicer) : chz12_kernel_of<CHZ_D768, false>(slicer);
+    return sc16 ? chz12_kernel_of<CHZ_D, true>(slicer) : chz12_kernel_of<CHZ_D, false>(slicer);
+}
+
+// What channelizer_run is given: the block, the form, and what the fused form writes into.
+struct ChzRunIn {
+    const void *iq = nullptr;                // `nsamp` new wideband samples, host or device (`mem`: AMPS_MEM_*)
+    size_t nsamp = 0;
+    int mem = AMPS_MEM_DEVICE;
+    bool sc16 = false;                       // interleaved 16-bit I/Q (4 bytes per sample), else fc32: read in place by the fused form, expanded to fc32 first otherwise
+    bool fused = false;                      // false: the channel-major block (*chan_iq / *ld / *nframes; even number of frames); true: slicer bits only, 64 frames at a time
+    uint64_t *gring = nullptr;               // fused: the slicer-bit ring, written at absolute sample index n_done..
+    uint32_t ring_words = 0;
+    uint64_t n_done = 0;
+    int slicer = AMPS_SLICER_ATAN_BOXCAR;
+    void (*after_main)(void *) = nullptr;    // called behind the filter-bank launch, in front of the carry and power launches (timing)
+    void *after_ctx = nullptr;
+};
+
+// Channelise in.nsamp new wideband samples.
+inline int channelizer_run(ChannelizerState &z, const ChzRunIn &in, hipStream_t s, const float2 **chan_iq, uint64_t *ld, uint32_t *nframes_out)
+{
+    const bool fused = in.fused;
+    const size_t nsamp = in.nsamp;
+    bool sc16 = in.sc16;
     if (!z.enabled) return -ENOSYS;
     if (!fused && z.groups > 1) return -ENOSYS;                   // channel groups exist in the fused form only
-    const void *d = iq;
-    const size_t sample_bytes = sc16 ? sizeof(chz_sc16) : sizeof(float2);
-    if (mem == AMPS_MEM_HOST) {
-        if (int rc = z.stage_fence.wait()) return rc;             // the previous push may still be reading the staging buffer
-        if (z.stage_bytes < sample_bytes * nsamp) {
-            if (z.stage) (void)hipFree(z.stage);
-            z.stage = nullptr; z.stage_bytes = 0;
-            if (hipMalloc((void **)&z.stage, sample_bytes * nsamp) != hipSuccess) return -ENOMEM;
-            z.stage_bytes = sample_bytes * nsamp;
-        }
-        // synchronous: the caller may reuse its buffer as soon as the push returns (see amps_recc_push_iq)
-        if (hipMemcpy(z.stage, iq, sample_bytes * nsamp, hipMemcpyHostToDevice) != hipSuccess) return -EIO;
-        d = z.stage;
+    const void *d = in.iq;
+    if (in.mem == AMPS_MEM_HOST) {                                // one row of bytes, as the caller's samples
+        const size_t bytes = (sc16 ? sizeof(chz_sc16) : sizeof(float2)) * nsamp;
+        const uint8_t *staged = nullptr;
+        uint64_t pitch = 0;
+        if (int rc = z.stage.stage((const uint8_t *)in.iq, bytes, bytes, 1, bytes, &staged, &pitch)) return rc;
+        d = staged;
     }
-    if (!fused && !z.out && hipMalloc((void **)&z.out, sizeof(float2) * (size_t)z.C * z.ld) != hipSuccess) return -ENOMEM;
+    if (!fused && !z.out && z.out.alloc((size_t)z.C * z.ld)) return -ENOMEM;
     const uint32_t hist = chz_hist(z.P, z.D);
     const uint32_t leftover = z.carry_len - hist;
     const uint64_t avail = (uint64_t)leftover + nsamp;
@@ -1306,15 +1264,13 @@ inline int channelizer_run(ChannelizerState &z, const void *iq, size_t nsamp, in
     if (sc16 && (!fused || z.short_prepass)) {
         // the block as fc32 in a buffer of its own, then everything as for an fc32 block.  Stream order keeps the buffer safe: the
         // kernels of the previous push that read it run before this conversion
-        if (z.cvt_samples < nsamp) {
-            if (z.cvt) { if (hipStreamSynchronize(s) != hipSuccess) return -EIO; (void)hipFree(z.cvt); }
-            z.cvt = nullptr; z.cvt_samples = 0;
-            if (hipMalloc((void **)&z.cvt, sizeof(float2) * nsamp) != hipSuccess) return -ENOMEM;
-            z.cvt_samples = nsamp;
+        if (z.cvt.capacity() < nsamp) {
+            if (z.cvt && hipStreamSynchronize(s) != hipSuccess) return -EIO;       // ... so they must have run before it is freed to grow
+            if (z.cvt.reserve(nsamp)) return -ENOMEM;
         }
         const uint32_t blocks = (uint32_t)std::min<size_t>((nsamp + 255) / 256, 65536);
-        hipLaunchKernelGGL(chz_short_to_float_kernel, dim3(blocks), dim3(256), 0, s, (const chz_sc16 *)d, z.cvt, (uint32_t)nsamp);
-        d = z.cvt;
+        hipLaunchKernelGGL(chz_short_to_float_kernel, dim3(blocks), dim3(256), 0, s, (const chz_sc16 *)d, z.cvt.get(), (uint32_t)nsamp);
+        d = z.cvt.get();
         sc16 = false;
     }
 #ifdef CHZ_TIMELINE
@@ -1325,31 +1281,31 @@ inline int channelizer_run(ChannelizerState &z, const void *iq, size_t nsamp, in
     bool carry_in_kernel = false;
     ChzArgs a{};
     if (nframes) {
-        a.block = (const float2 *)d; a.carry = z.carry[z.carry_cur]; a.taps = z.taps; a.out = z.out; a.ld = z.ld;
+        a.block = (const float2 *)d; a.carry = z.carry[z.carry_cur].get(); a.taps = z.taps.get(); a.out = z.out.get(); a.ld = z.ld;
         a.carry_len = z.carry_len; a.nsamp = (uint32_t)nsamp; a.nframes = nframes; a.hist = hist;
         // one resident round of 768-thread workgroups, one per CU; each refills its delay lines and re-runs eight pre-roll
         // frames when fused, so fewer, longer runs are cheaper
         uint32_t fpw = std::max<uint32_t>(64u, (nframes + z.target_wgs - 1) / z.target_wgs);
         fpw = (fpw + 63) / 64 * 64;
         a.frames_per_wg = fpw; a.first_bin = z.first_bin; a.n_channels = z.C;
-        a.bin2row = z.bin2row; a.grp_w = 64u / z.groups; a.grp_r = z.group;
+        a.bin2row = z.bin2row.get(); a.grp_w = 64u / z.groups; a.grp_r = z.group;
         a.odd_start = 0;
-        a.gring = gring; a.ring_words = ring_words; a.n_done = n_done;
+        a.gring = in.gring; a.ring_words = in.ring_words; a.n_done = in.n_done;
         a.stream_start = z.frames_done == 0 ? 1u : 0u;
         const dim3 g12((nframes + fpw - 1) / fpw), b12(768);
         carry_in_kernel = g12.x >= 64;                                // a slice of at most ~700 samples per workgroup; smaller grids leave it to the copy kernel
-        if (carry_in_kernel) { a.carry_out = z.carry[z.carry_cur ^ 1]; a.consumed = consumed; a.carry_out_len = hist + new_left; }
+        if (carry_in_kernel) { a.carry_out = z.carry[z.carry_cur ^ 1].get(); a.consumed = consumed; a.carry_out_len = hist + new_left; }
 #ifdef CHZ_TIMELINE
-        static unsigned long long *tl_dev = nullptr;
+        static DevBuf<unsigned long long> &tl_dev = *new DevBuf<unsigned long long>();   // kept for the life of the process
         constexpr size_t TLN = 12 * 8;
-        if (!tl_dev && hipMalloc((void **)&tl_dev, TLN * 8) != hipSuccess) return -ENOMEM;
-        (void)hipMemsetAsync(tl_dev, 0, TLN * 8, s);
-        a.tl = tl_dev;
-        a_tl_last = tl_dev;
+        if (!tl_dev && tl_dev.alloc(TLN)) return -ENOMEM;
+        (void)hipMemsetAsync(tl_dev.get(), 0, TLN * 8, s);
+        a.tl = tl_dev.get();
+        a_tl_last = tl_dev.get();
 #endif
-        hipLaunchKernelGGL(chz12_kernel_for(z.D, fused, slicer, sc16), g12, b12, 0, s, a);
+        hipLaunchKernelGGL(chz12_kernel_for(z.D, fused, in.slicer, sc16), g12, b12, 0, s, a);
     }
-    if (after_main) after_main(after_ctx);                            // timing: the span ends behind the filter-bank kernel, before the carry copy
+    if (in.after_main) in.after_main(in.after_ctx);                            // timing: the span ends behind the filter-bank kernel, before the carry copy
     // power snapshots (opt-in): behind the filter bank, from the block and the carry it read -- the carry buffers swap below
     if (fused && z.pow_ring && nframes) chz_power_launch(z, a, sc16, s);
 #ifdef CHZ_TIMELINE
@@ -1360,17 +1316,17 @@ inline int channelizer_run(ChannelizerState &z, const void *iq, size_t nsamp, in
     }
 #endif
     if (!carry_in_kernel) {
-        if (sc16) hipLaunchKernelGGL(chz_carry_short_kernel, dim3((hist + new_left + 255) / 256), dim3(256), 0, s, (const chz_sc16 *)d, z.carry[z.carry_cur],
-                                     z.carry[z.carry_cur ^ 1], z.carry_len, (uint32_t)nsamp, hist, consumed, hist + new_left);
-        else hipLaunchKernelGGL(chz_carry_kernel, dim3((hist + new_left + 255) / 256), dim3(256), 0, s, (const float2 *)d, z.carry[z.carry_cur],
-                                z.carry[z.carry_cur ^ 1], z.carry_len, (uint32_t)nsamp, hist, consumed, hist + new_left);
+        if (sc16) hipLaunchKernelGGL(chz_carry_short_kernel, dim3((hist + new_left + 255) / 256), dim3(256), 0, s, (const chz_sc16 *)d, z.carry[z.carry_cur].get(),
+                                     z.carry[z.carry_cur ^ 1].get(), z.carry_len, (uint32_t)nsamp, hist, consumed, hist + new_left);
+        else hipLaunchKernelGGL(chz_carry_kernel, dim3((hist + new_left + 255) / 256), dim3(256), 0, s, (const float2 *)d, z.carry[z.carry_cur].get(),
+                                z.carry[z.carry_cur ^ 1].get(), z.carry_len, (uint32_t)nsamp, hist, consumed, hist + new_left);
     }
     if (hipGetLastError() != hipSuccess) return -EIO;
-    if (mem == AMPS_MEM_HOST) { if (int rc = z.stage_fence.arm(s)) return rc; }
+    if (in.mem == AMPS_MEM_HOST) { if (int rc = z.stage.arm(s)) return rc; }
     z.carry_cur ^= 1;
     z.carry_len = hist + new_left;
     z.frames_done += nframes;
-    if (chan_iq) *chan_iq = z.out;
+    if (chan_iq) *chan_iq = z.out.get();
     if (ld) *ld = z.ld;
     *nframes_out = nframes;
     return 0;

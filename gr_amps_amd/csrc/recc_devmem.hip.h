@@ -1,0 +1,114 @@
+// recc_devmem.hip.h -- who owns the handle's memory: every hipMalloc / hipHostMalloc allocation of the library (recc_rccl.hip.h
+// apart, whose teardown is ordered around the communicator's abort) belongs to one of the owners below and is freed by it, and
+// host-resident input reaches the device through one staging path (HostStage).  Plain structs: the growth policy, the sizes and
+// the order of destruction stay with the code that uses them.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cerrno>
+#include <cstddef>
+#include <cstdint>
+#include <utility>
+
+namespace amps {
+
+// One device allocation of `capacity()` elements.  Move-only (the move constructor rules copies out); the destructor frees.
+template <typename T> class DevBuf {
+    T *p_ = nullptr;
+    size_t cap_ = 0;
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p_(std::exchange(o.p_, nullptr)), cap_(std::exchange(o.cap_, 0)) {}
+    DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { reset(); p_ = std::exchange(o.p_, nullptr); cap_ = std::exchange(o.cap_, 0); } return *this; }
+    ~DevBuf() { reset(); }
+    T *get() const { return p_; }
+    explicit operator bool() const { return p_ != nullptr; }
+    size_t capacity() const { return cap_; }
+    void reset() { if (p_) (void)hipFree(p_); p_ = nullptr; cap_ = 0; }
+    // a fresh allocation of n elements (n = 0: of one, so that a buffer that exists is never null); what was held is freed first
+    int alloc(size_t n)
+    {
+        reset();
+        if (n == 0) n = 1;
+        if (hipMalloc((void **)&p_, n * sizeof(T)) != hipSuccess) { p_ = nullptr; return -ENOMEM; }
+        cap_ = n;
+        return 0;
+    }
+    // grow-only, exactly to n: contents are not kept, and a failure leaves the buffer empty
+    int reserve(size_t n) { return n <= cap_ ? 0 : alloc(n); }
+};
+
+// One allocation of mapped pinned host memory: the kernels write through dev(), the host reads host() without a copy call
+// (record lists, kept-burst lists, list headers).
+template <typename T> class MappedBuf {
+    T *host_ = nullptr, *dev_ = nullptr;
+public:
+    MappedBuf() = default;
+    MappedBuf(MappedBuf &&o) noexcept : host_(std::exchange(o.host_, nullptr)), dev_(std::exchange(o.dev_, nullptr)) {}
+    MappedBuf &operator=(MappedBuf &&o) noexcept { if (this != &o) { reset(); host_ = std::exchange(o.host_, nullptr); dev_ = std::exchange(o.dev_, nullptr); } return *this; }
+    ~MappedBuf() { reset(); }
+    T *host() const { return host_; }
+    T *dev() const { return dev_; }
+    explicit operator bool() const { return host_ != nullptr; }
+    void reset() { if (host_) (void)hipHostFree(host_); host_ = nullptr; dev_ = nullptr; }
+    int alloc(size_t n)
+    {
+        reset();
+        if (hipHostMalloc((void **)&host_, n * sizeof(T), hipHostMallocMapped) != hipSuccess) { host_ = nullptr; return -ENOMEM; }
+        if (hipHostGetDevicePointer((void **)&dev_, host_, 0) != hipSuccess) { reset(); return -ENOMEM; }
+        return 0;
+    }
+};
+
+// the guard inside a HostStage (below): an event behind the last kernel that reads the staging buffer
+struct StageFence {
+    hipEvent_t ev = nullptr;
+    bool armed = false;
+    int wait()
+    {
+        if (armed) { if (hipEventSynchronize(ev) != hipSuccess) return -EIO; armed = false; }
+        return 0;
+    }
+    int arm(hipStream_t s)
+    {
+        if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return -ENOMEM;
+        if (hipEventRecord(ev, s) != hipSuccess) return -EIO;
+        armed = true;
+        return 0;
+    }
+    void destroy() { if (ev) (void)hipEventDestroy(ev); ev = nullptr; armed = false; }
+};
+
+// The device staging buffer of one seam for host-resident input, and its guard.  Copies from pageable host memory are neither
+// ordered after earlier kernels of a non-blocking stream nor guaranteed to have read their source when an Async call returns:
+// back-to-back pushes without a drain in between corrupted samples in the staging buffer while the previous push's kernels
+// were still reading it (found by scripts/fuzz_parity.py: intermittent wrong slicer bits), and blocks the caller freed right
+// after the call were copied late.  A host push therefore goes through stage() -- wait until the previous push's kernels have
+// released the buffer (before it is touched, freed to grow included), then copy SYNCHRONOUSLY, so the caller's block is free
+// when the push returns and the kernels are enqueued behind a finished copy -- enqueues its kernels, and calls arm() behind the
+// last one that reads the buffer.  An error return between the two arms nothing: nothing was enqueued that reads the buffer.
+struct HostStage {
+    DevBuf<uint8_t> buf;
+    StageFence fence;
+    HostStage() = default;
+    HostStage(HostStage &&o) noexcept : buf(std::move(o.buf)), fence(std::exchange(o.fence, StageFence())) {}
+    HostStage &operator=(HostStage &&o) noexcept { if (this != &o) { reset(); buf = std::move(o.buf); fence = std::exchange(o.fence, StageFence()); } return *this; }
+    ~HostStage() { reset(); }
+    void reset() { fence.destroy(); buf.reset(); }
+    // `rows` rows of `n` elements from the host block `src` (row pitch `ld` elements) into a buffer of at least `reserve`
+    // elements, rows packed: *dev is the device copy and *dev_ld = n its pitch
+    template <typename T> int stage(const T *src, size_t ld, size_t n, size_t rows, size_t reserve, const T **dev, uint64_t *dev_ld)
+    {
+        if (int rc = fence.wait()) return rc;
+        if (int rc = buf.reserve(std::max(reserve, rows * n) * sizeof(T))) return rc;
+        const hipError_t e = rows == 1 ? hipMemcpy(buf.get(), src, n * sizeof(T), hipMemcpyHostToDevice)
+                                       : hipMemcpy2D(buf.get(), n * sizeof(T), src, ld * sizeof(T), n * sizeof(T), rows, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return -EIO;
+        *dev = (const T *)buf.get();
+        *dev_ld = n;
+        return 0;
+    }
+    int arm(hipStream_t s) { return fence.arm(s); }
+};
+
+} // namespace amps

@@ -107,7 +107,7 @@ inline void chz_power_launch(const ChannelizerState &z, const ChzArgs &a, bool s
     const uint32_t first = (uint32_t)((0ull - a.n_done) & (uint64_t)(AMPS_RECC_POWER_STRIDE - 1));
     if (first >= a.nframes) return;                               // e.g. a 64-frame launch that covers s in [64, 128)
     const uint32_t nsnap = (a.nframes - first + AMPS_RECC_POWER_STRIDE - 1) / AMPS_RECC_POWER_STRIDE;
-    ChzPowerArgs p{ z.pow_ring, z.pow_slots - 1, first };
+    ChzPowerArgs p{ z.pow_ring.get(), z.pow_slots - 1, first };
     hipLaunchKernelGGL(chz_power_kernel_for(z.D, sc16), dim3(nsnap), dim3(256), 0, s, a, p);
 }
 

@@ -25,6 +25,7 @@
 #include <cstdint>
 #include <vector>
 #include "amps_recc.h"
+#include "recc_devmem.hip.h"
 
 namespace amps {
 
@@ -35,15 +36,15 @@ struct RefMM { float mu, omega, last; uint32_t tail, skip; };   // per channel; 
 struct RefState {
     bool ready = false;
     uint32_t C = 0, max_samples = 0;
-    float *atan_tab = nullptr;            // [258]
-    float *mmse = nullptr;                // [129][8]
-    float2 *last_iq = nullptr;            // [C]
-    RefMM *mm = nullptr;                  // [C]
-    float *d = nullptr;                   // [C][REF_TAIL + max_samples]
-    uint8_t *syms = nullptr;              // [C][sym_cap]
-    uint32_t *nsym = nullptr;             // [C]
+    DevBuf<float> atan_tab;               // [258]
+    DevBuf<float> mmse;                   // [129][8]
+    DevBuf<float2> last_iq;               // [C]
+    DevBuf<RefMM> mm;                     // [C]
+    DevBuf<float> d;                      // [C][REF_TAIL + max_samples]
+    DevBuf<uint8_t> syms;                 // [C][sym_cap]
+    DevBuf<uint32_t> nsym;                // [C]
     uint32_t sym_cap = 0;
-    float2 *stage = nullptr;
+    HostStage stage;                      // host-resident blocks: [C][max_samples]
     std::vector<float> atan_host, mmse_host;
 };
 
@@ -169,19 +170,14 @@ __global__ __launch_bounds__(64) void ref_mm_kernel(float *d, uint64_t dld, uint
     if (nsamp) last_iq[c] = iq[(uint64_t)c * ld + nsamp - 1];
 }
 
-inline void ref_destroy(RefState &r)
-{
-    void *bufs[] = { r.atan_tab, r.mmse, r.last_iq, r.mm, r.d, r.syms, r.nsym, r.stage };
-    for (void *p : bufs) if (p) (void)hipFree(p);
-    r = RefState();
-}
+inline void ref_destroy(RefState &r) { r = RefState(); }
 
 inline int ref_reset(RefState &r, hipStream_t s)
 {
     if (!r.ready) return 0;
-    if (hipMemsetAsync(r.last_iq, 0, sizeof(float2) * r.C, s) != hipSuccess) return -EIO;
+    if (hipMemsetAsync(r.last_iq.get(), 0, sizeof(float2) * r.C, s) != hipSuccess) return -EIO;
     std::vector<RefMM> init(r.C, RefMM{ 0.0f, 10.0f, 0.0f, 0u, 0u });   // mu 0, omega 10, last_sample 0 (grc/recctest.grc:846-874)
-    if (hipMemcpyAsync(r.mm, init.data(), sizeof(RefMM) * r.C, hipMemcpyHostToDevice, s) != hipSuccess) return -EIO;
+    if (hipMemcpyAsync(r.mm.get(), init.data(), sizeof(RefMM) * r.C, hipMemcpyHostToDevice, s) != hipSuccess) return -EIO;
     if (hipStreamSynchronize(s) != hipSuccess) return -EIO;
     return 0;
 }
@@ -194,12 +190,10 @@ inline int ref_create(RefState &r, uint32_t C, uint32_t max_samples, hipStream_t
     for (int i = 0; i < 258; i++) r.atan_host[i] = (float)std::atan((double)i / 255.0);
     r.mmse_host = ref_design_mmse();
     const uint64_t dld = (uint64_t)REF_TAIL + max_samples;
-    if (hipMalloc((void **)&r.atan_tab, sizeof(float) * 258) != hipSuccess || hipMalloc((void **)&r.mmse, sizeof(float) * 129 * 8) != hipSuccess ||
-        hipMalloc((void **)&r.last_iq, sizeof(float2) * C) != hipSuccess || hipMalloc((void **)&r.mm, sizeof(RefMM) * C) != hipSuccess ||
-        hipMalloc((void **)&r.d, sizeof(float) * C * dld) != hipSuccess || hipMalloc((void **)&r.syms, (size_t)C * r.sym_cap) != hipSuccess ||
-        hipMalloc((void **)&r.nsym, sizeof(uint32_t) * C) != hipSuccess) { ref_destroy(r); return -ENOMEM; }
-    if (hipMemcpy(r.atan_tab, r.atan_host.data(), sizeof(float) * 258, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(r.mmse, r.mmse_host.data(), sizeof(float) * 129 * 8, hipMemcpyHostToDevice) != hipSuccess) { ref_destroy(r); return -EIO; }
+    if (r.atan_tab.alloc(258) || r.mmse.alloc(129 * 8) || r.last_iq.alloc(C) || r.mm.alloc(C) || r.d.alloc(C * dld) ||
+        r.syms.alloc((size_t)C * r.sym_cap) || r.nsym.alloc(C)) { ref_destroy(r); return -ENOMEM; }
+    if (hipMemcpy(r.atan_tab.get(), r.atan_host.data(), sizeof(float) * 258, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(r.mmse.get(), r.mmse_host.data(), sizeof(float) * 129 * 8, hipMemcpyHostToDevice) != hipSuccess) { ref_destroy(r); return -EIO; }
     r.ready = true;
     return ref_reset(r, s);
 }
@@ -209,10 +203,10 @@ inline int ref_run(RefState &r, const float2 *iq, uint64_t ld, uint32_t nsamp, h
 {
     const uint64_t dld = (uint64_t)REF_TAIL + r.max_samples;
     if (nsamp) hipLaunchKernelGGL(ref_demod_kernel, dim3(std::min<uint32_t>((nsamp + 255) / 256, 1024u), r.C), dim3(256), 0, s,
-                                  iq, ld, nsamp, r.last_iq, r.atan_tab, r.d, dld);
+                                  iq, ld, nsamp, r.last_iq.get(), r.atan_tab.get(), r.d.get(), dld);
     // grc/recctest.grc:846-874: omega 10, gain_omega 0.25 * 0.175^2 * 3, gain_mu 0.05, omega_relative_limit 0.005
-    hipLaunchKernelGGL(ref_mm_kernel, dim3((r.C + 63) / 64), dim3(64), 0, s, r.d, dld, nsamp, r.mmse, r.mm, r.syms, r.sym_cap, r.nsym, r.C,
-                       10.0f, 10.0f * 0.005f, 0.25f * 0.175f * 0.175f * 3.0f, 0.05f, iq, ld, r.last_iq);
+    hipLaunchKernelGGL(ref_mm_kernel, dim3((r.C + 63) / 64), dim3(64), 0, s, r.d.get(), dld, nsamp, r.mmse.get(), r.mm.get(), r.syms.get(), r.sym_cap, r.nsym.get(), r.C,
+                       10.0f, 10.0f * 0.005f, 0.25f * 0.175f * 0.175f * 3.0f, 0.05f, iq, ld, r.last_iq.get());
     return hipGetLastError() == hipSuccess ? 0 : -EIO;
 }
 

@@ -117,12 +117,10 @@ struct XlateState {
     uint32_t C = 0, D = 0, ntaps = 0, ntp = 0, hist = 0, carry_cap = 0, carry_len = 0, max_out = 0;
     int cur = 0;
     uint64_t n_abs = 0, step = 0;
-    float *taps = nullptr;
-    float2 *carry[2] = { nullptr, nullptr };
-    float2 *out = nullptr;
-    float2 *stage = nullptr;
-    size_t stage_samples = 0;
-    StageFence stage_fence;
+    DevBuf<float> taps;
+    DevBuf<float2> carry[2];
+    DevBuf<float2> out;
+    HostStage stage;                 // host-resident blocks: [C][D * max_out]
     std::vector<float> taps_host;
 };
 
@@ -147,22 +145,13 @@ inline std::vector<float> xlate_design_taps(double gain, double fs, double cutof
     return out;
 }
 
-inline void xlate_destroy(XlateState &x)
-{
-    if (x.taps) (void)hipFree(x.taps);
-    if (x.carry[0]) (void)hipFree(x.carry[0]);
-    if (x.carry[1]) (void)hipFree(x.carry[1]);
-    if (x.out) (void)hipFree(x.out);
-    if (x.stage) (void)hipFree(x.stage);
-    x.stage_fence.destroy();
-    x = XlateState{};
-}
+inline void xlate_destroy(XlateState &x) { x = XlateState{}; }
 
 inline int xlate_reset(XlateState &x, hipStream_t s)
 {
     if (!x.enabled) return 0;
-    if (hipMemsetAsync(x.carry[0], 0, sizeof(float2) * (size_t)x.C * x.carry_cap, s) != hipSuccess) return -EIO;
-    if (hipMemsetAsync(x.carry[1], 0, sizeof(float2) * (size_t)x.C * x.carry_cap, s) != hipSuccess) return -EIO;
+    if (hipMemsetAsync(x.carry[0].get(), 0, sizeof(float2) * (size_t)x.C * x.carry_cap, s) != hipSuccess) return -EIO;
+    if (hipMemsetAsync(x.carry[1].get(), 0, sizeof(float2) * (size_t)x.C * x.carry_cap, s) != hipSuccess) return -EIO;
     x.cur = 0; x.carry_len = x.hist; x.n_abs = 0;
     return 0;
 }
@@ -182,11 +171,9 @@ inline int xlate_create(XlateState &x, uint32_t C, uint32_t D, uint32_t max_out,
     x.step = (uint64_t)(fr * 18446744073709551616.0L);
     std::vector<float> padded(ntp, 0.0f);
     for (size_t i = 0; i < taps.size(); i++) padded[i] = taps[i];
-    if (hipMalloc((void **)&x.taps, sizeof(float) * ntp) != hipSuccess) { xlate_destroy(x); return -ENOMEM; }
-    if (hipMalloc((void **)&x.carry[0], sizeof(float2) * (size_t)C * x.carry_cap) != hipSuccess) { xlate_destroy(x); return -ENOMEM; }
-    if (hipMalloc((void **)&x.carry[1], sizeof(float2) * (size_t)C * x.carry_cap) != hipSuccess) { xlate_destroy(x); return -ENOMEM; }
-    if (hipMalloc((void **)&x.out, sizeof(float2) * (size_t)C * max_out) != hipSuccess) { xlate_destroy(x); return -ENOMEM; }
-    if (hipMemcpy(x.taps, padded.data(), sizeof(float) * ntp, hipMemcpyHostToDevice) != hipSuccess) { xlate_destroy(x); return -EIO; }
+    int rc = x.taps.alloc(ntp) | x.carry[0].alloc((size_t)C * x.carry_cap) | x.carry[1].alloc((size_t)C * x.carry_cap) | x.out.alloc((size_t)C * max_out);
+    if (!rc && hipMemcpy(x.taps.get(), padded.data(), sizeof(float) * ntp, hipMemcpyHostToDevice) != hipSuccess) rc = -EIO;
+    if (rc) { xlate_destroy(x); return rc; }
     x.enabled = true;
     return xlate_reset(x, s);
 }
@@ -195,29 +182,19 @@ inline int xlate_create(XlateState &x, uint32_t C, uint32_t D, uint32_t max_out,
 inline int xlate_run(XlateState &x, const float2 *iq, uint64_t ld, size_t nsamp, int mem, hipStream_t s,
                      const float2 **out_iq, uint64_t *out_ld, uint32_t *nout)
 {
-    *out_iq = x.out; *out_ld = x.max_out; *nout = 0;
+    *out_iq = x.out.get(); *out_ld = x.max_out; *nout = 0;
     if (!x.enabled) return -ENOSYS;
     if (nsamp == 0) return 0;
     if (nsamp > (size_t)x.D * x.max_out) return -E2BIG;
     const float2 *d = iq;
     if (mem == AMPS_MEM_HOST) {
-        if (int rc = x.stage_fence.wait()) return rc;             // the previous push may still be reading the staging buffer
-        const size_t need = (size_t)x.C * x.D * x.max_out;
-        if (x.stage_samples < need) {
-            if (x.stage) (void)hipFree(x.stage);
-            x.stage = nullptr; x.stage_samples = 0;
-            if (hipMalloc((void **)&x.stage, sizeof(float2) * need) != hipSuccess) return -ENOMEM;
-            x.stage_samples = need;
-        }
-        if (hipMemcpy2D(x.stage, nsamp * sizeof(float2), iq, ld * sizeof(float2), nsamp * sizeof(float2), x.C,
-                        hipMemcpyHostToDevice) != hipSuccess) return -EIO;       // synchronous: see amps_recc_push_iq
-        d = x.stage; ld = nsamp;
+        if (int rc = x.stage.stage(iq, ld, nsamp, x.C, (size_t)x.C * x.D * x.max_out, &d, &ld)) return rc;
     }
     const uint64_t avail = (uint64_t)(x.carry_len - x.hist) + nsamp;
     const uint64_t n_out = avail / x.D;
     if (n_out > x.max_out) return -E2BIG;
     XlateArgs a{};
-    a.block = d; a.carry = x.carry[x.cur]; a.taps = x.taps; a.out = x.out; a.ld_in = ld; a.ld_out = x.max_out;
+    a.block = d; a.carry = x.carry[x.cur].get(); a.taps = x.taps.get(); a.out = x.out.get(); a.ld_in = ld; a.ld_out = x.max_out;
     a.n_abs0 = x.n_abs; a.step = x.step; a.carry_cap = x.carry_cap; a.carry_len = x.carry_len; a.hist = x.hist;
     a.nsamp = (uint32_t)nsamp; a.nout = (uint32_t)n_out; a.ntp = x.ntp;
     if (n_out) {
@@ -230,10 +207,10 @@ inline int xlate_run(XlateState &x, const float2 *iq, uint64_t ld, size_t nsamp,
     }
     const uint32_t consumed = (uint32_t)(n_out * x.D);
     const uint32_t new_len = x.hist + (uint32_t)(avail - (uint64_t)consumed);
-    hipLaunchKernelGGL(xlate_carry_kernel, dim3((new_len + 255) / 256, x.C), dim3(256), 0, s, d, ld, x.carry[x.cur], x.carry[x.cur ^ 1],
+    hipLaunchKernelGGL(xlate_carry_kernel, dim3((new_len + 255) / 256, x.C), dim3(256), 0, s, d, ld, x.carry[x.cur].get(), x.carry[x.cur ^ 1].get(),
                        x.carry_cap, x.carry_len, consumed, new_len);
     if (hipGetLastError() != hipSuccess) return -EIO;
-    if (mem == AMPS_MEM_HOST) { if (int rc = x.stage_fence.arm(s)) return rc; }
+    if (mem == AMPS_MEM_HOST) { if (int rc = x.stage.arm(s)) return rc; }
     x.cur ^= 1; x.carry_len = new_len; x.n_abs += consumed;
     *nout = (uint32_t)n_out;
     return 0;

@@ -6,10 +6,10 @@ slicer spec (A / B / C / D of include/amps_recc_numerics.h), symbol-clock and ca
 
 History: the first campaign (150 cases) failed 48 times -- host-resident blocks pushed back to back without a drain in
 between could be overwritten in the device staging buffer while the previous push's kernels were still reading it (a
-staged copy from pageable memory is not ordered after earlier kernels of a non-blocking stream): fixed with StageFence.
+staged copy from pageable memory is not ordered after earlier kernels of a non-blocking stream): fixed with a fence on the staging buffer.
 A second campaign failed 2 of 1500 host-block cases: hipMemcpy2DAsync from pageable memory had not read its source
 when it returned and the test freed the block: fixed with a synchronous staging copy (keep_host=True keeps the blocks
-alive, which is how the cause was isolated)."""
+alive, which is how the cause was isolated).  Both halves now live in one place, HostStage (gr_amps_amd/csrc/recc_devmem.hip.h)."""
 import numpy as np
 
 import oracle
