@@ -43,13 +43,13 @@ constexpr size_t LIST_WORDS = 4;   // a record list's device-side words: {slot a
 
 enum { T_FRONT = 0, T_RESOLVE, T_DECODE, T_CARRY, T_SYMBOLS, T_CHANNELIZER, T_XLATE, T_COUNT };
 
-struct TimedSpan { hipEvent_t a, b; int tag; uint64_t samples; };
+struct TimedSpan { Event a, b; int tag; uint64_t samples; };
 
 } // namespace
 
-// Every device and mapped-host allocation of the handle's own seams, each behind its owner (recc_devmem.hip.h).  A part of the handle
-// of its own so that amps_recc_destroy can free all of it at its place in the teardown without naming a buffer: a buffer added here
-// cannot be left off a list.
+// Every device and mapped-host allocation and every event of the handle's own seams, each behind its owner (recc_devmem.hip.h).  A
+// part of the handle of its own so that amps_recc_destroy can release all of it at its place in the teardown without naming a buffer
+// or an event: one added here cannot be left off a list.
 struct amps_recc_mem {
     // ---- IQ seam ----
     DevBuf<float2> carry[2];
@@ -66,6 +66,7 @@ struct amps_recc_mem {
     MappedBuf<uint32_t> hdr;                  // {nrecords, status} per record list: written by the capture kernel's last workgroup
     DevBuf<uint32_t> nrecords_buf[2];         // [LIST_WORDS] per list
     HostStage stage_iq;                       // host-resident IQ: [C][max_samples_per_push], allocated by the first host push
+    Event drain_event;                        // behind everything enqueued before drain_begin
 
     // ---- received power: amps_recc_burst_power scratch (grow-only) ----
     DevBuf<amps::ChzBurstQuery> pq_dev;
@@ -88,13 +89,16 @@ struct amps_recc_mem {
 
     // ---- debug taps (amps_recc_debug_demod) ----
     DevBuf<float> dbg_d, dbg_S;
+
+    // ---- timing: the spans in flight with their events (one that is never collected goes with the handle) and the spare events ----
+    std::vector<TimedSpan> spans;
+    std::vector<Event> event_pool;            // recycled by collect_spans
 };
 
 struct amps_recc : amps_recc_mem {
     amps_recc_cfg_t cfg{};
     int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    Stream stream;                    // the handle's own, or cfg.stream borrowed
     uint32_t C = 0, sps = 0;
 
     // ---- IQ seam ----
@@ -114,7 +118,6 @@ struct amps_recc : amps_recc_mem {
     bool list_clean[2] = { true, true };      // the device-side {nrecords, status} of the list are zero (or a launch that zeroes them is enqueued)
     int cur_buf = 0, open_buf = -1;
     bool open_untouched = false;      // no push has been enqueued since drain_begin: the open list's device counters are still there (header cross-check)
-    hipEvent_t drain_event = nullptr;
 
     // ---- channelizer seam ----
     ChannelizerState chz;
@@ -132,8 +135,6 @@ struct amps_recc : amps_recc_mem {
     bool timing = false;
     int timing_mode = 0;              // AMPS_RECC_TIMING_*
     uint32_t dominant_tick = 0;       // launches of the dominant kernel seen in DOMINANT_SAMPLED mode
-    std::vector<hipEvent_t> event_pool;   // recycled by collect_spans
-    std::vector<TimedSpan> spans;
     double ms[T_COUNT] = { 0 };
     uint32_t launches_front = 0, launches_chz = 0;
     uint64_t samples_front = 0;
@@ -174,12 +175,13 @@ inline void expand_packed_burst(uint8_t *dst, const uint8_t *src)
 }
 
 struct SpanGuard {   // records a pair of events around a launch when timing is on
-    amps_recc *h; int tag; uint64_t samples; hipEvent_t a = nullptr, b = nullptr; bool on;
-    static hipEvent_t take(amps_recc *h)
+    amps_recc *h; int tag; uint64_t samples; Event a, b; bool on;
+    static Event take(amps_recc *h)
     {
-        if (!h->event_pool.empty()) { hipEvent_t e = h->event_pool.back(); h->event_pool.pop_back(); return e; }
-        hipEvent_t e = nullptr;
-        return hipEventCreate(&e) == hipSuccess ? e : nullptr;
+        Event e;
+        if (!h->event_pool.empty()) { e = std::move(h->event_pool.back()); h->event_pool.pop_back(); }
+        else (void)e.create();
+        return e;
     }
     SpanGuard(amps_recc *h_, int tag_, uint64_t samples_ = 0) : h(h_), tag(tag_), samples(samples_), on(h_->timing)
     {
@@ -190,13 +192,13 @@ struct SpanGuard {   // records a pair of events around a launch when timing is 
         if (!on) return;
         a = take(h); b = take(h);
         if (!a || !b) { on = false; return; }
-        (void)hipEventRecord(a, h->stream);
+        (void)hipEventRecord(a.get(), h->stream.get());
     }
     void end()     // close the span now (the destructor then does nothing)
     {
         if (!on) return;
-        (void)hipEventRecord(b, h->stream);
-        h->spans.push_back({ a, b, tag, samples });
+        (void)hipEventRecord(b.get(), h->stream.get());
+        h->spans.push_back({ std::move(a), std::move(b), tag, samples });
         on = false;
     }
     static void end_cb(void *g) { static_cast<SpanGuard *>(g)->end(); }
@@ -207,15 +209,15 @@ void collect_spans(amps_recc *h)   // collects the spans whose events have compl
 {
     size_t keep = 0;
     for (auto &s : h->spans) {
-        if (hipEventQuery(s.b) != hipSuccess) { h->spans[keep++] = s; continue; }
+        if (hipEventQuery(s.b.get()) != hipSuccess) { h->spans[keep++] = std::move(s); continue; }
         float t = 0.f;
-        if (hipEventElapsedTime(&t, s.a, s.b) == hipSuccess) {
+        if (hipEventElapsedTime(&t, s.a.get(), s.b.get()) == hipSuccess) {
             h->ms[s.tag] += t;
             if (s.tag == T_FRONT) { h->launches_front++; h->samples_front += s.samples; }
             if (s.tag == T_CHANNELIZER) h->launches_chz++;
         }
-        h->event_pool.push_back(s.a);
-        h->event_pool.push_back(s.b);
+        h->event_pool.push_back(std::move(s.a));
+        h->event_pool.push_back(std::move(s.b));
     }
     h->spans.resize(keep);
 }
@@ -231,7 +233,7 @@ int debug_sync(amps_recc *h, const char *what)
 {
     if (!debug_sync_enabled()) return 0;
     std::fprintf(stderr, "amps_recc[debug]: %s ...", what); std::fflush(stderr);
-    hipError_t e = hipStreamSynchronize(h->stream);
+    hipError_t e = hipStreamSynchronize(h->stream.get());
     std::fprintf(stderr, " %s\n", e == hipSuccess ? "ok" : hipGetErrorString(e)); std::fflush(stderr);
     return e == hipSuccess ? 0 : -EIO;
 }
@@ -267,7 +269,7 @@ uint32_t next_pow2(uint64_t v) { uint64_t p = 1; while (p < v) p <<= 1; return (
 
 int reset_state(amps_recc *h)
 {
-    hipStream_t s = h->stream;
+    hipStream_t s = h->stream.get();
     if (h->carry[0]) {
         HIP_TRY(hipMemsetAsync(h->carry[0].get(), 0, sizeof(float2) * (size_t)h->C * CARRY_CAP, s));
         HIP_TRY(hipMemsetAsync(h->carry[1].get(), 0, sizeof(float2) * (size_t)h->C * CARRY_CAP, s));
@@ -509,7 +511,7 @@ int run_iq_device(amps_recc *h, const float2 *iq, uint64_t ld, uint32_t nsamp)
 {
     h->origin_locked = true;
     if (nsamp == 0) return 0;
-    hipStream_t s = h->stream;
+    hipStream_t s = h->stream.get();
     const uint32_t avail = h->r_prev + nsamp;
     const uint32_t P = (avail / 64) * 64, r_new = avail - P;
     const FrontGeom geom = front_geometry(h->C, P, h->max_waves);
@@ -647,11 +649,8 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
               : (cfg->flags & AMPS_RECC_FLAG_SLICER_ATAN) ? AMPS_SLICER_ATAN_BOXCAR : AMPS_SLICER_DEFAULT;
     h->timing = (cfg->flags & AMPS_RECC_FLAG_TIME_KERNELS) != 0;
     h->timing_mode = h->timing ? AMPS_RECC_TIMING_ALL : AMPS_RECC_TIMING_OFF;
-    if (cfg->stream) h->stream = (hipStream_t)cfg->stream;
-    else {
-        if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return -EIO; }
-        h->own_stream = true;
-    }
+    if (cfg->stream) h->stream.borrow((hipStream_t)cfg->stream);
+    else if (h->stream.create()) { delete h; return -EIO; }
     int rc = 0;
     const size_t C = h->C;
     step("stream created");
@@ -671,7 +670,7 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
     if (cfg->flags & AMPS_RECC_FLAG_KEEP_BURSTS)
         for (int b = 0; b < 2; b++) rc |= h->bsym_buf[b].alloc((size_t)cfg->max_bursts * AMPS_RECC_CAPTURE_SYMS);
     rc |= h->hdr.alloc(2 * HDR_STRIDE);
-    if (hipEventCreateWithFlags(&h->drain_event, hipEventDisableTiming) != hipSuccess) rc |= -ENOMEM;
+    rc |= h->drain_event.create(hipEventDisableTiming);
     if (!rc) select_record_list(h, 0);
     step("pinned record lists mapped");
     // IQ seam
@@ -705,7 +704,7 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
         if (resolve_uses_queue((uint32_t)C)) { rc |= h->capq.alloc(cfg->max_bursts); rc |= h->capq_count.alloc(1); }
     }
     step("IQ seam buffers allocated");
-    if (!rc && cfg->wideband_channels) rc = channelizer_create(h->chz, *cfg, h->stream);
+    if (!rc && cfg->wideband_channels) rc = channelizer_create(h->chz, *cfg, h->stream.get());
     step("channelizer created");
     if (!rc && (cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER)) {
         h->chz.pow_slots = 64u * h->ring_words / AMPS_RECC_POWER_STRIDE;         // the bit ring's window, a power of two (ring_words >= 32)
@@ -724,26 +723,22 @@ void amps_recc_destroy(amps_recc_t *h)
 {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    if (h->stream) { (void)sync_stream(h, h->stream); (void)hipStreamSynchronize(h->stream); }   // bounded first: a dead peer must not hang the destructor
+    if (h->stream) { (void)sync_stream(h, h->stream.get()); (void)hipStreamSynchronize(h->stream.get()); }   // bounded first: a dead peer must not hang the destructor
     collect_spans(h);
-    for (hipEvent_t e : h->event_pool) (void)hipEventDestroy(e);
-    h->event_pool.clear();
-    if (h->drain_event) (void)hipEventDestroy(h->drain_event);
     rccl_destroy(h->rccl);
-    static_cast<amps_recc_mem &>(*h) = amps_recc_mem();      // every buffer of the handle's own seams; then the other seams' states
+    static_cast<amps_recc_mem &>(*h) = amps_recc_mem();      // every buffer and event of the handle's own seams; then the other seams' states
     channelizer_destroy(h->chz);
     xlate_destroy(h->xl);
     ref_destroy(h->ref);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;                                                // and with it the stream, if it is the handle's own: all else is released by now
 }
 
 int amps_recc_reset(amps_recc_t *h)
 {
     if (!h) return -EINVAL;
     HIP_TRY(hipSetDevice(h->device));
-    (void)sync_stream(h, h->stream);          // bounded while a communicator lives (on expiry it is aborted and the stream drains)
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    (void)sync_stream(h, h->stream.get());          // bounded while a communicator lives (on expiry it is aborted and the stream drains)
+    HIP_TRY(hipStreamSynchronize(h->stream.get()));
     collect_spans(h);
     h->rccl.stale = false;                    // a fresh stream: whatever an aborted collective left behind is gone
     if (h->open_buf >= 0) { volatile uint32_t *hdr = h->hdr.host() + HDR_STRIDE * h->open_buf; hdr[0] = 0u; hdr[1] = 0u; h->open_buf = -1; }
@@ -760,7 +755,7 @@ int amps_recc_push_symbols(amps_recc_t *h, const uint8_t *syms, size_t ld, int n
     if (n > AMPS_RECC_MAX_WORK_ITEMS) return -EINVAL;      // lib/recc_impl.cc:103
     if (!syms || ld < (size_t)n) return -EINVAL;
     HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = h->stream;
+    hipStream_t s = h->stream.get();
     const uint8_t *dsyms = syms;
     uint64_t dld = ld;
     if (mem == AMPS_MEM_HOST) {
@@ -808,7 +803,7 @@ int amps_recc_decode_bursts(amps_recc_t *h, const uint8_t *bursts, size_t nburst
     if (!h || (!bursts && nbursts) || (!out && nbursts)) return -EINVAL;
     if (nbursts == 0) return 0;
     HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = h->stream;
+    hipStream_t s = h->stream.get();
     if (h->dec_out_dev.reserve(nbursts) || h->dec_in_dev.reserve(nbursts * AMPS_RECC_CAPTURE_SYMS) || h->dec_chan_dev.reserve(nbursts)) return -ENOMEM;
     const uint8_t *din = bursts;
     if (mem == AMPS_MEM_HOST) {
@@ -849,7 +844,7 @@ int amps_recc_push_iq(amps_recc_t *h, const float *iq, size_t ld, size_t nsamp, 
         if (int rc = h->stage_iq.stage(d, ld, nsamp, h->C, (size_t)h->C * h->cfg.max_samples_per_push, &d, &dld)) return rc;
     }
     int rc = run_iq_device(h, d, dld, (uint32_t)nsamp);
-    if (!rc && mem == AMPS_MEM_HOST) rc = h->stage_iq.arm(h->stream);
+    if (!rc && mem == AMPS_MEM_HOST) rc = h->stage_iq.arm(h->stream.get());
     return rc;
 }
 
@@ -858,7 +853,7 @@ namespace {
 int run_bits_device(amps_recc *h, uint32_t P)
 {
     if (P == 0) return 0;
-    hipStream_t s = h->stream;
+    hipStream_t s = h->stream.get();
     const FrontGeom geom = front_geometry(h->C, P, h->max_waves_bits);
     const uint32_t Tc = geom.Tc, span = geom.span, nwaves = geom.nwaves;
     if (search_in_resolve(h)) {
@@ -926,7 +921,7 @@ int push_wideband_block(amps_recc_t *h, const void *iq, size_t nsamp, int mem, b
         in.iq = iq; in.nsamp = nsamp; in.mem = mem; in.sc16 = sc16; in.fused = fused;
         in.gring = h->gring.get(); in.ring_words = h->ring_words; in.n_done = h->n_done; in.slicer = h->slicer;
         in.after_main = SpanGuard::end_cb; in.after_ctx = &g;
-        rc = channelizer_run(h->chz, in, h->stream, &chan_iq, &ld, &nout);
+        rc = channelizer_run(h->chz, in, h->stream.get(), &chan_iq, &ld, &nout);
     }
     if (rc) return rc;
     if (nout > h->cfg.max_samples_per_push) return -E2BIG;
@@ -1036,9 +1031,9 @@ int amps_recc_push_wideband_dist(amps_recc_t *h, const float *iq, size_t nsamp, 
     size_t n = 0;
     // (a missing block or nsamp = 0 at the root is the root's error -- both together its END OF STREAM, -ENODATA on every rank -- and
     // travels through the header: the other ranks learn of it)
-    if (int rc = rccl_distribute(h->rccl, (const float2 *)iq, mem == AMPS_MEM_HOST, nsamp, root, mode, h->stream, &blk, &slot, &n)) return rc;
+    if (int rc = rccl_distribute(h->rccl, (const float2 *)iq, mem == AMPS_MEM_HOST, nsamp, root, mode, h->stream.get(), &blk, &slot, &n)) return rc;
     const int rc = amps_recc_push_wideband(h, (const float *)blk, n, AMPS_MEM_DEVICE);
-    const int rc2 = rccl_block_consumed(h->rccl, slot, h->stream);
+    const int rc2 = rccl_block_consumed(h->rccl, slot, h->stream.get());
     if (npushed) *npushed = n;
     return rc ? rc : rc2;
 }
@@ -1060,7 +1055,7 @@ int amps_recc_drain_gather(amps_recc_t *h, amps_recc_burst_t *out, size_t cap, s
     // The handle's kernels wait for the data collectives: if a peer has gone, they never start, and an unbounded drain would sit behind
     // them for ever.  So the wait for the stream is bounded here (then the drain below finds it idle); on expiry the communicator is
     // aborted and the peers run into their own bound.
-    if (int rc = rccl_wait(h->rccl, h->stream)) return rc;
+    if (int rc = rccl_wait(h->rccl, h->stream.get())) return rc;
     // this rank's own list first; whatever it returns, the rank then takes part in the collective (the others are waiting in it) and
     // tells them through the status word: bit 0 = its list overflowed, bit 1 = its drain failed
     std::vector<amps_recc_burst_t> mine(h->cfg.max_bursts);
@@ -1095,7 +1090,7 @@ int amps_recc_set_xlate(amps_recc_t *h, const amps_recc_xlate_cfg_t *x)
     if (!h || !x || x->struct_size != sizeof(amps_recc_xlate_cfg_t)) return -EINVAL;
     if (!h->carry[0]) return -ENOSYS;                       // the IQ seam must be configured
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream.get()));
     if (x->decim == 0) { xlate_destroy(h->xl); return 0; }
     // defaults = the flow graph's values (grc/recctest.grc:115-155, 889-937)
     const double gain = x->gain != 0.0 ? x->gain : 3.0;
@@ -1106,7 +1101,7 @@ int amps_recc_set_xlate(amps_recc_t *h, const amps_recc_xlate_cfg_t *x)
     const double out_rate = x->rate_hz / x->decim;
     if (std::fabs(out_rate - 20e3 * h->sps) > 1e-6 * out_rate) return -EINVAL;
     std::vector<float> taps = xlate_design_taps(gain, x->rate_hz, cutoff, width);
-    return xlate_create(h->xl, h->C, x->decim, h->cfg.max_samples_per_push, x->rate_hz, x->center_hz, taps, h->stream);
+    return xlate_create(h->xl, h->C, x->decim, h->cfg.max_samples_per_push, x->rate_hz, x->center_hz, taps, h->stream.get());
 }
 
 int amps_recc_push_raw(amps_recc_t *h, const float *iq, size_t ld, size_t nsamp, int mem)
@@ -1123,7 +1118,7 @@ int amps_recc_push_raw(amps_recc_t *h, const float *iq, size_t ld, size_t nsamp,
     int rc;
     {
         SpanGuard g(h, T_XLATE, nsamp);
-        rc = xlate_run(h->xl, (const float2 *)iq, ld, nsamp, mem, h->stream, &f, &fld, &nout);
+        rc = xlate_run(h->xl, (const float2 *)iq, ld, nsamp, mem, h->stream.get(), &f, &fld, &nout);
     }
     if (rc) return rc;
     if (int rc2 = debug_sync(h, "xlate")) return rc2;
@@ -1139,14 +1134,14 @@ int amps_recc_debug_xlate(amps_recc_t *h, const float *iq, size_t ld, size_t nsa
     const float2 *f = nullptr;
     uint64_t fld = 0;
     uint32_t n = 0;
-    int rc = xlate_run(h->xl, (const float2 *)iq, ld, nsamp, mem, h->stream, &f, &fld, &n);
+    int rc = xlate_run(h->xl, (const float2 *)iq, ld, nsamp, mem, h->stream.get(), &f, &fld, &n);
     if (rc) return rc;
     *nout = n;
     if (n > out_ld) return -E2BIG;
     if (n)
         HIP_TRY(hipMemcpy2DAsync(out, out_ld * sizeof(float2), f, fld * sizeof(float2), (size_t)n * sizeof(float2), h->C,
-                                 hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+                                 hipMemcpyDeviceToHost, h->stream.get()));
+    HIP_TRY(hipStreamSynchronize(h->stream.get()));
     return 0;
 }
 
@@ -1158,7 +1153,7 @@ int amps_recc_refchain_symbols(amps_recc_t *h, const float *iq, size_t ld, size_
     if (h->sps != 10) return -EINVAL;                       // the flow graph's omega = 10 samples per symbol
     if (nsamp > h->cfg.max_samples_per_push) return -E2BIG;
     HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = h->stream;
+    hipStream_t s = h->stream.get();
     if (!h->ref.ready) { if (int rc = ref_create(h->ref, h->C, h->cfg.max_samples_per_push, s)) return rc; }
     if (sym_ld < h->ref.sym_cap && sym_ld < nsamp / 9 + 16) return -EINVAL;
     const float2 *d = (const float2 *)iq;
@@ -1179,7 +1174,7 @@ int amps_recc_refchain_tables(amps_recc_t *h, float *atan258, float *mmse1032)
     if (!h || !atan258 || !mmse1032) return -EINVAL;
     if (!h->cfg.max_samples_per_push) return -ENOSYS;
     HIP_TRY(hipSetDevice(h->device));
-    if (!h->ref.ready) { if (int rc = ref_create(h->ref, h->C, h->cfg.max_samples_per_push, h->stream)) return rc; }
+    if (!h->ref.ready) { if (int rc = ref_create(h->ref, h->C, h->cfg.max_samples_per_push, h->stream.get())) return rc; }
     std::memcpy(atan258, h->ref.atan_host.data(), sizeof(float) * 258);
     std::memcpy(mmse1032, h->ref.mmse_host.data(), sizeof(float) * 129 * 8);
     return 0;
@@ -1189,7 +1184,7 @@ int amps_recc_wait_event(amps_recc_t *h, void *hip_event)
 {
     if (!h || !hip_event) return -EINVAL;
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamWaitEvent(h->stream, (hipEvent_t)hip_event, 0));
+    HIP_TRY(hipStreamWaitEvent(h->stream.get(), (hipEvent_t)hip_event, 0));
     return 0;
 }
 
@@ -1197,7 +1192,7 @@ int amps_recc_record_event(amps_recc_t *h, void *hip_event)
 {
     if (!h || !hip_event) return -EINVAL;
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipEventRecord((hipEvent_t)hip_event, h->stream));
+    HIP_TRY(hipEventRecord((hipEvent_t)hip_event, h->stream.get()));
     return 0;
 }
 
@@ -1207,10 +1202,10 @@ int amps_recc_drain_begin(amps_recc_t *h)
     STALE_CHECK(h);
     if (h->open_buf >= 0) return -EBUSY;
     HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = h->stream;
+    hipStream_t s = h->stream.get();
     const int b = h->cur_buf;
     // the list's header is already on its way to host memory: the last capture workgroup of every push writes it
-    HIP_TRY(hipEventRecord(h->drain_event, s));
+    HIP_TRY(hipEventRecord(h->drain_event.get(), s));
     h->open_buf = b;
     h->open_untouched = true;
     select_record_list(h, b ^ 1);           // later pushes append to the other list
@@ -1246,7 +1241,7 @@ static int drain_end_impl(amps_recc_t *h, amps_recc_burst_t *out, uint8_t *burst
     // because one drain failed
     auto fail = [&](int rc) { hdr[0] = 0u; hdr[1] = 0u; h->open_buf = -1; return rc; };
     if (hipSetDevice(h->device) != hipSuccess) return fail(-EIO);
-    if (int wrc = sync_event(h, h->drain_event)) return fail(wrc);   // everything enqueued before drain_begin is done; later pushes may still run (bounded behind a collective)
+    if (int wrc = sync_event(h, h->drain_event.get())) return fail(wrc);   // everything enqueued before drain_begin is done; later pushes may still run (bounded behind a collective)
     if (h->rccl.stale) return fail(-ESTALE);
     collect_spans(h);
     uint32_t n = hdr[0];
@@ -1349,7 +1344,7 @@ int amps_recc_debug_demod(amps_recc_t *h, const float *iq, size_t nsamp, int mem
     }
     rc = amps_recc_push_iq(h, src, ld, nsamp, mem);
     if (!rc) {
-        if (hipStreamSynchronize(h->stream) != hipSuccess) rc = -EIO;
+        if (hipStreamSynchronize(h->stream.get()) != hipSuccess) rc = -EIO;
     }
     if (!rc && P) {
         if (demod && hipMemcpy(demod, h->dbg_d.get(), P * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) rc = -EIO;
@@ -1379,14 +1374,14 @@ int amps_recc_debug_channelize(amps_recc_t *h, const float *iq, size_t nsamp, in
     uint32_t nout = 0;
     ChzRunIn in;                                             // the unfused form on fc32: the channel-major block is the output
     in.iq = iq; in.nsamp = nsamp; in.mem = mem;
-    int rc = channelizer_run(h->chz, in, h->stream, &chan_iq, &ld, &nout);
+    int rc = channelizer_run(h->chz, in, h->stream.get(), &chan_iq, &ld, &nout);
     if (rc) return rc;
     *nframes = nout;
     if (nout > out_ld) return -E2BIG;
     if (nout)
         HIP_TRY(hipMemcpy2DAsync(out, out_ld * sizeof(float2), chan_iq, ld * sizeof(float2), nout * sizeof(float2), h->C,
-                                 hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+                                 hipMemcpyDeviceToHost, h->stream.get()));
+    HIP_TRY(hipStreamSynchronize(h->stream.get()));
     return 0;
 }
 
@@ -1396,7 +1391,7 @@ int amps_recc_debug_slicer_bits(amps_recc_t *h, uint64_t first, size_t n, uint8_
     if (!h->gring) return -ENOSYS;
     STALE_CHECK(h);
     HIP_TRY(hipSetDevice(h->device));
-    if (int rc = sync_stream(h, h->stream)) return rc;
+    if (int rc = sync_stream(h, h->stream.get())) return rc;
     // the slicers write ring words for [n_done, n_done + P) only, and n_done, origin and P are multiples of 64: after the wait the
     // ring holds the last R = 64 ring_words samples produced, never anything before the origin
     const uint64_t end = h->n_done, span = 64ull * h->ring_words;
@@ -1408,10 +1403,10 @@ int amps_recc_debug_slicer_bits(amps_recc_t *h, uint64_t first, size_t n, uint8_
     const uint64_t w0 = first >> 6, nw = ((first + n - 1) >> 6) - w0 + 1;      // <= ring_words
     const uint64_t s0 = w0 & (h->ring_words - 1), n1 = std::min<uint64_t>(nw, h->ring_words - s0);
     std::vector<uint64_t> words((size_t)h->C * nw);
-    HIP_TRY(hipMemcpy2DAsync(words.data(), nw * 8, h->gring.get() + s0, (size_t)h->ring_words * 8, n1 * 8, h->C, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpy2DAsync(words.data(), nw * 8, h->gring.get() + s0, (size_t)h->ring_words * 8, n1 * 8, h->C, hipMemcpyDeviceToHost, h->stream.get()));
     if (nw > n1)                                                                 // the range wraps round the ring's end
-        HIP_TRY(hipMemcpy2DAsync(words.data() + n1, nw * 8, h->gring.get(), (size_t)h->ring_words * 8, (nw - n1) * 8, h->C, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+        HIP_TRY(hipMemcpy2DAsync(words.data() + n1, nw * 8, h->gring.get(), (size_t)h->ring_words * 8, (nw - n1) * 8, h->C, hipMemcpyDeviceToHost, h->stream.get()));
+    HIP_TRY(hipStreamSynchronize(h->stream.get()));
     for (size_t c = 0; c < h->C; c++) {
         const uint64_t *w = words.data() + c * nw;
         uint8_t *o = out + c * out_ld;
@@ -1437,7 +1432,7 @@ int amps_recc_channel_power(amps_recc_t *h, uint64_t first_snap, size_t n, float
     if (!h->chz.pow_ring) return -ENOSYS;
     STALE_CHECK(h);
     HIP_TRY(hipSetDevice(h->device));
-    if (int rc = sync_stream(h, h->stream)) return rc;
+    if (int rc = sync_stream(h, h->stream.get())) return rc;
     uint64_t lo, hi;
     power_window(h, &lo, &hi);
     if (rows) *rows = h->C;
@@ -1448,9 +1443,9 @@ int amps_recc_channel_power(amps_recc_t *h, uint64_t first_snap, size_t n, float
     const uint32_t slots = h->chz.pow_slots;
     const size_t C = h->C, s0 = (size_t)(first_snap & (slots - 1)), n1 = std::min<size_t>(n, slots - s0);
     std::vector<float> snap(n * C);
-    HIP_TRY(hipMemcpyAsync(snap.data(), h->chz.pow_ring.get() + s0 * C, sizeof(float) * n1 * C, hipMemcpyDeviceToHost, h->stream));
-    if (n > n1) HIP_TRY(hipMemcpyAsync(snap.data() + n1 * C, h->chz.pow_ring.get(), sizeof(float) * (n - n1) * C, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpyAsync(snap.data(), h->chz.pow_ring.get() + s0 * C, sizeof(float) * n1 * C, hipMemcpyDeviceToHost, h->stream.get()));
+    if (n > n1) HIP_TRY(hipMemcpyAsync(snap.data() + n1 * C, h->chz.pow_ring.get(), sizeof(float) * (n - n1) * C, hipMemcpyDeviceToHost, h->stream.get()));
+    HIP_TRY(hipStreamSynchronize(h->stream.get()));
     for (size_t c = 0; c < C; c++)
         for (size_t i = 0; i < n; i++) out[c * out_ld + i] = snap[i * C + c];
     return 0;
@@ -1469,17 +1464,17 @@ int amps_recc_burst_power(amps_recc_t *h, const amps_recc_burst_t *recs, size_t 
         q[i] = ChzBurstQuery{ recs[i].position, (uint32_t)h->chan2row[recs[i].channel], 0u };
     }
     HIP_TRY(hipSetDevice(h->device));
-    if (int rc = sync_stream(h, h->stream)) return rc;            // the window is that of an idle stream; the copies below are synchronous
+    if (int rc = sync_stream(h, h->stream.get())) return rc;            // the window is that of an idle stream; the copies below are synchronous
     if (h->pq_dev.reserve(n) || h->pq_out.reserve(n)) return -ENOMEM;
     uint64_t lo, hi;
     power_window(h, &lo, &hi);
     HIP_TRY(hipMemcpy(h->pq_dev.get(), q.data(), sizeof(ChzBurstQuery) * n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(chz_power_gather_kernel, dim3((uint32_t)((n + 3) / 4)), dim3(256), 0, h->stream, h->chz.pow_ring.get(), h->C, h->chz.pow_slots - 1, lo, hi,
+    hipLaunchKernelGGL(chz_power_gather_kernel, dim3((uint32_t)((n + 3) / 4)), dim3(256), 0, h->stream.get(), h->chz.pow_ring.get(), h->C, h->chz.pow_slots - 1, lo, hi,
                        (uint32_t)AMPS_RECC_CAPTURE_SYMS * h->sps, h->pq_dev.get(), (uint32_t)n, h->pq_out.get());
     HIP_TRY(hipGetLastError());
     std::vector<uint2> res(n);
-    HIP_TRY(hipMemcpyAsync(res.data(), h->pq_out.get(), sizeof(uint2) * n, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpyAsync(res.data(), h->pq_out.get(), sizeof(uint2) * n, hipMemcpyDeviceToHost, h->stream.get()));
+    HIP_TRY(hipStreamSynchronize(h->stream.get()));
     for (size_t i = 0; i < n; i++) { std::memcpy(&mean_power[i], &res[i].x, sizeof(float)); n_snaps[i] = res[i].y; }
     return 0;
 }
@@ -1500,7 +1495,7 @@ int amps_recc_set_timing(amps_recc_t *h, int mode)
 {
     if (!h || mode < AMPS_RECC_TIMING_OFF || mode > AMPS_RECC_TIMING_DOMINANT_SAMPLED) return -EINVAL;
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream.get()));
     collect_spans(h);
     h->timing_mode = mode;
     h->dominant_tick = 0;
@@ -1513,7 +1508,7 @@ int amps_recc_get_timing(amps_recc_t *h, amps_recc_timing_t *t, int reset)
 {
     if (!h || !t) return -EINVAL;
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream.get()));
     collect_spans(h);
     std::memset(t, 0, sizeof(*t));
     t->struct_size = sizeof(*t);
@@ -1547,7 +1542,7 @@ static int bch_stage_in(amps_recc_t *h, const uint8_t *in, size_t nin, int mem, 
 {
     if (mem == AMPS_MEM_DEVICE) { *din = in; return 0; }
     if (int rc = bch_grow(h->bch_in, nin)) return rc;
-    if (hipMemcpyAsync(h->bch_in.get(), in, nin, hipMemcpyHostToDevice, h->stream) != hipSuccess) return -EIO;
+    if (hipMemcpyAsync(h->bch_in.get(), in, nin, hipMemcpyHostToDevice, h->stream.get()) != hipSuccess) return -EIO;
     *din = h->bch_in.get();
     return 0;
 }
@@ -1561,10 +1556,10 @@ int amps_bch_encode_words(amps_recc_t *h, const uint8_t *msg, size_t nwords, int
     if (int rc = bch_stage_in(h, msg, nwords * k, mem, &din)) return rc;
     const size_t nout = nwords * (size_t)(k + 12);
     if (int rc = bch_grow(h->bch_out, nout)) return rc;
-    hipLaunchKernelGGL(bch_encode_words_kernel, dim3((unsigned)std::min<size_t>((nwords + 255) / 256, 4096)), dim3(256), 0, h->stream,
+    hipLaunchKernelGGL(bch_encode_words_kernel, dim3((unsigned)std::min<size_t>((nwords + 255) / 256, 4096)), dim3(256), 0, h->stream.get(),
                        din, (uint32_t)nwords, k, h->bch_out.get());
-    HIP_TRY(hipMemcpyAsync(codewords, h->bch_out.get(), nout, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpyAsync(codewords, h->bch_out.get(), nout, hipMemcpyDeviceToHost, h->stream.get()));
+    HIP_TRY(hipStreamSynchronize(h->stream.get()));
     return 0;
 }
 
@@ -1577,12 +1572,12 @@ int amps_bch_decode_words(amps_recc_t *h, const uint8_t *codewords, size_t nword
     if (int rc = bch_stage_in(h, codewords, nwords * (size_t)(k + 12), mem, &din)) return rc;
     if (int rc = bch_grow(h->bch_out, nwords * (size_t)k)) return rc;
     if (bch_grow(h->bch_val, nwords) || bch_grow(h->bch_err, nwords)) return -ENOMEM;
-    hipLaunchKernelGGL(bch_decode_words_kernel, dim3((unsigned)std::min<size_t>((nwords + 255) / 256, 4096)), dim3(256), 0, h->stream,
+    hipLaunchKernelGGL(bch_decode_words_kernel, dim3((unsigned)std::min<size_t>((nwords + 255) / 256, 4096)), dim3(256), 0, h->stream.get(),
                        din, (uint32_t)nwords, k, h->bch_out.get(), h->bch_val.get(), h->bch_err.get());
-    HIP_TRY(hipMemcpyAsync(msg, h->bch_out.get(), nwords * k, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(valid, h->bch_val.get(), nwords, hipMemcpyDeviceToHost, h->stream));
-    if (nerrors) HIP_TRY(hipMemcpyAsync(nerrors, h->bch_err.get(), nwords, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpyAsync(msg, h->bch_out.get(), nwords * k, hipMemcpyDeviceToHost, h->stream.get()));
+    HIP_TRY(hipMemcpyAsync(valid, h->bch_val.get(), nwords, hipMemcpyDeviceToHost, h->stream.get()));
+    if (nerrors) HIP_TRY(hipMemcpyAsync(nerrors, h->bch_err.get(), nwords, hipMemcpyDeviceToHost, h->stream.get()));
+    HIP_TRY(hipStreamSynchronize(h->stream.get()));
     return 0;
 }
 

@@ -1,13 +1,14 @@
-// recc_devmem.hip.h -- who owns the handle's memory: every hipMalloc / hipHostMalloc allocation of the library (recc_rccl.hip.h
-// apart, whose teardown is ordered around the communicator's abort) belongs to one of the owners below and is freed by it, and
-// host-resident input reaches the device through one staging path (HostStage).  Plain structs: the growth policy, the sizes and
-// the order of destruction stay with the code that uses them.
+// recc_devmem.hip.h -- who owns the handle's HIP objects: every hipMalloc / hipHostMalloc allocation, every event and every stream
+// of the library belongs to one of the owners below and is released by it, and host-resident input reaches the device through one
+// staging path (HostStage).  Plain structs: the growth policy, the sizes, the moment of creation and the order of destruction stay
+// with the code that uses them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cerrno>
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
 #include <utility>
 
 namespace amps {
@@ -38,8 +39,8 @@ public:
     int reserve(size_t n) { return n <= cap_ ? 0 : alloc(n); }
 };
 
-// One allocation of mapped pinned host memory: the kernels write through dev(), the host reads host() without a copy call
-// (record lists, kept-burst lists, list headers).
+// One allocation of pinned host memory, mapped unless alloc is told otherwise: the kernels write through dev(), the host reads host()
+// without a copy call (record lists, kept-burst lists, list headers).  With hipHostMallocDefault it is pinned only: dev() stays null.
 template <typename T> class MappedBuf {
     T *host_ = nullptr, *dev_ = nullptr;
 public:
@@ -51,32 +52,76 @@ public:
     T *dev() const { return dev_; }
     explicit operator bool() const { return host_ != nullptr; }
     void reset() { if (host_) (void)hipHostFree(host_); host_ = nullptr; dev_ = nullptr; }
-    int alloc(size_t n)
+    int alloc(size_t n, unsigned flags = hipHostMallocMapped)
     {
         reset();
-        if (hipHostMalloc((void **)&host_, n * sizeof(T), hipHostMallocMapped) != hipSuccess) { host_ = nullptr; return -ENOMEM; }
-        if (hipHostGetDevicePointer((void **)&dev_, host_, 0) != hipSuccess) { reset(); return -ENOMEM; }
+        if (hipHostMalloc((void **)&host_, n * sizeof(T), flags) != hipSuccess) { host_ = nullptr; return -ENOMEM; }
+        if ((flags & hipHostMallocMapped) && hipHostGetDevicePointer((void **)&dev_, host_, 0) != hipSuccess) { reset(); return -ENOMEM; }
         return 0;
     }
 };
 
-// the guard inside a HostStage (below): an event behind the last kernel that reads the staging buffer
+// One event, created when its user says so: with hipEventDisableTiming for an ordering event, with no flags for a timing event.
+class Event {
+    hipEvent_t e_ = nullptr;
+public:
+    Event() = default;
+    Event(Event &&o) noexcept : e_(std::exchange(o.e_, nullptr)) {}
+    Event &operator=(Event &&o) noexcept { if (this != &o) { reset(); e_ = std::exchange(o.e_, nullptr); } return *this; }
+    ~Event() { reset(); }
+    hipEvent_t get() const { return e_; }
+    explicit operator bool() const { return e_ != nullptr; }
+    void reset() { if (e_) (void)hipEventDestroy(e_); e_ = nullptr; }
+    int create(unsigned flags = hipEventDefault)
+    {
+        reset();
+        if ((flags == hipEventDefault ? hipEventCreate(&e_) : hipEventCreateWithFlags(&e_, flags)) != hipSuccess) { e_ = nullptr; return -ENOMEM; }
+        return 0;
+    }
+};
+
+// One stream: a non-blocking one of the library's own (create), destroyed with its owner, or the caller's (borrow), never destroyed.
+class Stream {
+    hipStream_t s_ = nullptr;
+    bool own_ = false;
+public:
+    Stream() = default;
+    Stream(Stream &&o) noexcept : s_(std::exchange(o.s_, nullptr)), own_(std::exchange(o.own_, false)) {}
+    Stream &operator=(Stream &&o) noexcept { if (this != &o) { reset(); s_ = std::exchange(o.s_, nullptr); own_ = std::exchange(o.own_, false); } return *this; }
+    ~Stream() { reset(); }
+    hipStream_t get() const { return s_; }
+    explicit operator bool() const { return s_ != nullptr; }
+    void reset() { if (own_ && s_) (void)hipStreamDestroy(s_); s_ = nullptr; own_ = false; }
+    int create()
+    {
+        reset();
+        if (hipStreamCreateWithFlags(&s_, hipStreamNonBlocking) != hipSuccess) { s_ = nullptr; return -EIO; }
+        own_ = true;
+        return 0;
+    }
+    void borrow(hipStream_t s) { reset(); s_ = s; }
+};
+
+static_assert(!std::is_copy_constructible<DevBuf<float>>::value && !std::is_copy_constructible<MappedBuf<float>>::value &&
+              !std::is_copy_constructible<Event>::value && !std::is_copy_constructible<Stream>::value, "an owner is moved, never copied");
+
+// the guard inside a HostStage (below): an event, created by the first arm, behind the last kernel that reads the staging buffer
+// (a fence that was moved from has no event and waits for nothing)
 struct StageFence {
-    hipEvent_t ev = nullptr;
+    Event ev;
     bool armed = false;
     int wait()
     {
-        if (armed) { if (hipEventSynchronize(ev) != hipSuccess) return -EIO; armed = false; }
+        if (armed && ev) { if (hipEventSynchronize(ev.get()) != hipSuccess) return -EIO; armed = false; }
         return 0;
     }
     int arm(hipStream_t s)
     {
-        if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return -ENOMEM;
-        if (hipEventRecord(ev, s) != hipSuccess) return -EIO;
+        if (!ev && ev.create(hipEventDisableTiming)) return -ENOMEM;
+        if (hipEventRecord(ev.get(), s) != hipSuccess) return -EIO;
         armed = true;
         return 0;
     }
-    void destroy() { if (ev) (void)hipEventDestroy(ev); ev = nullptr; armed = false; }
 };
 
 // The device staging buffer of one seam for host-resident input, and its guard.  Copies from pageable host memory are neither
@@ -90,11 +135,6 @@ struct StageFence {
 struct HostStage {
     DevBuf<uint8_t> buf;
     StageFence fence;
-    HostStage() = default;
-    HostStage(HostStage &&o) noexcept : buf(std::move(o.buf)), fence(std::exchange(o.fence, StageFence())) {}
-    HostStage &operator=(HostStage &&o) noexcept { if (this != &o) { reset(); buf = std::move(o.buf); fence = std::exchange(o.fence, StageFence()); } return *this; }
-    ~HostStage() { reset(); }
-    void reset() { fence.destroy(); buf.reset(); }
     // `rows` rows of `n` elements from the host block `src` (row pitch `ld` elements) into a buffer of at least `reserve`
     // elements, rows packed: *dev is the device copy and *dev_ld = n its pitch
     template <typename T> int stage(const T *src, size_t ld, size_t n, size_t rows, size_t reserve, const T **dev, uint64_t *dev_ld)

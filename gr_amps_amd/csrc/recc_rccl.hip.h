@@ -36,6 +36,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
+#include "recc_devmem.hip.h"
 
 namespace amps {
 
@@ -107,20 +108,21 @@ struct RcclState {
     int nranks = 0, rank = 0;
     uint32_t timeout_ms = 30000;
     bool timeout_set = false;                                // amps_recc_rccl_set_timeout was called: the environment does not override it
-    hipStream_t cstream = nullptr;
-    float2 *buf[2] = { nullptr, nullptr };
+    Stream cstream;                                          // the library's own: the collectives run here
+    DevBuf<float2> buf[2];
     size_t buf_samples = 0;                                  // allocated per buffer (cap_common + slack for the scatter chunks)
     uint64_t cap_common = 0;                                 // the push size every rank's handle takes: min over the ranks
     uint32_t mb_common = 0;                                  // the longest record list of any rank: max over the ranks
-    hipEvent_t filled[2] = { nullptr, nullptr }, freed[2] = { nullptr, nullptr }, root_ready = nullptr;
+    Event filled[2], freed[2], root_ready;
     bool used[2] = { false, false };
     int slot = 0;
-    uint32_t *hdr_dev = nullptr, *hdr_host = nullptr;        // [HDR_WORDS (1 + nranks)]: this rank's words, then everybody's (host copy: pinned)
-    uint8_t *g_send = nullptr, *g_recv = nullptr;            // device [mb_common recsz] / [nranks mb_common recsz] bytes
+    DevBuf<uint32_t> hdr_dev;                                // [HDR_WORDS (1 + nranks)]: this rank's words, then everybody's
+    MappedBuf<uint32_t> hdr_host;                            // the host copy of the same: pinned, not mapped
+    DevBuf<uint8_t> g_send, g_recv;                          // [mb_common recsz] / [nranks mb_common recsz] bytes
     size_t g_cap = 0;                                        // bytes per rank in g_send / g_recv
     // timing of the data collectives (HIP events on cstream; harvested when a slot comes round again and by rccl_info)
     bool timing = false;
-    hipEvent_t t0[2] = { nullptr, nullptr }, t1[2] = { nullptr, nullptr };
+    Event t0[2], t1[2];
     bool t_open[2] = { false, false };
     double coll_ms = 0.0;
     uint64_t coll_bytes = 0, coll_count = 0;
@@ -133,22 +135,6 @@ inline const char *rccl_errstr(int rc)
     return api.GetErrorString ? api.GetErrorString(rc) : "error";
 }
 
-inline void rccl_free_buffers(RcclState &r)
-{
-    for (int i = 0; i < 2; i++) {
-        if (r.buf[i]) (void)hipFree(r.buf[i]);
-        if (r.filled[i]) (void)hipEventDestroy(r.filled[i]);
-        if (r.freed[i]) (void)hipEventDestroy(r.freed[i]);
-        if (r.t0[i]) (void)hipEventDestroy(r.t0[i]);
-        if (r.t1[i]) (void)hipEventDestroy(r.t1[i]);
-    }
-    if (r.root_ready) (void)hipEventDestroy(r.root_ready);
-    if (r.hdr_dev) (void)hipFree(r.hdr_dev);
-    if (r.hdr_host) (void)hipHostFree(r.hdr_host);
-    if (r.g_send) (void)hipFree(r.g_send);
-    if (r.g_recv) (void)hipFree(r.g_recv);
-}
-
 // the communicator is gone after this (ncclCommAbort makes collectives in flight return); peers run into their own bound
 inline void rccl_kill(RcclState &r)
 {
@@ -159,35 +145,21 @@ inline void rccl_kill(RcclState &r)
     r.stale = true;
 }
 
-inline int rccl_wait(RcclState &r, hipStream_t s);
-inline void rccl_destroy(RcclState &r)
-{
-    // bounded like every other wait on a collective (ADVICE r05): a peer that died inside the last data collective must not hang the
-    // destructor; on expiry rccl_wait has aborted the communicator, after which the stream drains by itself
-    if (r.cstream && r.comm && !r.dead) (void)rccl_wait(r, r.cstream);
-    if (r.cstream) (void)hipStreamSynchronize(r.cstream);
-    if (r.comm && rccl_api().ok()) (void)rccl_api().CommDestroy(r.comm);
-    rccl_free_buffers(r);
-    if (r.cstream) (void)hipStreamDestroy(r.cstream);
-    const uint32_t keep_ms = r.timeout_ms;
-    const bool keep_set = r.timeout_set, keep_stale = r.stale;
-    r = RcclState();
-    r.timeout_ms = keep_ms; r.timeout_set = keep_set; r.stale = keep_stale;   // a failed init leaves a fresh state, not a forgotten bound
-}
-
-// bounded wait of the host for stream s: 0, -EIO, or -ETIMEDOUT with the communicator aborted
-inline int rccl_wait(RcclState &r, hipStream_t s)
+// bounded wait of the host until `query` answers hipSuccess (`what` did not happen, for the message, if it never does): 0, -EIO, or
+// -ETIMEDOUT with the communicator aborted.  For a stream, and for an event (a drain's marker on the handle's stream, a timing event
+// on the collective stream).
+template <typename Query> inline int rccl_poll(RcclState &r, Query query, const char *what)
 {
     const auto t0 = std::chrono::steady_clock::now();
     for (uint32_t spins = 0;; spins++) {
-        const hipError_t e = hipStreamQuery(s);
+        const hipError_t e = query();
         if (e == hipSuccess) return 0;
         if (e != hipErrorNotReady) { (void)hipGetLastError(); rccl_kill(r); return -EIO; }
         (void)hipGetLastError();                                 // hipErrorNotReady is sticky in hipGetLastError otherwise
         if (spins > 4000) {
             const auto ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
             if ((uint64_t)ms >= r.timeout_ms) {
-                std::fprintf(stderr, "amps_recc: rank %d: no answer from the other ranks within %u ms: communicator aborted\n", r.rank, r.timeout_ms);
+                std::fprintf(stderr, "amps_recc: rank %d: %s within %u ms: communicator aborted\n", r.rank, what, r.timeout_ms);
                 rccl_kill(r);
                 return -ETIMEDOUT;
             }
@@ -195,26 +167,24 @@ inline int rccl_wait(RcclState &r, hipStream_t s)
         }
     }
 }
+inline int rccl_wait(RcclState &r, hipStream_t s) { return rccl_poll(r, [s] { return hipStreamQuery(s); }, "no answer from the other ranks"); }
+inline int rccl_wait_event(RcclState &r, hipEvent_t ev) { return rccl_poll(r, [ev] { return hipEventQuery(ev); }, "work queued behind a collective did not finish"); }
 
-// the same for an event (a drain's marker on the handle's stream, a timing event on the collective stream)
-inline int rccl_wait_event(RcclState &r, hipEvent_t ev)
+// The one way out of a communicator, for a failed init as for the handle's end.
+inline void rccl_destroy(RcclState &r)
 {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (uint32_t spins = 0;; spins++) {
-        const hipError_t e = hipEventQuery(ev);
-        if (e == hipSuccess) return 0;
-        if (e != hipErrorNotReady) { (void)hipGetLastError(); rccl_kill(r); return -EIO; }
-        (void)hipGetLastError();
-        if (spins > 4000) {
-            const auto ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
-            if ((uint64_t)ms >= r.timeout_ms) {
-                std::fprintf(stderr, "amps_recc: rank %d: work queued behind a collective did not finish within %u ms: communicator aborted\n", r.rank, r.timeout_ms);
-                rccl_kill(r);
-                return -ETIMEDOUT;
-            }
-            usleep(spins > 40000 ? 200 : 20);
-        }
-    }
+    // bounded like every other wait on a collective (ADVICE r05): a peer that died inside the last data collective must not hang the
+    // destructor; on expiry rccl_wait has aborted the communicator, after which the stream drains by itself
+    if (r.cstream && r.comm && !r.dead) (void)rccl_wait(r, r.cstream.get());
+    if (r.cstream) (void)hipStreamSynchronize(r.cstream.get());
+    if (r.comm && rccl_api().ok()) (void)rccl_api().CommDestroy(r.comm);
+    // Everything the state owns is released, in an explicit order: the buffers and the events go with the assignment, the stream after
+    // them, when `last` leaves the scope.  What stays is the caller's bound (a failed init leaves a fresh state, not a forgotten bound)
+    // and the verdict on the handle's stream.
+    Stream last = std::move(r.cstream);
+    RcclState fresh;
+    fresh.timeout_ms = r.timeout_ms; fresh.timeout_set = r.timeout_set; fresh.stale = r.stale;
+    r = std::move(fresh);
 }
 
 // 16 bytes of every rank to every rank; on return r.hdr_host[HDR_WORDS (1 + k) ...] = rank k's words.  Any failure on the way kills the
@@ -223,17 +193,17 @@ inline int rccl_exchange(RcclState &r, const uint32_t mine[RCCL_HDR_WORDS])
 {
     RcclApi &api = rccl_api();
     const size_t hb = sizeof(uint32_t) * RCCL_HDR_WORDS;
-    std::memcpy(r.hdr_host, mine, hb);
-    if (hipMemcpyAsync(r.hdr_dev, r.hdr_host, hb, hipMemcpyHostToDevice, r.cstream) != hipSuccess) { rccl_kill(r); return -EIO; }
-    if (int rc = api.AllGather(r.hdr_dev, r.hdr_dev + RCCL_HDR_WORDS, hb, RCCL_UINT8, r.comm, r.cstream)) {
+    std::memcpy(r.hdr_host.host(), mine, hb);
+    if (hipMemcpyAsync(r.hdr_dev.get(), r.hdr_host.host(), hb, hipMemcpyHostToDevice, r.cstream.get()) != hipSuccess) { rccl_kill(r); return -EIO; }
+    if (int rc = api.AllGather(r.hdr_dev.get(), r.hdr_dev.get() + RCCL_HDR_WORDS, hb, RCCL_UINT8, r.comm, r.cstream.get())) {
         std::fprintf(stderr, "amps_recc: ncclAllGather (header): %s\n", rccl_errstr(rc));
         rccl_kill(r);
         return -EIO;
     }
-    if (hipMemcpyAsync(r.hdr_host + RCCL_HDR_WORDS, r.hdr_dev + RCCL_HDR_WORDS, hb * (size_t)r.nranks, hipMemcpyDeviceToHost, r.cstream) != hipSuccess) { rccl_kill(r); return -EIO; }
-    return rccl_wait(r, r.cstream);
+    if (hipMemcpyAsync(r.hdr_host.host() + RCCL_HDR_WORDS, r.hdr_dev.get() + RCCL_HDR_WORDS, hb * (size_t)r.nranks, hipMemcpyDeviceToHost, r.cstream.get()) != hipSuccess) { rccl_kill(r); return -EIO; }
+    return rccl_wait(r, r.cstream.get());
 }
-inline const uint32_t *rccl_hdr_of(const RcclState &r, int k) { return r.hdr_host + RCCL_HDR_WORDS * (1 + (size_t)k); }
+inline const uint32_t *rccl_hdr_of(const RcclState &r, int k) { return r.hdr_host.host() + RCCL_HDR_WORDS * (1 + (size_t)k); }
 
 // the verdict of an exchange whose word 0 is a status (0 = fine, else a positive errno): 0 if every rank is fine, this rank's own
 // error if it has one, -EREMOTEIO if only others have
@@ -247,10 +217,10 @@ inline int rccl_verdict(const RcclState &r, uint32_t own)
 inline void rccl_harvest(RcclState &r, int slot, bool wait)
 {
     if (!r.t_open[slot]) return;
-    if (!wait && hipEventQuery(r.t1[slot]) != hipSuccess) { (void)hipGetLastError(); return; }
+    if (!wait && hipEventQuery(r.t1[slot].get()) != hipSuccess) { (void)hipGetLastError(); return; }
     float ms = 0.f;
-    if ((wait ? (r.comm && !r.dead ? (rccl_wait_event(r, r.t1[slot]) == 0 ? hipSuccess : hipErrorUnknown) : hipEventSynchronize(r.t1[slot])) : hipSuccess) == hipSuccess &&
-        hipEventElapsedTime(&ms, r.t0[slot], r.t1[slot]) == hipSuccess) {
+    if ((wait ? (r.comm && !r.dead ? (rccl_wait_event(r, r.t1[slot].get()) == 0 ? hipSuccess : hipErrorUnknown) : hipEventSynchronize(r.t1[slot].get())) : hipSuccess) == hipSuccess &&
+        hipEventElapsedTime(&ms, r.t0[slot].get(), r.t1[slot].get()) == hipSuccess) {
         r.coll_ms += ms;
         r.coll_count++;
     }
@@ -274,27 +244,20 @@ inline int rccl_init(RcclState &r, const uint8_t *id, int nranks, int rank, cons
     RcclId uid;
     std::memcpy(uid.internal, id, sizeof(uid.internal));
     const size_t hw = RCCL_HDR_WORDS * (1 + (size_t)nranks);
-    if (hipStreamCreateWithFlags(&r.cstream, hipStreamNonBlocking) != hipSuccess) { r.cstream = nullptr; own = own ? own : EIO; }
+    if (r.cstream.create()) own = own ? own : EIO;
     for (int i = 0; i < 2 && !own; i++)
-        if (hipEventCreateWithFlags(&r.filled[i], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&r.freed[i], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreate(&r.t0[i]) != hipSuccess || hipEventCreate(&r.t1[i]) != hipSuccess) own = ENOMEM;
-    if (!own && hipEventCreateWithFlags(&r.root_ready, hipEventDisableTiming) != hipSuccess) own = ENOMEM;
-    if (hipMalloc((void **)&r.hdr_dev, sizeof(uint32_t) * hw) != hipSuccess || hipHostMalloc((void **)&r.hdr_host, sizeof(uint32_t) * hw, hipHostMallocDefault) != hipSuccess || !r.cstream) {
-        // without the header words this rank cannot even say what went wrong: it does not join (see above)
-        rccl_free_buffers(r);
-        if (r.cstream) (void)hipStreamDestroy(r.cstream);
-        r = RcclState();
-        return -ENOMEM;
-    }
+        if (r.filled[i].create(hipEventDisableTiming) || r.freed[i].create(hipEventDisableTiming) || r.t0[i].create() || r.t1[i].create()) own = ENOMEM;
+    if (!own && r.root_ready.create(hipEventDisableTiming)) own = ENOMEM;
+    auto fail = [&](int code) { rccl_destroy(r); return code; };   // (rccl_destroy leaves a fresh state: the handle may try again)
+    // without the header words this rank cannot even say what went wrong: it does not join (see above)
+    if (r.hdr_dev.alloc(hw) || r.hdr_host.alloc(hw, hipHostMallocDefault) || !r.cstream) return fail(-ENOMEM);
     const int rc = api.CommInitRank(&r.comm, nranks, uid, rank);  // collective: returns when every rank has joined
     if (rc != 0) {
         std::fprintf(stderr, "amps_recc: ncclCommInitRank: %s\n", rccl_errstr(rc));
         r.comm = nullptr;
-        rccl_destroy(r);
-        return -EIO;
+        return fail(-EIO);
     }
     r.nranks = nranks; r.rank = rank;
-    auto fail = [&](int code) { rccl_destroy(r); return code; };   // (rccl_destroy leaves a fresh state: the handle may try again)
     // round 1: {status, groups, capacity in units of 64 samples, max_bursts} -> the common capacities
     const uint32_t w1[RCCL_HDR_WORDS] = { own, loc.groups, (uint32_t)std::min<uint64_t>(loc.cap_samples / RCCL_CHUNK_ALIGN, 0xffffffffu), loc.max_bursts };
     if (int e = rccl_exchange(r, w1)) return fail(e);
@@ -313,10 +276,10 @@ inline int rccl_init(RcclState &r, const uint8_t *id, int nranks, int rank, cons
     // round 2: the buffers for those capacities, and whether every rank got them
     own = 0;
     r.buf_samples = (size_t)cap + (size_t)RCCL_CHUNK_ALIGN * (size_t)nranks;
-    for (int i = 0; i < 2; i++) if (hipMalloc((void **)&r.buf[i], sizeof(float2) * r.buf_samples) != hipSuccess) { r.buf[i] = nullptr; own = ENOMEM; }
+    for (int i = 0; i < 2; i++) if (r.buf[i].alloc(r.buf_samples)) own = ENOMEM;
     r.g_cap = (size_t)mb * recsz;
-    if (hipMalloc((void **)&r.g_send, r.g_cap) != hipSuccess) { r.g_send = nullptr; own = ENOMEM; }
-    if (hipMalloc((void **)&r.g_recv, r.g_cap * (size_t)nranks) != hipSuccess) { r.g_recv = nullptr; own = ENOMEM; }
+    if (r.g_send.alloc(r.g_cap)) own = ENOMEM;
+    if (r.g_recv.alloc(r.g_cap * (size_t)nranks)) own = ENOMEM;
     if (own) (void)hipGetLastError();
     const uint32_t w2[RCCL_HDR_WORDS] = { own, 0, 0, 0 };
     if (int e = rccl_exchange(r, w2)) return fail(e);
@@ -380,26 +343,26 @@ inline int rccl_distribute(RcclState &r, const float2 *root_block, bool root_blo
     const int slot = r.slot;
     r.slot ^= 1;
     rccl_harvest(r, slot, false);
-    float2 *dst = r.buf[slot];
+    float2 *dst = r.buf[slot].get();
     const float2 *src = root_block;                              // where the root's samples are read from (root only)
     if (r.rank == root && root_block_on_host) {
         // a host block is staged into the receive buffer by a synchronous copy (the caller may reuse its memory on return; an async copy
         // from pageable memory gives no such guarantee) once the kernels of two pushes ago have read that buffer
         // (bounded: those kernels sit behind the collective that filled the buffer -- a peer that died inside it must not hang this rank here)
-        if (r.used[slot]) if (int e = rccl_wait_event(r, r.freed[slot])) return e;
+        if (r.used[slot]) if (int e = rccl_wait_event(r, r.freed[slot].get())) return e;
         if (hipMemcpy(dst, root_block, sizeof(float2) * nsamp, hipMemcpyHostToDevice) != hipSuccess) return broken("hipMemcpy (staging)", 0);
         src = dst;                                               // in place
     } else {
-        if (r.used[slot] && hipStreamWaitEvent(r.cstream, r.freed[slot], 0) != hipSuccess) return broken("hipStreamWaitEvent", 0);   // the kernels of two pushes ago have read it
+        if (r.used[slot] && hipStreamWaitEvent(r.cstream.get(), r.freed[slot].get(), 0) != hipSuccess) return broken("hipStreamWaitEvent", 0);   // the kernels of two pushes ago have read it
         if (r.rank == root) {
             // a device block belongs to the work the caller ordered on the handle's stream (amps_recc_wait_event, or a producer on the
             // stream passed in cfg.stream): the collective reads it on ANOTHER stream and has to wait for that work too
-            if (hipEventRecord(r.root_ready, consumer) != hipSuccess || hipStreamWaitEvent(r.cstream, r.root_ready, 0) != hipSuccess) return broken("hipEventRecord", 0);
+            if (hipEventRecord(r.root_ready.get(), consumer) != hipSuccess || hipStreamWaitEvent(r.cstream.get(), r.root_ready.get(), 0) != hipSuccess) return broken("hipEventRecord", 0);
         }
     }
-    if (r.timing && hipEventRecord(r.t0[slot], r.cstream) != hipSuccess) return broken("hipEventRecord", 0);
+    if (r.timing && hipEventRecord(r.t0[slot].get(), r.cstream.get()) != hipSuccess) return broken("hipEventRecord", 0);
     if (mode == RCCL_DIST_BROADCAST) {
-        if (int rc = api.Broadcast(r.rank == root ? (const void *)src : (const void *)dst, dst, 2 * nsamp, RCCL_FLOAT32, root, r.comm, r.cstream)) return broken("ncclBroadcast", rc);
+        if (int rc = api.Broadcast(r.rank == root ? (const void *)src : (const void *)dst, dst, 2 * nsamp, RCCL_FLOAT32, root, r.comm, r.cstream.get())) return broken("ncclBroadcast", rc);
     } else {
         // scatter: rank k's chunk = samples [k chunk, k chunk + cnt(k)); then everybody's chunk to everybody, in place
         const size_t chunk = ((nsamp + N - 1) / N + RCCL_CHUNK_ALIGN - 1) / RCCL_CHUNK_ALIGN * RCCL_CHUNK_ALIGN;
@@ -408,22 +371,22 @@ inline int rccl_distribute(RcclState &r, const float2 *root_block, bool root_blo
         int grc = 0;
         if (r.rank == root) {
             for (size_t k = 0; k < N && !grc; k++)
-                if ((int)k != root && cnt(k)) grc = api.Send(src + k * chunk, 2 * cnt(k), RCCL_FLOAT32, (int)k, r.comm, r.cstream);
-        } else if (cnt((size_t)r.rank)) grc = api.Recv(dst + (size_t)r.rank * chunk, 2 * cnt((size_t)r.rank), RCCL_FLOAT32, root, r.comm, r.cstream);
+                if ((int)k != root && cnt(k)) grc = api.Send(src + k * chunk, 2 * cnt(k), RCCL_FLOAT32, (int)k, r.comm, r.cstream.get());
+        } else if (cnt((size_t)r.rank)) grc = api.Recv(dst + (size_t)r.rank * chunk, 2 * cnt((size_t)r.rank), RCCL_FLOAT32, root, r.comm, r.cstream.get());
         const int erc = api.GroupEnd();
         if (grc || erc) return broken("ncclSend / ncclRecv", grc ? grc : erc);
         if (r.rank == root && src != dst && cnt((size_t)root) &&
-            hipMemcpyAsync(dst + (size_t)root * chunk, src + (size_t)root * chunk, sizeof(float2) * cnt((size_t)root), hipMemcpyDeviceToDevice, r.cstream) != hipSuccess)
+            hipMemcpyAsync(dst + (size_t)root * chunk, src + (size_t)root * chunk, sizeof(float2) * cnt((size_t)root), hipMemcpyDeviceToDevice, r.cstream.get()) != hipSuccess)
             return broken("hipMemcpyAsync (own chunk)", 0);
-        if (int rc = api.AllGather(dst + (size_t)r.rank * chunk, dst, 2 * chunk, RCCL_FLOAT32, r.comm, r.cstream)) return broken("ncclAllGather", rc);
+        if (int rc = api.AllGather(dst + (size_t)r.rank * chunk, dst, 2 * chunk, RCCL_FLOAT32, r.comm, r.cstream.get())) return broken("ncclAllGather", rc);
     }
     if (r.timing) {
-        if (hipEventRecord(r.t1[slot], r.cstream) != hipSuccess) return broken("hipEventRecord", 0);
+        if (hipEventRecord(r.t1[slot].get(), r.cstream.get()) != hipSuccess) return broken("hipEventRecord", 0);
         r.t_open[slot] = true;
         r.coll_bytes += sizeof(float2) * nsamp;
     }
     r.last_mode = mode;
-    if (hipEventRecord(r.filled[slot], r.cstream) != hipSuccess || hipStreamWaitEvent(consumer, r.filled[slot], 0) != hipSuccess) return broken("hipEventRecord", 0);
+    if (hipEventRecord(r.filled[slot].get(), r.cstream.get()) != hipSuccess || hipStreamWaitEvent(consumer, r.filled[slot].get(), 0) != hipSuccess) return broken("hipEventRecord", 0);
     *out = dst;
     *slot_out = slot;
     return 0;
@@ -431,7 +394,7 @@ inline int rccl_distribute(RcclState &r, const float2 *root_block, bool root_blo
 inline int rccl_block_consumed(RcclState &r, int slot, hipStream_t consumer)
 {
     if (slot < 0) return 0;                                      // used in place (one rank, device block)
-    if (hipEventRecord(r.freed[slot], consumer) != hipSuccess) return -EIO;
+    if (hipEventRecord(r.freed[slot].get(), consumer) != hipSuccess) return -EIO;
     r.used[slot] = true;
     return 0;
 }
@@ -460,17 +423,17 @@ inline int rccl_gather_records(RcclState &r, const void *mine, uint32_t n, uint3
     if (longest == 0) return 0;                               // every rank sees the same counts: nobody enters the second collective
     const size_t bytes = (size_t)longest * recsz;             // <= g_cap on every rank (mb_common is the maximum over the ranks)
     // a synchronous copy from pageable memory (complete on return; cstream is idle: the exchange above ended with a wait)
-    if (n && hipMemcpy(r.g_send, mine, (size_t)n * recsz, hipMemcpyHostToDevice) != hipSuccess) { rccl_kill(r); return -EIO; }
-    if (int rc = api.AllGather(r.g_send, r.g_recv, bytes, RCCL_UINT8, r.comm, r.cstream)) {
+    if (n && hipMemcpy(r.g_send.get(), mine, (size_t)n * recsz, hipMemcpyHostToDevice) != hipSuccess) { rccl_kill(r); return -EIO; }
+    if (int rc = api.AllGather(r.g_send.get(), r.g_recv.get(), bytes, RCCL_UINT8, r.comm, r.cstream.get())) {
         std::fprintf(stderr, "amps_recc: ncclAllGather (records): %s\n", rccl_errstr(rc));
         rccl_kill(r);
         return -EIO;
     }
-    if (int e = rccl_wait(r, r.cstream)) return e;
+    if (int e = rccl_wait(r, r.cstream.get())) return e;
     if (r.rank == root && all) {
         for (size_t k = 0; k < N; k++) {
             (*all)[k].resize((size_t)counts[k] * recsz);
-            if (counts[k] && hipMemcpy((*all)[k].data(), r.g_recv + k * bytes, (*all)[k].size(), hipMemcpyDeviceToHost) != hipSuccess) return -EIO;
+            if (counts[k] && hipMemcpy((*all)[k].data(), r.g_recv.get() + k * bytes, (*all)[k].size(), hipMemcpyDeviceToHost) != hipSuccess) return -EIO;
         }
     }
     return 0;

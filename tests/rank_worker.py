@@ -2,6 +2,7 @@
 box's one GPU, with AMPS_RECC_RCCL_LIB = the loop-back stand-in).  Everything goes through the C ABI (gr_amps_amd.capi); the result
 of the rank is a JSON file (+ the gathered records on the root).  No torch here: host blocks in, host records out."""
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -12,6 +13,30 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 D, FIRST, CW = 512, 96, 832
+
+
+def free_device_bytes():
+    """free device memory by hipMemGetInfo of the HIP runtime the library has brought into this process"""
+    hip = ctypes.CDLL(next(line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64.so" in line))
+    free, total = ctypes.c_size_t(), ctypes.c_size_t()
+    if hip.hipMemGetInfo(ctypes.byref(free), ctypes.byref(total)) != 0:
+        raise SystemExit("hipMemGetInfo failed")
+    return free.value
+
+
+def handle_cycles(capi):
+    """eight handles one after the other, each with a one-rank communicator whose two receive buffers, staging path, gather buffers
+    and timing events all get used: the free device memory after every close"""
+    free = []
+    for _ in range(8):
+        r = capi.Recc(n_channels=64, max_samples=2048, max_bursts=64, time_kernels=True, wideband={"channels": 1024, "decim": 768, "first_channel": FIRST})
+        r.rccl_init(capi.Recc.rccl_unique_id(), 1, 0)
+        for _ in range(2):
+            r.push_wideband_dist(np.zeros(64 * 768, np.complex64))
+        r.drain_gather()
+        r.close()
+        free.append(free_device_bytes())
+    return free
 
 
 def main():
@@ -36,6 +61,10 @@ def main():
         with open(os.path.join(a.dir, "rank%d.json" % a.rank), "w") as f:
             json.dump(out, f)
 
+    if a.scenario == "handle_cycles":
+        out["free_after_close"] = handle_cycles(capi)
+        finish()
+        return
     # the communicator id: rank 0 makes it, a file carries it (the control plane is the application's)
     idf = os.path.join(a.dir, "id.bin")
     if a.rank == 0:
@@ -63,10 +92,13 @@ def main():
     if a.scenario == "small_rank" and a.rank == a.nranks - 1:
         cap_frames = (n // 3) // D + 72                       # this rank's handle takes a third of what the others take
     with capi.Recc(n_channels=CW, sps=3, max_samples=cap_frames, max_bursts=64 if a.rank else 96, wideband=wb, time_kernels=True) as r:
+        if a.scenario == "bad_groups":
+            r.rccl_set_timeout(45000)                         # the caller's bound outlives an init that fails
         rc, _ = code_of(r.rccl_init, uid, a.nranks, a.rank)
         out["init"] = rc
         if rc:
             out["second_init_after_failure"] = None
+            out["timeout_after_failed_init"] = r.rccl_info()["timeout_ms"]
             finish()
             return
         out["info"] = r.rccl_info()

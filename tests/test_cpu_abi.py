@@ -100,16 +100,17 @@ def test_product_never_imports_the_oracle():
 
 
 def test_device_memory_has_one_owner_and_host_input_one_staging_path():
-    """Allocation and release are written once (recc_devmem.hip.h: DevBuf, MappedBuf; recc_rccl.hip.h keeps its own, ordered around
-    the communicator's abort), so no buffer can be left off a free list; and the fence of a staging buffer is driven by HostStage alone."""
+    """Allocation and release of memory, events and streams are written once (recc_devmem.hip.h: DevBuf, MappedBuf, Event, Stream), so
+    nothing can be left off a free list; and the fence of a staging buffer is driven by HostStage alone."""
     csrc = os.path.join(ROOT, "gr_amps_amd", "csrc")
     files = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
     assert "recc_devmem.hip.h" in files and "amps_recc.hip" in files
     bad = []
     for f in files:
+        if f == "recc_devmem.hip.h":
+            continue
         txt = open(os.path.join(csrc, f)).read()
-        if f not in ("recc_devmem.hip.h", "recc_rccl.hip.h"):
-            bad += [(f, m) for m in re.findall(r"\b(?:hipMalloc|hipFree|hipHostMalloc|hipHostFree)\b", txt)]
-        if f != "recc_devmem.hip.h":
-            bad += [(f, m) for m in re.findall(r"StageFence|\bfence\s*\.|fence\s*\.\s*(?:wait|arm|destroy|ev|armed)\b", txt)]
+        bad += [(f, m) for m in re.findall(r"\b(?:hipMalloc|hipFree|hipHostMalloc|hipHostFree|hipEventCreate|hipEventCreateWithFlags|hipEventDestroy|"
+                                           r"hipStreamCreate\w*|hipStreamDestroy)\b", txt)]
+        bad += [(f, m) for m in re.findall(r"StageFence|\bfence\s*\.|fence\s*\.\s*(?:wait|arm|destroy|ev|armed)\b", txt)]
     assert not bad, bad
