@@ -125,6 +125,36 @@ def test_short_bits_ragged_pushes(gpu, decim, spec, sid):
     assert count == 0, (count, where)
 
 
+def test_extreme_components_ragged_pushes(gpu, decim):
+    """quantise() keeps every component below 30 000, so the 16-bit reader's sign-extending conversion never meets the ends of its
+    range there: here a random 1 % of the block's components are -32768, -32767, -1, 0, 1 or 32767, pushed as sc16 in the RAGGED
+    schedule; the bits are exactly those of the fc32 twin of the same values"""
+    D = decim
+    q = _block(D)[0].copy()
+    rng = np.random.default_rng(16)
+    flat = q.reshape(-1)
+    idx = np.nonzero(rng.random(flat.size) < 0.01)[0]
+    flat[idx] = rng.choice(np.array([-32768, -32767, -1, 0, 1, 32767], np.int16), idx.size)
+    assert flat.min() == -32768 and flat.max() == 32767 and abs(idx.size / flat.size - 0.01) < 1e-3
+    assert all((flat[idx] == v).sum() > 1000 for v in (-32768, -32767, -1, 0, 1, 32767))
+    xf = (q[:, 0].astype(np.float32) + 1j * q[:, 1].astype(np.float32)).astype(np.complex64)
+    with _handle(D) as r:
+        r.push_wideband(xf)
+        want, produced = _bits(r)
+    assert produced == (len(q) // D) & ~63
+    off = 0
+    with _handle(D) as r:
+        for m in RAGGED(D):
+            m = len(q) - off if m is None else m
+            r.push_wideband_short(q[off:off + m])
+            off += m
+        assert off == len(q)
+        got, p = _bits(r)
+    assert p == produced
+    count, where = _mism(got, want)
+    assert count == 0, (count, where)
+
+
 @pytest.mark.parametrize("order", ["sf", "fs"])
 @pytest.mark.parametrize("spec,sid", SPECS)
 def test_short_and_fc32_pushes_alternate_on_one_handle(gpu, decim, spec, sid, order):
