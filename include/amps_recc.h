@@ -154,7 +154,10 @@ typedef struct amps_recc_cfg {
     uint32_t n_channels;           /* independent RECC instances handled per push (1 .. 2^20-1); a channel's
                                     * stream may run for 2^44 samples between resets (2.8 years at 200 ksps) */
     uint32_t samples_per_symbol;   /* IQ seam: samples per Manchester symbol (10 at 200 ksps); 2..16      */
-    uint32_t max_samples_per_push; /* IQ seam: capacity per channel per push (0 = IQ seam unused)         */
+    uint32_t max_samples_per_push; /* IQ seam: capacity per channel per push (0 = IQ seam unused).
+                                    * Wideband seam: the unit is FRAMES (channel-rate samples: wideband samples / wideband_decim), and
+                                    * what is bounded is what a push PRODUCES, the frames carried over from earlier pushes included:
+                                    * see amps_recc_push_wideband.  Either way it sizes the slicer-bit ring (amps_recc_debug_slicer_bits) */
     uint32_t max_bursts;           /* capacity of the device-side result list per push/drain (>=1)        */
     int32_t  device;               /* HIP device ordinal, -1 = current device                             */
     uint32_t flags;                /* AMPS_RECC_FLAG_*                                                    */
@@ -242,7 +245,14 @@ int amps_recc_decode_bursts(amps_recc_t *h, const uint8_t *bursts, size_t nburst
 int amps_recc_push_iq(amps_recc_t *h, const float *iq, size_t ld, size_t nsamp, int mem);
 
 /* channelizer seam: one wideband interleaved fc32 stream (fs = M * 30 kHz) -> polyphase
- * channelizer -> the same fused path on every active channel.  nsamp wideband samples. */
+ * channelizer -> the same fused path on every active channel.  nsamp wideband samples.
+ * Capacity: cfg.max_samples_per_push counts FRAMES here (one per wideband_decim samples).  A push produces the whole frames of
+ * the samples it is given plus those that earlier pushes left over -- in the fused form (the default) rounded down to a multiple
+ * of 64, so up to 63 frames and a fraction of one wait for the next push -- and is refused with -E2BIG, nothing consumed, when the
+ * frames it would produce exceed max_samples_per_push: up to 63 more than the block itself holds.  A block of at most
+ * max_samples_per_push - 63 frames is therefore always accepted, whatever was pushed before (the tests and bench.py create their
+ * handles for block + 72 frames); a block of exactly max_samples_per_push frames only while nothing is left over, as when every
+ * block so far was a multiple of 64 frames. */
 int amps_recc_push_wideband(amps_recc_t *h, const float *iq, size_t nsamp, int mem);
 
 /* like amps_recc_push_wideband, the block as interleaved 16-bit I/Q ("sc16": what converters, the wire formats of USRP-class devices
