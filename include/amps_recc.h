@@ -105,7 +105,17 @@ enum amps_recc_msg_class {
  *   valid only if it decodes AND no correction falls into the 15 shortening positions; fields are parsed from the
  *   corrected bits; every word the dispatch reads must be valid; the 7-bit coded DCC must be within one bit of a
  *   code word.  In this mode word_raw = voted bits, first_valid_rep = number of repeats equal to the voted word.
- *   On error-free bursts both modes produce the same words, fields and class. */
+ *   On error-free bursts both modes produce the same words, fields and class.
+ *   In full: the vote is over the Manchester-decoded bits (dcc, dcc_bad and manch_bad are as in reference mode).  The
+ *   IT++ three-root acceptance (S1 = 0, S3 a cube) counts as decoding, and its three positions are corrections like any
+ *   other: one of them in the shortening positions makes the word invalid.  word_dec = the 36 message bits of the voted
+ *   word, corrected where the word is valid (a correction in the parity leaves them alone) and as voted where it is
+ *   not; the fields of such a word are parsed from the voted bits.  The dispatch is the reference's on these fields and
+ *   valid[0]; the words it reads are A and B, word C where the registration or origination branch takes the serial
+ *   number, and the called-address words the origination branch consumes.  If any of those is invalid and the class
+ *   would be PAGE_RESPONSE or later, the class is AMPS_MSG_INVALID_WORD_A (has_esn, esn, dialed and n_called_words
+ *   stay as the branch left them); INVALID_WORD_A and E_ZERO stand as they are.  AMPS_BURST_FLAG_DCC_INVALID is set
+ *   when dcc[] differs in two or more of its 7 bits from each of 0000000, 0011111, 1100011, 1111100. */
 
 /* amps_recc_burst_t.flags */
 #define AMPS_BURST_FLAG_NONBINARY 0x1u /* a symbol byte outside {0,1} was seen (reference: assert(0), UB in Release) */

@@ -42,6 +42,77 @@ def test_gpu_bch63_equals_brute_force_on_all_syndromes_and_weight3_patterns(gpu)
     assert n_ok >= 2017 and n_quirk >= 21 and n_fail >= 2058 and n_ok + n_quirk + n_fail == len(rx)
 
 
+def _shortened_cases(nb, base, seed):
+    """[(received word, verdict, corrected word, nerr, outcome)] for the shortened (nb, nb - 12) code, from tests/bchref.py alone: every
+    error pattern of weight 0..3 inside the nb bits plus 2000 random ones of weight 4 and 2000 of weight 5, each added to the zero
+    word and to the code word `base`.  Words are integers, bit e = x^e; the 63 - nb shortening zeros are the bits from nb up.
+    Remainder and syndromes are linear, and a code word has none: they are the XOR of per-position tables over the pattern."""
+    lead = bchref.coset_leaders()
+    rem = [bchref.polymod(1 << e) for e in range(63)]
+    s1 = [bchref.EXP[e] for e in range(63)]
+    s3 = [bchref.EXP[(3 * e) % 63] for e in range(63)]
+    assert all(bchref.evaluate(1 << e, 1) == s1[e] and bchref.evaluate(1 << e, 3) == s3[e] for e in range(63))
+    rng = np.random.default_rng(seed)
+    patterns = [c for wt in range(4) for c in itertools.combinations(range(nb), wt)]
+    patterns += [tuple(int(e) for e in rng.choice(nb, size=wt, replace=False)) for wt in (4, 5) for _ in range(2000)]
+    cases = []
+    for pos in patterns:
+        pat = r = a1 = a3 = 0
+        for e in pos:
+            pat |= 1 << e; r ^= rem[e]; a1 ^= s1[e]; a3 ^= s3[e]
+        if r in lead:
+            wt, fix = lead[r]
+            verdict, outcome = (1, "corrected") if fix >> nb == 0 else (0, "leader in the zeros")
+        elif a1 == 0 and bchref.is_cube(a3):
+            wt, fix = 3, sum(1 << e for e in range(63) if s3[e] == a3)
+            assert bin(fix).count("1") == 3
+            verdict, outcome = (1, "three roots inside") if fix >> nb == 0 else (0, "three roots, one in the zeros")
+        else:
+            wt, fix, verdict, outcome = 0, 0, 0, "no decode"
+        for b in (0, base):
+            cases.append((b ^ pat, verdict, b ^ pat ^ (fix if verdict else 0), wt, outcome))
+    return cases
+
+
+@pytest.mark.parametrize("nb", [48, 40])
+def test_gpu_shortened_bch_equals_brute_force(gpu, nb):
+    """amps_bch_decode_words at k = 36 (RECC) and k = 28 (FOCC / FVC): verdict, message and number of corrections against the coset
+    leaders of tests/bchref.py on every error pattern of weight <= 3 (18 473 in 48 bits, 10 701 in 40) -- the refusal of a correction
+    among the shortening zeros and the three-root acceptance inside a shortened word are what the full-length pin above cannot reach"""
+    k = nb - 12
+    msg = np.random.default_rng(nb).integers(0, 2, (1, k)).astype(np.uint8)
+    shifts = np.arange(nb - 1, -1, -1, dtype=np.uint64)
+    with capi.Recc(n_channels=1, max_bursts=4) as r:
+        base = bchref.from_bits([0] * (63 - nb) + r.bch_encode(msg)[0].tolist())
+        assert bchref.polymod(base) == 0 and base >> 12 == bchref.from_bits([0] * (63 - k) + msg[0].tolist())
+        cases = _shortened_cases(nb, base, 7 * nb)
+        rx = np.array([c[0] for c in cases], np.uint64)
+        words = ((rx[:, None] >> shifts[None, :]) & np.uint64(1)).astype(np.uint8)
+        assert words[-1].tolist() == bchref.bits(cases[-1][0])[63 - nb:]          # the byte order: first transmitted bit first
+        got_msg, got_valid, got_nerr = r.bch_decode(words)
+    assert len(cases) == 2 * ({48: 18473, 40: 10701}[nb] + 4000)
+    want_valid = np.array([c[1] for c in cases], np.uint8)
+    want_msg = ((np.array([c[2] for c in cases], np.uint64)[:, None] >> shifts[None, :k]) & np.uint64(1)).astype(np.uint8)
+    want_nerr = np.array([c[3] for c in cases], np.uint8)
+    bad = np.nonzero(got_valid != want_valid)[0]
+    assert bad.size == 0, (bad.size, [(hex(cases[i][0]), cases[i][4]) for i in bad[:4]])
+    bad = np.nonzero((got_msg != want_msg).any(axis=1))[0]
+    assert bad.size == 0, (bad.size, [(hex(cases[i][0]), cases[i][4]) for i in bad[:4]])
+    ok = want_valid == 1
+    assert np.array_equal(got_nerr[ok], want_nerr[ok])
+    want_counts = {o: sum(c[4] == o for c in cases) for o in ("corrected", "leader in the zeros", "three roots inside", "three roots, one in the zeros", "no decode")}
+    got_counts = {"corrected": int(((got_valid == 1) & (got_nerr <= 2)).sum()), "three roots inside": int(((got_valid == 1) & (got_nerr == 3)).sum()),
+                  "refused": int((got_valid == 0).sum())}
+    print(f"\n({nb},{k}): {len(cases)} words; second statement {want_counts}; device {got_counts}")
+    assert got_counts["corrected"] == want_counts["corrected"] and got_counts["three roots inside"] == want_counts["three roots inside"]
+    assert got_counts["refused"] == want_counts["leader in the zeros"] + want_counts["three roots, one in the zeros"] + want_counts["no decode"]
+    assert want_counts["corrected"] >= 2 * (1 + nb + nb * (nb - 1) // 2) and want_counts["leader in the zeros"] > 0
+    if nb == 48:
+        assert want_counts["three roots inside"] >= 12          # x^p + x^(p+21) + x^(p+42), p < 6, on either base word
+    else:
+        assert want_counts["three roots inside"] == 0 == got_counts["three roots inside"]       # p + 42 >= 40 for every p
+
+
 def test_gpu_encoder_on_the_reference_in_source_words(gpu):
     c = KATS["in_source_constants"]
     words = [c["control_filler_word"], c["overhead_word_1"]]       # lib/focc_impl.cc:294, apps/testalloc.cc:39
