@@ -15,7 +15,8 @@ HOST     = $(PKG)/host
 # -fno-slp-vectorize: SLP packs the demod into v_pk_* + v_mov shuffles: -10 % (measured)
 HIPFLAGS = --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off -fno-fast-math -fno-slp-vectorize -Wall -Wno-unused-function
 HOSTINC  = -I$(HOST)/include -I$(HOST)/gr_min -Iinclude
-HOSTSRC  = $(HOST)/lib/recc_impl.cc $(HOST)/lib/recc_decode_impl.cc $(HOST)/lib/recc_fused_impl.cc $(HOST)/lib/recc_bank_impl.cc $(HOST)/lib/recc_wideband_impl.cc
+HOSTSRC  = $(HOST)/lib/recc_impl.cc $(HOST)/lib/recc_decode_impl.cc $(HOST)/lib/recc_fused_impl.cc $(HOST)/lib/recc_bank_impl.cc $(HOST)/lib/recc_wideband_impl.cc \
+           $(HOST)/lib/recc_subband_impl.cc
 
 all: $(PKG)/libamps_recc.so $(PKG)/libgnuradio-amps-mi355x.so $(PKG)/recctest oracle/libamps_oracle.so
 

@@ -1,0 +1,50 @@
+"""decode_subband.py -- the receiver most people can build: ONE modest SDR tuned to the middle of system A's 21 reverse control
+channels (AMPS channels 313 .. 333, 834.39 .. 834.99 MHz: 630 kHz), delivering one 800 ksps complex stream; the shared translate
+seam filters all 21 channels out of it in one launch (amps_recc_set_xlate_shared / amps_recc_push_raw_shared) and the fused chain
+behind it decodes them.  Replaces 21 x [freq_xlating_fir_filter_ccc -> quadrature_demod -> clock_recovery_mm -> binary_slicer ->
+amps.recc -> amps.recc_decode] of grc/recctest.grc.  Needs an MI355X: the library has no CPU path.
+
+    python examples/decode_subband.py             # one mobile per control channel, the stream pushed in ragged blocks
+"""
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from gr_amps_amd import capi, synth
+
+RATE, DECIM, NSAMP = 800e3, 4, 400_000            # 0.5 s of signal; 800 ksps / 4 = 200 ksps per channel: 10 samples per symbol
+TUNED = capi.reverse_channel_hz(323)              # the SDR sits on the middle channel
+centres = capi.control_channel_centers("A", TUNED)   # -300 kHz .. +300 kHz in 30 kHz steps
+
+try:
+    rx = capi.Recc(n_channels=len(centres), sps=10, max_samples=NSAMP // DECIM, max_bursts=64)
+except capi.AmpsError as e:
+    sys.exit("no MI355X here (%s): the library has no CPU fallback" % e)
+
+rng = np.random.default_rng(7)
+k = np.arange(NSAMP)
+x = np.zeros(NSAMP, np.complex128)
+sent = {}
+for c, fc in enumerate(centres):                  # one seizure burst per channel, at its own time
+    iq, truth = synth.make_channel_block(NSAMP, 1, seed=7000 + c, sps=10 * DECIM, snr_db=40.0, first=4000 + 11000 * c)
+    x += iq * np.exp(2j * np.pi * fc * k / RATE)
+    sent[c] = truth[0][2]
+x = x.astype(np.complex64)
+
+with rx:
+    rx.set_xlate_shared(RATE, centres, DECIM)
+    pos = 0
+    while pos < NSAMP:                            # blocks of any size: samples short of a decimation step wait in the handle
+        n = min(int(rng.integers(10_000, 150_000)), NSAMP - pos)
+        rx.push_raw_shared(x[pos:pos + n])
+        pos += n
+    recs = rx.drain()
+print("%d bursts sent, %d decoded" % (len(sent), len(recs)))
+for r in recs:
+    ch, got = int(r["channel"]), r["min"].decode()
+    print("  channel %3d (AMPS %d, %.2f MHz)  MIN %s  class %d  words valid %s  %s"
+          % (ch, 313 + ch, (TUNED + centres[ch]) / 1e6, got, int(r["msg_class"]), "".join(str(int(v)) for v in r["valid"]),
+             "ok" if sent.get(ch) == got else "MISMATCH"))
+sys.exit(0 if len(recs) == len(sent) and all(sent.get(int(r["channel"])) == r["min"].decode() for r in recs) else 1)

@@ -79,6 +79,14 @@ class XlateCfg(C.Structure):
     ]
 
 
+class XlateSharedCfg(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("decim", C.c_uint32), ("n_centers", C.c_uint32), ("_pad", C.c_uint32),
+        ("rate_hz", C.c_double), ("gain", C.c_double), ("cutoff_hz", C.c_double), ("width_hz", C.c_double),
+        ("center_hz", C.POINTER(C.c_double)),
+    ]
+
+
 class RcclInfo(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("alive", C.c_int32), ("nranks", C.c_int32), ("rank", C.c_int32),
@@ -115,7 +123,9 @@ EXPORTS = (
     "amps_recc_push_wideband_dist", "amps_recc_rccl_info", "amps_recc_rccl_abort", "amps_recc_rccl_set_timeout",
     "amps_recc_debug_slicer_bits", "amps_recc_push_wideband_short",
     "amps_recc_channel_power", "amps_recc_burst_power", "amps_recc_power_ring_snaps",
+    "amps_recc_set_xlate_shared", "amps_recc_push_raw_shared", "amps_recc_debug_xlate_shared",
 )
+_XLATE_SHARED = ("amps_recc_set_xlate_shared", "amps_recc_push_raw_shared", "amps_recc_debug_xlate_shared")
 _POWER = ("amps_recc_channel_power", "amps_recc_burst_power", "amps_recc_power_ring_snaps")
 _NEW_IN_ABI4 = ("amps_recc_push_wideband_dist", "amps_recc_rccl_info", "amps_recc_rccl_abort", "amps_recc_rccl_set_timeout")
 DIST_BROADCAST, DIST_SCATTER_ALLGATHER = 0, 1
@@ -193,12 +203,16 @@ def load():
     L.amps_recc_set_xlate.argtypes = [vp, C.POINTER(XlateCfg)]
     L.amps_recc_push_raw.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int]
     L.amps_recc_debug_xlate.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    if hasattr(L, "amps_recc_set_xlate_shared"):      # absent only from A/B builds of earlier revisions (AMPS_RECC_LIB)
+        L.amps_recc_set_xlate_shared.argtypes = [vp, C.POINTER(XlateSharedCfg)]
+        L.amps_recc_push_raw_shared.argtypes = [vp, vp, C.c_size_t, C.c_int]
+        L.amps_recc_debug_xlate_shared.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.amps_bch_encode_words.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp]
     L.amps_bch_decode_words.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, vp, vp]
     for name in EXPORTS:
         if name in ("amps_recc_default_slicer", "amps_recc_default_wideband_decim", "amps_recc_debug_exact_slice", "amps_recc_rccl_unique_id", "amps_recc_rccl_init",
                     "amps_recc_push_wideband_bcast", "amps_recc_drain_gather", "amps_recc_debug_slicer_bits",
-                    "amps_recc_push_wideband_short") + _NEW_IN_ABI4 + _POWER and not hasattr(L, name):
+                    "amps_recc_push_wideband_short") + _NEW_IN_ABI4 + _POWER + _XLATE_SHARED and not hasattr(L, name):
             continue
         if name not in ("amps_recc_strerror", "amps_recc_burst_size", "amps_recc_destroy"):   # every other entry point returns int
             getattr(L, name).restype = C.c_uint32 if name == "amps_recc_power_ring_snaps" else C.c_int
@@ -380,6 +394,47 @@ class Recc:
         rc = load().amps_recc_debug_xlate(self._h, ptr, n, n, mem, _hostptr(out), cap, C.byref(no))
         if rc:
             raise AmpsError(rc, "amps_recc_debug_xlate")
+        return out[:, :no.value].copy()
+
+    # ---- translate seam, shared form: many channels of one narrowband stream
+    def set_xlate_shared(self, rate_hz, centers_hz, decim, gain=0.0, cutoff_hz=0.0, width_hz=0.0):
+        """Channel c of the handle = the channel at centers_hz[c] (relative to the stream's centre) of ONE shared stream at rate_hz:
+        the flow graph's channel filter per centre, all of them in one launch, in front of the IQ seam (amps_recc_set_xlate_shared).
+        len(centers_hz) must be n_channels; zeros select the flow graph's gain / cutoff / transition width; decim 0 removes the stage."""
+        cen = np.ascontiguousarray(centers_hz, np.float64).reshape(-1)
+        x = XlateSharedCfg(C.sizeof(XlateSharedCfg), int(decim), cen.size, 0, rate_hz, gain, cutoff_hz, width_hz,
+                           cen.ctypes.data_as(C.POINTER(C.c_double)))
+        rc = load().amps_recc_set_xlate_shared(self._h, C.byref(x))
+        if rc:
+            raise AmpsError(rc, "amps_recc_set_xlate_shared")
+
+    @staticmethod
+    def _one_row(iq):
+        if isinstance(iq, np.ndarray):
+            return np.ascontiguousarray(iq, np.complex64).reshape(-1)
+        if iq.dim() != 1 and not (iq.dim() == 2 and iq.shape[-1] == 2 and not iq.is_complex()):
+            raise TypeError("the shared stream is one row: a 1-D complex64 tensor, not shape %r" % (tuple(iq.shape),))
+        return iq.contiguous()
+
+    def push_raw_shared(self, iq):
+        """one block of the shared stream: a 1-D complex64 numpy array (staged) or torch device tensor (read in place)"""
+        iq = self._one_row(iq)
+        ptr, mem, keep = _as_ptr(iq, self.sync_torch)
+        rc = load().amps_recc_push_raw_shared(self._h, ptr, iq.shape[0], mem)
+        if rc:
+            raise AmpsError(rc, "amps_recc_push_raw_shared")
+
+    def debug_xlate_shared(self, iq):
+        """Shared translate stage only (test tap): complex64 [n] -> complex64 [C][nout]."""
+        iq = self._one_row(iq)
+        n = iq.shape[0]
+        ptr, mem, keep = _as_ptr(iq)
+        cap = n + 8
+        out = np.zeros((self.n_channels, cap), np.complex64)
+        no = C.c_size_t(0)
+        rc = load().amps_recc_debug_xlate_shared(self._h, ptr, n, mem, _hostptr(out), cap, C.byref(no))
+        if rc:
+            raise AmpsError(rc, "amps_recc_debug_xlate_shared")
         return out[:, :no.value].copy()
 
     def push_wideband(self, iq):
@@ -703,3 +758,25 @@ def reply_words(rec):
     if rc:
         raise AmpsError(rc, "amps_recc_reply_words")
     return r
+
+
+def reverse_channel_hz(n):
+    """Centre frequency of AMPS reverse (mobile transmit) channel n: 825.000 MHz + 30 kHz n for 1 <= n <= 799, and
+    825.000 MHz + 30 kHz (n - 1023) for the extended channels 991 <= n <= 1023."""
+    n = int(n)
+    if 1 <= n <= 799:
+        return 825.0e6 + 30e3 * n
+    if 991 <= n <= 1023:
+        return 825.0e6 + 30e3 * (n - 1023)
+    raise ValueError("no AMPS channel %d (1..799, 991..1023)" % n)
+
+
+CONTROL_CHANNELS = {"A": range(313, 334), "B": range(334, 355), "AB": range(313, 355)}
+
+
+def control_channel_centers(system, tuned_hz):
+    """The reverse control channels of system "A" (313-333), "B" (334-354) or "AB" (313-354) as centres relative to a receiver
+    tuned to tuned_hz: what Recc.set_xlate_shared takes."""
+    if system not in CONTROL_CHANNELS:
+        raise ValueError("system must be one of %r" % sorted(CONTROL_CHANNELS))
+    return [reverse_channel_hz(n) - float(tuned_hz) for n in CONTROL_CHANNELS[system]]

@@ -20,6 +20,7 @@
 #include "recc_power.hip.h"
 #include "recc_rccl.hip.h"
 #include "recc_xlate.hip.h"
+#include "recc_xlate_shared.hip.h"
 #include "recc_bits.hip.h"
 #include "recc_refchain.hip.h"
 
@@ -127,6 +128,7 @@ struct amps_recc : amps_recc_mem {
 
     // ---- translate seam (recctest.grc channel filter) ----
     XlateState xl;
+    XlateSharedState xls;             // many channels of one shared stream (amps_recc_set_xlate_shared); excludes xl
 
     // ---- reference-timing seam (G2 -> G3 -> G4 as the flow graph wires them; created on first use) ----
     RefState ref;
@@ -300,6 +302,8 @@ int reset_state(amps_recc *h)
     if (rc) return rc;
     if (h->chz.pow_ring) HIP_TRY(hipMemsetAsync(h->chz.pow_ring.get(), 0, sizeof(float) * (size_t)h->chz.pow_slots * h->C, s));   // n_done = 0: no snapshot is held
     rc = xlate_reset(h->xl, s);
+    if (rc) return rc;
+    rc = xlate_shared_reset(h->xls, s);
     if (rc) return rc;
     rc = ref_reset(h->ref, s);
     if (rc) return rc;
@@ -729,6 +733,7 @@ void amps_recc_destroy(amps_recc_t *h)
     static_cast<amps_recc_mem &>(*h) = amps_recc_mem();      // every buffer and event of the handle's own seams; then the other seams' states
     channelizer_destroy(h->chz);
     xlate_destroy(h->xl);
+    xlate_shared_destroy(h->xls);
     ref_destroy(h->ref);
     delete h;                                                // and with it the stream, if it is the handle's own: all else is released by now
 }
@@ -1101,6 +1106,7 @@ int amps_recc_set_xlate(amps_recc_t *h, const amps_recc_xlate_cfg_t *x)
     const double out_rate = x->rate_hz / x->decim;
     if (std::fabs(out_rate - 20e3 * h->sps) > 1e-6 * out_rate) return -EINVAL;
     std::vector<float> taps = xlate_design_taps(gain, x->rate_hz, cutoff, width);
+    xlate_shared_destroy(h->xls);                           // the two translate stages exclude each other
     return xlate_create(h->xl, h->C, x->decim, h->cfg.max_samples_per_push, x->rate_hz, x->center_hz, taps, h->stream.get());
 }
 
@@ -1135,6 +1141,72 @@ int amps_recc_debug_xlate(amps_recc_t *h, const float *iq, size_t ld, size_t nsa
     uint64_t fld = 0;
     uint32_t n = 0;
     int rc = xlate_run(h->xl, (const float2 *)iq, ld, nsamp, mem, h->stream.get(), &f, &fld, &n);
+    if (rc) return rc;
+    *nout = n;
+    if (n > out_ld) return -E2BIG;
+    if (n)
+        HIP_TRY(hipMemcpy2DAsync(out, out_ld * sizeof(float2), f, fld * sizeof(float2), (size_t)n * sizeof(float2), h->C,
+                                 hipMemcpyDeviceToHost, h->stream.get()));
+    HIP_TRY(hipStreamSynchronize(h->stream.get()));
+    return 0;
+}
+
+int amps_recc_set_xlate_shared(amps_recc_t *h, const amps_recc_xlate_shared_cfg_t *x)
+{
+    if (!h || !x || x->struct_size != sizeof(amps_recc_xlate_shared_cfg_t)) return -EINVAL;
+    if (!h->carry[0]) return -ENOSYS;                       // the IQ seam must be configured
+    if (h->chz.enabled && h->chz.groups > 1) return -ENOSYS;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream.get()));
+    if (x->decim == 0) { xlate_shared_destroy(h->xls); return 0; }
+    if (!(x->decim == 1 || x->decim == 2 || x->decim == 4 || x->decim == 8)) return -EINVAL;
+    if (x->n_centers != h->C || !x->center_hz) return -EINVAL;
+    const double gain = x->gain != 0.0 ? x->gain : 3.0;
+    const double cutoff = x->cutoff_hz != 0.0 ? x->cutoff_hz : 10e3;
+    const double width = x->width_hz != 0.0 ? x->width_hz : 4.5e3;
+    if (!(x->rate_hz > 0.0) || !(cutoff > 0.0) || !(width > 0.0)) return -EINVAL;
+    const double out_rate = x->rate_hz / x->decim;
+    if (std::fabs(out_rate - 20e3 * h->sps) > 1e-6 * out_rate) return -EINVAL;
+    for (uint32_t c = 0; c < x->n_centers; c++)
+        if (!(std::fabs(x->center_hz[c]) <= x->rate_hz)) return -EINVAL;
+    std::vector<float> taps = xlate_design_taps(gain, x->rate_hz, cutoff, width);
+    if ((taps.size() + 7) / 8 * 8 > (size_t)XLS_MAX_TAPS) return -E2BIG;
+    xlate_destroy(h->xl);                                   // the two translate stages exclude each other
+    return xlate_shared_create(h->xls, h->C, x->decim, h->cfg.max_samples_per_push, x->rate_hz, x->center_hz, taps, h->stream.get());
+}
+
+int amps_recc_push_raw_shared(amps_recc_t *h, const float *iq, size_t nsamp, int mem)
+{
+    if (!h) return -EINVAL;
+    STALE_CHECK(h);
+    if (!h->xls.enabled) return -ENOSYS;
+    if (h->chz.enabled && h->chz.groups > 1) return -ENOSYS;
+    if (nsamp == 0) return 0;
+    if (!iq) return -EINVAL;
+    HIP_TRY(hipSetDevice(h->device));
+    const float2 *f = nullptr;
+    uint64_t fld = 0;
+    uint32_t nout = 0;
+    int rc;
+    {
+        SpanGuard g(h, T_XLATE, nsamp);
+        rc = xlate_shared_run(h->xls, (const float2 *)iq, nsamp, mem, h->stream.get(), &f, &fld, &nout);
+    }
+    if (rc) return rc;
+    if (int rc2 = debug_sync(h, "xlate_shared")) return rc2;
+    if (nout == 0) return 0;
+    return run_iq_device(h, f, fld, nout);
+}
+
+int amps_recc_debug_xlate_shared(amps_recc_t *h, const float *iq, size_t nsamp, int mem, float *out, size_t out_ld, size_t *nout)
+{
+    if (!h || !iq || !out || !nout) return -EINVAL;
+    if (!h->xls.enabled) return -ENOSYS;
+    HIP_TRY(hipSetDevice(h->device));
+    const float2 *f = nullptr;
+    uint64_t fld = 0;
+    uint32_t n = 0;
+    int rc = xlate_shared_run(h->xls, (const float2 *)iq, nsamp, mem, h->stream.get(), &f, &fld, &n);
     if (rc) return rc;
     *nout = n;
     if (n > out_ld) return -E2BIG;

@@ -19,6 +19,10 @@
 //   recctest raw  <file.fc32> [chunk] [center_hz] [cutoff_hz]   the flow graph's own capture format (grc/recctest.grc:591): 400 ksps fc32,
 //                                      channel at center_hz (default +160 kHz, :889-937) -> channel filter + fused chain on the GPU;
 //                                      cutoff_hz (default 0 = the flow graph's 10 kHz) widens the channel filter for mobiles off their carrier
+//   recctest sub  <file.raw> <chunk> <rate_hz> <decim> <c0,c1,...>   one narrowband fc32 capture at rate_hz holding several channels -> gr::amps::recc_subband
+//                                      (the channel filter per centre c0, c1, ... in Hz relative to the capture's centre, decimation `decim`, 10 samples
+//                                      per symbol behind it); prints for every record what `wide` prints: its channel (the index into the list), then
+//                                      its lines, decoded through the "bursts" port
 // Every message published on recc_decode's output ports is printed as one text line, which is what
 // tests/test_gpu_host_blocks.py compares with the oracle.
 #include <amps/recc.h>
@@ -26,6 +30,7 @@
 #include <amps/recc_bank.h>
 #include <amps/recc_fused.h>
 #include <amps/recc_wideband.h>
+#include <amps/recc_subband.h>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -75,7 +80,7 @@ struct sink : gr::block {   // prints what ampsbs.grc would route to focc / fvc 
 
 int main(int argc, char **argv)
 {
-    if (argc < 3) { std::fprintf(stderr, "usage: %s syms|iq|iqb|raw|bank|wide <file> [chunk] [center_hz | C | slicer]\n", argv[0]); return 2; }
+    if (argc < 3) { std::fprintf(stderr, "usage: %s syms|iq|iqb|raw|bank|wide|sub <file> [chunk] [center_hz | C | slicer | rate_hz decim c0,c1,...]\n", argv[0]); return 2; }
     const std::string mode = argv[1];
     const int chunk = argc > 3 ? std::atoi(argv[3]) : 4096;
     std::ifstream f(argv[2], std::ios::binary);
@@ -183,6 +188,37 @@ int main(int argc, char **argv)
                 if (src->work(n, ins, outs) != 0) return 1;
             }
             src->stop();                                              // as the scheduler does: the root announces its end of stream, the others join until they see it
+        } else if (mode == "sub") {
+            if (argc < 7) { std::fprintf(stderr, "usage: %s sub <file.raw> <chunk> <rate_hz> <decim> <c0,c1,...>\n", argv[0]); return 2; }
+            std::vector<double> centers;
+            for (const char *p = argv[6]; *p;) {
+                char *end = nullptr;
+                centers.push_back(std::strtod(p, &end));
+                if (end == p) { std::fprintf(stderr, "%s: bad list of centres\n", argv[6]); return 2; }
+                p = *end == ',' ? end + 1 : end;
+            }
+            auto src = gr::amps::recc_subband::make(std::atof(argv[4]), centers, std::atoi(argv[5]));
+            struct demux : gr::block {
+                std::shared_ptr<gr::basic_block> dec;
+                demux() : gr::block("demux", gr::io_signature::make(0, 0, 0), gr::io_signature::make(0, 0, 0))
+                {
+                    message_port_register_in(pmt::mp("bursts"));
+                    set_msg_handler(pmt::mp("bursts"), [this](pmt::pmt_t m) {
+                        std::printf("MSG channel %ld\n", pmt::to_long(pmt::car(m)));
+                        dec->dispatch("bursts", pmt::cdr(m));
+                    });
+                }
+                int general_work(int n, gr_vector_int &, gr_vector_const_void_star &, gr_vector_void_star &) override { return n; }
+            };
+            auto dm = std::make_shared<demux>();
+            dm->dec = dec;
+            gr::msg_connect(src, "bursts", dm, "bursts");
+            const size_t ns = data.size() / 8;
+            for (size_t off = 0; off < ns; off += (size_t)chunk) {
+                int n = (int)std::min<size_t>((size_t)chunk, ns - off);
+                gr_vector_const_void_star ins = { data.data() + 8 * off };
+                if (src->work(n, ins, outs) != 0) return 1;
+            }
         } else if (mode == "syms") {
             auto src = gr::amps::recc::make();
             gr::msg_connect(src, "bursts", dec, "bursts");

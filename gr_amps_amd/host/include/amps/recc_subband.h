@@ -1,0 +1,29 @@
+// gr::amps::recc_subband -- NEW block type (not in the reference): many 30 kHz channels of ONE narrowband stream in one block.
+// Input: ONE gr_complex stream at rate_hz (a few hundred ksps to 1.6 Msps: one modest SDR tuned to a system's control channels);
+// the block runs, for every centre of centers_hz, the flow graph's channel filter freq_xlating_fir_filter_ccc(decim,
+// firdes.low_pass(3, rate, cutoff, width), centre, rate) (grc/recctest.grc:889-937, taps :115-155) and the fused chain behind it
+// on the MI355X -- amps_recc_set_xlate_shared / amps_recc_push_raw_shared: all channels in one launch per stage -- and stands
+// where the reference would need that filter plus analog_quadrature_demod_cf -> digital_clock_recovery_mm_ff ->
+// digital_binary_slicer_fb -> amps_recc (:458, 846-874, 807, 310) once per channel.
+// Message ports:  "bursts"  pmt::cons(from_long(channel), blob(3374)) -- cdr = what amps_recc publishes (lib/recc_impl.cc:126);
+//                 "records" pmt::cons(from_long(channel), blob(amps_recc_burst_t)) -- the burst already decoded;
+// as gr::amps::recc_wideband publishes them.  channel c = the channel at centers_hz[c] relative to the stream's centre.
+#pragma once
+#include <amps/api.h>
+#include <vector>
+
+namespace gr {
+namespace amps {
+
+class AMPS_API recc_subband : virtual public gr::sync_block {
+public:
+    typedef AMPS_SPTR<recc_subband> sptr;
+    // rate_hz / decim must be samples_per_symbol x 20 kHz; decim: 1, 2, 4 or 8
+    // slicer: -1 = the library default, 0 .. 3 = numeric spec A .. D (include/amps_recc_numerics.h)
+    // cutoff_hz / width_hz: 0 = the flow graph's 10 kHz / 4.5 kHz
+    static sptr make(double rate_hz, const std::vector<double> &centers_hz, int decim = 4, int samples_per_symbol = 10, int slicer = -1,
+                     double cutoff_hz = 0.0, double width_hz = 0.0);
+};
+
+} // namespace amps
+} // namespace gr

@@ -1,0 +1,92 @@
+// recc_subband_impl.cc -- gr::amps::recc_subband: one narrowband complex stream in, (channel, burst) and (channel, record) pairs out.
+#include <amps/recc_subband.h>
+#include <cerrno>
+#include <cstdio>
+#include <stdexcept>
+#include <string>
+#include <vector>
+#include "amps_recc.h"
+
+namespace gr {
+namespace amps {
+
+class recc_subband_impl : public recc_subband {
+    amps_recc_t *d_handle;
+    int d_decim;
+    std::vector<amps_recc_burst_t> d_recs;
+    std::vector<unsigned char> d_bursts;
+    static const int kMaxOut = 1 << 18;            // channel-rate samples per push: 1.3 s at 200 ksps
+    static const int kMaxRecs = 1024;
+
+public:
+    recc_subband_impl(double rate_hz, const std::vector<double> &centers_hz, int decim, int sps, int slicer, double cutoff_hz, double width_hz)
+        : gr::sync_block("recc_subband", gr::io_signature::make(1, 1, 2 * sizeof(float)), gr::io_signature::make(0, 0, 0)),
+          d_handle(nullptr), d_decim(decim), d_recs(kMaxRecs), d_bursts((size_t)kMaxRecs * AMPS_RECC_CAPTURE_SYMS)
+    {
+        if (centers_hz.empty()) throw std::runtime_error("amps::recc_subband: no centres");
+        if (decim < 1) throw std::runtime_error("amps::recc_subband: decim must be 1, 2, 4 or 8");
+        amps_recc_cfg_t cfg = {};
+        cfg.struct_size = sizeof(cfg);
+        cfg.n_channels = (uint32_t)centers_hz.size();
+        cfg.samples_per_symbol = (uint32_t)sps;
+        cfg.max_samples_per_push = kMaxOut;
+        cfg.max_bursts = kMaxRecs;
+        cfg.device = -1;
+        cfg.flags = AMPS_RECC_FLAG_KEEP_BURSTS | (slicer == 0 ? AMPS_RECC_FLAG_SLICER_ATAN : slicer == 1 ? AMPS_RECC_FLAG_SLICER_PRODUCT
+                                                  : slicer == 2 ? AMPS_RECC_FLAG_SLICER_SINE : slicer == 3 ? AMPS_RECC_FLAG_SLICER_EXACT : 0u);
+        int rc = amps_recc_create(&d_handle, &cfg);
+        if (rc != 0) throw std::runtime_error(std::string("amps::recc_subband: ") + amps_recc_strerror(rc));
+        amps_recc_xlate_shared_cfg_t x = {};
+        x.struct_size = sizeof(x);
+        x.decim = (uint32_t)decim;
+        x.n_centers = (uint32_t)centers_hz.size();
+        x.rate_hz = rate_hz;
+        x.cutoff_hz = cutoff_hz;                       // 0 = the flow graph's 10 kHz / 4.5 kHz
+        x.width_hz = width_hz;
+        x.center_hz = centers_hz.data();
+        rc = amps_recc_set_xlate_shared(d_handle, &x);
+        if (rc != 0) {
+            amps_recc_destroy(d_handle);
+            throw std::runtime_error(std::string("amps::recc_subband (xlate): ") + amps_recc_strerror(rc));
+        }
+        message_port_register_out(pmt::mp("bursts"));
+        message_port_register_out(pmt::mp("records"));
+    }
+    ~recc_subband_impl() { amps_recc_destroy(d_handle); }
+
+    int work(int noutput_items, gr_vector_const_void_star &input_items, gr_vector_void_star &)
+    {
+        const float *in = (const float *)input_items[0];
+        const int max_push = (kMaxOut - 1) * d_decim;          // a leftover sample of the last push may complete one more output
+        int done = 0;
+        while (done < noutput_items) {
+            int n = noutput_items - done;
+            if (n > max_push) n = max_push;
+            int rc = amps_recc_push_raw_shared(d_handle, in + 2 * (size_t)done, (size_t)n, AMPS_MEM_HOST);
+            if (rc != 0) { std::fprintf(stderr, "amps::recc_subband: %s\n", amps_recc_strerror(rc)); return WORK_DONE; }
+            size_t nrec = 0;
+            rc = amps_recc_drain_bursts(d_handle, d_recs.data(), d_bursts.data(), kMaxRecs, &nrec);
+            // -ENOSPC: more bursts than the list holds were found; the ones that fit are returned and the list recovers on the
+            // next push -- a recoverable condition must not end the flow graph
+            if (rc == -ENOSPC) std::fprintf(stderr, "amps::recc_subband: %s (bursts dropped, continuing)\n", amps_recc_strerror(rc));
+            else if (rc != 0) { std::fprintf(stderr, "amps::recc_subband: %s\n", amps_recc_strerror(rc)); return WORK_DONE; }
+            for (size_t i = 0; i < nrec; i++) {
+                const pmt::pmt_t ch = pmt::from_long((long)d_recs[i].channel);
+                message_port_pub(pmt::mp("bursts"), pmt::cons(ch, pmt::mp(d_bursts.data() + i * AMPS_RECC_CAPTURE_SYMS, AMPS_RECC_CAPTURE_SYMS)));
+                message_port_pub(pmt::mp("records"), pmt::cons(ch, pmt::mp(&d_recs[i], sizeof(d_recs[i]))));
+            }
+            done += n;
+        }
+        consume_each(noutput_items);
+        return 0;
+    }
+};
+
+recc_subband::sptr recc_subband::make(double rate_hz, const std::vector<double> &centers_hz, int decim, int samples_per_symbol, int slicer,
+                                      double cutoff_hz, double width_hz)
+{
+    return gnuradio::get_initial_sptr(new recc_subband_impl(rate_hz, centers_hz, decim, samples_per_symbol, slicer, cutoff_hz, width_hz));
+}
+
+} // namespace amps
+} // namespace gr

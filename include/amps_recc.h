@@ -45,7 +45,9 @@ extern "C" {
                                      group split and allocates; every collective entry is bounded and carries a status word;
                                      (still 4, one entry point added and nothing changed: amps_recc_push_wideband_short, 16-bit I/Q through the wideband seam;
                                      still 4, three entry points and a flag added and nothing changed: amps_recc_channel_power / _burst_power /
-                                     _power_ring_snaps behind AMPS_RECC_FLAG_CHANNEL_POWER) */
+                                     _power_ring_snaps behind AMPS_RECC_FLAG_CHANNEL_POWER;
+                                     still 4, three entry points added and nothing changed: amps_recc_set_xlate_shared / _push_raw_shared /
+                                     _debug_xlate_shared, many channels of one shared narrowband stream) */
 
 /* protocol constants of the reference */
 #define AMPS_RECC_TRIGGER_SYMS 74   /* lib/recc_impl.cc:76-77: 37 bits x 2 Manchester symbols   */
@@ -296,6 +298,40 @@ int amps_recc_push_raw(amps_recc_t *h, const float *iq, size_t ld, size_t nsamp,
 /* test tap: run only the translate stage (continuing its stream); out is host [n_channels][out_ld] fc32 */
 int amps_recc_debug_xlate(amps_recc_t *h, const float *iq, size_t ld, size_t nsamp, int mem,
                           float *out, size_t out_ld, size_t *nout);
+
+/* translate seam, shared form: MANY channels of ONE narrowband stream -- one modest SDR tuned to a system's control channels delivers
+ * one fc32 stream of a few hundred ksps that holds many 30 kHz channels (a system's 21 reverse control channels span 630 kHz; the
+ * 400 ksps captures of grc/recctest.grc:591 hold up to 13) -- each translated to DC, low-passed and decimated by the filter above,
+ * then decoded by the fused IQ seam, all channels in one launch per stage.
+ * DEFINITION.  Record `channel` c is centre center_hz[c].  The filtered stream of channel c is what amps_recc_set_xlate with that
+ * centre (same rate, decim, gain, cutoff, width) plus amps_recc_push_raw of the same samples produce on a ONE-channel handle, bit
+ * for bit (amps_recc_debug_xlate_shared row c == amps_recc_debug_xlate there); the records are therefore those of that handle,
+ * except for `channel`.  Duplicate centres are legal and give duplicate records.
+ * decim: 1, 2, 4 or 8 (8 only here: 1.6 Msps at 10 samples per symbol, 1195 taps with the default filter); 0 removes the stage.
+ * rate_hz / decim must equal samples_per_symbol * 20 kHz; gain / cutoff_hz / width_hz = 0 select the flow graph's 3.0 / 10 kHz /
+ * 4.5 kHz as amps_recc_set_xlate does.  The two translate stages exclude each other: configuring one removes the other;
+ * amps_recc_push_raw on a shared-configured handle and amps_recc_push_raw_shared on a handle configured with amps_recc_set_xlate
+ * answer -ENOSYS, as both do on an unconfigured handle.  Resets nothing else; call before the first push.
+ * Errors: -EINVAL (null handle or cfg, wrong struct_size, n_centers != n_channels, null center_hz, a decim other than 0, 1, 2, 4, 8,
+ * rate mismatch, a centre beyond the rate); -E2BIG (the filter has more than 1280 taps, padded to a multiple of 8); -ENOSYS (a handle
+ * without the IQ seam, or a channel-group handle). */
+typedef struct amps_recc_xlate_shared_cfg {
+    uint32_t struct_size;
+    uint32_t decim;              /* 1, 2, 4 or 8; 0 removes the stage */
+    uint32_t n_centers;          /* must equal cfg.n_channels */
+    uint32_t _pad;
+    double   rate_hz;            /* rate_hz / decim == samples_per_symbol * 20 kHz */
+    double   gain, cutoff_hz, width_hz;  /* 0 = the flow graph's 3.0 / 10 kHz / 4.5 kHz, as amps_recc_set_xlate */
+    const double *center_hz;     /* [n_centers], |center| <= rate_hz; duplicates are legal */
+} amps_recc_xlate_shared_cfg_t;
+int amps_recc_set_xlate_shared(amps_recc_t *h, const amps_recc_xlate_shared_cfg_t *x);
+/* iq is ONE row of nsamp samples at rate_hz.  Any nsamp <= decim * max_samples_per_push (-E2BIG beyond); leftover samples (fewer than
+ * decim) wait for the next push.  Host and device blocks follow the ownership rules of amps_recc_push_raw; amps_recc_reset restarts
+ * the stream; ms_xlate of amps_recc_get_timing counts the kernel.  -ESTALE as the data seams. */
+int amps_recc_push_raw_shared(amps_recc_t *h, const float *iq, size_t nsamp, int mem);
+/* test tap: run only the shared translate stage (continuing its stream); out is host [n_channels][out_ld] fc32 */
+int amps_recc_debug_xlate_shared(amps_recc_t *h, const float *iq, size_t nsamp, int mem,
+                                 float *out, size_t out_ld, size_t *nout);
 
 /* Reference-timing seam (checking mode): the flow graph's OWN sub-chain in front of amps_recc, computed on the device as GNU
  * Radio 3.7 defines it -- analog.quadrature_demod_cf(1) -> digital.clock_recovery_mm_ff(omega 10, gain_omega .25*.175^2*3,
