@@ -20,7 +20,6 @@
 #include "recc_power.hip.h"
 #include "recc_rccl.hip.h"
 #include "recc_xlate.hip.h"
-#include "recc_xlate_shared.hip.h"
 #include "recc_bits.hip.h"
 #include "recc_refchain.hip.h"
 
@@ -127,8 +126,7 @@ struct amps_recc : amps_recc_mem {
     std::vector<int32_t> chan2row;            // whole-band channel number -> ring row, -1 for a channel this handle does not decode
 
     // ---- translate seam (recctest.grc channel filter) ----
-    XlateState xl;
-    XlateSharedState xls;             // many channels of one shared stream (amps_recc_set_xlate_shared); excludes xl
+    XlateState xl;                    // the translate stage in the form configured last (amps_recc_set_xlate / _set_xlate_shared)
 
     // ---- reference-timing seam (G2 -> G3 -> G4 as the flow graph wires them; created on first use) ----
     RefState ref;
@@ -302,8 +300,6 @@ int reset_state(amps_recc *h)
     if (rc) return rc;
     if (h->chz.pow_ring) HIP_TRY(hipMemsetAsync(h->chz.pow_ring.get(), 0, sizeof(float) * (size_t)h->chz.pow_slots * h->C, s));   // n_done = 0: no snapshot is held
     rc = xlate_reset(h->xl, s);
-    if (rc) return rc;
-    rc = xlate_shared_reset(h->xls, s);
     if (rc) return rc;
     rc = ref_reset(h->ref, s);
     if (rc) return rc;
@@ -733,7 +729,6 @@ void amps_recc_destroy(amps_recc_t *h)
     static_cast<amps_recc_mem &>(*h) = amps_recc_mem();      // every buffer and event of the handle's own seams; then the other seams' states
     channelizer_destroy(h->chz);
     xlate_destroy(h->xl);
-    xlate_shared_destroy(h->xls);
     ref_destroy(h->ref);
     delete h;                                                // and with it the stream, if it is the handle's own: all else is released by now
 }
@@ -1090,33 +1085,35 @@ int amps_recc_drain_gather(amps_recc_t *h, amps_recc_burst_t *out, size_t cap, s
     return ((st_or & 1u) || truncated) ? -ENOSPC : 0;
 }
 
-int amps_recc_set_xlate(amps_recc_t *h, const amps_recc_xlate_cfg_t *x)
+// rows x n fc32 of a device block (row pitch ld) to the caller's host [rows][out_ld], then wait: the tail of the debug taps
+static int copy_rows_out(amps_recc *h, const float2 *d, uint64_t ld, uint32_t n, float *out, size_t out_ld)
 {
-    if (!h || !x || x->struct_size != sizeof(amps_recc_xlate_cfg_t)) return -EINVAL;
-    if (!h->carry[0]) return -ENOSYS;                       // the IQ seam must be configured
-    HIP_TRY(hipSetDevice(h->device));
+    if (n > out_ld) return -E2BIG;
+    if (n)
+        HIP_TRY(hipMemcpy2DAsync(out, out_ld * sizeof(float2), d, ld * sizeof(float2), (size_t)n * sizeof(float2), h->C,
+                                 hipMemcpyDeviceToHost, h->stream.get()));
     HIP_TRY(hipStreamSynchronize(h->stream.get()));
-    if (x->decim == 0) { xlate_destroy(h->xl); return 0; }
-    // defaults = the flow graph's values (grc/recctest.grc:115-155, 889-937)
-    const double gain = x->gain != 0.0 ? x->gain : 3.0;
-    const double cutoff = x->cutoff_hz != 0.0 ? x->cutoff_hz : 10e3;
-    const double width = x->width_hz != 0.0 ? x->width_hz : 4.5e3;
-    if (!(x->rate_hz > 0.0) || !(cutoff > 0.0) || !(width > 0.0)) return -EINVAL;
-    // the filtered stream must arrive at the symbol rate the handle was built for
-    const double out_rate = x->rate_hz / x->decim;
-    if (std::fabs(out_rate - 20e3 * h->sps) > 1e-6 * out_rate) return -EINVAL;
-    std::vector<float> taps = xlate_design_taps(gain, x->rate_hz, cutoff, width);
-    xlate_shared_destroy(h->xls);                           // the two translate stages exclude each other
-    return xlate_create(h->xl, h->C, x->decim, h->cfg.max_samples_per_push, x->rate_hz, x->center_hz, taps, h->stream.get());
+    return 0;
 }
 
-int amps_recc_push_raw(amps_recc_t *h, const float *iq, size_t ld, size_t nsamp, int mem)
+// design the channel filter and create the translate stage in one of its forms; center_hz is [n_channels]
+static int xlate_configure(amps_recc *h, bool shared, uint32_t decim, double rate_hz, const double *center_hz, double gain, double cutoff, double width)
 {
-    if (!h) return -EINVAL;
-    if (!h->xl.enabled) return -ENOSYS;
-    if (h->chz.enabled && h->chz.groups > 1) return -ENOSYS;
-    if (nsamp == 0) return 0;
-    if (!iq || ld < nsamp) return -EINVAL;
+    // defaults = the flow graph's values (grc/recctest.grc:115-155, 889-937)
+    if (gain == 0.0) gain = 3.0;
+    if (cutoff == 0.0) cutoff = 10e3;
+    if (width == 0.0) width = 4.5e3;
+    if (!(rate_hz > 0.0) || !(cutoff > 0.0) || !(width > 0.0)) return -EINVAL;
+    // the filtered stream must arrive at the symbol rate the handle was built for
+    const double out_rate = rate_hz / decim;
+    if (std::fabs(out_rate - 20e3 * h->sps) > 1e-6 * out_rate) return -EINVAL;
+    return xlate_create(h->xl, shared, h->C, decim, h->cfg.max_samples_per_push, rate_hz, center_hz,
+                        xlate_design_taps(gain, rate_hz, cutoff, width), h->stream.get());
+}
+
+// run the translate stage on a block and hand its rows to the fused IQ seam
+static int xlate_push(amps_recc *h, const float *iq, size_t ld, size_t nsamp, int mem, const char *what)
+{
     HIP_TRY(hipSetDevice(h->device));
     const float2 *f = nullptr;
     uint64_t fld = 0;
@@ -1127,15 +1124,14 @@ int amps_recc_push_raw(amps_recc_t *h, const float *iq, size_t ld, size_t nsamp,
         rc = xlate_run(h->xl, (const float2 *)iq, ld, nsamp, mem, h->stream.get(), &f, &fld, &nout);
     }
     if (rc) return rc;
-    if (int rc2 = debug_sync(h, "xlate")) return rc2;
+    if (int rc2 = debug_sync(h, what)) return rc2;
     if (nout == 0) return 0;
     return run_iq_device(h, f, fld, nout);
 }
 
-int amps_recc_debug_xlate(amps_recc_t *h, const float *iq, size_t ld, size_t nsamp, int mem, float *out, size_t out_ld, size_t *nout)
+// test tap: run the translate stage alone and copy its rows out
+static int xlate_debug(amps_recc *h, const float *iq, size_t ld, size_t nsamp, int mem, float *out, size_t out_ld, size_t *nout)
 {
-    if (!h || !iq || !out || !nout || ld < nsamp) return -EINVAL;
-    if (!h->xl.enabled) return -ENOSYS;
     HIP_TRY(hipSetDevice(h->device));
     const float2 *f = nullptr;
     uint64_t fld = 0;
@@ -1143,12 +1139,35 @@ int amps_recc_debug_xlate(amps_recc_t *h, const float *iq, size_t ld, size_t nsa
     int rc = xlate_run(h->xl, (const float2 *)iq, ld, nsamp, mem, h->stream.get(), &f, &fld, &n);
     if (rc) return rc;
     *nout = n;
-    if (n > out_ld) return -E2BIG;
-    if (n)
-        HIP_TRY(hipMemcpy2DAsync(out, out_ld * sizeof(float2), f, fld * sizeof(float2), (size_t)n * sizeof(float2), h->C,
-                                 hipMemcpyDeviceToHost, h->stream.get()));
+    return copy_rows_out(h, f, fld, n, out, out_ld);
+}
+
+int amps_recc_set_xlate(amps_recc_t *h, const amps_recc_xlate_cfg_t *x)
+{
+    if (!h || !x || x->struct_size != sizeof(amps_recc_xlate_cfg_t)) return -EINVAL;
+    if (!h->carry[0]) return -ENOSYS;                       // the IQ seam must be configured
+    HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream.get()));
-    return 0;
+    if (x->decim == 0) { if (!h->xl.shared) xlate_destroy(h->xl); return 0; }   // removes the form this entry point configures
+    const std::vector<double> centers(h->C, x->center_hz);  // every row uses the same centre
+    return xlate_configure(h, false, x->decim, x->rate_hz, centers.data(), x->gain, x->cutoff_hz, x->width_hz);
+}
+
+int amps_recc_push_raw(amps_recc_t *h, const float *iq, size_t ld, size_t nsamp, int mem)
+{
+    if (!h) return -EINVAL;
+    if (!h->xl.enabled || h->xl.shared) return -ENOSYS;
+    if (h->chz.enabled && h->chz.groups > 1) return -ENOSYS;
+    if (nsamp == 0) return 0;
+    if (!iq || ld < nsamp) return -EINVAL;
+    return xlate_push(h, iq, ld, nsamp, mem, "xlate");
+}
+
+int amps_recc_debug_xlate(amps_recc_t *h, const float *iq, size_t ld, size_t nsamp, int mem, float *out, size_t out_ld, size_t *nout)
+{
+    if (!h || !iq || !out || !nout || ld < nsamp) return -EINVAL;
+    if (!h->xl.enabled || h->xl.shared) return -ENOSYS;
+    return xlate_debug(h, iq, ld, nsamp, mem, out, out_ld, nout);
 }
 
 int amps_recc_set_xlate_shared(amps_recc_t *h, const amps_recc_xlate_shared_cfg_t *x)
@@ -1158,63 +1177,27 @@ int amps_recc_set_xlate_shared(amps_recc_t *h, const amps_recc_xlate_shared_cfg_
     if (h->chz.enabled && h->chz.groups > 1) return -ENOSYS;
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream.get()));
-    if (x->decim == 0) { xlate_shared_destroy(h->xls); return 0; }
-    if (!(x->decim == 1 || x->decim == 2 || x->decim == 4 || x->decim == 8)) return -EINVAL;
+    if (x->decim == 0) { if (h->xl.shared) xlate_destroy(h->xl); return 0; }    // removes the form this entry point configures
     if (x->n_centers != h->C || !x->center_hz) return -EINVAL;
-    const double gain = x->gain != 0.0 ? x->gain : 3.0;
-    const double cutoff = x->cutoff_hz != 0.0 ? x->cutoff_hz : 10e3;
-    const double width = x->width_hz != 0.0 ? x->width_hz : 4.5e3;
-    if (!(x->rate_hz > 0.0) || !(cutoff > 0.0) || !(width > 0.0)) return -EINVAL;
-    const double out_rate = x->rate_hz / x->decim;
-    if (std::fabs(out_rate - 20e3 * h->sps) > 1e-6 * out_rate) return -EINVAL;
-    for (uint32_t c = 0; c < x->n_centers; c++)
-        if (!(std::fabs(x->center_hz[c]) <= x->rate_hz)) return -EINVAL;
-    std::vector<float> taps = xlate_design_taps(gain, x->rate_hz, cutoff, width);
-    if ((taps.size() + 7) / 8 * 8 > (size_t)XLS_MAX_TAPS) return -E2BIG;
-    xlate_destroy(h->xl);                                   // the two translate stages exclude each other
-    return xlate_shared_create(h->xls, h->C, x->decim, h->cfg.max_samples_per_push, x->rate_hz, x->center_hz, taps, h->stream.get());
+    return xlate_configure(h, true, x->decim, x->rate_hz, x->center_hz, x->gain, x->cutoff_hz, x->width_hz);
 }
 
 int amps_recc_push_raw_shared(amps_recc_t *h, const float *iq, size_t nsamp, int mem)
 {
     if (!h) return -EINVAL;
     STALE_CHECK(h);
-    if (!h->xls.enabled) return -ENOSYS;
+    if (!h->xl.enabled || !h->xl.shared) return -ENOSYS;
     if (h->chz.enabled && h->chz.groups > 1) return -ENOSYS;
     if (nsamp == 0) return 0;
     if (!iq) return -EINVAL;
-    HIP_TRY(hipSetDevice(h->device));
-    const float2 *f = nullptr;
-    uint64_t fld = 0;
-    uint32_t nout = 0;
-    int rc;
-    {
-        SpanGuard g(h, T_XLATE, nsamp);
-        rc = xlate_shared_run(h->xls, (const float2 *)iq, nsamp, mem, h->stream.get(), &f, &fld, &nout);
-    }
-    if (rc) return rc;
-    if (int rc2 = debug_sync(h, "xlate_shared")) return rc2;
-    if (nout == 0) return 0;
-    return run_iq_device(h, f, fld, nout);
+    return xlate_push(h, iq, nsamp, nsamp, mem, "xlate_shared");
 }
 
 int amps_recc_debug_xlate_shared(amps_recc_t *h, const float *iq, size_t nsamp, int mem, float *out, size_t out_ld, size_t *nout)
 {
     if (!h || !iq || !out || !nout) return -EINVAL;
-    if (!h->xls.enabled) return -ENOSYS;
-    HIP_TRY(hipSetDevice(h->device));
-    const float2 *f = nullptr;
-    uint64_t fld = 0;
-    uint32_t n = 0;
-    int rc = xlate_shared_run(h->xls, (const float2 *)iq, nsamp, mem, h->stream.get(), &f, &fld, &n);
-    if (rc) return rc;
-    *nout = n;
-    if (n > out_ld) return -E2BIG;
-    if (n)
-        HIP_TRY(hipMemcpy2DAsync(out, out_ld * sizeof(float2), f, fld * sizeof(float2), (size_t)n * sizeof(float2), h->C,
-                                 hipMemcpyDeviceToHost, h->stream.get()));
-    HIP_TRY(hipStreamSynchronize(h->stream.get()));
-    return 0;
+    if (!h->xl.enabled || !h->xl.shared) return -ENOSYS;
+    return xlate_debug(h, iq, nsamp, nsamp, mem, out, out_ld, nout);
 }
 
 int amps_recc_refchain_symbols(amps_recc_t *h, const float *iq, size_t ld, size_t nsamp, int mem,
@@ -1449,12 +1432,7 @@ int amps_recc_debug_channelize(amps_recc_t *h, const float *iq, size_t nsamp, in
     int rc = channelizer_run(h->chz, in, h->stream.get(), &chan_iq, &ld, &nout);
     if (rc) return rc;
     *nframes = nout;
-    if (nout > out_ld) return -E2BIG;
-    if (nout)
-        HIP_TRY(hipMemcpy2DAsync(out, out_ld * sizeof(float2), chan_iq, ld * sizeof(float2), nout * sizeof(float2), h->C,
-                                 hipMemcpyDeviceToHost, h->stream.get()));
-    HIP_TRY(hipStreamSynchronize(h->stream.get()));
-    return 0;
+    return copy_rows_out(h, chan_iq, ld, nout, out, out_ld);
 }
 
 int amps_recc_debug_slicer_bits(amps_recc_t *h, uint64_t first, size_t n, uint8_t *out, size_t out_ld, uint32_t *rows, uint64_t *produced)

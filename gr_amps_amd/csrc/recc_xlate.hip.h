@@ -1,19 +1,40 @@
-// recc_xlate.hip.h -- the single-channel front filter of grc/recctest.grc on gfx950:
+// recc_xlate.hip.h -- the front filter of grc/recctest.grc on gfx950, in two forms behind one host state:
 // freq_xlating_fir_filter_ccc (grc/recctest.grc:889-937) with firdes.low_pass taps (:115-155): translate the
 // channel at `center_hz` to DC, low-pass, decimate by D.  It stands in front of the fused IQ seam for the
 // ".raw" fc32 400 ksps captures the reference's test flow graph reads (grc/recctest.grc:591).
+//   per-row form (xlate_fir_kernel):   C input rows, one centre for all of them, C output rows;
+//   shared form (xlate_shared_kernel): ONE input row (a modest SDR tuned to a system's control channels: a few hundred ksps
+//                                      holding many 30 kHz channels), C centres, C output rows.
 //
 // The reference block multiplies by COMPLEX composite taps h[i] e^{j i phi} and then by a running rotator
 // (4 real MACs per tap, rotator renormalised every 512 outputs).  Algebraically
 //     y[k] = e^{-j phi D k} sum_i h[i] e^{j phi i} x[Dk - i] = sum_i h[i] z[Dk - i],   z[n] = x[n] e^{-j phi n}
-// so this kernel mixes each input sample ONCE while staging it into LDS (phase from an exact 64-bit phase
+// so a kernel mixes each input sample ONCE on its way into LDS (phase from an exact 64-bit phase
 // accumulator evaluated per sample: no rotator drift, any push boundary gives the same bits) and then runs a REAL-tap FIR on complex
 // data: one v_pk_fma per tap.  A lane produces 8/D adjacent outputs, so consecutive taps reuse the same LDS
 // words (14 ds_read_b64 per 32 v_pk_fma at D = 2); the LDS window is padded by one sample per eight so that the
 // lane stride of 8 samples is conflict free and the pad term of the address is wave-uniform (scalar) arithmetic.
+//
+// The arithmetic per output sample is written ONCE, in xl_window / xl_mix / xl_fir_store, and both kernels call it: the phasor of a
+// sample comes from its ABSOLUTE index through xl_phasor, one fp32 cmul per staged sample, one fma chain over the zero-padded real
+// taps in ascending tap order.  Row c of the shared form is therefore bit for bit what the per-row form gives a one-channel handle
+// configured with centre c: the identity include/amps_recc.h defines the shared form by and the tests hold it to, and the reason
+// nothing is "optimised" across channels in the float domain.  The two kernels stay two: they differ in what a workgroup stages.
+//
+// Per-row form: mixes while it stages, one workgroup per (tile, row); 31 808 bytes of LDS, 5 waves per SIMD, 1024 padded taps.
 // This is the file-tool path (one or a few channels); the 832-channel front end is the polyphase channelizer.
+//
+// Shared form: STAGED.  The grid is (input tiles, channel groups).  A workgroup reads its raw tile plus the filter history from HBM /
+// the carry ONCE into LDS and then, for each channel of its group: mixes the raw window into the padded window, barrier, FIR,
+// store, barrier.  The raw tile is read once per group instead of once per channel, and one launch serves all channels.  The host
+// picks the group size (xlate_shared_cpg) so that the grid has a few thousand workgroups where the block allows it -- balance over
+// the CUs matters more than the re-read of the raw tile, which comes from L2 (measured) -- and one group of all
+// channels only for very long blocks.  D = 8 (one output per lane) exists in this form only: 1.6 Msps at 10 samples per symbol, where
+// the flow graph's filter spec gives 1195 taps -- hence XLS_MAX_TAPS = 1280.  Static LDS: raw 26 624 + mixed 30 016 + taps 5 120 =
+// 61 760 bytes of the 65 536 one workgroup may own statically, 2 waves per SIMD.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cerrno>
 #include <cmath>
 #include <cstdint>
@@ -23,17 +44,19 @@
 namespace amps {
 
 constexpr int XL_TILE = 2048;        // input samples per workgroup (256 lanes x 8)
-constexpr int XL_MAX_TAPS = 1024;    // padded tap count limit
+constexpr int XL_MAX_TAPS = 1024;    // padded tap count limit of xlate_fir_kernel
+constexpr int XLS_MAX_TAPS = 1280;   // padded tap count limit of xlate_shared_kernel
 
 struct XlateArgs {
-    const float2 *block;     // [C][ld_in] new samples
-    const float2 *carry;     // [C][carry_cap]: hist samples of history, then the leftover (< D) unconsumed samples
+    const float2 *block;     // [rows][ld_in] new samples; rows = C (per-row form) or 1 (shared form)
+    const float2 *carry;     // [rows][carry_cap]: hist samples of history, then the leftover (< D) unconsumed samples
     const float *taps;       // [ntp], zero padded to a multiple of 8
+    const uint64_t *steps;   // [C]: center_hz[c] / rate_hz as a 0.64 fixed-point fraction of a turn
     float2 *out;             // [C][ld_out]
     uint64_t ld_in, ld_out;
     uint64_t n_abs0;         // absolute input index of the first unconsumed sample (virtual index v = hist)
-    uint64_t step;           // center_hz / rate_hz as a 0.64 fixed-point fraction of a turn
-    uint32_t carry_cap, carry_len, hist, nsamp, nout, ntp;
+    uint32_t carry_cap, carry_len, hist, nsamp, nout, ntp, C;
+    uint32_t cpg;            // shared form: channels per workgroup (blockIdx.y = group)
 };
 
 __host__ __device__ constexpr int xl_pad(int n) { return n + (n >> 3); }
@@ -46,38 +69,26 @@ __device__ __forceinline__ cf2 xl_phasor(uint64_t turns)
     return (cf2){ cs, sn };
 }
 
+// sample v of one input row's virtual stream: its carry, then its block, zero beyond
+__device__ __forceinline__ float2 xl_window(const XlateArgs &a, const float2 *car, const float2 *blk, int64_t v)
+{
+    if (v < (int64_t)a.carry_len) return car[v];
+    if (v < (int64_t)a.carry_len + a.nsamp) return blk[v - a.carry_len];
+    return make_float2(0.f, 0.f);
+}
+
+// the mix of the sample with absolute index nabs: the phasor is evaluated per sample from the absolute index (not a running
+// rotation), so a sample is mixed to the same bits whatever tile, push or handle it lands in
+__device__ __forceinline__ cf2 xl_mix(float2 s, uint64_t nabs, uint64_t step)
+{
+    return cmul((cf2){ s.x, s.y }, xl_phasor(nabs * step));
+}
+
+// the FIR over the mixed, padded window zs (tile-local sample n at zs[xl_pad(n)]) and the store of lane t's 8/D outputs k0 + ..
 template <int D>
-__global__ __launch_bounds__(256) void xlate_fir_kernel(XlateArgs a)
+__device__ __forceinline__ void xl_fir_store(const cf2 *zs, const float *hs, int t, int H, int ntp, float2 *out_row, uint32_t k0, uint32_t nout)
 {
     constexpr int OPT = 8 / D;                                   // outputs per lane
-    __shared__ cf2 zs[xl_pad(XL_TILE + XL_MAX_TAPS) + 8];
-    __shared__ float hs[XL_MAX_TAPS];
-    const int t = threadIdx.x;
-    const uint32_t c = blockIdx.y;
-    const uint32_t k0 = blockIdx.x * (XL_TILE / D);
-    const int H = (int)a.hist;                                   // = ntp - 1
-    const int ntp = (int)a.ntp;
-    const float2 *blk = a.block + (uint64_t)c * a.ld_in;
-    const float2 *car = a.carry + (uint64_t)c * a.carry_cap;
-    const int64_t vtot = (int64_t)a.carry_len + a.nsamp;
-
-    for (int i = t; i < ntp; i += 256) hs[i] = a.taps[i];
-    // stage + mix: tile-local sample n <-> virtual index v = D*k0 + n;  lane t takes n = t, t+256, ...
-    {
-        const int64_t v0 = (int64_t)D * k0;
-        // the phasor is evaluated per sample from the absolute index (not a running rotation), so a sample is mixed to
-        // the same bits whatever tile or push it lands in
-        const uint64_t nabs0 = a.n_abs0 + (uint64_t)(v0 - H);      // wraps consistently for the (zero) pre-stream history
-        for (int n = t; n < XL_TILE + H; n += 256) {
-            const int64_t v = v0 + n;
-            float2 s = make_float2(0.f, 0.f);
-            if (v < (int64_t)a.carry_len) s = car[v];
-            else if (v < vtot) s = blk[v - a.carry_len];
-            zs[xl_pad(n)] = cmul((cf2){ s.x, s.y }, xl_phasor((nabs0 + (uint64_t)n) * a.step));
-        }
-    }
-    __syncthreads();
-
     cf2 acc[OPT];
 #pragma unroll
     for (int j = 0; j < OPT; j++) acc[j] = (cf2){ 0.f, 0.f };
@@ -93,15 +104,68 @@ __global__ __launch_bounds__(256) void xlate_fir_kernel(XlateArgs a)
                 acc[j] = __builtin_elementwise_fma(zp[xl_pad(7 + D * j - e)], (cf2){ h, h }, acc[j]);
         }
     }
-    float2 *o = a.out + (uint64_t)c * a.ld_out;
 #pragma unroll
     for (int j = 0; j < OPT; j++) {
         const uint32_t k = k0 + OPT * t + j;
-        if (k < a.nout) o[k] = make_float2(acc[j].x, acc[j].y);
+        if (k < nout) out_row[k] = make_float2(acc[j].x, acc[j].y);
     }
 }
 
-// carry_out[c][i] = virtual[c][consumed + i], i < new_len  (separate buffers: the ranges can overlap)
+template <int D>
+__global__ __launch_bounds__(256) void xlate_fir_kernel(XlateArgs a)
+{
+    __shared__ cf2 zs[xl_pad(XL_TILE + XL_MAX_TAPS) + 8];
+    __shared__ float hs[XL_MAX_TAPS];
+    const int t = threadIdx.x;
+    const uint32_t c = blockIdx.y;
+    const uint32_t k0 = blockIdx.x * (XL_TILE / D);
+    const int H = (int)a.hist;                                   // = ntp - 1
+    const int ntp = (int)a.ntp;
+    const float2 *blk = a.block + (uint64_t)c * a.ld_in;
+    const float2 *car = a.carry + (uint64_t)c * a.carry_cap;
+    const int64_t v0 = (int64_t)D * k0;
+    const uint64_t nabs0 = a.n_abs0 + (uint64_t)(v0 - H);        // wraps consistently for the (zero) pre-stream history
+    const uint64_t step = a.steps[c];
+
+    for (int i = t; i < ntp; i += 256) hs[i] = a.taps[i];
+    // stage + mix: tile-local sample n <-> virtual index v = D*k0 + n;  lane t takes n = t, t+256, ...
+    for (int n = t; n < XL_TILE + H; n += 256)
+        zs[xl_pad(n)] = xl_mix(xl_window(a, car, blk, v0 + n), nabs0 + (uint64_t)n, step);
+    __syncthreads();
+    xl_fir_store<D>(zs, hs, t, H, ntp, a.out + (uint64_t)c * a.ld_out, k0, a.nout);
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void xlate_shared_kernel(XlateArgs a)
+{
+    __shared__ float2 xs[XL_TILE + XLS_MAX_TAPS];                // the raw window, staged once
+    __shared__ cf2 zs[xl_pad(XL_TILE + XLS_MAX_TAPS) + 8];       // the window mixed for the channel in hand
+    __shared__ float hs[XLS_MAX_TAPS];
+    static_assert(sizeof(float2) * (XL_TILE + XLS_MAX_TAPS) + sizeof(cf2) * (xl_pad(XL_TILE + XLS_MAX_TAPS) + 8) + sizeof(float) * XLS_MAX_TAPS <= 65536,
+                  "static LDS of one workgroup");
+    const int t = threadIdx.x;
+    const uint32_t k0 = blockIdx.x * (XL_TILE / D);
+    const int H = (int)a.hist;                                   // = ntp - 1
+    const int ntp = (int)a.ntp;
+    const int64_t v0 = (int64_t)D * k0;
+    const uint64_t nabs0 = a.n_abs0 + (uint64_t)(v0 - H);        // wraps consistently for the (zero) pre-stream history
+
+    for (int i = t; i < ntp; i += 256) hs[i] = a.taps[i];
+    // stage: tile-local sample n <-> virtual index v = D*k0 + n;  lane t takes n = t, t+256, ...
+    for (int n = t; n < XL_TILE + H; n += 256) xs[n] = xl_window(a, a.carry, a.block, v0 + n);
+    __syncthreads();
+
+    const uint32_t c_end = min(a.C, (blockIdx.y + 1) * a.cpg);
+    for (uint32_t c = blockIdx.y * a.cpg; c < c_end; c++) {
+        const uint64_t step = a.steps[c];
+        for (int n = t; n < XL_TILE + H; n += 256) zs[xl_pad(n)] = xl_mix(xs[n], nabs0 + (uint64_t)n, step);
+        __syncthreads();
+        xl_fir_store<D>(zs, hs, t, H, ntp, a.out + (uint64_t)c * a.ld_out, k0, a.nout);
+        __syncthreads();                                         // the next channel overwrites the mixed window
+    }
+}
+
+// carry_out[r][i] = virtual[r][consumed + i], i < new_len  (separate buffers: the ranges can overlap)
 __global__ void xlate_carry_kernel(const float2 *block, uint64_t ld_in, const float2 *carry_in, float2 *carry_out,
                                    uint32_t carry_cap, uint32_t carry_len, uint32_t consumed, uint32_t new_len)
 {
@@ -112,16 +176,31 @@ __global__ void xlate_carry_kernel(const float2 *block, uint64_t ld_in, const fl
     carry_out[(uint64_t)c * carry_cap + i] = v < carry_len ? carry_in[(uint64_t)c * carry_cap + v] : block[(uint64_t)c * ld_in + (v - carry_len)];
 }
 
+// What the two forms differ in on the host: the kernel for a decimation (none: the form does not have it) and the padded tap limit.
+typedef void (*xlate_kernel_t)(XlateArgs);
+inline xlate_kernel_t xlate_kernel_for(bool shared, uint32_t D)
+{
+    switch (D) {
+    case 1: return shared ? xlate_shared_kernel<1> : xlate_fir_kernel<1>;
+    case 2: return shared ? xlate_shared_kernel<2> : xlate_fir_kernel<2>;
+    case 4: return shared ? xlate_shared_kernel<4> : xlate_fir_kernel<4>;
+    case 8: return shared ? xlate_shared_kernel<8> : nullptr;
+    default: return nullptr;
+    }
+}
+inline uint32_t xlate_max_taps(bool shared) { return shared ? XLS_MAX_TAPS : XL_MAX_TAPS; }
+
 struct XlateState {
     bool enabled = false;
-    uint32_t C = 0, D = 0, ntaps = 0, ntp = 0, hist = 0, carry_cap = 0, carry_len = 0, max_out = 0;
+    bool shared = false;             // one input row for all channels, else one per channel
+    uint32_t C = 0, rows = 0, D = 0, ntp = 0, hist = 0, carry_cap = 0, carry_len = 0, max_out = 0;
     int cur = 0;
-    uint64_t n_abs = 0, step = 0;
+    uint64_t n_abs = 0;
     DevBuf<float> taps;
-    DevBuf<float2> carry[2];
-    DevBuf<float2> out;
-    HostStage stage;                 // host-resident blocks: [C][D * max_out]
-    std::vector<float> taps_host;
+    DevBuf<uint64_t> steps;          // [C]
+    DevBuf<float2> carry[2];         // [rows][carry_cap] (hist + D samples a row), double-buffered
+    DevBuf<float2> out;              // [C][max_out]
+    HostStage stage;                 // host-resident blocks: [rows][D * max_out]
 };
 
 // firdes.low_pass(gain, fs, cutoff, width, WIN_BLACKMAN) as the flow graph calls it (grc/recctest.grc:115-155):
@@ -150,35 +229,50 @@ inline void xlate_destroy(XlateState &x) { x = XlateState{}; }
 inline int xlate_reset(XlateState &x, hipStream_t s)
 {
     if (!x.enabled) return 0;
-    if (hipMemsetAsync(x.carry[0].get(), 0, sizeof(float2) * (size_t)x.C * x.carry_cap, s) != hipSuccess) return -EIO;
-    if (hipMemsetAsync(x.carry[1].get(), 0, sizeof(float2) * (size_t)x.C * x.carry_cap, s) != hipSuccess) return -EIO;
+    if (hipMemsetAsync(x.carry[0].get(), 0, sizeof(float2) * (size_t)x.rows * x.carry_cap, s) != hipSuccess) return -EIO;
+    if (hipMemsetAsync(x.carry[1].get(), 0, sizeof(float2) * (size_t)x.rows * x.carry_cap, s) != hipSuccess) return -EIO;
     x.cur = 0; x.carry_len = x.hist; x.n_abs = 0;
     return 0;
 }
 
-inline int xlate_create(XlateState &x, uint32_t C, uint32_t D, uint32_t max_out, double rate_hz, double center_hz,
+// center_hz is [C] (per-row form: C times the same centre).  A configuration that is refused (-EINVAL, -E2BIG) leaves x as it was.
+inline int xlate_create(XlateState &x, bool shared, uint32_t C, uint32_t D, uint32_t max_out, double rate_hz, const double *center_hz,
                         const std::vector<float> &taps, hipStream_t s)
 {
-    xlate_destroy(x);
-    if (!(D == 1 || D == 2 || D == 4) || taps.empty() || !(rate_hz > 0.0) || std::fabs(center_hz) > rate_hz) return -EINVAL;
+    if (!xlate_kernel_for(shared, D) || C == 0 || !center_hz || taps.empty() || !(rate_hz > 0.0)) return -EINVAL;
+    std::vector<uint64_t> steps(C);
+    for (uint32_t c = 0; c < C; c++) {
+        if (!(std::fabs(center_hz[c]) <= rate_hz)) return -EINVAL;   // a NaN included
+        // fraction of a turn per input sample, two's complement for negative offsets
+        const long double f = (long double)center_hz[c] / (long double)rate_hz;
+        const long double fr = f - std::floor(f);
+        steps[c] = (uint64_t)(fr * 18446744073709551616.0L);
+    }
     const uint32_t ntp = (uint32_t)((taps.size() + 7) / 8 * 8);
-    if (ntp > (uint32_t)XL_MAX_TAPS) return -E2BIG;
-    x.C = C; x.D = D; x.ntaps = (uint32_t)taps.size(); x.ntp = ntp; x.hist = ntp - 1; x.carry_cap = ntp + D; x.max_out = max_out;
-    x.taps_host = taps;
-    // fraction of a turn per input sample, two's complement for negative offsets
-    const long double f = (long double)center_hz / (long double)rate_hz;
-    const long double fr = f - std::floor(f);
-    x.step = (uint64_t)(fr * 18446744073709551616.0L);
+    if (ntp > xlate_max_taps(shared)) return -E2BIG;
+    xlate_destroy(x);
+    x.shared = shared; x.C = C; x.rows = shared ? 1 : C; x.D = D; x.ntp = ntp; x.hist = ntp - 1; x.carry_cap = ntp + D; x.max_out = max_out;
     std::vector<float> padded(ntp, 0.0f);
     for (size_t i = 0; i < taps.size(); i++) padded[i] = taps[i];
-    int rc = x.taps.alloc(ntp) | x.carry[0].alloc((size_t)C * x.carry_cap) | x.carry[1].alloc((size_t)C * x.carry_cap) | x.out.alloc((size_t)C * max_out);
+    int rc = x.taps.alloc(ntp) | x.steps.alloc(C) | x.carry[0].alloc((size_t)x.rows * x.carry_cap) | x.carry[1].alloc((size_t)x.rows * x.carry_cap)
+           | x.out.alloc((size_t)C * max_out);
     if (!rc && hipMemcpy(x.taps.get(), padded.data(), sizeof(float) * ntp, hipMemcpyHostToDevice) != hipSuccess) rc = -EIO;
+    if (!rc && hipMemcpy(x.steps.get(), steps.data(), sizeof(uint64_t) * C, hipMemcpyHostToDevice) != hipSuccess) rc = -EIO;
     if (rc) { xlate_destroy(x); return rc; }
     x.enabled = true;
     return xlate_reset(x, s);
 }
 
-// filter nsamp new samples per channel ([C][ld], host or device); *out_iq is [C][*out_ld] device memory holding *nout samples
+// channels per workgroup of the shared form: as many groups of as few channels as it takes to reach WANT workgroups; one group (the
+// raw tile read once) when the tiles alone are that many.  The output bits do not depend on it.
+inline uint32_t xlate_shared_cpg(uint32_t C, uint64_t tiles)
+{
+    constexpr uint64_t WANT = 4096;                              // workgroups: sixteen per CU of a 256-CU device (measured: DESIGN.md 4.7b)
+    const uint64_t groups = std::min<uint64_t>(C, std::max<uint64_t>(1, (WANT + tiles - 1) / tiles));
+    return (uint32_t)((C + groups - 1) / groups);
+}
+
+// filter nsamp new samples per input row ([rows][ld], host or device); *out_iq is [C][*out_ld] device memory holding *nout samples per row
 inline int xlate_run(XlateState &x, const float2 *iq, uint64_t ld, size_t nsamp, int mem, hipStream_t s,
                      const float2 **out_iq, uint64_t *out_ld, uint32_t *nout)
 {
@@ -188,26 +282,23 @@ inline int xlate_run(XlateState &x, const float2 *iq, uint64_t ld, size_t nsamp,
     if (nsamp > (size_t)x.D * x.max_out) return -E2BIG;
     const float2 *d = iq;
     if (mem == AMPS_MEM_HOST) {
-        if (int rc = x.stage.stage(iq, ld, nsamp, x.C, (size_t)x.C * x.D * x.max_out, &d, &ld)) return rc;
+        if (int rc = x.stage.stage(iq, ld, nsamp, x.rows, (size_t)x.rows * x.D * x.max_out, &d, &ld)) return rc;
     }
     const uint64_t avail = (uint64_t)(x.carry_len - x.hist) + nsamp;
     const uint64_t n_out = avail / x.D;
     if (n_out > x.max_out) return -E2BIG;
     XlateArgs a{};
-    a.block = d; a.carry = x.carry[x.cur].get(); a.taps = x.taps.get(); a.out = x.out.get(); a.ld_in = ld; a.ld_out = x.max_out;
-    a.n_abs0 = x.n_abs; a.step = x.step; a.carry_cap = x.carry_cap; a.carry_len = x.carry_len; a.hist = x.hist;
-    a.nsamp = (uint32_t)nsamp; a.nout = (uint32_t)n_out; a.ntp = x.ntp;
+    a.block = d; a.carry = x.carry[x.cur].get(); a.taps = x.taps.get(); a.steps = x.steps.get(); a.out = x.out.get(); a.ld_in = ld; a.ld_out = x.max_out;
+    a.n_abs0 = x.n_abs; a.carry_cap = x.carry_cap; a.carry_len = x.carry_len; a.hist = x.hist;
+    a.nsamp = (uint32_t)nsamp; a.nout = (uint32_t)n_out; a.ntp = x.ntp; a.C = x.C;
     if (n_out) {
-        const dim3 grid((uint32_t)((n_out * x.D + XL_TILE - 1) / XL_TILE), x.C);
-        switch (x.D) {
-        case 1: hipLaunchKernelGGL(xlate_fir_kernel<1>, grid, dim3(256), 0, s, a); break;
-        case 2: hipLaunchKernelGGL(xlate_fir_kernel<2>, grid, dim3(256), 0, s, a); break;
-        default: hipLaunchKernelGGL(xlate_fir_kernel<4>, grid, dim3(256), 0, s, a); break;
-        }
+        const uint64_t tiles = (n_out * x.D + XL_TILE - 1) / XL_TILE;
+        a.cpg = x.shared ? xlate_shared_cpg(x.C, tiles) : 1;     // per-row form: a workgroup per (tile, row)
+        hipLaunchKernelGGL(xlate_kernel_for(x.shared, x.D), dim3((uint32_t)tiles, (x.C + a.cpg - 1) / a.cpg), dim3(256), 0, s, a);
     }
     const uint32_t consumed = (uint32_t)(n_out * x.D);
     const uint32_t new_len = x.hist + (uint32_t)(avail - (uint64_t)consumed);
-    hipLaunchKernelGGL(xlate_carry_kernel, dim3((new_len + 255) / 256, x.C), dim3(256), 0, s, d, ld, x.carry[x.cur].get(), x.carry[x.cur ^ 1].get(),
+    hipLaunchKernelGGL(xlate_carry_kernel, dim3((new_len + 255) / 256, x.rows), dim3(256), 0, s, d, ld, x.carry[x.cur].get(), x.carry[x.cur ^ 1].get(),
                        x.carry_cap, x.carry_len, consumed, new_len);
     if (hipGetLastError() != hipSuccess) return -EIO;
     if (mem == AMPS_MEM_HOST) { if (int rc = x.stage.arm(s)) return rc; }

@@ -283,7 +283,10 @@ int amps_recc_push_wideband_short(amps_recc_t *h, const int16_t *iq, size_t nsam
  * grc/recctest.grc:889-937 with taps :115-155 -- so that its ".raw" fc32 captures (400 ksps, channel at
  * +-160 kHz, :591) can be pushed directly.  rate_hz / decim must equal samples_per_symbol * 20 kHz.
  * gain / cutoff_hz / width_hz = 0 select the flow graph's 3.0 / 10 kHz / 4.5 kHz (299 taps at 400 ksps).
- * decim = 0 removes the stage.  Resets nothing else; call before the first push. */
+ * decim = 0 removes the stage.  Resets nothing else; call before the first push.
+ * -EINVAL for a center_hz beyond the rate or not a number (NaN), as amps_recc_set_xlate_shared answers for each of its centres;
+ * -E2BIG for a filter of more than 1024 taps (padded to a multiple of 8).  A configuration that is refused leaves the handle's
+ * translate stage as it was. */
 typedef struct amps_recc_xlate_cfg {
     uint32_t struct_size;
     uint32_t decim;            /* 1, 2 or 4 */

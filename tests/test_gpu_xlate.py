@@ -4,6 +4,8 @@ flow graph's 400 ksps ".raw" captures can be pushed as they are.
 
 Float stage: compared with the oracle's restatement of the GNU Radio block (composite complex taps + rotator, fp32) and
 with the exact formula in float64, tolerance stated below.  Downstream of it the comparison is word-level and bit-exact."""
+import errno
+
 import numpy as np
 import pytest
 
@@ -63,24 +65,31 @@ def test_xlate_other_decimations(gpu, decim, sps):
     assert np.abs(y[1] - _exact(x[::-1], taps, 0.11 * fs, fs, decim)).max() <= TOL_EXACT
 
 
+@pytest.mark.parametrize("nch", [1, 3])
 @pytest.mark.parametrize("blocks", [[1, 2, 3, 298, 299, 300, 4097], [2047, 2049, 1, 1, 1], [7777] * 5])
-def test_xlate_streaming_is_bitwise(gpu, blocks):
+def test_xlate_streaming_is_bitwise(gpu, blocks, nch):
     """Pushing in ragged blocks (odd sizes leave a sample waiting for the decimator) gives the same bits as one push:
-    the mixer phase is a function of the absolute sample index, the carry holds the filter history."""
-    rng = np.random.default_rng(9)
+    the mixer phase is a function of the absolute sample index, the carry holds the filter history.  With three rows of
+    different noise every row keeps a carry of its own: each equals what a one-channel handle makes of that row alone."""
     n = sum(blocks)
-    x = (rng.standard_normal(n) + 1j * rng.standard_normal(n)).astype(np.complex64)
-    with capi.Recc(n_channels=1, sps=10, max_samples=n, max_bursts=4) as r:
+    x = np.stack([np.random.default_rng(9 + c).standard_normal((2, n)) for c in range(nch)])
+    x = (x[:, 0] + 1j * x[:, 1]).astype(np.complex64)
+    with capi.Recc(n_channels=nch, sps=10, max_samples=n, max_bursts=4) as r:
         r.set_xlate(rate_hz=400e3, center_hz=-160e3, decim=2)
-        whole = r.debug_xlate(x[None, :])[0]
+        whole = r.debug_xlate(x)
         r.reset()
         parts, o = [], 0
         for b in blocks:
-            parts.append(r.debug_xlate(x[None, o:o + b])[0])
+            parts.append(r.debug_xlate(x[:, o:o + b]))
             o += b
-    got = np.concatenate(parts)
-    assert got.size == whole.size == n // 2
+    got = np.concatenate(parts, axis=1)
+    assert got.shape == whole.shape == (nch, n // 2)
     assert np.array_equal(got.view(np.uint32), whole.view(np.uint32))
+    for c in range(nch) if nch > 1 else ():
+        with capi.Recc(n_channels=1, sps=10, max_samples=n, max_bursts=4) as r:
+            r.set_xlate(rate_hz=400e3, center_hz=-160e3, decim=2)
+            alone = r.debug_xlate(x[c:c + 1])[0]
+        assert np.array_equal(whole[c].view(np.uint32), alone.view(np.uint32)), c
 
 
 def test_raw400_words_equal_reference_cpu_chain(gpu):
@@ -121,6 +130,9 @@ def test_xlate_argument_errors(gpu):
             r.set_xlate(rate_hz=400e3, center_hz=160e3, decim=4)         # 100 ksps != 10 samples/symbol
         with pytest.raises(capi.AmpsError):
             r.set_xlate(rate_hz=400e3, center_hz=160e3, decim=3)
+        with pytest.raises(capi.AmpsError) as e:
+            r.set_xlate(rate_hz=400e3, center_hz=float("nan"), decim=2)  # a centre that is no number
+        assert e.value.code == -errno.EINVAL
         r.set_xlate(rate_hz=400e3, center_hz=160e3, decim=2)
         with pytest.raises(capi.AmpsError):
             r.push_raw(np.zeros((1, 2 * 4096 + 2), np.complex64))        # more than decim * max_samples
