@@ -1132,6 +1132,7 @@ inline int channelizer_reset(ChannelizerState &z, hipStream_t s)
     const size_t cap = chz_carry_cap(z.P, z.D);
     if (hipMemsetAsync(z.carry[0].get(), 0, sizeof(float2) * cap, s) != hipSuccess) return -EIO;
     if (hipMemsetAsync(z.carry[1].get(), 0, sizeof(float2) * cap, s) != hipSuccess) return -EIO;
+    if (z.pow_ring) HIP_TRY(hipMemsetAsync(z.pow_ring.get(), 0, sizeof(float) * (size_t)z.pow_slots * z.C, s));   // the stream starts again: no snapshot is held
     z.carry_cur = 0;
     z.carry_len = chz_hist(z.P, z.D);                // all-zero history, no leftover
     z.frames_done = 0;
@@ -1189,7 +1190,7 @@ inline int channelizer_create(ChannelizerState &z, const amps_recc_cfg_t &cfg, h
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
             z.target_wgs = (uint32_t)prop.multiProcessorCount;
     }
-    { const char *e = std::getenv("AMPS_RECC_SHORT_PREPASS"); z.short_prepass = e && e[0] == '1'; }
+    z.short_prepass = env_read("AMPS_RECC_SHORT_PREPASS", env_one);   // at every create, not once: scripts/bench_short_input.py changes it between two handles of one process
     z.enabled = true;
     (void)s;
     return 0;

@@ -19,6 +19,8 @@
 #include <stdint.h>
 #include "amps_recc.h"
 #include "amps_recc_numerics.h"
+#include "recc_devmem.hip.h"
+#include "recc_record_host.h"   // PACKED_*, REC_*_OFF
 
 namespace amps {
 
@@ -443,21 +445,7 @@ __device__ __forceinline__ void decode_core_store(const DecodeCore &s, amps_recc
     for (int i = lane; i < (int)(sizeof(amps_recc_burst_t) / 4); i += 64) ((uint32_t *)out)[i] = ((const uint32_t *)&s.rec)[i];
 }
 
-// ---- the record on its way to the host (round 5).  The capture kernels write their records straight into mapped, pinned HOST memory;
-// 588 of a record's 728 bytes are the one-byte-per-bit arrays word_raw[7][48] and word_dec[7][36] the reference's own layout asks for
-// (lib/recc_decode_impl.cc:92-95).  1664 records per push of the channel-major bench are 1.2 MB of 728-byte PCIe writes that the kernel
-// cannot retire before they have crossed the link: 0.050 ms of "resolve + capture + decode" there was mostly that.  So the bits travel
-// as bits -- PACKED_RECORD_BYTES = 216 instead of 728 -- and amps_recc_drain expands them while it gathers the sorted records into the
-// caller's buffer anyway (expand_packed_record: one 8-byte table entry per packed byte).  Layout, in dwords:
-//    0 .. 12   the record's first 52 bytes as they are (channel .. first_valid_rep)
-//   13 .. 23   word_raw: bit 8 j + i of dword 13 + g = byte 32 g + 4 j + i of the array (bytes past the array's 336: don't care)
-//   24 .. 31   word_dec likewise (252 bytes)
-//   32 .. 53   the record's last 88 bytes as they are (a_F .. _pad4)
-constexpr int PACKED_RECORD_BYTES = 216;
-constexpr int PACKED_BURST_BYTES = (AMPS_RECC_CAPTURE_SYMS + 31) / 32 * 4;   // 424: the kept 3374-symbol blob, a bit per symbol (recc_resolve.hip.h: capture_store_wave)
-constexpr int REC_RAW_OFF = 52, REC_DEC_OFF = 388, REC_TAIL_OFF = 640;
-static_assert(offsetof(amps_recc_burst_t, word_raw) == REC_RAW_OFF && offsetof(amps_recc_burst_t, word_dec) == REC_DEC_OFF &&
-              offsetof(amps_recc_burst_t, a_F) == REC_TAIL_OFF && sizeof(amps_recc_burst_t) - REC_TAIL_OFF == 88, "packed record layout");
+// the record on its way to the host: bits as bits, PACKED_RECORD_BYTES instead of 728 (layout and expansion: recc_record_host.h)
 __device__ __forceinline__ void decode_core_store_packed(const DecodeCore &s, uint32_t *__restrict__ out, int lane)
 {
     const uint32_t *rec = (const uint32_t *)&s.rec;
@@ -657,6 +645,65 @@ __device__ __forceinline__ void decode_burst_wave(DecodeScratch &s, uint32_t cha
     const int lane = threadIdx.x & 63;
     manchester_from_sym<BlockSync>(s.k, s.sym, lane);
     decode_core_wave<BlockSync>(s.k, channel, position, out, majority, lane);
+}
+
+// BCH(63,51) shortened to (k+12, k): one code word per lane (amps_bch_encode_words / amps_bch_decode_words)
+__global__ __launch_bounds__(256) void bch_encode_words_kernel(const uint8_t *msg, uint32_t n, int k, uint8_t *cw)
+{
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        // systematic encode, parity = m(x) x^12 mod g(x) (bch_short_encode, in registers: no per-lane byte arrays)
+        unsigned rem = 0;
+        for (int j = 0; j < k; j++) {
+            const unsigned bit = msg[(uint64_t)i * k + j] & 1u;
+            const unsigned fb = ((rem >> 11) & 1u) ^ bit;
+            rem = (rem << 1) & 0xfffu;
+            if (fb) rem ^= 0x539u;
+            cw[(uint64_t)i * (k + 12) + j] = (uint8_t)bit;
+        }
+        for (int j = 0; j < 12; j++) cw[(uint64_t)i * (k + 12) + k + j] = (uint8_t)((rem >> (11 - j)) & 1u);
+    }
+}
+__global__ __launch_bounds__(256) void bch_decode_words_kernel(const uint8_t *cw, uint32_t n, int k, uint8_t *msg, uint8_t *valid,
+                                                               uint8_t *nerr)
+{
+    const int nb = k + 12;
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        // the code word as a polynomial in one register (bit e = coefficient of x^e = byte nb - 1 - e): corrections are bit flips,
+        // not stores into a per-lane byte array at a computed index (which the compiler turned into 63 compare-and-select chains
+        // and 124 spilled SGPRs)
+        uint64_t w = 0;
+        for (int j = 0; j < nb; j++) w |= (uint64_t)(cw[(uint64_t)i * nb + j] & 1u) << (nb - 1 - j);
+        const uint64_t raw = w;
+        BchResult r = bch63_decode_packed(w);
+        int ok = r.ok;
+#pragma unroll
+        for (int f = 0; f < 3; f++) {
+            const int e = r.e[f];
+            if (e >= nb) ok = 0;                           // a "correction" inside the shortening zeros
+            else if (r.ok && e >= 0) w ^= 1ull << e;
+        }
+        const uint64_t out = ok ? w : raw;
+        for (int j = 0; j < k; j++) msg[(uint64_t)i * k + j] = (uint8_t)((out >> (nb - 1 - j)) & 1ull);
+        valid[i] = (uint8_t)ok;
+        nerr[i] = (uint8_t)(ok ? r.nflip : 0xff);
+    }
+}
+
+// amps_bch_encode_words / amps_bch_decode_words: the scratch lives in the handle and only ever grows: a call costs one launch, its
+// copies and one synchronise
+struct BchScratch { DevBuf<uint8_t> in, out, val, err; };
+inline int bch_grow(DevBuf<uint8_t> &b, size_t need)
+{
+    if (need <= b.capacity()) return 0;
+    return b.reserve(need < 4096 ? 4096 : need + need / 2);
+}
+inline int bch_stage_in(BchScratch &b, hipStream_t s, const uint8_t *in, size_t nin, int mem, const uint8_t **din)
+{
+    if (mem == AMPS_MEM_DEVICE) { *din = in; return 0; }
+    if (int rc = bch_grow(b.in, nin)) return rc;
+    if (hipMemcpyAsync(b.in.get(), in, nin, hipMemcpyHostToDevice, s) != hipSuccess) return -EIO;
+    *din = b.in.get();
+    return 0;
 }
 
 } // namespace amps

@@ -8,10 +8,30 @@
 #include <cerrno>
 #include <cstddef>
 #include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
 #include <type_traits>
 #include <utility>
 
+// a HIP call that must succeed: says which one failed and returns the library's error code for it
+#define HIP_TRY(expr)                                                                   \
+    do {                                                                                \
+        hipError_t e_ = (expr);                                                         \
+        if (e_ != hipSuccess) {                                                         \
+            std::fprintf(stderr, "amps_recc: %s failed: %s\n", #expr, hipGetErrorString(e_)); \
+            return e_ == hipErrorOutOfMemory ? -ENOMEM : -EIO;                          \
+        }                                                                               \
+    } while (0)
+
 namespace amps {
+
+// The library's environment switches: a name and a test of its value (never null).  env_is reads a switch when its call site is
+// first reached and keeps the answer for the life of the process; env_read reads it now.
+typedef bool (*env_test_t)(const char *value);
+inline bool env_one(const char *v) { return v[0] == '1'; }             // NAME=1
+inline bool env_read(const char *name, env_test_t test) { const char *e = std::getenv(name); return e && test(e); }
+#define env_is(name, test) ([] { static const bool v_ = amps::env_read(name, test); return v_; }())
 
 // One device allocation of `capacity()` elements.  Move-only (the move constructor rules copies out); the destructor frees.
 template <typename T> class DevBuf {

@@ -130,4 +130,77 @@ __global__ __launch_bounds__(256) void chz_power_gather_kernel(const float *ring
     if (lane == 0) out[rec] = make_uint2(count ? __float_as_uint(sum / (float)count) : 0u, count);
 }
 
+// ---- host side: the queries behind amps_recc_channel_power / amps_recc_burst_power.  The ring itself is z.pow_ring: the filter
+// bank's launches fill it. ----
+struct PowerState {
+    std::vector<int32_t> chan2row;            // whole-band channel number -> ring row, -1 for a channel this handle does not decode
+    DevBuf<ChzBurstQuery> pq_dev;             // amps_recc_burst_power scratch (grow-only)
+    DevBuf<uint2> pq_out;
+};
+
+// ring_words: of the slicer-bit ring, whose window the power ring shares (a power of two, >= 32)
+inline int power_create(PowerState &p, ChannelizerState &z, uint32_t n_channels, uint32_t ring_words)
+{
+    z.pow_slots = 64u * ring_words / AMPS_RECC_POWER_STRIDE;
+    p.chan2row.assign(n_channels, -1);
+    for (size_t r = 0; r < z.row2chan.size(); r++) p.chan2row[z.row2chan[r]] = (int32_t)r;
+    return z.pow_ring.alloc((size_t)z.pow_slots * z.C);
+}
+
+// the snapshots the power ring holds once the stream is idle: [lo, hi), hi = one past the newest (snapshot j exists iff 256 j < n_done)
+inline void power_window(const ChannelizerState &z, uint64_t n_done, uint64_t origin, uint64_t *lo, uint64_t *hi)
+{
+    const uint64_t S = AMPS_RECC_POWER_STRIDE;
+    *hi = (n_done + S - 1) / S;
+    *lo = std::max<uint64_t>((origin + S - 1) / S, *hi > z.pow_slots ? *hi - z.pow_slots : 0);
+}
+
+// amps_recc_channel_power on an idle stream at position n_done
+inline int power_channels(const ChannelizerState &z, uint64_t n_done, uint64_t origin, hipStream_t s, uint64_t first_snap, size_t n, float *out,
+                          size_t out_ld, uint32_t *rows, uint64_t *produced_snaps)
+{
+    uint64_t lo, hi;
+    power_window(z, n_done, origin, &lo, &hi);
+    if (rows) *rows = z.C;
+    if (produced_snaps) *produced_snaps = hi;
+    if (n == 0) return 0;
+    if (first_snap < lo || first_snap > hi || n > hi - first_snap) return -ERANGE;
+    // the ring is snapshot-major: n slots (two runs where the range wraps) to the host, transposed there
+    const uint32_t slots = z.pow_slots;
+    const size_t C = z.C, s0 = (size_t)(first_snap & (slots - 1)), n1 = std::min<size_t>(n, slots - s0);
+    std::vector<float> snap(n * C);
+    HIP_TRY(hipMemcpyAsync(snap.data(), z.pow_ring.get() + s0 * C, sizeof(float) * n1 * C, hipMemcpyDeviceToHost, s));
+    if (n > n1) HIP_TRY(hipMemcpyAsync(snap.data() + n1 * C, z.pow_ring.get(), sizeof(float) * (n - n1) * C, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (size_t c = 0; c < C; c++)
+        for (size_t i = 0; i < n; i++) out[c * out_ld + i] = snap[i * C + c];
+    return 0;
+}
+
+// amps_recc_burst_power: idle() makes the device current and waits for the stream (the window is that of an idle stream; the copies
+// below are synchronous) once the records have been found to name channels of this handle, which keeps the entry point's order of
+// answers: -EINVAL for a foreign channel comes before any wait; span = samples of a capture
+template <class Idle> int power_bursts(PowerState &p, const ChannelizerState &z, uint64_t n_done, uint64_t origin, uint32_t span, hipStream_t s, Idle &&idle,
+                                       const amps_recc_burst_t *recs, size_t n, float *mean_power, uint32_t *n_snaps)
+{
+    std::vector<ChzBurstQuery> q(n);
+    for (size_t i = 0; i < n; i++) {
+        if (recs[i].channel >= p.chan2row.size() || p.chan2row[recs[i].channel] < 0) return -EINVAL;
+        q[i] = ChzBurstQuery{ recs[i].position, (uint32_t)p.chan2row[recs[i].channel], 0u };
+    }
+    if (int rc = idle()) return rc;
+    if (p.pq_dev.reserve(n) || p.pq_out.reserve(n)) return -ENOMEM;
+    uint64_t lo, hi;
+    power_window(z, n_done, origin, &lo, &hi);
+    HIP_TRY(hipMemcpy(p.pq_dev.get(), q.data(), sizeof(ChzBurstQuery) * n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(chz_power_gather_kernel, dim3((uint32_t)((n + 3) / 4)), dim3(256), 0, s, z.pow_ring.get(), z.C, z.pow_slots - 1, lo, hi,
+                       span, p.pq_dev.get(), (uint32_t)n, p.pq_out.get());
+    HIP_TRY(hipGetLastError());
+    std::vector<uint2> res(n);
+    HIP_TRY(hipMemcpyAsync(res.data(), p.pq_out.get(), sizeof(uint2) * n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (size_t i = 0; i < n; i++) { std::memcpy(&mean_power[i], &res[i].x, sizeof(float)); n_snaps[i] = res[i].y; }
+    return 0;
+}
+
 } // namespace amps

@@ -17,9 +17,6 @@
 
 namespace amps {
 
-// one packed key (channel, position) for the capture queue and the host's sort: 2^44 samples per channel stream (2.8 years at 200 ksps), 2^20 channels
-constexpr int CAPQ_POS_BITS = 44;
-
 struct ResolveArgs {
     const uint64_t *det;       // [C][max_chunks][det_cap]
     const uint32_t *detcount;  // [C][max_chunks]
@@ -151,7 +148,7 @@ constexpr uint32_t DONE_GROUPS = 32;       // done_blocks[0] = top counter, [1 +
 // because a release waits for the counting wave's 728-byte record stores to cross PCIe.  The packed count needs no ordering at all, so
 // the read-modify-writes stay RELAXED (an acquire on them measured +2.5 us).  The status word is read
 // relaxed as well: the one bit that can be set inside the publishing launch -- 4, record list overflow -- is implied by the count the
-// host compares with max_bursts anyway (drain_end_impl), bit 2 (capture queue overflow) is set by the kernel in FRONT of the one that
+// host compares with max_bursts anyway (records_end, recc_records.hip.h), bit 2 (capture queue overflow) is set by the kernel in FRONT of the one that
 // publishes in the queue form, bit 1 by the search kernel in front of both: kernel boundaries order those.
 // AMPS_RECC_CHECK_HEADER (on in the test suite) still cross-checks the header against a copy of the device counters.
 __device__ __forceinline__ unsigned long long count_done(unsigned long long *p, uint32_t done, unsigned long long reserved)
@@ -436,48 +433,6 @@ __global__ __launch_bounds__(64) void recc_decode_bursts_kernel(const uint8_t *b
         __syncthreads();
         decode_burst_wave(s, chan ? chan[q] : 0u, 0ull, out + q, majority != 0);
         __syncthreads();
-    }
-}
-
-// BCH(63,51) shortened to (k+12, k): one code word per lane (amps_bch_encode_words / amps_bch_decode_words)
-__global__ __launch_bounds__(256) void bch_encode_words_kernel(const uint8_t *msg, uint32_t n, int k, uint8_t *cw)
-{
-    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        // systematic encode, parity = m(x) x^12 mod g(x) (bch_short_encode, in registers: no per-lane byte arrays)
-        unsigned rem = 0;
-        for (int j = 0; j < k; j++) {
-            const unsigned bit = msg[(uint64_t)i * k + j] & 1u;
-            const unsigned fb = ((rem >> 11) & 1u) ^ bit;
-            rem = (rem << 1) & 0xfffu;
-            if (fb) rem ^= 0x539u;
-            cw[(uint64_t)i * (k + 12) + j] = (uint8_t)bit;
-        }
-        for (int j = 0; j < 12; j++) cw[(uint64_t)i * (k + 12) + k + j] = (uint8_t)((rem >> (11 - j)) & 1u);
-    }
-}
-__global__ __launch_bounds__(256) void bch_decode_words_kernel(const uint8_t *cw, uint32_t n, int k, uint8_t *msg, uint8_t *valid,
-                                                               uint8_t *nerr)
-{
-    const int nb = k + 12;
-    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        // the code word as a polynomial in one register (bit e = coefficient of x^e = byte nb - 1 - e): corrections are bit flips,
-        // not stores into a per-lane byte array at a computed index (which the compiler turned into 63 compare-and-select chains
-        // and 124 spilled SGPRs)
-        uint64_t w = 0;
-        for (int j = 0; j < nb; j++) w |= (uint64_t)(cw[(uint64_t)i * nb + j] & 1u) << (nb - 1 - j);
-        const uint64_t raw = w;
-        BchResult r = bch63_decode_packed(w);
-        int ok = r.ok;
-#pragma unroll
-        for (int f = 0; f < 3; f++) {
-            const int e = r.e[f];
-            if (e >= nb) ok = 0;                           // a "correction" inside the shortening zeros
-            else if (r.ok && e >= 0) w ^= 1ull << e;
-        }
-        const uint64_t out = ok ? w : raw;
-        for (int j = 0; j < k; j++) msg[(uint64_t)i * k + j] = (uint8_t)((out >> (nb - 1 - j)) & 1ull);
-        valid[i] = (uint8_t)ok;
-        nerr[i] = (uint8_t)(ok ? r.nflip : 0xff);
     }
 }
 

@@ -14,6 +14,7 @@
 #include <stdint.h>
 #include "amps_recc.h"
 #include "recc_front.hip.h" // TRIG_LO / TRIG_HI
+#include "recc_timing.hip.h"
 
 namespace amps {
 
@@ -219,6 +220,83 @@ __global__ __launch_bounds__(256, 2) void recc_symbols_kernel(SymbolsArgs a)
         }
     }
     if (tid == 0) { a.len[c] = len; a.curstart[c] = cur; }
+}
+
+// ---- host side: the seam's buffers, amps_recc_push_symbols behind its argument checks ----
+struct SymbolsState {
+    uint32_t C = 0, max_bursts = 0;
+    DevBuf<uint8_t> symbuf;           // [C][AMPS_RECC_SYMBUF]
+    DevBuf<uint32_t> sym_len;
+    DevBuf<int32_t> sym_cur;
+    DevBuf<uint8_t> sym_stage;        // [C][MAX_WORK_ITEMS]
+    DevBuf<uint8_t> bursts_dev;       // [max_bursts][3374]
+    DevBuf<uint32_t> burst_chan_dev;
+    DevBuf<uint32_t> nbursts_dev;
+    DevBuf<amps_recc_burst_t> dec_out_dev;   // decode_bursts staging (grow-only)
+    DevBuf<uint8_t> dec_in_dev;
+    DevBuf<uint32_t> dec_chan_dev;
+};
+
+inline int symbols_create(SymbolsState &y, uint32_t C, uint32_t max_bursts)
+{
+    y.C = C; y.max_bursts = max_bursts;
+    return y.symbuf.alloc((size_t)C * AMPS_RECC_SYMBUF) | y.sym_len.alloc(C) | y.sym_cur.alloc(C) | y.sym_stage.alloc((size_t)C * (AMPS_RECC_MAX_WORK_ITEMS + 1))
+         | y.bursts_dev.alloc((size_t)max_bursts * AMPS_RECC_CAPTURE_SYMS) | y.burst_chan_dev.alloc(max_bursts) | y.nbursts_dev.alloc(1);
+}
+
+inline int symbols_reset(SymbolsState &y, hipStream_t s)
+{
+    HIP_TRY(hipMemsetAsync(y.symbuf.get(), 0, (size_t)y.C * AMPS_RECC_SYMBUF, s));
+    HIP_TRY(hipMemsetAsync(y.sym_len.get(), 0, sizeof(uint32_t) * y.C, s));
+    HIP_TRY(hipMemsetAsync(y.sym_cur.get(), 0xff, sizeof(int32_t) * y.C, s));
+    HIP_TRY(hipMemsetAsync(y.nbursts_dev.get(), 0, sizeof(uint32_t), s));
+    return 0;
+}
+
+// one work() call of every channel: n new symbols per row of syms ([C][ld], host or device); `status` is the current record list's
+// status word (bit 3: burst list overflow)
+inline int symbols_push(SymbolsState &y, TimingState &tm, hipStream_t s, uint32_t *status, const uint8_t *syms, size_t ld, int n, int mem,
+                        uint8_t *bursts_out, uint32_t *burst_channel, size_t cap, size_t *nout)
+{
+    const uint8_t *dsyms = syms;
+    uint64_t dld = ld;
+    if (mem == AMPS_MEM_HOST) {
+        dld = AMPS_RECC_MAX_WORK_ITEMS + 1;
+        HIP_TRY(hipMemcpy2DAsync(y.sym_stage.get(), dld, syms, ld, (size_t)n, y.C, hipMemcpyHostToDevice, s));
+        dsyms = y.sym_stage.get();
+    }
+    HIP_TRY(hipMemsetAsync(y.nbursts_dev.get(), 0, sizeof(uint32_t), s));
+    SymbolsArgs a{};
+    a.syms = dsyms; a.ld = dld; a.n = n; a.symbuf = y.symbuf.get(); a.len = y.sym_len.get(); a.curstart = y.sym_cur.get();
+    a.bursts = y.bursts_dev.get(); a.burst_chan = y.burst_chan_dev.get(); a.nbursts = y.nbursts_dev.get();
+    a.cap = y.max_bursts; a.status = status;
+    {
+        SpanGuard g(tm, s, false, T_SYMBOLS);
+        hipLaunchKernelGGL(recc_symbols_kernel, dim3(y.C), dim3(256), 0, s, a);
+    }
+    HIP_TRY(hipGetLastError());
+    uint32_t nb = 0;
+    HIP_TRY(hipMemcpyAsync(&nb, y.nbursts_dev.get(), sizeof(nb), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    collect_spans(tm);
+    int rc = 0;
+    if (nb > y.max_bursts) { nb = y.max_bursts; rc = -ENOSPC; }
+    if (nb == 0) return rc;
+    std::vector<uint32_t> chan(nb);
+    std::vector<uint8_t> data((size_t)nb * AMPS_RECC_CAPTURE_SYMS);
+    HIP_TRY(hipMemcpy(chan.data(), y.burst_chan_dev.get(), sizeof(uint32_t) * nb, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(data.data(), y.bursts_dev.get(), data.size(), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> order(nb);
+    for (uint32_t i = 0; i < nb; i++) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y_) { return chan[x] < chan[y_]; });
+    size_t k = 0;
+    for (; k < nb && k < cap; k++) {
+        if (bursts_out) std::memcpy(bursts_out + k * AMPS_RECC_CAPTURE_SYMS, &data[(size_t)order[k] * AMPS_RECC_CAPTURE_SYMS], AMPS_RECC_CAPTURE_SYMS);
+        if (burst_channel) burst_channel[k] = chan[order[k]];
+    }
+    *nout = k;
+    if (nb > cap) rc = -ENOSPC;
+    return rc;
 }
 
 } // namespace amps
