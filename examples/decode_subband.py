@@ -5,6 +5,8 @@ behind it decodes them.  Replaces 21 x [freq_xlating_fir_filter_ccc -> quadratur
 amps.recc -> amps.recc_decode] of grc/recctest.grc.  Needs an MI355X: the library has no CPU path.
 
     python examples/decode_subband.py             # one mobile per control channel, the stream pushed in ragged blocks
+    python examples/decode_subband.py --sc16      # the same stream as an SDR delivers it: interleaved int16, pushed as it is
+                                                  # (amps_recc_push_raw_shared_as; --sc8 / --cu8 likewise take capi.SAMPLES_SC8 / _CU8)
 """
 import os
 import sys
@@ -32,13 +34,19 @@ for c, fc in enumerate(centres):                  # one seizure burst per channe
     x += iq * np.exp(2j * np.pi * fc * k / RATE)
     sent[c] = truth[0][2]
 x = x.astype(np.complex64)
+SC16 = "--sc16" in sys.argv[1:]
+if SC16:                                          # what the SDR's converter does: scale to the converter's range and round; the seam reads
+    x = np.rint(np.stack([x.real, x.imag], -1) * 2048.0).astype(np.int16)   # the [n, 2] int16 block in place -- no float copy on the host
 
 with rx:
     rx.set_xlate_shared(RATE, centres, DECIM)
     pos = 0
     while pos < NSAMP:                            # blocks of any size: samples short of a decimation step wait in the handle
         n = min(int(rng.integers(10_000, 150_000)), NSAMP - pos)
-        rx.push_raw_shared(x[pos:pos + n])
+        if SC16:
+            rx.push_raw_shared_as(x[pos:pos + n], capi.SAMPLES_SC16)
+        else:
+            rx.push_raw_shared(x[pos:pos + n])
         pos += n
     recs = rx.drain()
 print("%d bursts sent, %d decoded" % (len(sent), len(recs)))

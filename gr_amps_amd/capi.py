@@ -124,11 +124,16 @@ EXPORTS = (
     "amps_recc_debug_slicer_bits", "amps_recc_push_wideband_short",
     "amps_recc_channel_power", "amps_recc_burst_power", "amps_recc_power_ring_snaps",
     "amps_recc_set_xlate_shared", "amps_recc_push_raw_shared", "amps_recc_debug_xlate_shared",
+    "amps_recc_push_raw_shared_as", "amps_recc_push_raw_as", "amps_recc_debug_xlate_shared_as", "amps_recc_debug_xlate_as",
 )
+_XLATE_AS = ("amps_recc_push_raw_shared_as", "amps_recc_push_raw_as", "amps_recc_debug_xlate_shared_as", "amps_recc_debug_xlate_as")
 _XLATE_SHARED = ("amps_recc_set_xlate_shared", "amps_recc_push_raw_shared", "amps_recc_debug_xlate_shared")
 _POWER = ("amps_recc_channel_power", "amps_recc_burst_power", "amps_recc_power_ring_snaps")
 _NEW_IN_ABI4 = ("amps_recc_push_wideband_dist", "amps_recc_rccl_info", "amps_recc_rccl_abort", "amps_recc_rccl_set_timeout")
 DIST_BROADCAST, DIST_SCATTER_ALLGATHER = 0, 1
+# sample formats of the translate seams' _as entry points (AMPS_RECC_SAMPLES_*): the element dtype of a block, two per sample
+SAMPLES_FC32, SAMPLES_SC16, SAMPLES_SC8, SAMPLES_CU8 = 0, 1, 2, 3
+SAMPLE_DTYPES = {SAMPLES_FC32: np.dtype(np.float32), SAMPLES_SC16: np.dtype(np.int16), SAMPLES_SC8: np.dtype(np.int8), SAMPLES_CU8: np.dtype(np.uint8)}
 DIST_MODES = {"broadcast": DIST_BROADCAST, "scatter_allgather": DIST_SCATTER_ALLGATHER, 0: 0, 1: 1}
 
 _lib = None
@@ -207,12 +212,17 @@ def load():
         L.amps_recc_set_xlate_shared.argtypes = [vp, C.POINTER(XlateSharedCfg)]
         L.amps_recc_push_raw_shared.argtypes = [vp, vp, C.c_size_t, C.c_int]
         L.amps_recc_debug_xlate_shared.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    if hasattr(L, "amps_recc_push_raw_shared_as"):    # absent only from A/B builds of earlier revisions (AMPS_RECC_LIB)
+        L.amps_recc_push_raw_shared_as.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int]
+        L.amps_recc_push_raw_as.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int]
+        L.amps_recc_debug_xlate_shared_as.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.amps_recc_debug_xlate_as.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.amps_bch_encode_words.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp]
     L.amps_bch_decode_words.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, vp, vp]
     for name in EXPORTS:
         if name in ("amps_recc_default_slicer", "amps_recc_default_wideband_decim", "amps_recc_debug_exact_slice", "amps_recc_rccl_unique_id", "amps_recc_rccl_init",
                     "amps_recc_push_wideband_bcast", "amps_recc_drain_gather", "amps_recc_debug_slicer_bits",
-                    "amps_recc_push_wideband_short") + _NEW_IN_ABI4 + _POWER + _XLATE_SHARED and not hasattr(L, name):
+                    "amps_recc_push_wideband_short") + _NEW_IN_ABI4 + _POWER + _XLATE_SHARED + _XLATE_AS and not hasattr(L, name):
             continue
         if name not in ("amps_recc_strerror", "amps_recc_burst_size", "amps_recc_destroy"):   # every other entry point returns int
             getattr(L, name).restype = C.c_uint32 if name == "amps_recc_power_ring_snaps" else C.c_int
@@ -242,6 +252,62 @@ def _as_ptr(x, sync_torch=True):
         a = x.numpy()
         return _hostptr(a), MEM_HOST, a
     raise TypeError(type(x))
+
+
+def convert_samples(a, format):
+    """The DEFINITION of the translate seams' sample formats (include/amps_recc.h, AMPS_RECC_SAMPLES_*), in numpy: a block of
+    `format`'s dtype, shaped [..., n, 2] or [..., 2n], to complex64 [..., n] by the plain conversion, no scaling -- int16 / int8:
+    ((float)i, (float)q); uint8 (offset binary): ((float)i - 127.5, (float)q - 127.5); fc32: the float32 pairs (or complex64) as they
+    are.  Every value is exact in binary32.  Recc.push_raw_shared_as(a, format) IS Recc.push_raw_shared(convert_samples(a, format)),
+    and so for the other three _as calls.  A dtype that does not match the format is a TypeError, never a cast."""
+    if format not in SAMPLE_DTYPES:
+        raise ValueError("unknown sample format %r" % (format,))
+    if not isinstance(a, np.ndarray):
+        raise TypeError("convert_samples takes a numpy array, not %s" % type(a).__name__)
+    if format == SAMPLES_FC32 and a.dtype == np.complex64:
+        return a
+    if a.dtype != SAMPLE_DTYPES[format]:
+        raise TypeError("sample format %d takes %s samples, not %s" % (format, SAMPLE_DTYPES[format], a.dtype))
+    if a.ndim == 0 or (a.shape[-1] != 2 or a.ndim < 2) and a.shape[-1] % 2:
+        raise TypeError("samples are [..., n, 2] or [..., 2n], not %r" % (a.shape,))
+    pairs = a if a.ndim >= 2 and a.shape[-1] == 2 else a.reshape(a.shape[:-1] + (a.shape[-1] // 2, 2))
+    f = pairs.astype(np.float32)
+    if format == SAMPLES_CU8:
+        f -= np.float32(127.5)
+    return np.ascontiguousarray(f).view(np.complex64)[..., 0]
+
+
+def _typed_block(iq, format, rows, who):
+    """A block of `format` for an _as entry point -> (contiguous array or tensor, samples per row).  rows = None: one row, shaped
+    [n, 2] or [2n]; else [rows, n, 2] or [rows, 2n].  fc32 blocks may also be complex64 ([n] / [rows, n]).  Anything else is a TypeError."""
+    if format not in SAMPLE_DTYPES:
+        return iq, None                                   # the library answers -EINVAL: the binding does not second-guess it
+    want = SAMPLE_DTYPES[format]
+    if isinstance(iq, np.ndarray):
+        dt, is_complex = iq.dtype, iq.dtype == np.complex64
+    elif hasattr(iq, "data_ptr") and hasattr(iq, "is_cuda"):
+        import torch
+        if not iq.is_cuda:
+            raise TypeError("%s takes a numpy array or a CUDA tensor, not a tensor on %s" % (who, iq.device))
+        is_complex = iq.dtype == torch.complex64
+        dt = np.dtype(str(iq.dtype).replace("torch.", "")) if not iq.is_complex() else np.dtype(np.complex64)
+    else:
+        raise TypeError(type(iq))
+    if not (dt == want or (format == SAMPLES_FC32 and is_complex)):
+        raise TypeError("%s with sample format %d takes %s samples, not %s" % (who, format, want, dt))
+    shape = tuple(iq.shape)
+    lead = 0 if rows is None else 1
+    if rows is not None and (len(shape) < 2 or shape[0] != rows):
+        raise TypeError("%s takes %d rows, not shape %r" % (who, rows, shape))
+    if is_complex:
+        ok, n = len(shape) == lead + 1, shape[-1] if shape else 0
+    elif len(shape) == lead + 2 and shape[-1] == 2:
+        ok, n = True, shape[-2]
+    else:
+        ok, n = len(shape) == lead + 1 and shape[-1] % 2 == 0, (shape[-1] // 2 if shape else 0)
+    if not ok:
+        raise TypeError("%s takes shape %s[n, 2] or %s[2n], not %r" % (who, "[rows, " if lead else "", "[rows, " if lead else "", shape))
+    return (np.ascontiguousarray(iq) if isinstance(iq, np.ndarray) else iq.contiguous()), n
 
 
 class Recc:
@@ -435,6 +501,55 @@ class Recc:
         rc = load().amps_recc_debug_xlate_shared(self._h, ptr, n, mem, _hostptr(out), cap, C.byref(no))
         if rc:
             raise AmpsError(rc, "amps_recc_debug_xlate_shared")
+        return out[:, :no.value].copy()
+
+    # ---- translate seams on an SDR's integer samples (sc16, sc8, cu8), read in place: include/amps_recc.h, AMPS_RECC_SAMPLES_*
+    def push_raw_shared_as(self, iq, format):
+        """push_raw_shared on a block in `format` (SAMPLES_*): a numpy array of the format's dtype shaped [n, 2] or [2n] (staged as it
+        is) or a torch device tensor of that dtype (read in place).  By definition push_raw_shared(convert_samples(iq, format)); a
+        dtype that does not match the format is a TypeError, never a cast."""
+        iq, n = _typed_block(iq, format, None, "push_raw_shared_as")
+        ptr, mem, keep = _as_ptr(iq, self.sync_torch)
+        rc = load().amps_recc_push_raw_shared_as(self._h, ptr, n or 0, format, mem)
+        if rc:
+            raise AmpsError(rc, "amps_recc_push_raw_shared_as")
+
+    def debug_xlate_shared_as(self, iq, format):
+        """Shared translate stage only (test tap) on a block in `format`: [n, 2] or [2n] -> complex64 [C][nout]."""
+        iq, n = _typed_block(iq, format, None, "debug_xlate_shared_as")
+        n = n or 0
+        ptr, mem, keep = _as_ptr(iq)
+        cap = n + 8
+        out = np.zeros((self.n_channels, cap), np.complex64)
+        no = C.c_size_t(0)
+        rc = load().amps_recc_debug_xlate_shared_as(self._h, ptr, n, format, mem, _hostptr(out), cap, C.byref(no))
+        if rc:
+            raise AmpsError(rc, "amps_recc_debug_xlate_shared_as")
+        return out[:, :no.value].copy()
+
+    def push_raw_as(self, iq, format, nsamp=None):
+        """push_raw on rows in `format`: [C, n, 2] or [C, 2n] of the format's dtype, numpy or torch device tensor; the first nsamp
+        samples of each row (default: all n, the row pitch)."""
+        iq, ld = _typed_block(iq, format, self.n_channels, "push_raw_as")
+        ld = ld or 0
+        nsamp = ld if nsamp is None else nsamp
+        ptr, mem, keep = _as_ptr(iq, self.sync_torch)
+        rc = load().amps_recc_push_raw_as(self._h, ptr, ld, nsamp, format, mem)
+        if rc:
+            raise AmpsError(rc, "amps_recc_push_raw_as")
+
+    def debug_xlate_as(self, iq, format, nsamp=None):
+        """Translate stage only (test tap) on rows in `format`: [C, n, 2] or [C, 2n] -> complex64 [C][nout]."""
+        iq, ld = _typed_block(iq, format, self.n_channels, "debug_xlate_as")
+        ld = ld or 0
+        nsamp = ld if nsamp is None else nsamp
+        ptr, mem, keep = _as_ptr(iq)
+        cap = nsamp + 8
+        out = np.zeros((self.n_channels, cap), np.complex64)
+        no = C.c_size_t(0)
+        rc = load().amps_recc_debug_xlate_as(self._h, ptr, ld, nsamp, format, mem, _hostptr(out), cap, C.byref(no))
+        if rc:
+            raise AmpsError(rc, "amps_recc_debug_xlate_as")
         return out[:, :no.value].copy()
 
     def push_wideband(self, iq):

@@ -473,7 +473,7 @@ static int xlate_configure(amps_recc *h, bool shared, uint32_t decim, double rat
 }
 
 // run the translate stage on a block and hand its rows to the fused IQ seam
-static int xlate_push(amps_recc *h, const float *iq, size_t ld, size_t nsamp, int mem, const char *what)
+static int xlate_push(amps_recc *h, const void *iq, size_t ld, size_t nsamp, int format, int mem, const char *what)
 {
     HIP_TRY(hipSetDevice(h->device));
     const float2 *f = nullptr;
@@ -482,7 +482,7 @@ static int xlate_push(amps_recc *h, const float *iq, size_t ld, size_t nsamp, in
     int rc;
     {
         SpanGuard g(h->tm, h->stream.get(), h->chz.enabled, T_XLATE, nsamp);
-        rc = xlate_run(h->xl, (const float2 *)iq, ld, nsamp, mem, h->stream.get(), &f, &fld, &nout);
+        rc = xlate_run(h->xl, iq, ld, nsamp, format, mem, h->stream.get(), &f, &fld, &nout);
     }
     if (rc) return rc;
     if (int rc2 = debug_sync(h->stream.get(), what)) return rc2;
@@ -491,13 +491,13 @@ static int xlate_push(amps_recc *h, const float *iq, size_t ld, size_t nsamp, in
 }
 
 // test tap: run the translate stage alone and copy its rows out
-static int xlate_debug(amps_recc *h, const float *iq, size_t ld, size_t nsamp, int mem, float *out, size_t out_ld, size_t *nout)
+static int xlate_debug(amps_recc *h, const void *iq, size_t ld, size_t nsamp, int format, int mem, float *out, size_t out_ld, size_t *nout)
 {
     HIP_TRY(hipSetDevice(h->device));
     const float2 *f = nullptr;
     uint64_t fld = 0;
     uint32_t n = 0;
-    int rc = xlate_run(h->xl, (const float2 *)iq, ld, nsamp, mem, h->stream.get(), &f, &fld, &n);
+    int rc = xlate_run(h->xl, iq, ld, nsamp, format, mem, h->stream.get(), &f, &fld, &n);
     if (rc) return rc;
     *nout = n;
     return copy_rows_out(h, f, fld, n, out, out_ld);
@@ -514,21 +514,29 @@ int amps_recc_set_xlate(amps_recc_t *h, const amps_recc_xlate_cfg_t *x)
     return xlate_configure(h, false, x->decim, x->rate_hz, centers.data(), x->gain, x->cutoff_hz, x->width_hz);
 }
 
-int amps_recc_push_raw(amps_recc_t *h, const float *iq, size_t ld, size_t nsamp, int mem)
+// a sample format of the translate seams (AMPS_RECC_SAMPLES_*)
+static bool xlate_format_ok(int format) { return xlate_sample_bytes(format) != 0; }
+
+int amps_recc_push_raw_as(amps_recc_t *h, const void *iq, size_t ld, size_t nsamp, int format, int mem)
 {
-    if (!h) return -EINVAL;
+    if (!h || !xlate_format_ok(format)) return -EINVAL;
     if (!h->xl.enabled || h->xl.shared) return -ENOSYS;
     if (is_group_handle(h)) return -ENOSYS;
     if (nsamp == 0) return 0;
     if (!iq || ld < nsamp) return -EINVAL;
-    return xlate_push(h, iq, ld, nsamp, mem, "xlate");
+    return xlate_push(h, iq, ld, nsamp, format, mem, "xlate");
 }
+int amps_recc_push_raw(amps_recc_t *h, const float *iq, size_t ld, size_t nsamp, int mem) { return amps_recc_push_raw_as(h, iq, ld, nsamp, AMPS_RECC_SAMPLES_FC32, mem); }
 
+int amps_recc_debug_xlate_as(amps_recc_t *h, const void *iq, size_t ld, size_t nsamp, int format, int mem, float *out, size_t out_ld, size_t *nout)
+{
+    if (!h || !iq || !out || !nout || ld < nsamp || !xlate_format_ok(format)) return -EINVAL;
+    if (!h->xl.enabled || h->xl.shared) return -ENOSYS;
+    return xlate_debug(h, iq, ld, nsamp, format, mem, out, out_ld, nout);
+}
 int amps_recc_debug_xlate(amps_recc_t *h, const float *iq, size_t ld, size_t nsamp, int mem, float *out, size_t out_ld, size_t *nout)
 {
-    if (!h || !iq || !out || !nout || ld < nsamp) return -EINVAL;
-    if (!h->xl.enabled || h->xl.shared) return -ENOSYS;
-    return xlate_debug(h, iq, ld, nsamp, mem, out, out_ld, nout);
+    return amps_recc_debug_xlate_as(h, iq, ld, nsamp, AMPS_RECC_SAMPLES_FC32, mem, out, out_ld, nout);
 }
 
 int amps_recc_set_xlate_shared(amps_recc_t *h, const amps_recc_xlate_shared_cfg_t *x)
@@ -543,22 +551,27 @@ int amps_recc_set_xlate_shared(amps_recc_t *h, const amps_recc_xlate_shared_cfg_
     return xlate_configure(h, true, x->decim, x->rate_hz, x->center_hz, x->gain, x->cutoff_hz, x->width_hz);
 }
 
-int amps_recc_push_raw_shared(amps_recc_t *h, const float *iq, size_t nsamp, int mem)
+int amps_recc_push_raw_shared_as(amps_recc_t *h, const void *iq, size_t nsamp, int format, int mem)
 {
-    if (!h) return -EINVAL;
+    if (!h || !xlate_format_ok(format)) return -EINVAL;
     STALE_CHECK(h);
     if (!h->xl.enabled || !h->xl.shared) return -ENOSYS;
     if (is_group_handle(h)) return -ENOSYS;
     if (nsamp == 0) return 0;
     if (!iq) return -EINVAL;
-    return xlate_push(h, iq, nsamp, nsamp, mem, "xlate_shared");
+    return xlate_push(h, iq, nsamp, nsamp, format, mem, "xlate_shared");
 }
+int amps_recc_push_raw_shared(amps_recc_t *h, const float *iq, size_t nsamp, int mem) { return amps_recc_push_raw_shared_as(h, iq, nsamp, AMPS_RECC_SAMPLES_FC32, mem); }
 
+int amps_recc_debug_xlate_shared_as(amps_recc_t *h, const void *iq, size_t nsamp, int format, int mem, float *out, size_t out_ld, size_t *nout)
+{
+    if (!h || !iq || !out || !nout || !xlate_format_ok(format)) return -EINVAL;
+    if (!h->xl.enabled || !h->xl.shared) return -ENOSYS;
+    return xlate_debug(h, iq, nsamp, nsamp, format, mem, out, out_ld, nout);
+}
 int amps_recc_debug_xlate_shared(amps_recc_t *h, const float *iq, size_t nsamp, int mem, float *out, size_t out_ld, size_t *nout)
 {
-    if (!h || !iq || !out || !nout) return -EINVAL;
-    if (!h->xl.enabled || !h->xl.shared) return -ENOSYS;
-    return xlate_debug(h, iq, nsamp, nsamp, mem, out, out_ld, nout);
+    return amps_recc_debug_xlate_shared_as(h, iq, nsamp, AMPS_RECC_SAMPLES_FC32, mem, out, out_ld, nout);
 }
 
 int amps_recc_refchain_symbols(amps_recc_t *h, const float *iq, size_t ld, size_t nsamp, int mem,

@@ -39,7 +39,8 @@
 #include <cmath>
 #include <cstdint>
 #include <vector>
-#include "recc_channelizer.hip.h"   // cf2, cmul
+#include "amps_recc.h"              // AMPS_RECC_SAMPLES_*
+#include "recc_channelizer.hip.h"   // cf2, cmul, chz_sc16
 
 namespace amps {
 
@@ -47,8 +48,21 @@ constexpr int XL_TILE = 2048;        // input samples per workgroup (256 lanes x
 constexpr int XL_MAX_TAPS = 1024;    // padded tap count limit of xlate_fir_kernel
 constexpr int XLS_MAX_TAPS = 1280;   // padded tap count limit of xlate_shared_kernel
 
+// The block's sample types (include/amps_recc.h, AMPS_RECC_SAMPLES_*): float2 for fc32, and three PODs in the style of chz_sc16 for
+// the integer wire formats, read IN PLACE: one dword (sc16) or one 16-bit load (sc8, cu8) per lane and sample, consecutive lanes on
+// consecutive samples.  An integer form is DEFINED as the fc32 form on the plainly converted block, and every conversion below is
+// exact in binary32 (cu8: (float)i is exact and i - 127.5 has 9 significant bits), so converting where the sample is fetched --
+// xl_window, the one fetch of each kernel -- leaves every later operation on the bits it has in the fc32 form.
+using xl_sc16 = chz_sc16;
+struct alignas(2) xl_sc8 { int8_t x, y; };
+struct alignas(2) xl_cu8 { uint8_t x, y; };
+__device__ __forceinline__ float2 xl_cvt(float2 s) { return s; }
+__device__ __forceinline__ float2 xl_cvt(xl_sc16 s) { return make_float2((float)s.x, (float)s.y); }
+__device__ __forceinline__ float2 xl_cvt(xl_sc8 s) { return make_float2((float)s.x, (float)s.y); }
+__device__ __forceinline__ float2 xl_cvt(xl_cu8 s) { return make_float2((float)s.x - 127.5f, (float)s.y - 127.5f); }
+
 struct XlateArgs {
-    const float2 *block;     // [rows][ld_in] new samples; rows = C (per-row form) or 1 (shared form)
+    const void *block;       // [rows][ld_in] new samples of the kernel's sample type; rows = C (per-row form) or 1 (shared form)
     const float2 *carry;     // [rows][carry_cap]: hist samples of history, then the leftover (< D) unconsumed samples
     const float *taps;       // [ntp], zero padded to a multiple of 8
     const uint64_t *steps;   // [C]: center_hz[c] / rate_hz as a 0.64 fixed-point fraction of a turn
@@ -69,11 +83,12 @@ __device__ __forceinline__ cf2 xl_phasor(uint64_t turns)
     return (cf2){ cs, sn };
 }
 
-// sample v of one input row's virtual stream: its carry, then its block, zero beyond
-__device__ __forceinline__ float2 xl_window(const XlateArgs &a, const float2 *car, const float2 *blk, int64_t v)
+// sample v of one input row's virtual stream: its carry (fc32 whatever the pushes were), then its block converted, zero beyond
+template <typename T>
+__device__ __forceinline__ float2 xl_window(const XlateArgs &a, const float2 *car, const T *blk, int64_t v)
 {
     if (v < (int64_t)a.carry_len) return car[v];
-    if (v < (int64_t)a.carry_len + a.nsamp) return blk[v - a.carry_len];
+    if (v < (int64_t)a.carry_len + a.nsamp) return xl_cvt(blk[v - a.carry_len]);
     return make_float2(0.f, 0.f);
 }
 
@@ -111,7 +126,7 @@ __device__ __forceinline__ void xl_fir_store(const cf2 *zs, const float *hs, int
     }
 }
 
-template <int D>
+template <int D, typename T>
 __global__ __launch_bounds__(256) void xlate_fir_kernel(XlateArgs a)
 {
     __shared__ cf2 zs[xl_pad(XL_TILE + XL_MAX_TAPS) + 8];
@@ -121,7 +136,7 @@ __global__ __launch_bounds__(256) void xlate_fir_kernel(XlateArgs a)
     const uint32_t k0 = blockIdx.x * (XL_TILE / D);
     const int H = (int)a.hist;                                   // = ntp - 1
     const int ntp = (int)a.ntp;
-    const float2 *blk = a.block + (uint64_t)c * a.ld_in;
+    const T *blk = (const T *)a.block + (uint64_t)c * a.ld_in;
     const float2 *car = a.carry + (uint64_t)c * a.carry_cap;
     const int64_t v0 = (int64_t)D * k0;
     const uint64_t nabs0 = a.n_abs0 + (uint64_t)(v0 - H);        // wraps consistently for the (zero) pre-stream history
@@ -135,10 +150,10 @@ __global__ __launch_bounds__(256) void xlate_fir_kernel(XlateArgs a)
     xl_fir_store<D>(zs, hs, t, H, ntp, a.out + (uint64_t)c * a.ld_out, k0, a.nout);
 }
 
-template <int D>
+template <int D, typename T>
 __global__ __launch_bounds__(256) void xlate_shared_kernel(XlateArgs a)
 {
-    __shared__ float2 xs[XL_TILE + XLS_MAX_TAPS];                // the raw window, staged once
+    __shared__ float2 xs[XL_TILE + XLS_MAX_TAPS];                // the raw window, staged once (fc32 for every sample type)
     __shared__ cf2 zs[xl_pad(XL_TILE + XLS_MAX_TAPS) + 8];       // the window mixed for the channel in hand
     __shared__ float hs[XLS_MAX_TAPS];
     static_assert(sizeof(float2) * (XL_TILE + XLS_MAX_TAPS) + sizeof(cf2) * (xl_pad(XL_TILE + XLS_MAX_TAPS) + 8) + sizeof(float) * XLS_MAX_TAPS <= 65536,
@@ -152,7 +167,7 @@ __global__ __launch_bounds__(256) void xlate_shared_kernel(XlateArgs a)
 
     for (int i = t; i < ntp; i += 256) hs[i] = a.taps[i];
     // stage: tile-local sample n <-> virtual index v = D*k0 + n;  lane t takes n = t, t+256, ...
-    for (int n = t; n < XL_TILE + H; n += 256) xs[n] = xl_window(a, a.carry, a.block, v0 + n);
+    for (int n = t; n < XL_TILE + H; n += 256) xs[n] = xl_window(a, a.carry, (const T *)a.block, v0 + n);
     __syncthreads();
 
     const uint32_t c_end = min(a.C, (blockIdx.y + 1) * a.cpg);
@@ -165,27 +180,62 @@ __global__ __launch_bounds__(256) void xlate_shared_kernel(XlateArgs a)
     }
 }
 
-// carry_out[r][i] = virtual[r][consumed + i], i < new_len  (separate buffers: the ranges can overlap)
-__global__ void xlate_carry_kernel(const float2 *block, uint64_t ld_in, const float2 *carry_in, float2 *carry_out,
+// carry_out[r][i] = virtual[r][consumed + i], i < new_len  (separate buffers: the ranges can overlap).  The carry is fc32: the samples
+// taken from the block are converted here, which is what lets the sample type change from one push to the next.
+template <typename T>
+__global__ void xlate_carry_kernel(const void *block, uint64_t ld_in, const float2 *carry_in, float2 *carry_out,
                                    uint32_t carry_cap, uint32_t carry_len, uint32_t consumed, uint32_t new_len)
 {
     const uint32_t c = blockIdx.y;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= new_len) return;
     const uint64_t v = (uint64_t)consumed + i;
-    carry_out[(uint64_t)c * carry_cap + i] = v < carry_len ? carry_in[(uint64_t)c * carry_cap + v] : block[(uint64_t)c * ld_in + (v - carry_len)];
+    carry_out[(uint64_t)c * carry_cap + i] = v < carry_len ? carry_in[(uint64_t)c * carry_cap + v] : xl_cvt(((const T *)block)[(uint64_t)c * ld_in + (v - carry_len)]);
 }
 
 // What the two forms differ in on the host: the kernel for a decimation (none: the form does not have it) and the padded tap limit.
+// What the sample formats differ in: the kernels' sample type, its size, and nothing else.
 typedef void (*xlate_kernel_t)(XlateArgs);
-inline xlate_kernel_t xlate_kernel_for(bool shared, uint32_t D)
+typedef void (*xlate_carry_kernel_t)(const void *, uint64_t, const float2 *, float2 *, uint32_t, uint32_t, uint32_t, uint32_t);
+template <typename T> inline xlate_kernel_t xlate_kernel_of(bool shared, uint32_t D)
 {
     switch (D) {
-    case 1: return shared ? xlate_shared_kernel<1> : xlate_fir_kernel<1>;
-    case 2: return shared ? xlate_shared_kernel<2> : xlate_fir_kernel<2>;
-    case 4: return shared ? xlate_shared_kernel<4> : xlate_fir_kernel<4>;
-    case 8: return shared ? xlate_shared_kernel<8> : nullptr;
+    case 1: return shared ? xlate_shared_kernel<1, T> : xlate_fir_kernel<1, T>;
+    case 2: return shared ? xlate_shared_kernel<2, T> : xlate_fir_kernel<2, T>;
+    case 4: return shared ? xlate_shared_kernel<4, T> : xlate_fir_kernel<4, T>;
+    case 8: return shared ? xlate_shared_kernel<8, T> : nullptr;
     default: return nullptr;
+    }
+}
+inline xlate_kernel_t xlate_kernel_for(bool shared, uint32_t D, int format = AMPS_RECC_SAMPLES_FC32)
+{
+    switch (format) {
+    case AMPS_RECC_SAMPLES_FC32: return xlate_kernel_of<float2>(shared, D);
+    case AMPS_RECC_SAMPLES_SC16: return xlate_kernel_of<xl_sc16>(shared, D);
+    case AMPS_RECC_SAMPLES_SC8: return xlate_kernel_of<xl_sc8>(shared, D);
+    case AMPS_RECC_SAMPLES_CU8: return xlate_kernel_of<xl_cu8>(shared, D);
+    default: return nullptr;
+    }
+}
+inline xlate_carry_kernel_t xlate_carry_kernel_for(int format)
+{
+    switch (format) {
+    case AMPS_RECC_SAMPLES_FC32: return xlate_carry_kernel<float2>;
+    case AMPS_RECC_SAMPLES_SC16: return xlate_carry_kernel<xl_sc16>;
+    case AMPS_RECC_SAMPLES_SC8: return xlate_carry_kernel<xl_sc8>;
+    case AMPS_RECC_SAMPLES_CU8: return xlate_carry_kernel<xl_cu8>;
+    default: return nullptr;
+    }
+}
+// bytes of one sample of a format; 0: no such format
+inline size_t xlate_sample_bytes(int format)
+{
+    switch (format) {
+    case AMPS_RECC_SAMPLES_FC32: return sizeof(float2);
+    case AMPS_RECC_SAMPLES_SC16: return sizeof(xl_sc16);
+    case AMPS_RECC_SAMPLES_SC8: return sizeof(xl_sc8);
+    case AMPS_RECC_SAMPLES_CU8: return sizeof(xl_cu8);
+    default: return 0;
     }
 }
 inline uint32_t xlate_max_taps(bool shared) { return shared ? XLS_MAX_TAPS : XL_MAX_TAPS; }
@@ -272,17 +322,24 @@ inline uint32_t xlate_shared_cpg(uint32_t C, uint64_t tiles)
     return (uint32_t)((C + groups - 1) / groups);
 }
 
-// filter nsamp new samples per input row ([rows][ld], host or device); *out_iq is [C][*out_ld] device memory holding *nout samples per row
-inline int xlate_run(XlateState &x, const float2 *iq, uint64_t ld, size_t nsamp, int mem, hipStream_t s,
+// filter nsamp new samples per input row ([rows][ld] samples of `format`, host or device, read as they are); *out_iq is [C][*out_ld]
+// device memory holding *nout samples per row
+inline int xlate_run(XlateState &x, const void *iq, uint64_t ld, size_t nsamp, int format, int mem, hipStream_t s,
                      const float2 **out_iq, uint64_t *out_ld, uint32_t *nout)
 {
     *out_iq = x.out.get(); *out_ld = x.max_out; *nout = 0;
+    const size_t sz = xlate_sample_bytes(format);
+    if (!sz) return -EINVAL;
     if (!x.enabled) return -ENOSYS;
     if (nsamp == 0) return 0;
     if (nsamp > (size_t)x.D * x.max_out) return -E2BIG;
-    const float2 *d = iq;
+    const void *d = iq;
     if (mem == AMPS_MEM_HOST) {
-        if (int rc = x.stage.stage(iq, ld, nsamp, x.rows, (size_t)x.rows * x.D * x.max_out, &d, &ld)) return rc;
+        // the block travels in its own format, staged by the byte; the reserve is that of the largest fc32 block, which covers them all
+        const uint8_t *db = nullptr;
+        uint64_t ld_bytes = 0;
+        if (int rc = x.stage.stage((const uint8_t *)iq, ld * sz, nsamp * sz, x.rows, sizeof(float2) * x.rows * x.D * x.max_out, &db, &ld_bytes)) return rc;
+        d = db; ld = nsamp;
     }
     const uint64_t avail = (uint64_t)(x.carry_len - x.hist) + nsamp;
     const uint64_t n_out = avail / x.D;
@@ -294,11 +351,11 @@ inline int xlate_run(XlateState &x, const float2 *iq, uint64_t ld, size_t nsamp,
     if (n_out) {
         const uint64_t tiles = (n_out * x.D + XL_TILE - 1) / XL_TILE;
         a.cpg = x.shared ? xlate_shared_cpg(x.C, tiles) : 1;     // per-row form: a workgroup per (tile, row)
-        hipLaunchKernelGGL(xlate_kernel_for(x.shared, x.D), dim3((uint32_t)tiles, (x.C + a.cpg - 1) / a.cpg), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(xlate_kernel_for(x.shared, x.D, format), dim3((uint32_t)tiles, (x.C + a.cpg - 1) / a.cpg), dim3(256), 0, s, a);
     }
     const uint32_t consumed = (uint32_t)(n_out * x.D);
     const uint32_t new_len = x.hist + (uint32_t)(avail - (uint64_t)consumed);
-    hipLaunchKernelGGL(xlate_carry_kernel, dim3((new_len + 255) / 256, x.rows), dim3(256), 0, s, d, ld, x.carry[x.cur].get(), x.carry[x.cur ^ 1].get(),
+    hipLaunchKernelGGL(xlate_carry_kernel_for(format), dim3((new_len + 255) / 256, x.rows), dim3(256), 0, s, d, ld, x.carry[x.cur].get(), x.carry[x.cur ^ 1].get(),
                        x.carry_cap, x.carry_len, consumed, new_len);
     if (hipGetLastError() != hipSuccess) return -EIO;
     if (mem == AMPS_MEM_HOST) { if (int rc = x.stage.arm(s)) return rc; }

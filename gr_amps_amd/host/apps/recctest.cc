@@ -22,7 +22,9 @@
 //   recctest sub  <file.raw> <chunk> <rate_hz> <decim> <c0,c1,...>   one narrowband fc32 capture at rate_hz holding several channels -> gr::amps::recc_subband
 //                                      (the channel filter per centre c0, c1, ... in Hz relative to the capture's centre, decimation `decim`, 10 samples
 //                                      per symbol behind it); prints for every record what `wide` prints: its channel (the index into the list), then
-//                                      its lines, decoded through the "bursts" port
+//                                      its lines, decoded through the "bursts" port.  The file's extension gives its sample format: .sc16 is
+//                                      interleaved int16, .sc8 / .cs8 int8, .cu8 offset-binary uint8 (what USRP-class, HackRF and RTL-SDR tools
+//                                      write), read as they are through the block's input format; anything else is fc32
 // Every message published on recc_decode's output ports is printed as one text line, which is what
 // tests/test_gpu_host_blocks.py compares with the oracle.
 #include <amps/recc.h>
@@ -197,7 +199,12 @@ int main(int argc, char **argv)
                 if (end == p) { std::fprintf(stderr, "%s: bad list of centres\n", argv[6]); return 2; }
                 p = *end == ',' ? end + 1 : end;
             }
-            auto src = gr::amps::recc_subband::make(std::atof(argv[4]), centers, std::atoi(argv[5]));
+            const std::string path = argv[2];
+            const size_t dot = path.rfind('.');
+            const std::string ext = dot == std::string::npos ? "" : path.substr(dot);
+            const int format = ext == ".sc16" ? 1 : ext == ".sc8" || ext == ".cs8" ? 2 : ext == ".cu8" ? 3 : 0;   // AMPS_RECC_SAMPLES_*
+            const size_t item = format == 0 ? 8 : format == 1 ? 4 : 2;   // bytes per sample
+            auto src = gr::amps::recc_subband::make(std::atof(argv[4]), centers, std::atoi(argv[5]), 10, -1, 0.0, 0.0, format);
             struct demux : gr::block {
                 std::shared_ptr<gr::basic_block> dec;
                 demux() : gr::block("demux", gr::io_signature::make(0, 0, 0), gr::io_signature::make(0, 0, 0))
@@ -213,10 +220,10 @@ int main(int argc, char **argv)
             auto dm = std::make_shared<demux>();
             dm->dec = dec;
             gr::msg_connect(src, "bursts", dm, "bursts");
-            const size_t ns = data.size() / 8;
+            const size_t ns = data.size() / item;
             for (size_t off = 0; off < ns; off += (size_t)chunk) {
                 int n = (int)std::min<size_t>((size_t)chunk, ns - off);
-                gr_vector_const_void_star ins = { data.data() + 8 * off };
+                gr_vector_const_void_star ins = { data.data() + item * off };
                 if (src->work(n, ins, outs) != 0) return 1;
             }
         } else if (mode == "syms") {

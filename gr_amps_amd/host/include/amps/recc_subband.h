@@ -1,5 +1,6 @@
 // gr::amps::recc_subband -- NEW block type (not in the reference): many 30 kHz channels of ONE narrowband stream in one block.
-// Input: ONE gr_complex stream at rate_hz (a few hundred ksps to 1.6 Msps: one modest SDR tuned to a system's control channels);
+// Input: ONE gr_complex stream at rate_hz (a few hundred ksps to 1.6 Msps: one modest SDR tuned to a system's control channels), or
+// with input_format the SDR's own integer items;
 // the block runs, for every centre of centers_hz, the flow graph's channel filter freq_xlating_fir_filter_ccc(decim,
 // firdes.low_pass(3, rate, cutoff, width), centre, rate) (grc/recctest.grc:889-937, taps :115-155) and the fused chain behind it
 // on the MI355X -- amps_recc_set_xlate_shared / amps_recc_push_raw_shared: all channels in one launch per stage -- and stands
@@ -21,8 +22,12 @@ public:
     // rate_hz / decim must be samples_per_symbol x 20 kHz; decim: 1, 2, 4 or 8
     // slicer: -1 = the library default, 0 .. 3 = numeric spec A .. D (include/amps_recc_numerics.h)
     // cutoff_hz / width_hz: 0 = the flow graph's 10 kHz / 4.5 kHz
+    // input_format: AMPS_RECC_SAMPLES_* of include/amps_recc.h.  0 = one gr_complex per item; 1 (sc16) = two shorts, what a UHD source set
+    //         to sc16 or an "interleaved short" file source delivers; 2 (sc8) = two signed bytes (HackRF); 3 (cu8) = two offset-binary
+    //         unsigned bytes (RTL-SDR).  The block pushes the items as they are (amps_recc_push_raw_shared_as: 4 or 2 bytes per sample
+    //         to the device, no float copy on the host); the records are those of the plainly converted stream.
     static sptr make(double rate_hz, const std::vector<double> &centers_hz, int decim = 4, int samples_per_symbol = 10, int slicer = -1,
-                     double cutoff_hz = 0.0, double width_hz = 0.0);
+                     double cutoff_hz = 0.0, double width_hz = 0.0, int input_format = 0);
 };
 
 } // namespace amps

@@ -1,5 +1,6 @@
 // recc_subband_impl.cc -- gr::amps::recc_subband: one narrowband complex stream in, (channel, burst) and (channel, record) pairs out.
 #include <amps/recc_subband.h>
+#include <algorithm>
 #include <cerrno>
 #include <cstdio>
 #include <stdexcept>
@@ -13,16 +14,24 @@ namespace amps {
 class recc_subband_impl : public recc_subband {
     amps_recc_t *d_handle;
     int d_decim;
+    int d_format;                                  // AMPS_RECC_SAMPLES_*: what one input item holds
     std::vector<amps_recc_burst_t> d_recs;
     std::vector<unsigned char> d_bursts;
     static const int kMaxOut = 1 << 18;            // channel-rate samples per push: 1.3 s at 200 ksps
     static const int kMaxRecs = 1024;
+    // bytes of one input item: two floats, two shorts or two bytes; 0 = no such format
+    static size_t item_size(int format)
+    {
+        return format == AMPS_RECC_SAMPLES_FC32 ? 2 * sizeof(float) : format == AMPS_RECC_SAMPLES_SC16 ? 2 * sizeof(short)
+             : format == AMPS_RECC_SAMPLES_SC8 || format == AMPS_RECC_SAMPLES_CU8 ? 2 : 0;
+    }
 
 public:
-    recc_subband_impl(double rate_hz, const std::vector<double> &centers_hz, int decim, int sps, int slicer, double cutoff_hz, double width_hz)
-        : gr::sync_block("recc_subband", gr::io_signature::make(1, 1, 2 * sizeof(float)), gr::io_signature::make(0, 0, 0)),
-          d_handle(nullptr), d_decim(decim), d_recs(kMaxRecs), d_bursts((size_t)kMaxRecs * AMPS_RECC_CAPTURE_SYMS)
+    recc_subband_impl(double rate_hz, const std::vector<double> &centers_hz, int decim, int sps, int slicer, double cutoff_hz, double width_hz, int input_format)
+        : gr::sync_block("recc_subband", gr::io_signature::make(1, 1, (int)std::max<size_t>(item_size(input_format), 1)), gr::io_signature::make(0, 0, 0)),
+          d_handle(nullptr), d_decim(decim), d_format(input_format), d_recs(kMaxRecs), d_bursts((size_t)kMaxRecs * AMPS_RECC_CAPTURE_SYMS)
     {
+        if (!item_size(input_format)) throw std::runtime_error("amps::recc_subband: input_format must be 0 (fc32), 1 (sc16), 2 (sc8) or 3 (cu8)");
         if (centers_hz.empty()) throw std::runtime_error("amps::recc_subband: no centres");
         if (decim < 1) throw std::runtime_error("amps::recc_subband: decim must be 1, 2, 4 or 8");
         amps_recc_cfg_t cfg = {};
@@ -56,13 +65,14 @@ public:
 
     int work(int noutput_items, gr_vector_const_void_star &input_items, gr_vector_void_star &)
     {
-        const float *in = (const float *)input_items[0];
+        const unsigned char *in = (const unsigned char *)input_items[0];
+        const size_t item = item_size(d_format);
         const int max_push = (kMaxOut - 1) * d_decim;          // a leftover sample of the last push may complete one more output
         int done = 0;
         while (done < noutput_items) {
             int n = noutput_items - done;
             if (n > max_push) n = max_push;
-            int rc = amps_recc_push_raw_shared(d_handle, in + 2 * (size_t)done, (size_t)n, AMPS_MEM_HOST);
+            int rc = amps_recc_push_raw_shared_as(d_handle, in + item * (size_t)done, (size_t)n, d_format, AMPS_MEM_HOST);
             if (rc != 0) { std::fprintf(stderr, "amps::recc_subband: %s\n", amps_recc_strerror(rc)); return WORK_DONE; }
             size_t nrec = 0;
             rc = amps_recc_drain_bursts(d_handle, d_recs.data(), d_bursts.data(), kMaxRecs, &nrec);
@@ -83,9 +93,9 @@ public:
 };
 
 recc_subband::sptr recc_subband::make(double rate_hz, const std::vector<double> &centers_hz, int decim, int samples_per_symbol, int slicer,
-                                      double cutoff_hz, double width_hz)
+                                      double cutoff_hz, double width_hz, int input_format)
 {
-    return gnuradio::get_initial_sptr(new recc_subband_impl(rate_hz, centers_hz, decim, samples_per_symbol, slicer, cutoff_hz, width_hz));
+    return gnuradio::get_initial_sptr(new recc_subband_impl(rate_hz, centers_hz, decim, samples_per_symbol, slicer, cutoff_hz, width_hz, input_format));
 }
 
 } // namespace amps

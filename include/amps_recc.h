@@ -47,7 +47,9 @@ extern "C" {
                                      still 4, three entry points and a flag added and nothing changed: amps_recc_channel_power / _burst_power /
                                      _power_ring_snaps behind AMPS_RECC_FLAG_CHANNEL_POWER;
                                      still 4, three entry points added and nothing changed: amps_recc_set_xlate_shared / _push_raw_shared /
-                                     _debug_xlate_shared, many channels of one shared narrowband stream) */
+                                     _debug_xlate_shared, many channels of one shared narrowband stream;
+                                     still 4, four entry points added and nothing changed: amps_recc_push_raw_shared_as / _push_raw_as /
+                                     _debug_xlate_shared_as / _debug_xlate_as, the translate seams on an SDR's integer samples (AMPS_RECC_SAMPLES_*)) */
 
 /* protocol constants of the reference */
 #define AMPS_RECC_TRIGGER_SYMS 74   /* lib/recc_impl.cc:76-77: 37 bits x 2 Manchester symbols   */
@@ -275,7 +277,8 @@ int amps_recc_push_wideband(amps_recc_t *h, const float *iq, size_t nsamp, int m
  * device blocks, nsamp == 0 returns 0.  The two calls may be mixed freely on one handle, push by push.  A device block need only be
  * 4-byte aligned (a slice that starts at an odd sample is legal).  The fused filter bank reads the 16-bit block in place, 4 bytes
  * per sample from the host and from HBM; no fc32 copy of it exists (the checking form AMPS_RECC_FLAG_UNFUSED_WIDEBAND expands it first).
- * Not offered in 16 bits: amps_recc_push_wideband_dist / _bcast (the blocks RCCL carries stay fc32) and the IQ and translate seams. */
+ * Not offered in 16 bits: amps_recc_push_wideband_dist / _bcast (the blocks RCCL carries stay fc32) and the IQ seam, whose callers have
+ * already filtered in float.  The translate seams take 16-bit and 8-bit samples through their _as entry points (AMPS_RECC_SAMPLES_*). */
 int amps_recc_push_wideband_short(amps_recc_t *h, const int16_t *iq, size_t nsamp, int mem);
 
 /* translate seam: the channel filter the reference's test flow graph wires in front of the
@@ -335,6 +338,29 @@ int amps_recc_push_raw_shared(amps_recc_t *h, const float *iq, size_t nsamp, int
 /* test tap: run only the shared translate stage (continuing its stream); out is host [n_channels][out_ld] fc32 */
 int amps_recc_debug_xlate_shared(amps_recc_t *h, const float *iq, size_t nsamp, int mem,
                                  float *out, size_t out_ld, size_t *nout);
+
+/* translate seams on an SDR's integer samples, read IN PLACE.  No SDR delivers fc32: USRP-class devices, Lime and Pluto deliver
+ * interleaved int16 ("sc16"), HackRF int8 ("sc8"), RTL-SDR offset-binary uint8 ("cu8"), and their capture files hold the same. */
+#define AMPS_RECC_SAMPLES_FC32 0   /* float I, float Q: what the plain entry points take            */
+#define AMPS_RECC_SAMPLES_SC16 1   /* int16 I, int16 Q:  sample = ((float)i, (float)q)               */
+#define AMPS_RECC_SAMPLES_SC8  2   /* int8  I, int8  Q:  sample = ((float)i, (float)q)               */
+#define AMPS_RECC_SAMPLES_CU8  3   /* uint8 I, uint8 Q, offset binary: ((float)i - 127.5f, (float)q - 127.5f) */
+/* DEFINITION.  Each _as call is the fc32 call of the same name (amps_recc_push_raw_shared, _push_raw, _debug_xlate_shared,
+ * _debug_xlate) on the block converted by the plain conversion above, no scaling.  Every conversion is exact in binary32, so the
+ * result is the same stream, the same carry, the same output bits from the stage, the same records and the same error codes.
+ * format == AMPS_RECC_SAMPLES_FC32 IS the fc32 call; an unknown format is -EINVAL.  Formats may be mixed freely on one handle, push
+ * by push, with each other and with the fc32 entry points (the stage's carry is fc32).  ld and nsamp count SAMPLES, whatever their
+ * size.  A device block need only be aligned to one sample: 4 bytes for sc16, 2 bytes for sc8 and cu8 (a slice that starts at an odd
+ * sample is legal).  Every other error, nsamp == 0, and the ownership rules for host and device blocks are those of the fc32 calls.
+ * The block is read in its own format by the stage's kernels -- 4 or 2 bytes per sample over the host link and from HBM; no fc32
+ * copy of it exists on the host or on the device.
+ * No scaling and no DC removal are offered: the stage is linear, so the filter's `gain` is the place for a scale, and a tuner's DC
+ * lands on centre 0, where no control channel sits.
+ * Not offered in integer formats: amps_recc_push_iq, 8-bit input on the wideband seam, the distributed pushes. */
+int amps_recc_push_raw_shared_as(amps_recc_t *h, const void *iq, size_t nsamp, int format, int mem);
+int amps_recc_push_raw_as(amps_recc_t *h, const void *iq, size_t ld, size_t nsamp, int format, int mem);
+int amps_recc_debug_xlate_shared_as(amps_recc_t *h, const void *iq, size_t nsamp, int format, int mem, float *out, size_t out_ld, size_t *nout);
+int amps_recc_debug_xlate_as(amps_recc_t *h, const void *iq, size_t ld, size_t nsamp, int format, int mem, float *out, size_t out_ld, size_t *nout);
 
 /* Reference-timing seam (checking mode): the flow graph's OWN sub-chain in front of amps_recc, computed on the device as GNU
  * Radio 3.7 defines it -- analog.quadrature_demod_cf(1) -> digital.clock_recovery_mm_ff(omega 10, gain_omega .25*.175^2*3,
