@@ -138,7 +138,6 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
     const bool wide768 = cfg->wideband_channels && cfg->wideband_decim == (uint32_t)CHZ_D768;
     if (cfg->max_samples_per_push && !(wide768 ? cfg->samples_per_symbol == 2 : sps_supported(cfg->samples_per_symbol))) return -EINVAL;
     if (cfg->wideband_channels && (cfg->samples_per_symbol != (wide768 ? 2u : 3u) || cfg->max_samples_per_push == 0)) return -EINVAL;
-    if (wide768 && search_form(true, false, 2) == SEARCH_FRONT_BITS) return -EINVAL;   // AMPS_RECC_BITS_KERNEL=front: the streaming kernel's bit-domain mode is built for 3 samples per symbol
     if (cfg->sync_tolerance > AMPS_RECC_MAX_SYNC_TOLERANCE) return -EINVAL;
     const uint32_t sl = cfg->flags & (AMPS_RECC_FLAG_SLICER_PRODUCT | AMPS_RECC_FLAG_SLICER_SINE | AMPS_RECC_FLAG_SLICER_ATAN | AMPS_RECC_FLAG_SLICER_EXACT);
     if (sl & (sl - 1)) return -EINVAL;                             // at most one slicer spec

@@ -1,10 +1,10 @@
 // recc_bits.hip.h -- bit-domain trigger correlator behind the fused channelizer (wideband seam; exact match, or at most
 // cfg.sync_tolerance wrong symbols with TOL = true).
 //
-// chz_fused_kernel leaves only slicer bits in HBM (1 bit per channel sample).  recc_front_kernel<SPS,1,BITS=true> can
-// search them, but it inherits the IQ kernel's layout -- four lanes share one dword of positions, 512 positions per wave
-// iteration -- and spends ~9 lane-instructions per position on what is a handful of funnel shifts.  Here a lane owns 32
-// consecutive positions outright: it reads its own dword and the K = ceil(SPS*73/32) dwords before it (from a small LDS
+// chz_fused_kernel leaves only slicer bits in HBM (1 bit per channel sample).  The streaming kernel of the IQ seam used to
+// have a mode that searched them (round 2, since retired), but it inherited that kernel's layout -- four lanes share one
+// dword of positions, 512 positions per wave iteration -- and spent ~9 lane-instructions per position on what is a handful
+// of funnel shifts.  Here a lane owns 32 consecutive positions outright: it reads its own dword and the K = ceil(SPS*73/32) dwords before it (from a small LDS
 // window that the wave fills with ONE coalesced load per 2048 positions), and every trigger tap is one v_alignbit plus
 // one and/andn2 with compile-time shift and polarity.  16 taps of the word-sync part prefilter (noise passes with
 // probability 2^-16 per position); the other 58 run behind a wave-uniform branch.

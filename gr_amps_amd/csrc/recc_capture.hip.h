@@ -1,7 +1,8 @@
 // recc_capture.hip.h -- host side of the capture seam: the trigger search and the resolve / capture / decode tail behind both the IQ
-// seam (streaming kernel on channel-major IQ, recc_front.hip.h) and the wideband seam (slicer bits already in the ring,
-// recc_bits.hip.h or the search stage of the resolve kernel, recc_resolve.hip.h).  One state: the buffers, the launch geometry fixed
-// at create, and the position in the stream.  Records go to the handle's record lists (recc_records.hip.h).
+// seam (streaming kernel on channel-major IQ, recc_front.hip.h) and the wideband seam (slicer bits already in the ring: the search
+// stage of the resolve kernel, recc_resolve.hip.h, or the same search as a launch of its own, recc_bits.hip.h).  One state: the
+// buffers, the launch geometry fixed at create, and the position in the stream.  Records go to the handle's record lists
+// (recc_records.hip.h).
 #pragma once
 #include "recc_resolve.hip.h"
 #include "recc_records.hip.h"
@@ -26,7 +27,7 @@ struct CaptureState {
     // launch geometry
     uint32_t ring_words = 0;
     uint32_t max_waves = 0, max_chunks = 0, det_cap = 0;   // front-launch geometry bounds (see front_geometry)
-    uint32_t max_waves_bits = 0;                           // the same for the bit-domain kernel (more waves fit: 72 VGPRs, 2 KB LDS)
+    uint32_t max_waves_bits = 0;                           // the same for the bit-domain search kernel (more waves fit: it holds no samples)
     // position in the stream
     int carry_cur = 0;
     uint64_t n_done = 0, origin = 0;  // origin: absolute index of the stream's first sample (amps_recc_set_origin)
@@ -60,7 +61,7 @@ typedef void (*front_kernel_t)(FrontArgs);
 template <int SPS, int SL> front_kernel_t front_kernel_of(bool tol)
 {
     constexpr int DEPTH = (SL == AMPS_SLICER_ATAN_BOXCAR || SL == AMPS_SLICER_EXACT) ? 1 : 2;
-    return tol ? recc_front_kernel<SPS, 1, false, true, SL> : recc_front_kernel<SPS, DEPTH, false, false, SL>;
+    return tol ? recc_front_kernel<SPS, 1, true, SL> : recc_front_kernel<SPS, DEPTH, false, SL>;
 }
 template <int SPS> front_kernel_t front_kernel_of(int slicer, bool tol)
 {
@@ -84,24 +85,20 @@ inline front_kernel_t front_kernel_for(uint32_t sps, int slicer, bool tol)
 }
 inline bool sps_supported(uint32_t sps) { return sps != 2 && front_kernel_for(sps, AMPS_SLICER_DEFAULT, false) != nullptr; }
 
-// Which form the wideband seam's trigger search takes.  AMPS_RECC_BITS_KERNEL (read here and nowhere else): a first letter f =
-// FRONT_BITS, the bit-domain mode of the streaming kernel, recc_front_kernel<3, 1, BITS> -- an independent implementation of the same
-// search: the two must agree; exactly "separate" = BITS_KERNEL, the search as its own launch (recc_bits_kernel, rounds 2-5) instead of
-// the search stage inside the resolve kernel -- an independent launch structure the GPU suite checks the default against.  The search
-// stage inside the resolve kernel serves the many-channel form (no capture queue) at the wideband seam's two rates.
-enum SearchForm { SEARCH_IN_RESOLVE, SEARCH_BITS_KERNEL, SEARCH_FRONT_BITS };
-inline SearchForm search_form(bool wideband, bool queue, uint32_t sps)
+// Which of its two forms the wideband seam's trigger search takes: true = the search stage inside the resolve kernel, which serves
+// the many-channel form (no capture queue) at the wideband seam's two rates; false = the search as a launch of its own in front of it
+// (recc_bits_kernel, rounds 2-5).  AMPS_RECC_BITS_KERNEL (read here and nowhere else) set to exactly "separate" asks for the second
+// everywhere -- an independent launch structure the GPU suite checks the default against; any other value means the default.
+inline bool search_in_resolve(bool wideband, bool queue, uint32_t sps)
 {
-    if (env_is("AMPS_RECC_BITS_KERNEL", [](const char *v) { return v[0] == 'f'; })) return SEARCH_FRONT_BITS;
     const bool separate = env_is("AMPS_RECC_BITS_KERNEL", [](const char *v) { return std::strcmp(v, "separate") == 0; });
-    return wideband && !queue && !separate && (sps == 2 || sps == 3) ? SEARCH_IN_RESOLVE : SEARCH_BITS_KERNEL;
+    return wideband && !queue && !separate && (sps == 2 || sps == 3);
 }
 
-// The bit-domain search kernel for (search form, samples per symbol, tolerant sync): capture_run_bits launches it, and capture_create
-// sizes max_waves_bits by its occupancy.
-inline front_kernel_t bits_kernel_for(SearchForm form, uint32_t sps, bool tol)
+// The bit-domain search kernel for (samples per symbol, tolerant sync): capture_run_bits launches it, and capture_create sizes
+// max_waves_bits by its occupancy.
+inline front_kernel_t bits_kernel_for(uint32_t sps, bool tol)
 {
-    if (form == SEARCH_FRONT_BITS) return tol ? recc_front_kernel<3, 1, true, true> : recc_front_kernel<3, 1, true>;
     if (sps == 2) return tol ? recc_bits_kernel<2, true> : recc_bits_kernel<2, false>;
     return tol ? recc_bits_kernel<3, true> : recc_bits_kernel<3, false>;
 }
@@ -146,7 +143,7 @@ inline int capture_create(CaptureState &c, const amps_recc_cfg_t &cfg, uint32_t 
     const uint32_t cu_waves = (uint32_t)prop.multiProcessorCount * 4u;
     c.max_waves = cu_waves * blocks_per_cu(front_kernel_for(c.sps, slicer, c.tol != 0), 2);   // exactly one resident round of the kernel capture_run_iq will pick
     // (max_chunks below assumes at most 32 waves per CU)
-    c.max_waves_bits = cu_waves * std::min(blocks_per_cu(bits_kernel_for(search_form(wideband, queue, c.sps), c.sps, c.tol != 0), 4), 8u);
+    c.max_waves_bits = cu_waves * std::min(blocks_per_cu(bits_kernel_for(c.sps, c.tol != 0), 4), 8u);
     const uint64_t max_tiles = (maxs + 63 + TILE - 1) / TILE;
     const uint64_t max_span = std::max<uint64_t>(MIN_SPAN, (C * max_tiles + c.max_waves - 1) / c.max_waves);
     c.max_chunks = (uint32_t)(prop.multiProcessorCount * 32u / C + 3);   // bound for any occupancy
@@ -185,7 +182,7 @@ inline FrontGeom front_geometry(uint32_t C, uint32_t P, uint32_t max_waves)
     return { Tc, (uint32_t)((G + nwaves - 1) / nwaves), nwaves };
 }
 // The resolve kernel of a push of P samples (and the capture kernel of the queue form) behind a front launch of geometry g.  search:
-// the trigger search runs inside the kernel (SEARCH_IN_RESOLVE), and the push's housekeeping with it: zero2 from records_appending
+// the trigger search runs inside the kernel (search_in_resolve), and the push's housekeeping with it: zero2 from records_appending
 // (det and detcount then go unread: that form keeps its hits in LDS).
 inline void launch_resolve(CaptureState &c, const RecordListView &list, TimingState &tm, const FrontGeom &g, uint32_t P, hipStream_t s, bool search = false, uint32_t *zero2 = nullptr)
 {
@@ -297,16 +294,16 @@ inline int capture_run_bits(CaptureState &c, RecordLists &L, TimingState &tm, hi
     if (P == 0) return 0;
     const FrontGeom geom = front_geometry(c.C, P, c.max_waves_bits);
     const uint32_t Tc = geom.Tc, span = geom.span, nwaves = geom.nwaves;
-    const SearchForm form = search_form(c.wideband, (bool)c.capq, c.sps);
-    // round 6, SEARCH_IN_RESOLVE: ONE launch -- every channel's workgroup searches its own slicer bits (a quarter of the push per wave,
+    const bool in_resolve = search_in_resolve(c.wideband, (bool)c.capq, c.sps);
+    // round 6, the search in the resolve kernel: ONE launch -- every channel's workgroup searches its own slicer bits (a quarter of the push per wave,
     // hits in LDS), then resolves, captures and decodes them as ever; the launch's housekeeping goes with it
     uint32_t *zero2 = nullptr;
-    if (form == SEARCH_IN_RESOLVE) zero2 = records_appending(L);
+    if (in_resolve) zero2 = records_appending(L);
     else {
         if ((uint64_t)(Tc + span - 1) / span + 1 > c.max_chunks) return -E2BIG;
         const FrontArgs fa = front_args(c, L, geom, 0, P, P);
         SpanGuard g(tm, s, c.wideband, T_FRONT, P);
-        hipLaunchKernelGGL(bits_kernel_for(form, c.sps, fa.tol != 0), dim3((nwaves + 3) / 4), dim3(256), 0, s, fa);
+        hipLaunchKernelGGL(bits_kernel_for(c.sps, fa.tol != 0), dim3((nwaves + 3) / 4), dim3(256), 0, s, fa);
         g.end();
 #ifdef BITS_TIMELINE
         if (const char *path = std::getenv("AMPS_RECC_BITS_TIMELINE")) {
@@ -316,7 +313,7 @@ inline int capture_run_bits(CaptureState &c, RecordLists &L, TimingState &tm, hi
         }
 #endif
     }
-    launch_resolve(c, records_current(L), tm, geom, P, s, form == SEARCH_IN_RESOLVE, zero2);
+    launch_resolve(c, records_current(L), tm, geom, P, s, in_resolve, zero2);
     HIP_TRY(hipGetLastError());
     c.n_done += P;
     return 0;

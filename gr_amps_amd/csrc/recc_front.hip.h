@@ -379,27 +379,26 @@ __host__ __device__ __forceinline__ uint32_t exact_slice_word2(uint32_t SX, uint
     return ~K.p[2] & (K.p[0] | K.p[1] | ~SC);                           // K > 0, or K == 0 and Im(y conj(y[n-2])) not negative
 }
 
-// BITS = true is the bit-domain form used behind the fused channelizer: the slicer bits of this launch are
-// already in the HBM ring (written by chz_fused_kernel), so a tile is just 16 dwords read from it and only the
-// correlator / emit stages (P3a, P3b) run.
 // TOL = true replaces the exact trigger match by "at most a.tol of the 74 symbols differ" (a
 // divergence from the reference's memmem, off by default): no prefilter is sound then, so every tile pays a
 // bit-sliced population count over all 74 taps (~350 instructions per lane per tile instead of ~25).
-// SL = AMPS_SLICER_PRODUCT: slicer spec B (sign of Im(x[n] conj(x[n-SPS]))) instead of discriminator + boxcar: the tile's
-// raw samples are staged in the wave's LDS buffer and each lane slices 8 consecutive samples with one v_pk_mul, one
-// v_sub and one v_alignbit each -- the kernel is then bound by its HBM reads alone.
-template <int SPS, int DEPTH, bool BITS = false, bool TOL = false, int SL = AMPS_SLICER_ATAN_BOXCAR>
+// SL picks the slicer spec of include/amps_recc_numerics.h.  A (AMPS_SLICER_ATAN_BOXCAR) and C (AMPS_SLICER_SINE) demodulate
+// into the wave's LDS buffers and slice a boxcar over one symbol (P1, P2 below).  B (AMPS_SLICER_PRODUCT: the sign of
+// Im(x[n] conj(x[n-SPS]))) and D (AMPS_SLICER_EXACT) stage the tile's raw samples there instead and each lane slices 8
+// consecutive samples -- for B with one v_pk_mul, one v_sub and one v_alignbit each: the kernel is then bound by its HBM
+// reads alone.
+template <int SPS, int DEPTH, bool TOL = false, int SL = AMPS_SLICER_ATAN_BOXCAR>
 __global__ __launch_bounds__(256, FRONT_BLOCKS_PER_CU) void recc_front_kernel(FrontArgs a)
 {
     constexpr bool EXACT = SL == AMPS_SLICER_EXACT;
     constexpr bool PROD = SL == AMPS_SLICER_PRODUCT || EXACT;          // specs B and D stage the tile's raw samples in LDS
-    static_assert(!PROD || (!BITS && SPS < XHIST), "specs B / D run on IQ");
+    static_assert(!PROD || SPS < XHIST, "specs B / D: the partner sample lies in the history prefix");
     front_housekeeping(a);
     static_assert(SPS >= 2 && SPS <= 16, "samples per symbol");
     constexpr int H = SPS - 1;                  // boxcar history
     constexpr int D = AMPS_DEDUP_SYMBOLS * SPS; // dedup / run window in samples (<= 32)
     static_assert(H <= DHIST, "history prefix too small");
-    __shared__ float    s_d_all[4][BITS ? 8 : PROD ? 2 * XBUF : 2 * DBUF];   // demod buffers (spec B: one float2 sample buffer): not used in the bit domain (keeps its LDS at 2 KB)
+    __shared__ float    s_d_all[4][PROD ? 2 * XBUF : 2 * DBUF];   // demod buffers (specs B / D: one float2 sample buffer)
     __shared__ uint32_t s_g_all[4][GW32 + 2];   // [GW32] mirrors [0] so a tap can always read dwords qd, qd+1
     __shared__ uint32_t s_m_all[4][GW32];
     __shared__ uint32_t s_x_all[EXACT ? 4 : 1][EXACT ? 3 * (GW32 + 2) : 1];   // spec D: the three sign streams as bit rings shaped like s_g
@@ -415,7 +414,7 @@ __global__ __launch_bounds__(256, FRONT_BLOCKS_PER_CU) void recc_front_kernel(Fr
     const uint64_t g_end_all = (uint64_t)a.n_channels * Tc;
     uint64_t g0 = (uint64_t)w_id * a.span;
     uint64_t g1 = g0 + a.span; if (g1 > g_end_all) g1 = g_end_all;
-    if (!BITS && a.carry_out) {
+    if (a.carry_out) {
         // round 4: the ~9 KB per channel the next push starts from are copied here, 1-4 samples per lane, instead of by a kernel of
         // their own behind this one (5 us + a launch gap per push); the two carry buffers alternate, so nothing read below is written
         const uint32_t nw_all = gridDim.x * 4u;
@@ -498,25 +497,15 @@ __global__ __launch_bounds__(256, FRONT_BLOCKS_PER_CU) void recc_front_kernel(Fr
 #pragma unroll
         for (int u = 0; u < 3; u++) { s_x[u * (GW32 + 2) + lane] = 0u; if (lane < 2) s_x[u * (GW32 + 2) + GW32 + lane] = 0u; }
     }
-    if constexpr (!BITS) for (int i = lane; i < (PROD ? 2 * XBUF : 2 * DBUF); i += 64) s_d[i] = 0.f;
+    for (int i = lane; i < (PROD ? 2 * XBUF : 2 * DBUF); i += 64) s_d[i] = 0.f;
 
     float4 cur[4], nxt[DEPTH][4];                // tile k in use, tiles k+1..k+DEPTH in flight (DEPTH x 4 KiB per wave)
     float last_x = 0.f, last_y = 0.f;            // last sample of the previous tile (wave-uniform)
     uint32_t ndet = 0;                           // hits appended by this wave (wave-uniform)
     bool hit_prev = false;                       // the previous tile had a trigger hit (wave-uniform)
-    if constexpr (!BITS) {
-        load_tile(cur, chunk_start - HALO);
+    load_tile(cur, chunk_start - HALO);
 #pragma unroll
-        for (int d = 0; d + 1 < DEPTH; d++) load_tile(nxt[d], chunk_start - HALO + (d + 1) * TILE);   // K >= 1: all exist up to d = 1
-    }
-    const uint32_t *gring32 = (const uint32_t *)(a.gring + (uint64_t)c * a.ring_words);
-    auto load_bits = [&](int kk) -> uint32_t {        // BITS mode: dword `lane` of tile kk of this segment (lanes 0..15)
-        if (lane >= TILE / 32) return 0u;
-        const int64_t n32 = (int64_t)a.n_done + chunk_start + (int64_t)kk * TILE + 32 * lane;
-        return n32 < 0 ? ~0u : gring32[(uint64_t)(n32 >> 5) & (2ull * a.ring_words - 1)];
-    };
-    uint32_t bw0 = 0u, bw1 = 0u, bw2 = 0u;           // tiles k, k+1, k+2 of the loop below (K >= 1)
-    if constexpr (BITS) { bw0 = load_bits(-2); bw1 = load_bits(-1); bw2 = load_bits(0); }
+    for (int d = 0; d + 1 < DEPTH; d++) load_tile(nxt[d], chunk_start - HALO + (d + 1) * TILE);   // K >= 1: all exist up to d = 1
 
     // k = -2, -1 are the halo tiles [chunk_start-1024, chunk_start): recomputed, never stored or emitted
     for (int k = -2; k < K; k++) {
@@ -524,17 +513,7 @@ __global__ __launch_bounds__(256, FRONT_BLOCKS_PER_CU) void recc_front_kernel(Fr
         const int slot = (k + 2) & 3;                          // bit-ring slot of this tile
         float *const dcur = s_d + ((k + 2) & 1) * DBUF;        // demod buffer of this tile
         float *const dnxt = s_d + ((k + 3) & 1) * DBUF;        // ... of the next tile (gets our tail as history)
-        if constexpr (BITS) {
-            // the tile's 512 slicer bits come from the HBM ring (fetched three tiles ahead: a bare load per tile is ~1 us of
-            // exposed latency); samples before the stream are ones (x = 0 -> g = 1)
-            const uint32_t w = bw0;
-            bw0 = bw1; bw1 = bw2;
-            bw2 = (k + 3 < K) ? load_bits(k + 3) : 0u;
-            if (lane < TILE / 32) {
-                s_g[slot * (TILE / 32) + lane] = w;
-                if (slot == 0 && lane < 2) s_g[GW32 + lane] = w;      // mirror of dwords 0,1
-            }
-        } else if constexpr (PROD) {
+        if constexpr (PROD) {
         // ---- spec B: stage the tile's samples in LDS, then every lane slices samples 8*lane .. 8*lane+7 ----
         if (k + DEPTH < K) load_tile(nxt[DEPTH - 1], t0 + DEPTH * TILE);
         f2 *const xs = (f2 *)s_d;
@@ -688,7 +667,7 @@ __global__ __launch_bounds__(256, FRONT_BLOCKS_PER_CU) void recc_front_kernel(Fr
             ((uint8_t *)s_g)[slot * (TILE / 8) + lane] = (uint8_t)byte;
             if (slot == 0 && lane < 8) ((uint8_t *)s_g)[GW32 * 4 + lane] = (uint8_t)byte;   // mirror of dwords 0,1
         }
-        }   // !BITS
+        }   // !PROD
         __builtin_amdgcn_wave_barrier();
         // ---- P3a: bit-parallel exact match of the 74-symbol trigger; publish slicer words ----
         bool hit = false;
@@ -790,7 +769,7 @@ __global__ __launch_bounds__(256, FRONT_BLOCKS_PER_CU) void recc_front_kernel(Fr
             if (part == 0) {
                 s_m[slot * (TILE / 32) + wq] = acc;
                 const int64_t relw = t0 / 64 + (wq >> 1);      // rel 64-bit word index
-                if (!BITS && k >= 0 && relw < words_end) {
+                if (k >= 0 && relw < words_end) {
                     uint64_t absw = a.n_done / 64 + (uint64_t)relw;
                     uint32_t *g32 = (uint32_t *)(a.gring + (uint64_t)c * a.ring_words + (absw & a.ring_mask));
                     g32[wq & 1] = s_g[slot * (TILE / 32) + wq];
@@ -842,13 +821,11 @@ __global__ __launch_bounds__(256, FRONT_BLOCKS_PER_CU) void recc_front_kernel(Fr
             }
         }
         hit_prev = hit;
-        if constexpr (!BITS) {
 #pragma unroll
-            for (int q = 0; q < 4; q++) {
-                cur[q] = nxt[0][q];
+        for (int q = 0; q < 4; q++) {
+            cur[q] = nxt[0][q];
 #pragma unroll
-                for (int d = 0; d + 1 < DEPTH; d++) nxt[d][q] = nxt[d + 1][q];
-            }
+            for (int d = 0; d + 1 < DEPTH; d++) nxt[d][q] = nxt[d + 1][q];
         }
     }
     if (lane == 0) a.detcount[(uint64_t)c * a.max_chunks + chunk] = ndet < a.det_cap ? ndet : a.det_cap;

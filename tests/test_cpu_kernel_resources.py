@@ -42,7 +42,7 @@ def test_filter_bank_kernel_budget(res):
 
 def test_streaming_kernel_budget(res):
     for sps in (3, 4, 5, 6, 8, 10, 12):
-        for name, r in _one(res, "void amps::recc_front_kernel<%d, 1, false, false, " % sps).items():
+        for name, r in _one(res, "void amps::recc_front_kernel<%d, 1, false, " % sps).items():
             assert r["vgprs"] <= 128 and r["waves_per_simd"] >= 4, (name, r)
             assert r["scratch_bytes_per_lane"] <= 64, (name, r)        # a few spilled loop invariants, none in the tile loop
             assert r["lds_bytes"] <= 40 * 1024, (name, r)              # four workgroups per CU
@@ -52,15 +52,15 @@ def test_streaming_kernel_budget(res):
     # its sample loop costs one 64-bit segment invariant its register: stored in the kernel's set-up, reloaded once per SEGMENT, never in
     # the tile loop)
     for sl, spill_ok in ((0, 0), (3, 2)):
-        for name, r in _one(res, "void amps::recc_front_kernel<10, 1, false, false, %d>" % sl).items():
+        for name, r in _one(res, "void amps::recc_front_kernel<10, 1, false, %d>" % sl).items():
             assert r["vgpr_spill"] <= spill_ok and r["scratch_bytes_per_lane"] <= 8 * spill_ok, (name, r)
 
 
 def test_streaming_kernel_variants(res):
-    # only what a handle can reach: eight rates x four slicer specs x {exact, tolerant sync}, each at the one tile depth its spec takes
-    # (1 for A / D and for tolerant sync, 2 for B / C), plus the bit-domain form with and without tolerant sync
+    # only what a handle can reach: eight rates x four slicer specs x {exact, tolerant sync} = 64, each at the one tile depth its spec
+    # takes (1 for A / D and for tolerant sync, 2 for B / C); the kernel runs on IQ and on nothing else
     hits = _one(res, "void amps::recc_front_kernel<")
-    assert len(hits) == 66, sorted(hits)
+    assert len(hits) == 64, sorted(hits)
     assert not [name for name in hits if name.split("<")[1].split(", ")[1] == "3"], sorted(hits)   # no depth-3 form
 
 

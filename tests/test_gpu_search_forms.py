@@ -1,9 +1,8 @@
-"""-m gpu: the three launch structures of the wideband seam's trigger search give the same records, byte for byte.
+"""-m gpu: the two launch structures of the wideband seam's trigger search give the same records, byte for byte.
 
   default                          the search stage INSIDE the resolve kernel (round 6: recc_resolve_kernel<..., SEARCH>, one launch per push
                                    behind the filter bank; a quarter of the channel's push per wave, hits in LDS)
   AMPS_RECC_BITS_KERNEL=separate   recc_bits_kernel as its own launch in front of the resolve kernel (rounds 2-5), hits in HBM lists
-  AMPS_RECC_BITS_KERNEL=front      the streaming kernel's bit-domain mode (D = 512 only): an independent implementation of the search
 
 The knob is read once per process, so every form runs in its own interpreter on the same stream: ragged pushes, exact and tolerant sync,
 both decimations, bursts at the edges of the quarters included."""
@@ -61,6 +60,3 @@ def test_search_inside_the_resolve_kernel_equals_the_separate_launch(gpu, decim,
     n0, h0 = _run(decim, tol, None)
     n1, h1 = _run(decim, tol, "separate")
     assert n0 == n1 == 14 and h0 == h1
-    if decim == 512:                                         # the streaming kernel's bit-domain mode exists at three samples per symbol
-        n2, h2 = _run(decim, tol, "front")
-        assert (n2, h2) == (n0, h0)
