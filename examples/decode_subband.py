@@ -7,6 +7,9 @@ amps.recc -> amps.recc_decode] of grc/recctest.grc.  Needs an MI355X: the librar
     python examples/decode_subband.py             # one mobile per control channel, the stream pushed in ragged blocks
     python examples/decode_subband.py --sc16      # the same stream as an SDR delivers it: interleaved int16, pushed as it is
                                                   # (amps_recc_push_raw_shared_as; --sc8 / --cu8 likewise take capi.SAMPLES_SC8 / _CU8)
+    python examples/decode_subband.py --rtl       # an RTL-SDR at its usual 2.4 Msps, tuned between the two systems: BOTH systems' 42
+                                                  # control channels (313 .. 354, 1.26 MHz) from one cu8 stream, decimated by 12
+                                                  # (capi.subband_plan(2.4e6) lists the decimations a rate admits)
 """
 import os
 import sys
@@ -16,9 +19,18 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gr_amps_amd import capi, synth
 
-RATE, DECIM, NSAMP = 800e3, 4, 400_000            # 0.5 s of signal; 800 ksps / 4 = 200 ksps per channel: 10 samples per symbol
-TUNED = capi.reverse_channel_hz(323)              # the SDR sits on the middle channel
-centres = capi.control_channel_centers("A", TUNED)   # -300 kHz .. +300 kHz in 30 kHz steps
+RTL = "--rtl" in sys.argv[1:]
+if RTL:
+    RATE, DECIM, NSAMP = 2.4e6, 12, 1_200_000     # 0.5 s of signal; 2.4 Msps / 12 = 200 ksps per channel
+    assert (DECIM, 10, 1793) in capi.subband_plan(RATE)          # the channel filter has 1793 taps at this rate
+    TUNED = 0.5 * (capi.reverse_channel_hz(333) + capi.reverse_channel_hz(334))   # between the systems: no channel on the tuner's DC
+    centres = capi.control_channel_centers("AB", TUNED)          # -615 kHz .. +615 kHz in 30 kHz steps
+    FIRST, GAP = 12000, 16000
+else:
+    RATE, DECIM, NSAMP = 800e3, 4, 400_000        # 0.5 s of signal; 800 ksps / 4 = 200 ksps per channel: 10 samples per symbol
+    TUNED = capi.reverse_channel_hz(323)          # the SDR sits on the middle channel
+    centres = capi.control_channel_centers("A", TUNED)   # -300 kHz .. +300 kHz in 30 kHz steps
+    FIRST, GAP = 4000, 11000
 
 try:
     rx = capi.Recc(n_channels=len(centres), sps=10, max_samples=NSAMP // DECIM, max_bursts=64)
@@ -30,7 +42,7 @@ k = np.arange(NSAMP)
 x = np.zeros(NSAMP, np.complex128)
 sent = {}
 for c, fc in enumerate(centres):                  # one seizure burst per channel, at its own time
-    iq, truth = synth.make_channel_block(NSAMP, 1, seed=7000 + c, sps=10 * DECIM, snr_db=40.0, first=4000 + 11000 * c)
+    iq, truth = synth.make_channel_block(NSAMP, 1, seed=7000 + c, sps=10 * DECIM, snr_db=40.0, first=FIRST + GAP * c)
     x += iq * np.exp(2j * np.pi * fc * k / RATE)
     sent[c] = truth[0][2]
 x = x.astype(np.complex64)
@@ -38,13 +50,16 @@ SC16 = "--sc16" in sys.argv[1:]
 if SC16:                                          # what the SDR's converter does: scale to the converter's range and round; the seam reads
     x = np.rint(np.stack([x.real, x.imag], -1) * 2048.0).astype(np.int16)   # the [n, 2] int16 block in place -- no float copy on the host
 
+if RTL:                                           # the dongle's converter: 8 bits, offset binary; 42 carriers at 4 units each stay within it
+    x = np.clip(np.floor(np.stack([x.real, x.imag], -1) * 4.0 + 128.0), 0, 255).astype(np.uint8)
+
 with rx:
     rx.set_xlate_shared(RATE, centres, DECIM)
     pos = 0
     while pos < NSAMP:                            # blocks of any size: samples short of a decimation step wait in the handle
         n = min(int(rng.integers(10_000, 150_000)), NSAMP - pos)
-        if SC16:
-            rx.push_raw_shared_as(x[pos:pos + n], capi.SAMPLES_SC16)
+        if SC16 or RTL:
+            rx.push_raw_shared_as(x[pos:pos + n], capi.SAMPLES_SC16 if SC16 else capi.SAMPLES_CU8)
         else:
             rx.push_raw_shared(x[pos:pos + n])
         pos += n

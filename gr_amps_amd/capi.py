@@ -87,6 +87,10 @@ class XlateSharedCfg(C.Structure):
     ]
 
 
+class XlatePlan(C.Structure):
+    _fields_ = [("decim", C.c_uint32), ("samples_per_symbol", C.c_uint32), ("ntaps", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class RcclInfo(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("alive", C.c_int32), ("nranks", C.c_int32), ("rank", C.c_int32),
@@ -125,6 +129,7 @@ EXPORTS = (
     "amps_recc_channel_power", "amps_recc_burst_power", "amps_recc_power_ring_snaps",
     "amps_recc_set_xlate_shared", "amps_recc_push_raw_shared", "amps_recc_debug_xlate_shared",
     "amps_recc_push_raw_shared_as", "amps_recc_push_raw_as", "amps_recc_debug_xlate_shared_as", "amps_recc_debug_xlate_as",
+    "amps_recc_xlate_shared_plan",
 )
 _XLATE_AS = ("amps_recc_push_raw_shared_as", "amps_recc_push_raw_as", "amps_recc_debug_xlate_shared_as", "amps_recc_debug_xlate_as")
 _XLATE_SHARED = ("amps_recc_set_xlate_shared", "amps_recc_push_raw_shared", "amps_recc_debug_xlate_shared")
@@ -217,12 +222,14 @@ def load():
         L.amps_recc_push_raw_as.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int]
         L.amps_recc_debug_xlate_shared_as.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.amps_recc_debug_xlate_as.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    if hasattr(L, "amps_recc_xlate_shared_plan"):     # absent only from A/B builds of earlier revisions (AMPS_RECC_LIB)
+        L.amps_recc_xlate_shared_plan.argtypes = [C.c_double, C.c_double, C.POINTER(XlatePlan), C.c_size_t]
     L.amps_bch_encode_words.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp]
     L.amps_bch_decode_words.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, vp, vp]
     for name in EXPORTS:
         if name in ("amps_recc_default_slicer", "amps_recc_default_wideband_decim", "amps_recc_debug_exact_slice", "amps_recc_rccl_unique_id", "amps_recc_rccl_init",
                     "amps_recc_push_wideband_bcast", "amps_recc_drain_gather", "amps_recc_debug_slicer_bits",
-                    "amps_recc_push_wideband_short") + _NEW_IN_ABI4 + _POWER + _XLATE_SHARED + _XLATE_AS and not hasattr(L, name):
+                    "amps_recc_push_wideband_short", "amps_recc_xlate_shared_plan") + _NEW_IN_ABI4 + _POWER + _XLATE_SHARED + _XLATE_AS and not hasattr(L, name):
             continue
         if name not in ("amps_recc_strerror", "amps_recc_burst_size", "amps_recc_destroy"):   # every other entry point returns int
             getattr(L, name).restype = C.c_uint32 if name == "amps_recc_power_ring_snaps" else C.c_int
@@ -466,7 +473,9 @@ class Recc:
     def set_xlate_shared(self, rate_hz, centers_hz, decim, gain=0.0, cutoff_hz=0.0, width_hz=0.0):
         """Channel c of the handle = the channel at centers_hz[c] (relative to the stream's centre) of ONE shared stream at rate_hz:
         the flow graph's channel filter per centre, all of them in one launch, in front of the IQ seam (amps_recc_set_xlate_shared).
-        len(centers_hz) must be n_channels; zeros select the flow graph's gain / cutoff / transition width; decim 0 removes the stage."""
+        len(centers_hz) must be n_channels; zeros select the flow graph's gain / cutoff / transition width; decim 0 removes the stage.
+        decim is 1, 2, 4 or 8 (filters of up to 1280 taps) or 5, 6, 10, 12, 16 or 20 (up to 2400: the default filter to 3.2 Msps), and
+        rate_hz / decim must be the handle's sps x 20 kHz: subband_plan(rate_hz) lists the (decim, sps) pairs a rate admits."""
         cen = np.ascontiguousarray(centers_hz, np.float64).reshape(-1)
         x = XlateSharedCfg(C.sizeof(XlateSharedCfg), int(decim), cen.size, 0, rate_hz, gain, cutoff_hz, width_hz,
                            cen.ctypes.data_as(C.POINTER(C.c_double)))
@@ -887,6 +896,20 @@ def reverse_channel_hz(n):
 
 
 CONTROL_CHANNELS = {"A": range(313, 334), "B": range(334, 355), "AB": range(313, 355)}
+
+
+def subband_plan(rate_hz, width_hz=0.0):
+    """Which decimation for a stream at rate_hz?  The (decim, sps, ntaps) triples Recc.set_xlate_shared accepts for that rate on a
+    handle of `sps` samples per symbol, ascending by decim; ntaps is the channel filter's length at transition width width_hz (0 = the
+    flow graph's 4.5 kHz).  Empty for a rate no decimation serves (2.048 Msps, or 4 Msps under the default width).  Needs no GPU
+    (amps_recc_xlate_shared_plan)."""
+    L = load()
+    n = L.amps_recc_xlate_shared_plan(rate_hz, width_hz, None, 0)
+    if n < 0:
+        raise AmpsError(n, "amps_recc_xlate_shared_plan")
+    out = (XlatePlan * max(n, 1))()
+    n = L.amps_recc_xlate_shared_plan(rate_hz, width_hz, out, n)
+    return [(int(p.decim), int(p.samples_per_symbol), int(p.ntaps)) for p in out[:n]]
 
 
 def control_channel_centers(system, tuned_hz):

@@ -463,10 +463,11 @@ static int xlate_configure(amps_recc *h, bool shared, uint32_t decim, double rat
     if (gain == 0.0) gain = 3.0;
     if (cutoff == 0.0) cutoff = 10e3;
     if (width == 0.0) width = 4.5e3;
-    if (!(rate_hz > 0.0) || !(cutoff > 0.0) || !(width > 0.0)) return -EINVAL;
-    // the filtered stream must arrive at the symbol rate the handle was built for
-    const double out_rate = rate_hz / decim;
-    if (std::fabs(out_rate - 20e3 * h->sps) > 1e-6 * out_rate) return -EINVAL;
+    if (!(cutoff > 0.0)) return -EINVAL;
+    // the form's decimations, the symbol rate the handle was built for and the filter's length: xlate_admit, which the plan asks too.
+    // -E2BIG is left to xlate_create, which checks the centres first
+    uint32_t ntaps = 0;
+    if (xlate_admit(shared, decim, h->sps, rate_hz, width, &ntaps) == -EINVAL) return -EINVAL;
     return xlate_create(h->xl, shared, h->C, decim, h->cfg.max_samples_per_push, rate_hz, center_hz,
                         xlate_design_taps(gain, rate_hz, cutoff, width), h->stream.get());
 }
@@ -548,6 +549,22 @@ int amps_recc_set_xlate_shared(amps_recc_t *h, const amps_recc_xlate_shared_cfg_
     if (x->decim == 0) { if (h->xl.shared) xlate_destroy(h->xl); return 0; }    // removes the form this entry point configures
     if (x->n_centers != h->C || !x->center_hz) return -EINVAL;
     return xlate_configure(h, true, x->decim, x->rate_hz, x->center_hz, x->gain, x->cutoff_hz, x->width_hz);
+}
+
+int amps_recc_xlate_shared_plan(double rate_hz, double width_hz, amps_recc_xlate_plan_t *out, size_t cap)
+{
+    if (width_hz == 0.0) width_hz = 4.5e3;                     // the default of xlate_configure
+    if (!(rate_hz > 0.0) || std::isinf(rate_hz) || !(width_hz > 0.0) || (cap && !out)) return -EINVAL;
+    int n = 0;
+    for (uint32_t decim = 1; decim <= (uint32_t)XLW_MAX_D; decim++) {
+        const double sps = std::nearbyint(rate_hz / decim / 20e3);
+        if (!(sps >= 1.0 && sps <= 64.0) || !sps_supported((uint32_t)sps)) continue;
+        uint32_t ntaps = 0;
+        if (xlate_admit(true, decim, (uint32_t)sps, rate_hz, width_hz, &ntaps)) continue;
+        if ((size_t)n < cap) out[n] = amps_recc_xlate_plan_t{ decim, (uint32_t)sps, ntaps, 0 };
+        n++;
+    }
+    return n;
 }
 
 int amps_recc_push_raw_shared_as(amps_recc_t *h, const void *iq, size_t nsamp, int format, int mem)

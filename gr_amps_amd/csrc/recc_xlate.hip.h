@@ -32,6 +32,11 @@
 // channels only for very long blocks.  D = 8 (one output per lane) exists in this form only: 1.6 Msps at 10 samples per symbol, where
 // the flow graph's filter spec gives 1195 taps -- hence XLS_MAX_TAPS = 1280.  Static LDS: raw 26 624 + mixed 30 016 + taps 5 120 =
 // 61 760 bytes of the 65 536 one workgroup may own statically, 2 waves per SIMD.
+//
+// Shared form, wide (xlate_shared_wide_kernel): the decimations that do not divide 8 -- 5, 6, 10, 12, 16, 20, the rates SDRs deliver
+// (1.0 ... 3.2 Msps, up to 2400 padded taps).  A tile is 256 OUTPUTS, one per lane, D is a kernel argument, one workgroup per (tile,
+// channel) mixes straight from memory.  The mixed window is kept by PHASE: sample n at row n mod D, column n / D, so the lanes of a
+// wave, which want samples D apart, read consecutive 8-byte words.  70 240 bytes of LDS, 2 workgroups per CU.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -47,6 +52,13 @@ namespace amps {
 constexpr int XL_TILE = 2048;        // input samples per workgroup (256 lanes x 8)
 constexpr int XL_MAX_TAPS = 1024;    // padded tap count limit of xlate_fir_kernel
 constexpr int XLS_MAX_TAPS = 1280;   // padded tap count limit of xlate_shared_kernel
+constexpr int XLW_OUT = 256;         // outputs per workgroup of xlate_shared_wide_kernel (one per lane)
+constexpr int XLW_MAX_TAPS = 2400;   // its padded tap count limit: the flow graph's filter spec at 3.2 Msps gives 2391
+constexpr int XLW_MAX_D = 20;        // its largest decimation
+// its mixed window: D rows (phases) of xlw_row(D) samples, and D xlw_row(D) < D (XLW_OUT + 3) + XLW_MAX_TAPS for every D
+constexpr int XLW_ZS = XLW_MAX_D * (XLW_OUT + 3) + XLW_MAX_TAPS;
+// The decimations of the wide kernel: the shared form only, D as a kernel argument, tiles of XLW_OUT outputs.
+__host__ __device__ constexpr bool xlate_is_wide(uint32_t D) { return D == 5 || D == 6 || D == 10 || D == 12 || D == 16 || D == 20; }
 
 // The block's sample types (include/amps_recc.h, AMPS_RECC_SAMPLES_*): float2 for fc32, and three PODs in the style of chz_sc16 for
 // the integer wire formats, read IN PLACE: one dword (sc16) or one 16-bit load (sc8, cu8) per lane and sample, consecutive lanes on
@@ -70,7 +82,10 @@ struct XlateArgs {
     uint64_t ld_in, ld_out;
     uint64_t n_abs0;         // absolute input index of the first unconsumed sample (virtual index v = hist)
     uint32_t carry_cap, carry_len, hist, nsamp, nout, ntp, C;
-    uint32_t cpg;            // shared form: channels per workgroup (blockIdx.y = group)
+    union {
+        uint32_t cpg;        // shared form, staged: channels per workgroup (blockIdx.y = group)
+        uint32_t D;          // shared form, wide: the decimation, which that kernel takes as an argument (a workgroup per channel)
+    };
 };
 
 __host__ __device__ constexpr int xl_pad(int n) { return n + (n >> 3); }
@@ -180,6 +195,79 @@ __global__ __launch_bounds__(256) void xlate_shared_kernel(XlateArgs a)
     }
 }
 
+// row length of the wide kernel's phase-major window at decimation D: the columns an output tile can touch at the tap limit
+// (XLW_OUT - 1 + ceil(XLW_MAX_TAPS / D)) and one more, made odd so that the D rows start on different banks (the stores of consecutive
+// samples go to consecutive rows).  It depends on D alone, so the FIR's LDS offsets are compile-time constants per decimation.
+__host__ __device__ constexpr int xlw_row(int D) { return (XLW_OUT + (XLW_MAX_TAPS + D - 1) / D) | 1; }
+
+// lane t's output from the phase-major window: zp = zs + t, (output t, tap i) at zp[r L + b] with H - i = D b + r.  Ascending taps
+// walk r downwards through column b (the head: the taps above the last whole column), then through whole columns towards column 0.
+template <int D>
+__device__ __forceinline__ cf2 xlw_fir(const cf2 *zp, const float *hs, int H, int ntp)
+{
+    constexpr int L = xlw_row(D);
+    static_assert(D * L <= XLW_ZS, "the window of this decimation");
+    cf2 acc = (cf2){ 0.f, 0.f };
+    const cf2 *col = zp + H / D;
+    int i = 0;
+    for (int r = H % D; r >= 0; r--, i++) {
+        const float h = hs[i];
+        acc = __builtin_elementwise_fma(col[r * L], (cf2){ h, h }, acc);
+    }
+    for (col--; i < ntp; i += D, col--) {                        // ntp - i is a multiple of D here
+#pragma unroll
+        for (int e = 0; e < D; e++) {
+            const float h = hs[i + e];
+            acc = __builtin_elementwise_fma(col[(D - 1 - e) * L], (cf2){ h, h }, acc);
+        }
+    }
+    return acc;
+}
+
+// The shared form for the decimations that do not divide 8.  One workgroup per (tile of XLW_OUT outputs, channel); lane t owns output
+// k0 + t.  Tile-local sample n <-> virtual index v = D*k0 + n as above; (output m, tap i) is sample D m + (H - i).  The window is
+// stored by phase, sample n at zs[(n % D) * L + n / D]: with H - i = D b + r, lane t reads zs[r L + b + t] -- the lanes of a wave
+// on consecutive words, whatever D is, and (r, b) wave-uniform.  D is a kernel argument: the staging takes it as it comes, the FIR
+// is unrolled once per decimation inside the one kernel (four instantiations, one per sample type).
+template <typename T>
+__global__ __launch_bounds__(256) void xlate_shared_wide_kernel(XlateArgs a)
+{
+    __shared__ cf2 zs[XLW_ZS];
+    __shared__ float hs[XLW_MAX_TAPS];
+    static_assert(sizeof(cf2) * XLW_ZS + sizeof(float) * XLW_MAX_TAPS <= 80 * 1024, "two workgroups per CU");
+    const int t = threadIdx.x;
+    const uint32_t c = blockIdx.y;
+    const uint32_t k0 = blockIdx.x * XLW_OUT;
+    const int D = (int)a.D;
+    const int H = (int)a.hist;                                   // = ntp - 1
+    const int ntp = (int)a.ntp;
+    if (!xlate_is_wide(a.D) || ntp < 1 || ntp > XLW_MAX_TAPS) return;   // the host's limits (xlate_max_taps), held here too
+    const int L = xlw_row(D);
+    const int64_t v0 = (int64_t)D * k0;
+    const uint64_t nabs0 = a.n_abs0 + (uint64_t)(v0 - H);        // wraps consistently for the (zero) pre-stream history
+    const uint64_t step = a.steps[c];
+
+    for (int i = t; i < ntp; i += 256) hs[i] = a.taps[i];
+    const int W = D * (XLW_OUT - 1) + ntp;                       // the samples the tile's outputs read
+    for (int n = t; n < W; n += 256) {
+        const int col = n / D;
+        zs[(n - col * D) * L + col] = xl_mix(xl_window(a, a.carry, (const T *)a.block, v0 + n), nabs0 + (uint64_t)n, step);
+    }
+    __syncthreads();
+
+    cf2 acc;
+    switch (D) {
+    case 5: acc = xlw_fir<5>(zs + t, hs, H, ntp); break;
+    case 6: acc = xlw_fir<6>(zs + t, hs, H, ntp); break;
+    case 10: acc = xlw_fir<10>(zs + t, hs, H, ntp); break;
+    case 12: acc = xlw_fir<12>(zs + t, hs, H, ntp); break;
+    case 16: acc = xlw_fir<16>(zs + t, hs, H, ntp); break;
+    default: acc = xlw_fir<20>(zs + t, hs, H, ntp); break;
+    }
+    const uint32_t k = k0 + t;
+    if (k < a.nout) a.out[(uint64_t)c * a.ld_out + k] = make_float2(acc.x, acc.y);
+}
+
 // carry_out[r][i] = virtual[r][consumed + i], i < new_len  (separate buffers: the ranges can overlap).  The carry is fc32: the samples
 // taken from the block are converted here, which is what lets the sample type change from one push to the next.
 template <typename T>
@@ -204,7 +292,7 @@ template <typename T> inline xlate_kernel_t xlate_kernel_of(bool shared, uint32_
     case 2: return shared ? xlate_shared_kernel<2, T> : xlate_fir_kernel<2, T>;
     case 4: return shared ? xlate_shared_kernel<4, T> : xlate_fir_kernel<4, T>;
     case 8: return shared ? xlate_shared_kernel<8, T> : nullptr;
-    default: return nullptr;
+    default: return shared && xlate_is_wide(D) ? xlate_shared_wide_kernel<T> : nullptr;
     }
 }
 inline xlate_kernel_t xlate_kernel_for(bool shared, uint32_t D, int format = AMPS_RECC_SAMPLES_FC32)
@@ -238,7 +326,7 @@ inline size_t xlate_sample_bytes(int format)
     default: return 0;
     }
 }
-inline uint32_t xlate_max_taps(bool shared) { return shared ? XLS_MAX_TAPS : XL_MAX_TAPS; }
+inline uint32_t xlate_max_taps(bool shared, uint32_t D) { return !shared ? XL_MAX_TAPS : xlate_is_wide(D) ? XLW_MAX_TAPS : XLS_MAX_TAPS; }
 
 struct XlateState {
     bool enabled = false;
@@ -255,10 +343,16 @@ struct XlateState {
 
 // firdes.low_pass(gain, fs, cutoff, width, WIN_BLACKMAN) as the flow graph calls it (grc/recctest.grc:115-155):
 // ntaps = int(74 fs / (22 width)) made odd; windowed sinc normalised to DC gain `gain`
+inline int xlate_ntaps(double fs, double width)
+{
+    const double want = 74.0 * fs / (22.0 * width);
+    int n = want < 1e9 ? (int)want : 1000000000;                 // far beyond every kernel's limit
+    if (!(n & 1)) n++;
+    return n;
+}
 inline std::vector<float> xlate_design_taps(double gain, double fs, double cutoff, double width)
 {
-    int n = (int)(74.0 * fs / (22.0 * width));
-    if (!(n & 1)) n++;
+    const int n = xlate_ntaps(fs, width);
     const int m = (n - 1) / 2;
     std::vector<double> t((size_t)n);
     const double w0 = 2.0 * M_PI * cutoff / fs;
@@ -272,6 +366,21 @@ inline std::vector<float> xlate_design_taps(double gain, double fs, double cutof
     std::vector<float> out((size_t)n);
     for (int i = 0; i < n; i++) out[(size_t)i] = (float)(t[(size_t)i] * gain / sum);
     return out;
+}
+
+// What a form accepts of a stream at rate_hz decimated by D for a handle of sps samples per symbol, in the order the configuration
+// answers: a kernel for D and the symbol rate met (-EINVAL), the filter's length within that kernel's limit (-E2BIG).  *ntaps = the
+// filter's length wherever the rates are numbers.  amps_recc_set_xlate[_shared] and amps_recc_xlate_shared_plan both ask here.
+inline int xlate_admit(bool shared, uint32_t D, uint32_t sps, double rate_hz, double width_hz, uint32_t *ntaps)
+{
+    *ntaps = 0;
+    if (!(rate_hz > 0.0) || !(width_hz > 0.0) || std::isinf(rate_hz)) return -EINVAL;
+    *ntaps = (uint32_t)xlate_ntaps(rate_hz, width_hz);
+    if (!xlate_kernel_for(shared, D)) return -EINVAL;
+    // the filtered stream must arrive at the symbol rate the handle was built for
+    const double out_rate = rate_hz / D;
+    if (std::fabs(out_rate - 20e3 * sps) > 1e-6 * out_rate) return -EINVAL;
+    return (*ntaps + 7) / 8 * 8 > xlate_max_taps(shared, D) ? -E2BIG : 0;
 }
 
 inline void xlate_destroy(XlateState &x) { x = XlateState{}; }
@@ -299,7 +408,7 @@ inline int xlate_create(XlateState &x, bool shared, uint32_t C, uint32_t D, uint
         steps[c] = (uint64_t)(fr * 18446744073709551616.0L);
     }
     const uint32_t ntp = (uint32_t)((taps.size() + 7) / 8 * 8);
-    if (ntp > xlate_max_taps(shared)) return -E2BIG;
+    if (ntp > xlate_max_taps(shared, D)) return -E2BIG;
     xlate_destroy(x);
     x.shared = shared; x.C = C; x.rows = shared ? 1 : C; x.D = D; x.ntp = ntp; x.hist = ntp - 1; x.carry_cap = ntp + D; x.max_out = max_out;
     std::vector<float> padded(ntp, 0.0f);
@@ -349,9 +458,12 @@ inline int xlate_run(XlateState &x, const void *iq, uint64_t ld, size_t nsamp, i
     a.n_abs0 = x.n_abs; a.carry_cap = x.carry_cap; a.carry_len = x.carry_len; a.hist = x.hist;
     a.nsamp = (uint32_t)nsamp; a.nout = (uint32_t)n_out; a.ntp = x.ntp; a.C = x.C;
     if (n_out) {
-        const uint64_t tiles = (n_out * x.D + XL_TILE - 1) / XL_TILE;
-        a.cpg = x.shared ? xlate_shared_cpg(x.C, tiles) : 1;     // per-row form: a workgroup per (tile, row)
-        hipLaunchKernelGGL(xlate_kernel_for(x.shared, x.D, format), dim3((uint32_t)tiles, (x.C + a.cpg - 1) / a.cpg), dim3(256), 0, s, a);
+        // a tile is XL_TILE inputs, or XLW_OUT outputs of the wide kernel; a workgroup per (tile, row) but for the staged shared form
+        const bool wide = x.shared && xlate_is_wide(x.D);
+        const uint64_t tiles = wide ? (n_out + XLW_OUT - 1) / XLW_OUT : (n_out * x.D + XL_TILE - 1) / XL_TILE;
+        const uint32_t cpg = x.shared && !wide ? xlate_shared_cpg(x.C, tiles) : 1;
+        if (wide) a.D = x.D; else a.cpg = cpg;
+        hipLaunchKernelGGL(xlate_kernel_for(x.shared, x.D, format), dim3((uint32_t)tiles, (x.C + cpg - 1) / cpg), dim3(256), 0, s, a);
     }
     const uint32_t consumed = (uint32_t)(n_out * x.D);
     const uint32_t new_len = x.hist + (uint32_t)(avail - (uint64_t)consumed);

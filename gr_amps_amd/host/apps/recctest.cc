@@ -20,8 +20,9 @@
 //                                      channel at center_hz (default +160 kHz, :889-937) -> channel filter + fused chain on the GPU;
 //                                      cutoff_hz (default 0 = the flow graph's 10 kHz) widens the channel filter for mobiles off their carrier
 //   recctest sub  <file.raw> <chunk> <rate_hz> <decim> <c0,c1,...>   one narrowband fc32 capture at rate_hz holding several channels -> gr::amps::recc_subband
-//                                      (the channel filter per centre c0, c1, ... in Hz relative to the capture's centre, decimation `decim`, 10 samples
-//                                      per symbol behind it); prints for every record what `wide` prints: its channel (the index into the list), then
+//                                      (the channel filter per centre c0, c1, ... in Hz relative to the capture's centre, decimation `decim` -- 1, 2, 4,
+//                                      5, 6, 8, 10, 12, 16 or 20, with rate_hz / decim = 200 ksps: 2.4 Msps / 12, 2.0 / 10, 3.2 / 16, 1.0 / 5 ... -- and 10
+//                                      samples per symbol behind it; a refused rate is answered with the pairs that rate admits); prints for every record what `wide` prints: its channel (the index into the list), then
 //                                      its lines, decoded through the "bursts" port.  The file's extension gives its sample format: .sc16 is
 //                                      interleaved int16, .sc8 / .cs8 int8, .cu8 offset-binary uint8 (what USRP-class, HackRF and RTL-SDR tools
 //                                      write), read as they are through the block's input format; anything else is fc32
@@ -191,7 +192,8 @@ int main(int argc, char **argv)
             }
             src->stop();                                              // as the scheduler does: the root announces its end of stream, the others join until they see it
         } else if (mode == "sub") {
-            if (argc < 7) { std::fprintf(stderr, "usage: %s sub <file.raw> <chunk> <rate_hz> <decim> <c0,c1,...>\n", argv[0]); return 2; }
+            if (argc < 7) { std::fprintf(stderr, "usage: %s sub <file.raw> <chunk> <rate_hz> <decim> <c0,c1,...>\n"
+                                                "  decim: 1, 2, 4, 5, 6, 8, 10, 12, 16 or 20, rate_hz / decim = 200000 (10 samples per symbol)\n", argv[0]); return 2; }
             std::vector<double> centers;
             for (const char *p = argv[6]; *p;) {
                 char *end = nullptr;

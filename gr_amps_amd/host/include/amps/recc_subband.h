@@ -1,5 +1,5 @@
 // gr::amps::recc_subband -- NEW block type (not in the reference): many 30 kHz channels of ONE narrowband stream in one block.
-// Input: ONE gr_complex stream at rate_hz (a few hundred ksps to 1.6 Msps: one modest SDR tuned to a system's control channels), or
+// Input: ONE gr_complex stream at rate_hz (a few hundred ksps to 3.2 Msps: one modest SDR tuned to a system's control channels), or
 // with input_format the SDR's own integer items;
 // the block runs, for every centre of centers_hz, the flow graph's channel filter freq_xlating_fir_filter_ccc(decim,
 // firdes.low_pass(3, rate, cutoff, width), centre, rate) (grc/recctest.grc:889-937, taps :115-155) and the fused chain behind it
@@ -19,7 +19,8 @@ namespace amps {
 class AMPS_API recc_subband : virtual public gr::sync_block {
 public:
     typedef AMPS_SPTR<recc_subband> sptr;
-    // rate_hz / decim must be samples_per_symbol x 20 kHz; decim: 1, 2, 4 or 8
+    // rate_hz / decim must be samples_per_symbol x 20 kHz; decim: 1, 2, 4, 5, 6, 8, 10, 12, 16 or 20 (2.4 Msps / 12, 2.0 / 10, 3.2 / 16 ...);
+    // a refused combination is answered with what the rate admits (amps_recc_xlate_shared_plan)
     // slicer: -1 = the library default, 0 .. 3 = numeric spec A .. D (include/amps_recc_numerics.h)
     // cutoff_hz / width_hz: 0 = the flow graph's 10 kHz / 4.5 kHz
     // input_format: AMPS_RECC_SAMPLES_* of include/amps_recc.h.  0 = one gr_complex per item; 1 (sc16) = two shorts, what a UHD source set

@@ -26,6 +26,23 @@ class recc_subband_impl : public recc_subband {
              : format == AMPS_RECC_SAMPLES_SC8 || format == AMPS_RECC_SAMPLES_CU8 ? 2 : 0;
     }
 
+    // what to ask for instead of a refused (rate, decim, samples per symbol): the plan of that rate
+    static std::string refused(double rate_hz, double width_hz, int decim, int sps)
+    {
+        amps_recc_xlate_plan_t plan[16];
+        const int n = amps_recc_xlate_shared_plan(rate_hz, width_hz, plan, 16);
+        char buf[96];
+        std::snprintf(buf, sizeof buf, "; asked: %g sps / %d at %d samples per symbol; ", rate_hz, decim, sps);
+        std::string s = buf;
+        if (n <= 0) return s + "no decimation serves this rate and transition width (decimations 1, 2, 4, 5, 6, 8, 10, 12, 16, 20; see amps_recc_xlate_shared_plan)";
+        s += "this rate admits (decim, samples per symbol, taps):";
+        for (int i = 0; i < std::min(n, 16); i++) {
+            std::snprintf(buf, sizeof buf, " (%u, %u, %u)", plan[i].decim, plan[i].samples_per_symbol, plan[i].ntaps);
+            s += buf;
+        }
+        return s;
+    }
+
 public:
     recc_subband_impl(double rate_hz, const std::vector<double> &centers_hz, int decim, int sps, int slicer, double cutoff_hz, double width_hz, int input_format)
         : gr::sync_block("recc_subband", gr::io_signature::make(1, 1, (int)std::max<size_t>(item_size(input_format), 1)), gr::io_signature::make(0, 0, 0)),
@@ -33,7 +50,7 @@ public:
     {
         if (!item_size(input_format)) throw std::runtime_error("amps::recc_subband: input_format must be 0 (fc32), 1 (sc16), 2 (sc8) or 3 (cu8)");
         if (centers_hz.empty()) throw std::runtime_error("amps::recc_subband: no centres");
-        if (decim < 1) throw std::runtime_error("amps::recc_subband: decim must be 1, 2, 4 or 8");
+        if (decim < 1) throw std::runtime_error("amps::recc_subband: decim must be 1, 2, 4, 5, 6, 8, 10, 12, 16 or 20");
         amps_recc_cfg_t cfg = {};
         cfg.struct_size = sizeof(cfg);
         cfg.n_channels = (uint32_t)centers_hz.size();
@@ -56,7 +73,7 @@ public:
         rc = amps_recc_set_xlate_shared(d_handle, &x);
         if (rc != 0) {
             amps_recc_destroy(d_handle);
-            throw std::runtime_error(std::string("amps::recc_subband (xlate): ") + amps_recc_strerror(rc));
+            throw std::runtime_error(std::string("amps::recc_subband (xlate): ") + amps_recc_strerror(rc) + refused(rate_hz, width_hz, decim, sps));
         }
         message_port_register_out(pmt::mp("bursts"));
         message_port_register_out(pmt::mp("records"));

@@ -49,7 +49,9 @@ extern "C" {
                                      still 4, three entry points added and nothing changed: amps_recc_set_xlate_shared / _push_raw_shared /
                                      _debug_xlate_shared, many channels of one shared narrowband stream;
                                      still 4, four entry points added and nothing changed: amps_recc_push_raw_shared_as / _push_raw_as /
-                                     _debug_xlate_shared_as / _debug_xlate_as, the translate seams on an SDR's integer samples (AMPS_RECC_SAMPLES_*)) */
+                                     _debug_xlate_shared_as / _debug_xlate_as, the translate seams on an SDR's integer samples (AMPS_RECC_SAMPLES_*);
+                                     still 4, one entry point added and nothing changed: amps_recc_xlate_shared_plan, with the shared translate seam's
+                                     decimations 5, 6, 10, 12, 16 and 20) */
 
 /* protocol constants of the reference */
 #define AMPS_RECC_TRIGGER_SYMS 74   /* lib/recc_impl.cc:76-77: 37 bits x 2 Manchester symbols   */
@@ -313,17 +315,25 @@ int amps_recc_debug_xlate(amps_recc_t *h, const float *iq, size_t ld, size_t nsa
  * centre (same rate, decim, gain, cutoff, width) plus amps_recc_push_raw of the same samples produce on a ONE-channel handle, bit
  * for bit (amps_recc_debug_xlate_shared row c == amps_recc_debug_xlate there); the records are therefore those of that handle,
  * except for `channel`.  Duplicate centres are legal and give duplicate records.
- * decim: 1, 2, 4 or 8 (8 only here: 1.6 Msps at 10 samples per symbol, 1195 taps with the default filter); 0 removes the stage.
+ * For the decimations amps_recc_set_xlate does not have, the same identity holds against a ONE-channel handle of this entry point
+ * (row c == row 0 of amps_recc_debug_xlate_shared there), and the stream itself is the formula y_c[k] = sum_i h[i] z_c[decim k - i],
+ * z_c[n] = x[n] e^{-j 2 pi center_hz[c] n / rate_hz}, as one fp32 fma chain in ascending tap order.
+ * decim: 1, 2, 4 or 8 (8 only here: 1.6 Msps at 10 samples per symbol, 1195 taps with the default filter), or 5, 6, 10, 12, 16 or 20
+ * (only here: the rates SDRs deliver -- 1.0 Msps / 5, 1.2 / 6, 2.0 / 10, 2.4 / 12, 3.2 / 16 at 10 samples per symbol, 2.4 Msps / 20 at 6;
+ * amps_recc_xlate_shared_plan lists what a rate admits); 0 removes the stage.
  * rate_hz / decim must equal samples_per_symbol * 20 kHz; gain / cutoff_hz / width_hz = 0 select the flow graph's 3.0 / 10 kHz /
  * 4.5 kHz as amps_recc_set_xlate does.  The two translate stages exclude each other: configuring one removes the other;
  * amps_recc_push_raw on a shared-configured handle and amps_recc_push_raw_shared on a handle configured with amps_recc_set_xlate
  * answer -ENOSYS, as both do on an unconfigured handle.  Resets nothing else; call before the first push.
- * Errors: -EINVAL (null handle or cfg, wrong struct_size, n_centers != n_channels, null center_hz, a decim other than 0, 1, 2, 4, 8,
- * rate mismatch, a centre beyond the rate); -E2BIG (the filter has more than 1280 taps, padded to a multiple of 8); -ENOSYS (a handle
- * without the IQ seam, or a channel-group handle). */
+ * Errors: -EINVAL (null handle or cfg, wrong struct_size, n_centers != n_channels, null center_hz, a decim other than 0, 1, 2, 4, 5,
+ * 6, 8, 10, 12, 16, 20, rate mismatch, a centre beyond the rate); -E2BIG (the filter, padded to a multiple of 8, has more than 1280
+ * taps at decim 1, 2, 4, 8 or more than 2400 at decim 5, 6, 10, 12, 16, 20: the default filter fits up to 3.2 Msps, 2391 taps);
+ * -ENOSYS (a handle without the IQ seam, or a channel-group handle).
+ * A 4 Msps stream (HackRF) at decim 20 needs width_hz >= 5.61 kHz under the 2400 limit: int(74 * 4e6 / (22 * width_hz)) made odd is
+ * 2399 at 5610 Hz, 2403 at 5600 Hz and 2989 at the default 4.5 kHz. */
 typedef struct amps_recc_xlate_shared_cfg {
     uint32_t struct_size;
-    uint32_t decim;              /* 1, 2, 4 or 8; 0 removes the stage */
+    uint32_t decim;              /* 1, 2, 4, 5, 6, 8, 10, 12, 16 or 20; 0 removes the stage */
     uint32_t n_centers;          /* must equal cfg.n_channels */
     uint32_t _pad;
     double   rate_hz;            /* rate_hz / decim == samples_per_symbol * 20 kHz */
@@ -331,6 +341,13 @@ typedef struct amps_recc_xlate_shared_cfg {
     const double *center_hz;     /* [n_centers], |center| <= rate_hz; duplicates are legal */
 } amps_recc_xlate_shared_cfg_t;
 int amps_recc_set_xlate_shared(amps_recc_t *h, const amps_recc_xlate_shared_cfg_t *x);
+/* "Which decimation do I ask for?"  The (decim, samples_per_symbol) pairs amps_recc_set_xlate_shared accepts for a stream at rate_hz
+ * with transition width width_hz (0 = the flow graph's 4.5 kHz), ascending by decim; ntaps = the filter's length.  Returns how many
+ * there are (may exceed cap, of which the first cap are written; out may be NULL with cap 0); 0 for a rate no decimation serves
+ * (2.048 Msps, 2.5 Msps: there is no fractional resampler); -EINVAL for a rate that is not a positive number.  Host arithmetic only:
+ * no handle and no device needed, and it asks the same function the configuration asks, so the two cannot disagree. */
+typedef struct amps_recc_xlate_plan { uint32_t decim, samples_per_symbol, ntaps, _pad; } amps_recc_xlate_plan_t;
+int amps_recc_xlate_shared_plan(double rate_hz, double width_hz, amps_recc_xlate_plan_t *out, size_t cap);
 /* iq is ONE row of nsamp samples at rate_hz.  Any nsamp <= decim * max_samples_per_push (-E2BIG beyond); leftover samples (fewer than
  * decim) wait for the next push.  Host and device blocks follow the ownership rules of amps_recc_push_raw; amps_recc_reset restarts
  * the stream; ms_xlate of amps_recc_get_timing counts the kernel.  -ESTALE as the data seams. */
