@@ -182,7 +182,7 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
     step("pinned record lists mapped");
     if (!rc && cfg->max_samples_per_push) rc = capture_create(h->cap, *cfg, h->C, h->slicer, cfg->wideband_channels != 0, dev);
     step("IQ seam buffers allocated");
-    if (!rc && cfg->wideband_channels) rc = channelizer_create(h->chz, *cfg, h->stream.get());
+    if (!rc && cfg->wideband_channels) rc = channelizer_create(h->chz, *cfg);
     step("channelizer created");
     if (!rc && (cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER)) rc = power_create(h->pow, h->chz, cfg->n_channels, h->cap.ring_words);
     if (!rc) rc = reset_state(h);

@@ -200,9 +200,8 @@ inline void launch_resolve(CaptureState &c, const RecordListView &list, TimingSt
     ra.capq = c.capq.get(); ra.capq_count = c.capq_count.get(); ra.capq_cap = list.rec_cap;
     const size_t lds = c.capq ? 0 : resolve_dyn_lds(c.sps);
 #ifdef RESOLVE_TIMELINE
-    static DevBuf<unsigned long long> &tl_dev = *new DevBuf<unsigned long long>();   // kept for the life of the process
-    if (!tl_dev) (void)tl_dev.alloc((size_t)24 * 4096);
-    if (tl_dev && c.C <= 4096) { (void)hipMemsetAsync(tl_dev.get(), 0, (size_t)24 * 8 * c.C, s); ra.tl = tl_dev.get(); }
+    static TimelineBuf &tl = *new TimelineBuf();                 // kept for the life of the process
+    ra.tl = tl.clear((size_t)24 * 4096, (size_t)24 * c.C, s);   // [C][24]; a handle with more than 4096 channels goes without
 #endif
     // The wide instantiation (a channel cut into more wave segments than 256 lanes compact in one batch) exists for handles with few
     // channels, which always take the queue form: its 36.9 KB of static LDS next to the fused capture form's dynamic LDS is a
@@ -220,11 +219,7 @@ inline void launch_resolve(CaptureState &c, const RecordListView &list, TimingSt
     }
     span.end();
 #ifdef RESOLVE_TIMELINE
-    if (const char *path = std::getenv("AMPS_RECC_RESOLVE_TIMELINE")) {   // the last launch's stamps, raw
-        std::vector<unsigned long long> tl((size_t)24 * c.C);
-        if (ra.tl && hipStreamSynchronize(s) == hipSuccess && hipMemcpy(tl.data(), ra.tl, tl.size() * 8, hipMemcpyDeviceToHost) == hipSuccess)
-            if (FILE *f = std::fopen(path, "wb")) { std::fwrite(tl.data(), 8, tl.size(), f); std::fclose(f); }
-    }
+    if (ra.tl) tl.dump("AMPS_RECC_RESOLVE_TIMELINE", (size_t)24 * c.C, s);   // the last launch's stamps
 #endif
 }
 

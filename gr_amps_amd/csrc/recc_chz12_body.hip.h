@@ -1,7 +1,9 @@
 // recc_chz12_body.hip.h -- the body of the filter-bank kernel, included once per entry point by recc_channelizer.hip.h (no include
 // guard): chz12_kernel (T = float2, an fc32 block) and chz12_short_kernel (T = chz_sc16, a block of 16-bit I/Q read in place).
-// In scope: the template parameters P, MODE, DEC, the argument `ChzArgs a`, the sample type T of a.block, and the macro
-// CHZ12_BODY_SHORT (1 where T is chz_sc16).  The three ring waits that expand packed samples are chosen by the macro and not by
+// In scope: the template parameters P, MODE, DEC, the argument `ChzArgs a`, the sample type T of a.block, the macro
+// CHZ12_BODY_SHORT (1 where T is chz_sc16), and what recc_channelizer.hip.h includes and defines in front of the entry points: the
+// fold role's parts (recc_chz_fold.hip.h), the passes (recc_chz_fft.hip.h), the slicer (recc_chz_slicer.hip.h), chz_carry_sample and
+// the CHZ_STAMP / CHZ_TL_* timeline macros.  The three ring waits that expand packed samples are chosen by the macro and not by
 // `if constexpr`: a discarded branch that names the half-step's age was enough to move registers in the SLICER role of five of the
 // ten fc32 kernels.
 // Why text and not a function: moved into a __device__ __forceinline__ function -- nothing else changed -- the ten fc32 kernels came
@@ -72,8 +74,7 @@
         // ------------------------------------------------------------------ fold role
         const int t = tid & 255;
         const int64_t lead0 = (int64_t)a.carry_len - (int64_t)a.hist;
-        const int64_t fl = ((int64_t)a.nsamp - D + lead0) / D;              // floor for the non-negative values the FAST path sees
-        const ChzIn<T> in{ (const T *)a.block, a.carry, (int64_t)a.hist, lead0, (int64_t)a.carry_len, (int64_t)a.nsamp, (uint32_t)(fl < 0 ? 0 : fl) };
+        const ChzIn<T> in{ (const T *)a.block, a.carry, (int64_t)a.hist, lead0, (int64_t)a.carry_len, (int64_t)a.nsamp };
         cf2 coef[4][P / 2];
 #pragma unroll
         for (int j = 0; j < 4; j++)
@@ -83,7 +84,7 @@
 #pragma unroll
         for (int k1 = 1; k1 < 4; k1++) tw1[k1 - 1] = chz_twiddle((t >> 4) * k1, 64);
         if constexpr (DEC == CHZ_D768) {
-        // ---- D = 768 (section "D = 768" above): twelve ring slots per branch, three new samples per branch and half-step
+        // ---- D = 768 (recc_chz_fold.hip.h, section "D = 768"): twelve ring slots per branch, three new samples per branch and half-step
         cf2 ring[4][CHZ768_R];
         {
             const int64_t vend = fs * D;                          // multiple of M (fs is a multiple of four)
@@ -136,13 +137,13 @@
                     chz768_loads_generic<BASE>(ring, in, F, t);
                 } else {
                     const uint32_t so = (uint32_t)(h - h_edge) * (uint32_t)(NB * D * sizeof(T));   // this half-step inside the workgroup's descriptor
-                    chz768_fold2_ring<P, BASE, 0>(ring, coef, tw1, dst, t, [&] { chz768_loads_a<BASE, true>(ring, in, F, t, rsrc, so); });
+                    chz768_fold2_ring<P, BASE, 0>(ring, coef, tw1, dst, t, [&] { chz768_loads_a<BASE>(ring, in, t, rsrc, so); });
 #if CHZ12_BODY_SHORT
                     chz768_ring_wait<BASE, 2, true>(ring, h - h_edge);
 #else
                     chz768_ring_wait<BASE, 2>(ring);
 #endif
-                    chz768_fold2_ring<P, BASE, 2>(ring, coef, tw1, dst, t, [&] { chz768_loads_b<BASE, true>(ring, in, F, t, rsrc, so); });
+                    chz768_fold2_ring<P, BASE, 2>(ring, coef, tw1, dst, t, [&] { chz768_loads_b<BASE>(ring, in, t, rsrc, so); });
                 }
                 CHZ_STAMP(h, 2);
             }
@@ -174,8 +175,8 @@
                 for (int q = 0; q < P; q++) ring[jb][q] = in.generic_nb(vlast - (int64_t)M * (P - 1 - q));
             }
         }
-        chz_load_half_ring<P, 0, P, false>(ring, in, fs, t);
-        chz_load_half_ring<P, 0, P + 2, false>(ring, in, fs + NB, t);
+        chz_load_half_ring<P, 0, P>(ring, in, fs, t);
+        chz_load_half_ring<P, 0, P + 2>(ring, in, fs + NB, t);
         constexpr int PERIOD = (P + 4) / 2;                       // half-steps until the ring is back where it started (6)
         static_assert(PERIOD == 6, "the unrolled loop below is written for P = 8");
         // half-step h loads the frames of half-step h + 2: the fast loader is right once those lie inside the new block
@@ -220,15 +221,15 @@
                 if constexpr (EDGE) {
                     chz_fold2_ring<P, BASE, 0>(ring, coef, tw1, dst, t, [] {});
                     chz_fold2_ring<P, BASE, 2>(ring, coef, tw1, dst, t, [] {});
-                    chz_load_half_ring<P, BASE, P + 4, false>(ring, in, F + 2 * NB, t);
+                    chz_load_half_ring<P, BASE, P + 4>(ring, in, F + 2 * NB, t);
                 } else {
                     const uint32_t so = (uint32_t)(h - h_edge) * (uint32_t)(NB * D * sizeof(T));   // this half-step inside the workgroup's descriptor
-                    chz_load1_ring<P, BASE, P + 4, 0, true>(ring, in, F + 2 * NB, t, rsrc, so);
+                    chz_load1_ring<P, BASE, P + 4, 0>(ring, in, t, rsrc, so);
                     chz_fold2_ring<P, BASE, 0>(ring, coef, tw1, dst, t, [&] {
-                        chz_load1_ring<P, BASE, P + 4, 1, true>(ring, in, F + 2 * NB, t, rsrc, so);
-                        chz_load1_ring<P, BASE, P + 4, 2, true>(ring, in, F + 2 * NB, t, rsrc, so);
+                        chz_load1_ring<P, BASE, P + 4, 1>(ring, in, t, rsrc, so);
+                        chz_load1_ring<P, BASE, P + 4, 2>(ring, in, t, rsrc, so);
                     });
-                    chz_fold2_ring<P, BASE, 2>(ring, coef, tw1, dst, t, [&] { chz_load1_ring<P, BASE, P + 4, 3, true>(ring, in, F + 2 * NB, t, rsrc, so); });
+                    chz_fold2_ring<P, BASE, 2>(ring, coef, tw1, dst, t, [&] { chz_load1_ring<P, BASE, P + 4, 3>(ring, in, t, rsrc, so); });
                 }
                 CHZ_STAMP(h, 2);
             }

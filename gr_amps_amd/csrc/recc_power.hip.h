@@ -41,7 +41,7 @@ __global__ __launch_bounds__(256) void chz_power_kernel(ChzArgs a, ChzPowerArgs 
     const int lane = t & 63;
     const int64_t F = (int64_t)p.first_frame + (int64_t)AMPS_RECC_POWER_STRIDE * blockIdx.x;
     const int64_t lead0 = (int64_t)a.carry_len - (int64_t)a.hist;
-    const ChzIn<T> in{ (const T *)a.block, a.carry, (int64_t)a.hist, lead0, (int64_t)a.carry_len, (int64_t)a.nsamp, 0u };
+    const ChzIn<T> in{ (const T *)a.block, a.carry, (int64_t)a.hist, lead0, (int64_t)a.carry_len, (int64_t)a.nsamp };
     const int64_t n0 = (F + 1) * DEC - L;                         // >= -hist: the carry holds it
     // the whole window first: 32 independent loads (64 dwords of an sc16 block), consecutive lanes on consecutive samples
     cf2 x[4][P];

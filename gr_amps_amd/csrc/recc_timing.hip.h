@@ -1,6 +1,8 @@
 // recc_timing.hip.h -- kernel timing (AMPS_RECC_FLAG_TIME_KERNELS, amps_recc_set_timing / amps_recc_get_timing): pairs of events round
 // the launches of a handle, collected into per-stage sums once they have completed.
 #pragma once
+#include <cstdio>
+#include <cstdlib>
 #include <vector>
 #include "amps_recc.h"
 #include "recc_devmem.hip.h"
@@ -71,5 +73,29 @@ inline void collect_spans(TimingState &t)   // collects the spans whose events h
 }
 
 inline void timing_set_mode(TimingState &t, int mode) { t.mode = mode; t.dominant_tick = 0; }
+
+#if defined(CHZ_TIMELINE) || defined(RESOLVE_TIMELINE)
+// Host side of the timeline builds (-DCHZ_TIMELINE: scripts/chz_timeline.py, -DRESOLVE_TIMELINE: scripts/resolve_timeline.py): the
+// device buffer a kernel writes its clock stamps into.  The file is the stamps as they lie in the buffer, 8 bytes each, no header.
+struct TimelineBuf {
+    DevBuf<unsigned long long> dev;
+    // the buffer -- `cap` stamps, allocated at the first call -- with its first n stamps cleared on the stream; null if it cannot be had
+    unsigned long long *clear(size_t cap, size_t n, hipStream_t s)
+    {
+        if (n > cap || (!dev && dev.alloc(cap))) return nullptr;
+        (void)hipMemsetAsync(dev.get(), 0, n * 8, s);
+        return dev.get();
+    }
+    // if the environment variable `env` names a file: wait for the stream, copy the first n stamps back and write them there
+    void dump(const char *env, size_t n, hipStream_t s) const
+    {
+        const char *path = std::getenv(env);
+        if (!path) return;
+        std::vector<unsigned long long> tl(n);
+        if (hipStreamSynchronize(s) == hipSuccess && hipMemcpy(tl.data(), dev.get(), n * 8, hipMemcpyDeviceToHost) == hipSuccess)
+            if (FILE *f = std::fopen(path, "wb")) { std::fwrite(tl.data(), 8, n, f); std::fclose(f); }
+    }
+};
+#endif
 
 } // namespace amps

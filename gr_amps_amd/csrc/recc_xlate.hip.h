@@ -45,7 +45,8 @@
 #include <cstdint>
 #include <vector>
 #include "amps_recc.h"              // AMPS_RECC_SAMPLES_*
-#include "recc_channelizer.hip.h"   // cf2, cmul, chz_sc16
+#include "recc_chz_common.hip.h"    // cf2, cmul, chz_sc16
+#include "recc_devmem.hip.h"
 
 namespace amps {
 

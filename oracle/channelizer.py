@@ -1,7 +1,7 @@
 """numpy (float64) model of the polyphase channelizer seam -- TEST INFRASTRUCTURE ONLY.
 
 Weighted-overlap-add filter bank, the textbook form of what gr_amps_amd/csrc/recc_channelizer.hip.h
-computes: frame m covers samples [ (m+1)D - L, (m+1)D ), is weighted by the prototype h, folded modulo M
+(the fold in recc_chz_fold.hip.h, the FFT in recc_chz_fft.hip.h) computes: frame m covers samples [ (m+1)D - L, (m+1)D ), is weighted by the prototype h, folded modulo M
 with an absolute phase reference and transformed by an M-point DFT.  Samples before the stream are zero.
 It replaces M instances of the reference's freq_xlating_fir_filter_ccc (grc/recctest.grc:889-937).
 """

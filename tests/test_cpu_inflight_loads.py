@@ -1,6 +1,6 @@
 """not gpu: nothing touches a register while an untracked load into it is in flight.
 
-The fold role of chz12_kernel prefetches its inputs with inline-asm `global_load_dwordx2` (recc_channelizer.hip.h:
+The fold role of chz12_kernel prefetches its inputs with inline-asm `global_load_dwordx2` (recc_chz_fold.hip.h:
 chz_load1_ring) so that the compiler's own vmcnt bookkeeping does not drain them at every barrier; the wave waits with a manual
 `s_waitcnt vmcnt(8)` two half-steps later.  The compiler therefore believes the destination registers hold their values from the
 moment the asm statement ends -- and is free to copy them (register-allocation copies at control-flow joins), which on the
@@ -148,7 +148,7 @@ def test_no_register_with_a_load_in_flight_is_touched(asm_text):
     assert len(res) == 10, [r[0] for r in res]                     # the unfused form and the four slicer specs, at D = 512 and at D = 768
     for name, nloads, nwaits, issues in res:
         if "Li768E" in name and "Lin1E" in name:
-            assert nloads == 0, (name, nloads)                     # the unfused form at D = 768 has no fast loader (recc_channelizer.hip.h)
+            assert nloads == 0, (name, nloads)                     # the unfused form at D = 768 has no fast loader (recc_chz12_body.hip.h)
         elif "Li768E" in name:
             assert nloads == 48 and nwaits == 8, (name, nloads, nwaits)   # four unrolled half-steps of twelve loads and two waits
         else:

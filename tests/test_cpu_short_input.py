@@ -3,7 +3,8 @@ checked without a device -- the symbol and its argument validation, the register
 instantiations, and the scan of tests/test_cpu_inflight_loads.py restated for them.
 
 The sc16 fold role loads a packed sample with an untracked `buffer_load_dword` into the LOW register of the ring slot's own pair and
-expands it in place (two v_cvt_f32_i32 with a word select) behind the manual wait that covers it.  That expansion is exactly the kind
+expands it in place (two v_cvt_f32_i32 with a word select) behind the manual wait that covers it (recc_chz_fold.hip.h: chz_load1_ring,
+chz_expand_short, chz_ring_wait).  That expansion is exactly the kind
 of instruction the scan exists for: moved in front of its wait, or fed from a copy, it would read a register whose load has not
 landed.  The walk is the one of test_cpu_inflight_loads.py (straight through the text, on at the loop's latch), the load pattern is
 `buffer_load_dword` with a single destination register."""
