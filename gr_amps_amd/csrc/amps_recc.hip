@@ -463,11 +463,11 @@ static int xlate_configure(amps_recc *h, bool shared, uint32_t decim, double rat
     if (gain == 0.0) gain = 3.0;
     if (cutoff == 0.0) cutoff = 10e3;
     if (width == 0.0) width = 4.5e3;
-    if (!(cutoff > 0.0)) return -EINVAL;
-    // the form's decimations, the symbol rate the handle was built for and the filter's length: xlate_admit, which the plan asks too.
-    // -E2BIG is left to xlate_create, which checks the centres first
+    // a filter the design can make (three taps or more, a cut-off within rate / 2), the form's decimations, the symbol rate the handle
+    // was built for and the filter's length: xlate_admit, which the plan asks too.  -E2BIG is left to xlate_create, which checks the
+    // centres first
     uint32_t ntaps = 0;
-    if (xlate_admit(shared, decim, h->sps, rate_hz, width, &ntaps) == -EINVAL) return -EINVAL;
+    if (xlate_admit(shared, decim, h->sps, rate_hz, cutoff, width, &ntaps) == -EINVAL) return -EINVAL;
     return xlate_create(h->xl, shared, h->C, decim, h->cfg.max_samples_per_push, rate_hz, center_hz,
                         xlate_design_taps(gain, rate_hz, cutoff, width), h->stream.get());
 }
@@ -560,7 +560,7 @@ int amps_recc_xlate_shared_plan(double rate_hz, double width_hz, amps_recc_xlate
         const double sps = std::nearbyint(rate_hz / decim / 20e3);
         if (!(sps >= 1.0 && sps <= 64.0) || !sps_supported((uint32_t)sps)) continue;
         uint32_t ntaps = 0;
-        if (xlate_admit(true, decim, (uint32_t)sps, rate_hz, width_hz, &ntaps)) continue;
+        if (xlate_admit(true, decim, (uint32_t)sps, rate_hz, 10e3, width_hz, &ntaps)) continue;   // the default cut-off of xlate_configure
         if ((size_t)n < cap) out[n] = amps_recc_xlate_plan_t{ decim, (uint32_t)sps, ntaps, 0 };
         n++;
     }

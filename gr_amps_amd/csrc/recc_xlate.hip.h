@@ -370,13 +370,17 @@ inline std::vector<float> xlate_design_taps(double gain, double fs, double cutof
 }
 
 // What a form accepts of a stream at rate_hz decimated by D for a handle of sps samples per symbol, in the order the configuration
-// answers: a kernel for D and the symbol rate met (-EINVAL), the filter's length within that kernel's limit (-E2BIG).  *ntaps = the
-// filter's length wherever the rates are numbers.  amps_recc_set_xlate[_shared] and amps_recc_xlate_shared_plan both ask here.
-inline int xlate_admit(bool shared, uint32_t D, uint32_t sps, double rate_hz, double width_hz, uint32_t *ntaps)
+// answers: a filter the design formula can make, a kernel for D and the symbol rate met (-EINVAL), the filter's length within that
+// kernel's limit (-E2BIG).  *ntaps = the filter's length wherever the rates are numbers.  amps_recc_set_xlate[_shared] and
+// amps_recc_xlate_shared_plan both ask here.
+// The design divides by ntaps - 1 (the window) and firdes.low_pass itself refuses a cut-off beyond rate / 2: a width of 74 rate / 44
+// (1.68 rate) or more gives one tap, 0 / 0 = NaN, so fewer than three taps and a cut-off above Nyquist are no filter.
+inline int xlate_admit(bool shared, uint32_t D, uint32_t sps, double rate_hz, double cutoff_hz, double width_hz, uint32_t *ntaps)
 {
     *ntaps = 0;
     if (!(rate_hz > 0.0) || !(width_hz > 0.0) || std::isinf(rate_hz)) return -EINVAL;
     *ntaps = (uint32_t)xlate_ntaps(rate_hz, width_hz);
+    if (*ntaps < 3 || !(cutoff_hz > 0.0) || !(cutoff_hz <= 0.5 * rate_hz)) return -EINVAL;
     if (!xlate_kernel_for(shared, D)) return -EINVAL;
     // the filtered stream must arrive at the symbol rate the handle was built for
     const double out_rate = rate_hz / D;

@@ -290,6 +290,9 @@ int amps_recc_push_wideband_short(amps_recc_t *h, const int16_t *iq, size_t nsam
  * gain / cutoff_hz / width_hz = 0 select the flow graph's 3.0 / 10 kHz / 4.5 kHz (299 taps at 400 ksps).
  * decim = 0 removes the stage.  Resets nothing else; call before the first push.
  * -EINVAL for a center_hz beyond the rate or not a number (NaN), as amps_recc_set_xlate_shared answers for each of its centres;
+ * -EINVAL for a filter the design cannot make: a width_hz that gives fewer than 3 taps (int(74 rate_hz / (22 width_hz)) made odd: a
+ * width of about 1.68 rate_hz or more gives one tap and a window of 0 / 0) or a cutoff_hz above rate_hz / 2, which firdes.low_pass
+ * refuses too;
  * -E2BIG for a filter of more than 1024 taps (padded to a multiple of 8).  A configuration that is refused leaves the handle's
  * translate stage as it was. */
 typedef struct amps_recc_xlate_cfg {
@@ -326,7 +329,8 @@ int amps_recc_debug_xlate(amps_recc_t *h, const float *iq, size_t ld, size_t nsa
  * amps_recc_push_raw on a shared-configured handle and amps_recc_push_raw_shared on a handle configured with amps_recc_set_xlate
  * answer -ENOSYS, as both do on an unconfigured handle.  Resets nothing else; call before the first push.
  * Errors: -EINVAL (null handle or cfg, wrong struct_size, n_centers != n_channels, null center_hz, a decim other than 0, 1, 2, 4, 5,
- * 6, 8, 10, 12, 16, 20, rate mismatch, a centre beyond the rate); -E2BIG (the filter, padded to a multiple of 8, has more than 1280
+ * 6, 8, 10, 12, 16, 20, rate mismatch, a centre beyond the rate, a width_hz that gives fewer than 3 taps or a cutoff_hz above
+ * rate_hz / 2, as amps_recc_set_xlate); -E2BIG (the filter, padded to a multiple of 8, has more than 1280
  * taps at decim 1, 2, 4, 8 or more than 2400 at decim 5, 6, 10, 12, 16, 20: the default filter fits up to 3.2 Msps, 2391 taps);
  * -ENOSYS (a handle without the IQ seam, or a channel-group handle).
  * A 4 Msps stream (HackRF) at decim 20 needs width_hz >= 5.61 kHz under the 2400 limit: int(74 * 4e6 / (22 * width_hz)) made odd is
@@ -344,7 +348,8 @@ int amps_recc_set_xlate_shared(amps_recc_t *h, const amps_recc_xlate_shared_cfg_
 /* "Which decimation do I ask for?"  The (decim, samples_per_symbol) pairs amps_recc_set_xlate_shared accepts for a stream at rate_hz
  * with transition width width_hz (0 = the flow graph's 4.5 kHz), ascending by decim; ntaps = the filter's length.  Returns how many
  * there are (may exceed cap, of which the first cap are written; out may be NULL with cap 0); 0 for a rate no decimation serves
- * (2.048 Msps, 2.5 Msps: there is no fractional resampler); -EINVAL for a rate that is not a positive number.  Host arithmetic only:
+ * (2.048 Msps, 2.5 Msps: there is no fractional resampler) or a width that gives fewer than 3 taps, which the configuration refuses;
+ * -EINVAL for a rate that is not a positive number.  Host arithmetic only:
  * no handle and no device needed, and it asks the same function the configuration asks, so the two cannot disagree. */
 typedef struct amps_recc_xlate_plan { uint32_t decim, samples_per_symbol, ntaps, _pad; } amps_recc_xlate_plan_t;
 int amps_recc_xlate_shared_plan(double rate_hz, double width_hz, amps_recc_xlate_plan_t *out, size_t cap);

@@ -76,6 +76,27 @@ def test_plan_refuses_a_rate_that_is_not_a_positive_number():
     assert L.amps_recc_xlate_shared_plan(2.4e6, 0.0, None, 4) == -errno.EINVAL      # room announced, none given
 
 
+def test_plan_lists_no_filter_the_design_cannot_make():
+    """int(74 rate / (22 width)) made odd is 1 from a width of 74 rate / 44 (1.68 rate) upwards: the window divides by ntaps - 1 and
+    every tap is NaN.  Such a width is a number, so the call succeeds, and lists nothing; three taps -- the shortest filter the formula
+    makes -- are listed as before, and so is everything longer."""
+    L = capi.load()
+    out = (capi.XlatePlan * 8)()
+    for rate in (2.4e6, 1.2e6, 400e3):
+        edge = 74.0 * rate / 44.0
+        assert len(PLANS[rate]) > 0
+        for width in (1.0001 * edge, 1.7 * rate, 10 * rate, 1e300):                 # one tap
+            assert capi.subband_plan(rate, width) == [], (rate, width)
+            for i in range(8):
+                out[i].decim = 99
+            assert L.amps_recc_xlate_shared_plan(rate, width, out, 8) == 0
+            assert all(p.decim == 99 for p in out)                                         # and nothing written
+        for width, n in ((0.9999 * edge, 3), (74.0 * rate / (22.0 * 3.5), 3), (74.0 * rate / (22.0 * 5.5), 5), (74.0 * rate / (22.0 * 7.5), 7)):
+            assert capi.subband_plan(rate, width) == [(d, s, n) for d, s, _ in PLANS[rate]], (rate, width)
+    assert L.amps_recc_xlate_shared_plan(2.4e6, float("inf"), out, 8) == 0                 # int(0) made odd: one tap
+    assert L.amps_recc_xlate_shared_plan(2.4e6, float("nan"), out, 8) == -errno.EINVAL
+
+
 @pytest.fixture(scope="module")
 def res():
     if not os.path.exists(build.hipcc()) or not shutil.which("c++filt"):
