@@ -10,6 +10,9 @@ amps.recc -> amps.recc_decode] of grc/recctest.grc.  Needs an MI355X: the librar
     python examples/decode_subband.py --rtl       # an RTL-SDR at its usual 2.4 Msps, tuned between the two systems: BOTH systems' 42
                                                   # control channels (313 .. 354, 1.26 MHz) from one cu8 stream, decimated by 12
                                                   # (capi.subband_plan(2.4e6) lists the decimations a rate admits)
+    python examples/decode_subband.py --rtl2048   # the same dongle at 2.048 Msps, the rate most RTL-SDR tools default to: no integer
+                                                  # decimation reaches a symbol rate, so the stage resamples by 5/64 to 160 ksps, 8
+                                                  # samples per symbol (Recc.set_xlate_resampled; capi.resample_plan(2.048e6))
 """
 import os
 import sys
@@ -19,8 +22,16 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gr_amps_amd import capi, synth
 
-RTL = "--rtl" in sys.argv[1:]
-if RTL:
+RTL2048 = "--rtl2048" in sys.argv[1:]
+RTL = "--rtl" in sys.argv[1:] or RTL2048
+INTERP, SPS = 1, 10
+if RTL2048:
+    RATE, INTERP, DECIM, SPS, NSAMP = 2.048e6, 5, 64, 8, 1_024_000   # 0.5 s of signal; 2.048 Msps x 5/64 = 160 ksps per channel
+    assert capi.subband_plan(RATE) == [] and (INTERP, DECIM, SPS, 1531) in capi.resample_plan(RATE)   # 1531 taps per phase
+    TUNED = 0.5 * (capi.reverse_channel_hz(333) + capi.reverse_channel_hz(334))
+    centres = capi.control_channel_centers("AB", TUNED)
+    FIRST, GAP = 10000, 13500
+elif RTL:
     RATE, DECIM, NSAMP = 2.4e6, 12, 1_200_000     # 0.5 s of signal; 2.4 Msps / 12 = 200 ksps per channel
     assert (DECIM, 10, 1793) in capi.subband_plan(RATE)          # the channel filter has 1793 taps at this rate
     TUNED = 0.5 * (capi.reverse_channel_hz(333) + capi.reverse_channel_hz(334))   # between the systems: no channel on the tuner's DC
@@ -33,7 +44,7 @@ else:
     FIRST, GAP = 4000, 11000
 
 try:
-    rx = capi.Recc(n_channels=len(centres), sps=10, max_samples=NSAMP // DECIM, max_bursts=64)
+    rx = capi.Recc(n_channels=len(centres), sps=SPS, max_samples=NSAMP // DECIM if INTERP == 1 else NSAMP * INTERP // DECIM + 1, max_bursts=64)
 except capi.AmpsError as e:
     sys.exit("no MI355X here (%s): the library has no CPU fallback" % e)
 
@@ -42,7 +53,7 @@ k = np.arange(NSAMP)
 x = np.zeros(NSAMP, np.complex128)
 sent = {}
 for c, fc in enumerate(centres):                  # one seizure burst per channel, at its own time
-    iq, truth = synth.make_channel_block(NSAMP, 1, seed=7000 + c, sps=10 * DECIM, snr_db=40.0, first=FIRST + GAP * c)
+    iq, truth = synth.make_channel_block(NSAMP, 1, seed=7000 + c, sps=RATE / 20e3 if INTERP > 1 else 10 * DECIM, snr_db=40.0, first=FIRST + GAP * c)
     x += iq * np.exp(2j * np.pi * fc * k / RATE)
     sent[c] = truth[0][2]
 x = x.astype(np.complex64)
@@ -54,7 +65,10 @@ if RTL:                                           # the dongle's converter: 8 bi
     x = np.clip(np.floor(np.stack([x.real, x.imag], -1) * 4.0 + 128.0), 0, 255).astype(np.uint8)
 
 with rx:
-    rx.set_xlate_shared(RATE, centres, DECIM)
+    if INTERP > 1:
+        rx.set_xlate_resampled(RATE, centres, INTERP, DECIM)
+    else:
+        rx.set_xlate_shared(RATE, centres, DECIM)
     pos = 0
     while pos < NSAMP:                            # blocks of any size: samples short of a decimation step wait in the handle
         n = min(int(rng.integers(10_000, 150_000)), NSAMP - pos)

@@ -91,6 +91,18 @@ class XlatePlan(C.Structure):
     _fields_ = [("decim", C.c_uint32), ("samples_per_symbol", C.c_uint32), ("ntaps", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class XlateResampleCfg(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("interp", C.c_uint32), ("decim", C.c_uint32), ("n_centers", C.c_uint32), ("_pad", C.c_uint32),
+        ("rate_hz", C.c_double), ("gain", C.c_double), ("cutoff_hz", C.c_double), ("width_hz", C.c_double),
+        ("center_hz", C.POINTER(C.c_double)),
+    ]
+
+
+class ResamplePlan(C.Structure):
+    _fields_ = [("interp", C.c_uint32), ("decim", C.c_uint32), ("samples_per_symbol", C.c_uint32), ("ntaps_per_phase", C.c_uint32)]
+
+
 class RcclInfo(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("alive", C.c_int32), ("nranks", C.c_int32), ("rank", C.c_int32),
@@ -130,7 +142,9 @@ EXPORTS = (
     "amps_recc_set_xlate_shared", "amps_recc_push_raw_shared", "amps_recc_debug_xlate_shared",
     "amps_recc_push_raw_shared_as", "amps_recc_push_raw_as", "amps_recc_debug_xlate_shared_as", "amps_recc_debug_xlate_as",
     "amps_recc_xlate_shared_plan",
+    "amps_recc_set_xlate_resampled", "amps_recc_xlate_resample_plan",
 )
+_XLATE_RESAMPLED = ("amps_recc_set_xlate_resampled", "amps_recc_xlate_resample_plan")
 _XLATE_AS = ("amps_recc_push_raw_shared_as", "amps_recc_push_raw_as", "amps_recc_debug_xlate_shared_as", "amps_recc_debug_xlate_as")
 _XLATE_SHARED = ("amps_recc_set_xlate_shared", "amps_recc_push_raw_shared", "amps_recc_debug_xlate_shared")
 _POWER = ("amps_recc_channel_power", "amps_recc_burst_power", "amps_recc_power_ring_snaps")
@@ -224,12 +238,15 @@ def load():
         L.amps_recc_debug_xlate_as.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     if hasattr(L, "amps_recc_xlate_shared_plan"):     # absent only from A/B builds of earlier revisions (AMPS_RECC_LIB)
         L.amps_recc_xlate_shared_plan.argtypes = [C.c_double, C.c_double, C.POINTER(XlatePlan), C.c_size_t]
+    if hasattr(L, "amps_recc_set_xlate_resampled"):   # absent only from A/B builds of earlier revisions (AMPS_RECC_LIB)
+        L.amps_recc_set_xlate_resampled.argtypes = [vp, C.POINTER(XlateResampleCfg)]
+        L.amps_recc_xlate_resample_plan.argtypes = [C.c_double, C.c_double, C.POINTER(ResamplePlan), C.c_size_t]
     L.amps_bch_encode_words.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp]
     L.amps_bch_decode_words.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, vp, vp]
     for name in EXPORTS:
         if name in ("amps_recc_default_slicer", "amps_recc_default_wideband_decim", "amps_recc_debug_exact_slice", "amps_recc_rccl_unique_id", "amps_recc_rccl_init",
                     "amps_recc_push_wideband_bcast", "amps_recc_drain_gather", "amps_recc_debug_slicer_bits",
-                    "amps_recc_push_wideband_short", "amps_recc_xlate_shared_plan") + _NEW_IN_ABI4 + _POWER + _XLATE_SHARED + _XLATE_AS and not hasattr(L, name):
+                    "amps_recc_push_wideband_short", "amps_recc_xlate_shared_plan") + _NEW_IN_ABI4 + _POWER + _XLATE_SHARED + _XLATE_AS + _XLATE_RESAMPLED and not hasattr(L, name):
             continue
         if name not in ("amps_recc_strerror", "amps_recc_burst_size", "amps_recc_destroy"):   # every other entry point returns int
             getattr(L, name).restype = C.c_uint32 if name == "amps_recc_power_ring_snaps" else C.c_int
@@ -482,6 +499,18 @@ class Recc:
         rc = load().amps_recc_set_xlate_shared(self._h, C.byref(x))
         if rc:
             raise AmpsError(rc, "amps_recc_set_xlate_shared")
+
+    def set_xlate_resampled(self, rate_hz, centers_hz, interp, decim, gain=0.0, cutoff_hz=0.0, width_hz=0.0):
+        """set_xlate_shared for the rates no integer decimation serves: the shared stream is resampled by interp / decim (2.048 Msps
+        x 5/64, 2.5 Msps x 2/25, ...) to the handle's sps x 20 kHz by a polyphase resampler behind the per-channel mix
+        (amps_recc_set_xlate_resampled).  interp is 2 ... 5, decim up to 64 and coprime to it; resample_plan(rate_hz) lists the
+        (interp, decim, sps) a rate admits.  push_raw_shared[_as] and debug_xlate_shared[_as] then run this stage; decim 0 removes it."""
+        cen = np.ascontiguousarray(centers_hz, np.float64).reshape(-1)
+        x = XlateResampleCfg(C.sizeof(XlateResampleCfg), int(interp), int(decim), cen.size, 0, rate_hz, gain, cutoff_hz, width_hz,
+                             cen.ctypes.data_as(C.POINTER(C.c_double)))
+        rc = load().amps_recc_set_xlate_resampled(self._h, C.byref(x))
+        if rc:
+            raise AmpsError(rc, "amps_recc_set_xlate_resampled")
 
     @staticmethod
     def _one_row(iq):
@@ -910,6 +939,18 @@ def subband_plan(rate_hz, width_hz=0.0):
     out = (XlatePlan * max(n, 1))()
     n = L.amps_recc_xlate_shared_plan(rate_hz, width_hz, out, n)
     return [(int(p.decim), int(p.samples_per_symbol), int(p.ntaps)) for p in out[:n]]
+
+
+def resample_plan(rate_hz, width_hz=0.0):
+    """Which ratio for a stream at rate_hz that subband_plan has no decimation for?  The (interp, decim, sps, ntaps_per_phase)
+    Recc.set_xlate_resampled accepts for that rate, ascending by (interp, decim).  Needs no GPU (amps_recc_xlate_resample_plan)."""
+    L = load()
+    n = L.amps_recc_xlate_resample_plan(rate_hz, width_hz, None, 0)
+    if n < 0:
+        raise AmpsError(n, "amps_recc_xlate_resample_plan")
+    out = (ResamplePlan * max(n, 1))()
+    n = L.amps_recc_xlate_resample_plan(rate_hz, width_hz, out, n)
+    return [(int(p.interp), int(p.decim), int(p.samples_per_symbol), int(p.ntaps_per_phase)) for p in out[:n]]
 
 
 def control_channel_centers(system, tuned_hz):

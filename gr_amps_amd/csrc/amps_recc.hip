@@ -546,7 +546,7 @@ int amps_recc_set_xlate_shared(amps_recc_t *h, const amps_recc_xlate_shared_cfg_
     if (is_group_handle(h)) return -ENOSYS;
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream.get()));
-    if (x->decim == 0) { if (h->xl.shared) xlate_destroy(h->xl); return 0; }    // removes the form this entry point configures
+    if (x->decim == 0) { if (h->xl.shared && h->xl.L == 1) xlate_destroy(h->xl); return 0; }   // removes the form this entry point configures
     if (x->n_centers != h->C || !x->center_hz) return -EINVAL;
     return xlate_configure(h, true, x->decim, x->rate_hz, x->center_hz, x->gain, x->cutoff_hz, x->width_hz);
 }
@@ -564,6 +564,42 @@ int amps_recc_xlate_shared_plan(double rate_hz, double width_hz, amps_recc_xlate
         if ((size_t)n < cap) out[n] = amps_recc_xlate_plan_t{ decim, (uint32_t)sps, ntaps, 0 };
         n++;
     }
+    return n;
+}
+
+// the shared form behind a rational resampler: the same state, kernels chosen in xlate_run
+int amps_recc_set_xlate_resampled(amps_recc_t *h, const amps_recc_xlate_resample_cfg_t *x)
+{
+    if (!h || !x || x->struct_size != sizeof(amps_recc_xlate_resample_cfg_t)) return -EINVAL;
+    if (!h->cap.carry[0]) return -ENOSYS;                       // the IQ seam must be configured
+    if (is_group_handle(h)) return -ENOSYS;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream.get()));
+    if (x->decim == 0) { if (h->xl.shared && h->xl.L != 1) xlate_destroy(h->xl); return 0; }   // removes the form this entry point configures
+    if (x->n_centers != h->C || !x->center_hz) return -EINVAL;
+    // the defaults of xlate_configure; the prototype is the flow graph's filter at the up-sampled rate, its gain times interp for
+    // the zero stuffing
+    const double gain = x->gain == 0.0 ? 3.0 : x->gain, cutoff = x->cutoff_hz == 0.0 ? 10e3 : x->cutoff_hz, width = x->width_hz == 0.0 ? 4.5e3 : x->width_hz;
+    uint32_t npp = 0;
+    if (xlate_resample_admit(x->interp, x->decim, h->sps, x->rate_hz, cutoff, width, &npp) == -EINVAL) return -EINVAL;
+    return xlate_create(h->xl, true, h->C, x->decim, h->cfg.max_samples_per_push, x->rate_hz, x->center_hz,
+                        xlate_design_taps(gain * x->interp, x->interp * x->rate_hz, cutoff, width), h->stream.get(), x->interp);
+}
+
+int amps_recc_xlate_resample_plan(double rate_hz, double width_hz, amps_recc_resample_plan_t *out, size_t cap)
+{
+    if (width_hz == 0.0) width_hz = 4.5e3;                     // the default of amps_recc_set_xlate_resampled
+    if (!(rate_hz > 0.0) || std::isinf(rate_hz) || !(width_hz > 0.0) || (cap && !out)) return -EINVAL;
+    int n = 0;
+    for (uint32_t interp = XLR_MIN_L; interp <= (uint32_t)XLR_MAX_L; interp++)
+        for (uint32_t decim = interp + 1; decim <= (uint32_t)XLR_MAX_M; decim++) {
+            const double sps = std::nearbyint(rate_hz * interp / decim / 20e3);
+            if (!(sps >= 1.0 && sps <= 64.0) || !sps_supported((uint32_t)sps)) continue;
+            uint32_t npp = 0;
+            if (xlate_resample_admit(interp, decim, (uint32_t)sps, rate_hz, 10e3, width_hz, &npp)) continue;   // the default cut-off
+            if ((size_t)n < cap) out[n] = amps_recc_resample_plan_t{ interp, decim, (uint32_t)sps, npp };
+            n++;
+        }
     return n;
 }
 

@@ -37,6 +37,12 @@
 // (1.0 ... 3.2 Msps, up to 2400 padded taps).  A tile is 256 OUTPUTS, one per lane, D is a kernel argument, one workgroup per (tile,
 // channel) mixes straight from memory.  The mixed window is kept by PHASE: sample n at row n mod D, column n / D, so the lanes of a
 // wave, which want samples D apart, read consecutive 8-byte words.  70 240 bytes of LDS, 2 workgroups per CU.
+//
+// Shared form, rational (xlate_shared_rational_kernel): resampling by L / M for the rates no integer decimation serves (2.048 Msps
+// x 5/64, 2.5 Msps x 2/25, ...).  The polyphase resampler: output k sits at input q_k = floor(k M / L) and uses the
+// taps of phase p_k = (k M) mod L.  The outputs of one residue k mod L are an integer decimation by M with ONE tap set, so a
+// workgroup is L interleaved copies of the wide kernel's FIR: wave r owns residue r, the window is kept by phase mod M as above,
+// and the L tap sets sit in LDS beside it.  L, M and the row length are kernel arguments; 80 KB of LDS, 2 workgroups per CU.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -269,6 +275,99 @@ __global__ __launch_bounds__(256) void xlate_shared_wide_kernel(XlateArgs a)
     if (k < a.nout) a.out[(uint64_t)c * a.ld_out + k] = make_float2(acc.x, acc.y);
 }
 
+// ---- the rational form: resampling by L / M
+constexpr int XLR_MIN_L = 2, XLR_MAX_L = 5;   // interpolations (L = 1 is the integer forms above)
+constexpr int XLR_MAX_M = 64;                 // largest decimation
+constexpr int XLR_MAX_TAPS = 2400;            // padded taps PER PHASE
+constexpr int XLR_MAX_WAVES = 5;              // waves of a workgroup: L residues x S sub-tiles of 64 L outputs
+constexpr int XLR_LDS_BYTES = 80 * 1024;      // the L tap sets, then the mixed window
+__host__ __device__ constexpr uint32_t xlr_gcd(uint32_t a, uint32_t b) { return b == 0 ? a : xlr_gcd(b, a % b); }
+// sub-tiles of a workgroup: as many as keep it within XLR_MAX_WAVES waves (two at L = 2, else one)
+__host__ __device__ constexpr int xlr_subtiles(int L) { return XLR_MAX_WAVES / L; }
+// row length of the phase-major window (M rows): the columns that H + 64 S M staged samples reach, made odd as xlw_row is
+__host__ __device__ constexpr int xlr_row(int M, int ntp, int S) { return (64 * S + (ntp - 1 + M - 1) / M) | 1; }
+__host__ __device__ constexpr int64_t xlr_lds_bytes(int L, int M, int ntp, int S) { return (int64_t)sizeof(float) * L * ntp + (int64_t)sizeof(cf2) * M * xlr_row(M, ntp, S); }
+// The limits of the rational kernel, in this one place: the host asks before it configures (xlate_resample_admit, xlate_create) and
+// the kernel asks again at its top.  0, -EINVAL (no such ratio) or -E2BIG (taps per phase, or tap sets + window beyond the LDS).
+__host__ __device__ constexpr int xlr_limits(uint32_t L, uint32_t M, uint32_t ntp, uint32_t S)
+{
+    if (L < (uint32_t)XLR_MIN_L || L > (uint32_t)XLR_MAX_L || M <= L || M > (uint32_t)XLR_MAX_M || xlr_gcd(L, M) != 1) return -EINVAL;
+    if (S < 1 || L * S > (uint32_t)XLR_MAX_WAVES || ntp < 8 || (ntp & 7)) return -EINVAL;
+    if (ntp > (uint32_t)XLR_MAX_TAPS || xlr_lds_bytes((int)L, (int)M, (int)ntp, (int)S) > XLR_LDS_BYTES) return -E2BIG;
+    return 0;
+}
+// sub-tiles the host launches with: the most the LDS holds
+__host__ __device__ constexpr uint32_t xlr_pick_subtiles(uint32_t L, uint32_t M, uint32_t ntp)
+{
+    uint32_t S = (uint32_t)xlr_subtiles((int)L);
+    while (S > 1 && xlr_limits(L, M, ntp, S)) S--;
+    return S;
+}
+
+struct XlateRationalArgs : XlateArgs {   // block, carry, steps, out, ld_*, n_abs0, carry_*, hist, nsamp, nout, ntp, C as above; D unused
+    uint64_t k_abs0;         // absolute index of this push's first output
+    uint32_t L, M;           // the stream is resampled by L / M; taps is [L][ntp], phase p at taps + p ntp
+    uint32_t S, RL;          // sub-tiles per workgroup (blockDim = 64 L S) and the window's row length, xlr_row(M, ntp, S)
+};
+
+// One workgroup per (tile of 64 L S outputs, channel).  K0 = the tile's first absolute output, K0 M = L Q0 + P0.  Wave w = L s + r
+// (sub-tile s, residue r), lane j owns output K0 + 64 L s + L j + r, which sits at input Q0 + (64 s + j) M + off with
+// off = floor((P0 + r M) / L) < M and uses phase p = (P0 + r M) mod L: both wave-uniform.  Tile-local sample n <-> absolute input
+// Q0 - H + n, kept at zs[(n % M) RL + n / M]; (that output, tap i) is sample (64 s + j) M + H + off - i: with H + off - i = M b + r',
+// zs[r' RL + b + 64 s + j] -- the lanes of a wave on consecutive words.  Ascending taps walk r' downwards through column b, then
+// through whole columns towards column 0, where they end at r' = off.
+template <typename T>
+__global__ __launch_bounds__(64 * XLR_MAX_WAVES) void xlate_shared_rational_kernel(XlateRationalArgs a)
+{
+    __shared__ float4 lds[XLR_LDS_BYTES / sizeof(float4)];
+    const int L = (int)a.L, M = (int)a.M, S = (int)a.S, RL = (int)a.RL;
+    const int H = (int)a.hist;                                   // = ntp - 1
+    const int ntp = (int)a.ntp;
+    // the host's limits (xlr_limits), held here too
+    if (xlr_limits(a.L, a.M, a.ntp, a.S) || RL != xlr_row(M, ntp, S) || (int)blockDim.x != 64 * L * S || H != ntp - 1) return;
+    float *hs = (float *)lds;
+    cf2 *zs = (cf2 *)(hs + L * ntp);                              // L ntp is a multiple of 8 floats
+    const int t = threadIdx.x, BD = 64 * L * S;
+    const uint32_t c = blockIdx.y;
+    const uint64_t KM = (a.k_abs0 + (uint64_t)blockIdx.x * (uint32_t)BD) * (uint32_t)M;
+    const uint64_t Q0 = KM / (uint32_t)L;
+    const int P0 = (int)(KM - Q0 * (uint32_t)L);
+    const int64_t v0 = (int64_t)(Q0 - a.n_abs0);                  // virtual index of tile-local sample 0: Q0 >= n_abs0, see xlate_run
+    const uint64_t nabs0 = Q0 - (uint64_t)H;                      // wraps consistently for the (zero) pre-stream history
+    const uint64_t step = a.steps[c];
+
+    for (int i = t; i < L * ntp; i += BD) hs[i] = a.taps[i];
+    const int W = H + 64 * S * M;                                // the samples the tile's outputs can read, whatever P0 is
+    const int dcol = BD / M, drow = BD - dcol * M;
+    int col = t / M, row = t - col * M;
+    for (int n = t; n < W; n += BD) {
+        zs[row * RL + col] = xl_mix(xl_window(a, a.carry, (const T *)a.block, v0 + n), nabs0 + (uint64_t)n, step);
+        row += drow; col += dcol;
+        if (row >= M) { row -= M; col++; }
+    }
+    __syncthreads();
+
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6), j = t & 63;
+    const int s = w / L, r = w - s * L;
+    const int off = (P0 + r * M) / L, p = (P0 + r * M) - off * L;
+    const float *h = hs + p * ntp;
+    const cf2 *zl = zs + 64 * s + j;
+    const int b0 = (H + off) / M, r0 = (H + off) - b0 * M;
+    cf2 acc = (cf2){ 0.f, 0.f };
+    int i = 0;
+    for (int b = b0; b >= 0; b--) {                              // ascending tap order: the summation order of the spec
+        const int hi = b == b0 ? r0 : M - 1, lo = b == 0 ? off : 0;
+        const cf2 *zp = zl + hi * RL + b;
+#pragma unroll 8
+        for (int e = hi; e >= lo; e--, i++, zp -= RL) {
+            const float hv = h[i];
+            acc = __builtin_elementwise_fma(*zp, (cf2){ hv, hv }, acc);
+        }
+    }
+    const uint64_t k = (uint64_t)blockIdx.x * (uint32_t)BD + (uint32_t)(L * (64 * s + j) + r);
+    if (k < a.nout) a.out[(uint64_t)c * a.ld_out + k] = make_float2(acc.x, acc.y);
+}
+
 // carry_out[r][i] = virtual[r][consumed + i], i < new_len  (separate buffers: the ranges can overlap).  The carry is fc32: the samples
 // taken from the block are converted here, which is what lets the sample type change from one push to the next.
 template <typename T>
@@ -328,18 +427,31 @@ inline size_t xlate_sample_bytes(int format)
     }
 }
 inline uint32_t xlate_max_taps(bool shared, uint32_t D) { return !shared ? XL_MAX_TAPS : xlate_is_wide(D) ? XLW_MAX_TAPS : XLS_MAX_TAPS; }
+typedef void (*xlate_rational_kernel_t)(XlateRationalArgs);
+inline xlate_rational_kernel_t xlate_rational_kernel_for(int format)
+{
+    switch (format) {
+    case AMPS_RECC_SAMPLES_FC32: return xlate_shared_rational_kernel<float2>;
+    case AMPS_RECC_SAMPLES_SC16: return xlate_shared_rational_kernel<xl_sc16>;
+    case AMPS_RECC_SAMPLES_SC8: return xlate_shared_rational_kernel<xl_sc8>;
+    case AMPS_RECC_SAMPLES_CU8: return xlate_shared_rational_kernel<xl_cu8>;
+    default: return nullptr;
+    }
+}
 
 struct XlateState {
     bool enabled = false;
     bool shared = false;             // one input row for all channels, else one per channel
     uint32_t C = 0, rows = 0, D = 0, ntp = 0, hist = 0, carry_cap = 0, carry_len = 0, max_out = 0;
+    uint32_t L = 1;                  // rational form: the stream is resampled by L / D and taps is [L][ntp]; 1: the integer forms
     int cur = 0;
     uint64_t n_abs = 0;
+    uint64_t k_abs = 0;              // rational form: absolute index of the next output
     DevBuf<float> taps;
     DevBuf<uint64_t> steps;          // [C]
-    DevBuf<float2> carry[2];         // [rows][carry_cap] (hist + D samples a row), double-buffered
+    DevBuf<float2> carry[2];         // [rows][carry_cap] (hist + D samples a row; hist + 1 of the rational form), double-buffered
     DevBuf<float2> out;              // [C][max_out]
-    HostStage stage;                 // host-resident blocks: [rows][D * max_out]
+    HostStage stage;                 // host-resident blocks: [rows][D * max_out / L]
 };
 
 // firdes.low_pass(gain, fs, cutoff, width, WIN_BLACKMAN) as the flow graph calls it (grc/recctest.grc:115-155):
@@ -388,6 +500,25 @@ inline int xlate_admit(bool shared, uint32_t D, uint32_t sps, double rate_hz, do
     return (*ntaps + 7) / 8 * 8 > xlate_max_taps(shared, D) ? -E2BIG : 0;
 }
 
+// The rational form's counterpart: a stream at rate_hz resampled by L / M.  The prototype is designed at the up-sampled rate L rate_hz;
+// *ntaps_per_phase = ceil(its length / L) wherever the rates are numbers.  -EINVAL: no filter, no such ratio, the symbol rate not met;
+// -E2BIG: xlr_limits.  amps_recc_set_xlate_resampled and amps_recc_xlate_resample_plan both ask here.
+inline int xlate_resample_admit(uint32_t L, uint32_t M, uint32_t sps, double rate_hz, double cutoff_hz, double width_hz, uint32_t *ntaps_per_phase)
+{
+    *ntaps_per_phase = 0;
+    if (!(rate_hz > 0.0) || !(width_hz > 0.0) || std::isinf(rate_hz)) return -EINVAL;
+    if (L < (uint32_t)XLR_MIN_L || L > (uint32_t)XLR_MAX_L) return -EINVAL;
+    const uint32_t ng = (uint32_t)xlate_ntaps(L * rate_hz, width_hz);
+    *ntaps_per_phase = (ng + L - 1) / L;
+    if (ng < 3 || !(cutoff_hz > 0.0) || !(cutoff_hz <= 0.5 * L * rate_hz)) return -EINVAL;
+    const uint32_t ntp = (*ntaps_per_phase + 7) / 8 * 8;
+    if (xlr_limits(L, M, 8, 1) == -EINVAL) return -EINVAL;
+    // the resampled stream must arrive at the symbol rate the handle was built for
+    const double out_rate = rate_hz * L / M;
+    if (std::fabs(out_rate - 20e3 * sps) > 1e-6 * out_rate) return -EINVAL;
+    return ng > 1000000u ? -E2BIG : xlr_limits(L, M, ntp, 1);
+}
+
 inline void xlate_destroy(XlateState &x) { x = XlateState{}; }
 
 inline int xlate_reset(XlateState &x, hipStream_t s)
@@ -395,15 +526,18 @@ inline int xlate_reset(XlateState &x, hipStream_t s)
     if (!x.enabled) return 0;
     if (hipMemsetAsync(x.carry[0].get(), 0, sizeof(float2) * (size_t)x.rows * x.carry_cap, s) != hipSuccess) return -EIO;
     if (hipMemsetAsync(x.carry[1].get(), 0, sizeof(float2) * (size_t)x.rows * x.carry_cap, s) != hipSuccess) return -EIO;
-    x.cur = 0; x.carry_len = x.hist; x.n_abs = 0;
+    x.cur = 0; x.carry_len = x.hist; x.n_abs = 0; x.k_abs = 0;
     return 0;
 }
 
 // center_hz is [C] (per-row form: C times the same centre).  A configuration that is refused (-EINVAL, -E2BIG) leaves x as it was.
+// L > 1: the rational form (shared, D = M), taps = the prototype at the up-sampled rate, split here into its L phases.
 inline int xlate_create(XlateState &x, bool shared, uint32_t C, uint32_t D, uint32_t max_out, double rate_hz, const double *center_hz,
-                        const std::vector<float> &taps, hipStream_t s)
+                        const std::vector<float> &taps, hipStream_t s, uint32_t L = 1)
 {
-    if (!xlate_kernel_for(shared, D) || C == 0 || !center_hz || taps.empty() || !(rate_hz > 0.0)) return -EINVAL;
+    const bool rational = L != 1;
+    if (rational ? !shared || xlr_limits(L, D, 8, 1) == -EINVAL : !xlate_kernel_for(shared, D)) return -EINVAL;
+    if (C == 0 || !center_hz || taps.empty() || !(rate_hz > 0.0)) return -EINVAL;
     std::vector<uint64_t> steps(C);
     for (uint32_t c = 0; c < C; c++) {
         if (!(std::fabs(center_hz[c]) <= rate_hz)) return -EINVAL;   // a NaN included
@@ -412,15 +546,18 @@ inline int xlate_create(XlateState &x, bool shared, uint32_t C, uint32_t D, uint
         const long double fr = f - std::floor(f);
         steps[c] = (uint64_t)(fr * 18446744073709551616.0L);
     }
-    const uint32_t ntp = (uint32_t)((taps.size() + 7) / 8 * 8);
-    if (ntp > xlate_max_taps(shared, D)) return -E2BIG;
+    if (taps.size() > 1000000u) return -E2BIG;
+    const uint32_t ntp = (uint32_t)(((taps.size() + L - 1) / L + 7) / 8 * 8);   // per phase
+    if (rational ? xlr_limits(L, D, ntp, 1) != 0 : ntp > xlate_max_taps(shared, D)) return -E2BIG;
     xlate_destroy(x);
-    x.shared = shared; x.C = C; x.rows = shared ? 1 : C; x.D = D; x.ntp = ntp; x.hist = ntp - 1; x.carry_cap = ntp + D; x.max_out = max_out;
-    std::vector<float> padded(ntp, 0.0f);
-    for (size_t i = 0; i < taps.size(); i++) padded[i] = taps[i];
-    int rc = x.taps.alloc(ntp) | x.steps.alloc(C) | x.carry[0].alloc((size_t)x.rows * x.carry_cap) | x.carry[1].alloc((size_t)x.rows * x.carry_cap)
+    x.shared = shared; x.C = C; x.rows = shared ? 1 : C; x.D = D; x.L = L; x.ntp = ntp; x.hist = ntp - 1; x.max_out = max_out;
+    // the rational form's next output never sits before the stream's end (xlate_run): its carry is the history alone
+    x.carry_cap = rational ? ntp : ntp + D;
+    std::vector<float> padded((size_t)L * ntp, 0.0f);             // phase p, tap i = taps[L i + p], zero beyond
+    for (size_t i = 0; i < taps.size(); i++) padded[(i % L) * ntp + i / L] = taps[i];
+    int rc = x.taps.alloc(padded.size()) | x.steps.alloc(C) | x.carry[0].alloc((size_t)x.rows * x.carry_cap) | x.carry[1].alloc((size_t)x.rows * x.carry_cap)
            | x.out.alloc((size_t)C * max_out);
-    if (!rc && hipMemcpy(x.taps.get(), padded.data(), sizeof(float) * ntp, hipMemcpyHostToDevice) != hipSuccess) rc = -EIO;
+    if (!rc && hipMemcpy(x.taps.get(), padded.data(), sizeof(float) * padded.size(), hipMemcpyHostToDevice) != hipSuccess) rc = -EIO;
     if (!rc && hipMemcpy(x.steps.get(), steps.data(), sizeof(uint64_t) * C, hipMemcpyHostToDevice) != hipSuccess) rc = -EIO;
     if (rc) { xlate_destroy(x); return rc; }
     x.enabled = true;
@@ -446,37 +583,48 @@ inline int xlate_run(XlateState &x, const void *iq, uint64_t ld, size_t nsamp, i
     if (!sz) return -EINVAL;
     if (!x.enabled) return -ENOSYS;
     if (nsamp == 0) return 0;
-    if (nsamp > (size_t)x.D * x.max_out) return -E2BIG;
+    // the inputs max_out outputs take: D each, or D / L of the rational form (L = 1 otherwise)
+    const uint64_t max_in = (uint64_t)x.D * x.max_out / x.L;
+    if (nsamp > max_in) return -E2BIG;
+    const bool rational = x.L != 1;
     const void *d = iq;
     if (mem == AMPS_MEM_HOST) {
         // the block travels in its own format, staged by the byte; the reserve is that of the largest fc32 block, which covers them all
         const uint8_t *db = nullptr;
         uint64_t ld_bytes = 0;
-        if (int rc = x.stage.stage((const uint8_t *)iq, ld * sz, nsamp * sz, x.rows, sizeof(float2) * x.rows * x.D * x.max_out, &db, &ld_bytes)) return rc;
+        if (int rc = x.stage.stage((const uint8_t *)iq, ld * sz, nsamp * sz, x.rows, sizeof(float2) * x.rows * max_in, &db, &ld_bytes)) return rc;
         d = db; ld = nsamp;
     }
     const uint64_t avail = (uint64_t)(x.carry_len - x.hist) + nsamp;
-    const uint64_t n_out = avail / x.D;
+    // Rational form: after N inputs in all the stream has delivered the outputs k with floor(k D / L) <= N - 1, ceil(L N / D) of them.
+    // The next output therefore sits at or beyond the stream's end: every input is consumed at once (n_abs = N), the carry is the
+    // history alone, and output k's newest sample floor(k D / L) >= n_abs has the virtual index hist + floor(k D / L) - n_abs.
+    const uint64_t n_out = rational ? ((x.n_abs + nsamp) * x.L + x.D - 1) / x.D - x.k_abs : avail / x.D;
     if (n_out > x.max_out) return -E2BIG;
-    XlateArgs a{};
+    XlateRationalArgs a{};
     a.block = d; a.carry = x.carry[x.cur].get(); a.taps = x.taps.get(); a.steps = x.steps.get(); a.out = x.out.get(); a.ld_in = ld; a.ld_out = x.max_out;
     a.n_abs0 = x.n_abs; a.carry_cap = x.carry_cap; a.carry_len = x.carry_len; a.hist = x.hist;
     a.nsamp = (uint32_t)nsamp; a.nout = (uint32_t)n_out; a.ntp = x.ntp; a.C = x.C;
-    if (n_out) {
+    if (n_out && rational) {
+        // a tile is 64 L S outputs, a workgroup per (tile, channel) of as many threads
+        a.k_abs0 = x.k_abs; a.L = x.L; a.M = x.D; a.S = xlr_pick_subtiles(x.L, x.D, x.ntp); a.RL = (uint32_t)xlr_row((int)x.D, (int)x.ntp, (int)a.S);
+        const uint32_t per = 64 * a.L * a.S;
+        hipLaunchKernelGGL(xlate_rational_kernel_for(format), dim3((uint32_t)((n_out + per - 1) / per), x.C), dim3(per), 0, s, a);
+    } else if (n_out) {
         // a tile is XL_TILE inputs, or XLW_OUT outputs of the wide kernel; a workgroup per (tile, row) but for the staged shared form
         const bool wide = x.shared && xlate_is_wide(x.D);
         const uint64_t tiles = wide ? (n_out + XLW_OUT - 1) / XLW_OUT : (n_out * x.D + XL_TILE - 1) / XL_TILE;
         const uint32_t cpg = x.shared && !wide ? xlate_shared_cpg(x.C, tiles) : 1;
         if (wide) a.D = x.D; else a.cpg = cpg;
-        hipLaunchKernelGGL(xlate_kernel_for(x.shared, x.D, format), dim3((uint32_t)tiles, (x.C + cpg - 1) / cpg), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(xlate_kernel_for(x.shared, x.D, format), dim3((uint32_t)tiles, (x.C + cpg - 1) / cpg), dim3(256), 0, s, (XlateArgs)a);
     }
-    const uint32_t consumed = (uint32_t)(n_out * x.D);
+    const uint32_t consumed = rational ? (uint32_t)nsamp : (uint32_t)(n_out * x.D);
     const uint32_t new_len = x.hist + (uint32_t)(avail - (uint64_t)consumed);
     hipLaunchKernelGGL(xlate_carry_kernel_for(format), dim3((new_len + 255) / 256, x.rows), dim3(256), 0, s, d, ld, x.carry[x.cur].get(), x.carry[x.cur ^ 1].get(),
                        x.carry_cap, x.carry_len, consumed, new_len);
     if (hipGetLastError() != hipSuccess) return -EIO;
     if (mem == AMPS_MEM_HOST) { if (int rc = x.stage.arm(s)) return rc; }
-    x.cur ^= 1; x.carry_len = new_len; x.n_abs += consumed;
+    x.cur ^= 1; x.carry_len = new_len; x.n_abs += consumed; x.k_abs += rational ? n_out : 0;
     *nout = (uint32_t)n_out;
     return 0;
 }

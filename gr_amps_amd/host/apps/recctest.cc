@@ -20,6 +20,7 @@
 //                                      channel at center_hz (default +160 kHz, :889-937) -> channel filter + fused chain on the GPU;
 //                                      cutoff_hz (default 0 = the flow graph's 10 kHz) widens the channel filter for mobiles off their carrier
 //   recctest sub  <file.raw> <chunk> <rate_hz> <decim> <c0,c1,...>   one narrowband fc32 capture at rate_hz holding several channels -> gr::amps::recc_subband
+//                 (<decim> may be L/M, e.g. 5/64 for a 2.048 Msps capture: the rational resampler)
 //                                      (the channel filter per centre c0, c1, ... in Hz relative to the capture's centre, decimation `decim` -- 1, 2, 4,
 //                                      5, 6, 8, 10, 12, 16 or 20, with rate_hz / decim = 200 ksps: 2.4 Msps / 12, 2.0 / 10, 3.2 / 16, 1.0 / 5 ... -- and 10
 //                                      samples per symbol behind it; a refused rate is answered with the pairs that rate admits); prints for every record what `wide` prints: its channel (the index into the list), then
@@ -193,7 +194,8 @@ int main(int argc, char **argv)
             src->stop();                                              // as the scheduler does: the root announces its end of stream, the others join until they see it
         } else if (mode == "sub") {
             if (argc < 7) { std::fprintf(stderr, "usage: %s sub <file.raw> <chunk> <rate_hz> <decim> <c0,c1,...>\n"
-                                                "  decim: 1, 2, 4, 5, 6, 8, 10, 12, 16 or 20, rate_hz / decim = 200000 (10 samples per symbol)\n", argv[0]); return 2; }
+                                                "  decim: 1, 2, 4, 5, 6, 8, 10, 12, 16 or 20, rate_hz / decim = 200000 (10 samples per symbol);\n"
+                                                "         or L/M, the rational resampler: 5/64 at 2048000 (8 samples per symbol), 2/25 at 2500000\n", argv[0]); return 2; }
             std::vector<double> centers;
             for (const char *p = argv[6]; *p;) {
                 char *end = nullptr;
@@ -206,7 +208,12 @@ int main(int argc, char **argv)
             const std::string ext = dot == std::string::npos ? "" : path.substr(dot);
             const int format = ext == ".sc16" ? 1 : ext == ".sc8" || ext == ".cs8" ? 2 : ext == ".cu8" ? 3 : 0;   // AMPS_RECC_SAMPLES_*
             const size_t item = format == 0 ? 8 : format == 1 ? 4 : 2;   // bytes per sample
-            auto src = gr::amps::recc_subband::make(std::atof(argv[4]), centers, std::atoi(argv[5]), 10, -1, 0.0, 0.0, format);
+            // <decim> is D, or L/M for the rational resampler; the samples per symbol are what the rate then gives (10 at rate / D = 200 ksps)
+            const char *slash = std::strchr(argv[5], '/');
+            const int interp = slash ? std::atoi(argv[5]) : 1, decim = std::atoi(slash ? slash + 1 : argv[5]);
+            const double rate = std::atof(argv[4]);
+            const int sps = decim > 0 && interp > 0 ? (int)std::lround(rate * interp / decim / 20e3) : 10;
+            auto src = gr::amps::recc_subband::make(rate, centers, decim, sps, -1, 0.0, 0.0, format, interp);
             struct demux : gr::block {
                 std::shared_ptr<gr::basic_block> dec;
                 demux() : gr::block("demux", gr::io_signature::make(0, 0, 0), gr::io_signature::make(0, 0, 0))

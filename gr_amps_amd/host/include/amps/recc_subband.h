@@ -23,12 +23,15 @@ public:
     // a refused combination is answered with what the rate admits (amps_recc_xlate_shared_plan)
     // slicer: -1 = the library default, 0 .. 3 = numeric spec A .. D (include/amps_recc_numerics.h)
     // cutoff_hz / width_hz: 0 = the flow graph's 10 kHz / 4.5 kHz
+    // interp: 1 = decimation alone (the above); 2 ... 5 = the rational resampler, the stream resampled by interp / decim for the rates no
+    //         decimation serves -- 2.048 Msps x 5/64 at 8 samples per symbol, 2.5 Msps x 2/25 at 10 (amps_recc_set_xlate_resampled;
+    //         decim up to 64, coprime to interp).  A refused combination is answered with both plans.
     // input_format: AMPS_RECC_SAMPLES_* of include/amps_recc.h.  0 = one gr_complex per item; 1 (sc16) = two shorts, what a UHD source set
     //         to sc16 or an "interleaved short" file source delivers; 2 (sc8) = two signed bytes (HackRF); 3 (cu8) = two offset-binary
     //         unsigned bytes (RTL-SDR).  The block pushes the items as they are (amps_recc_push_raw_shared_as: 4 or 2 bytes per sample
     //         to the device, no float copy on the host); the records are those of the plainly converted stream.
     static sptr make(double rate_hz, const std::vector<double> &centers_hz, int decim = 4, int samples_per_symbol = 10, int slicer = -1,
-                     double cutoff_hz = 0.0, double width_hz = 0.0, int input_format = 0);
+                     double cutoff_hz = 0.0, double width_hz = 0.0, int input_format = 0, int interp = 1);
 };
 
 } // namespace amps

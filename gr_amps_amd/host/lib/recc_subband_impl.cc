@@ -13,7 +13,7 @@ namespace amps {
 
 class recc_subband_impl : public recc_subband {
     amps_recc_t *d_handle;
-    int d_decim;
+    int d_decim, d_interp;                         // the stream is resampled by d_interp / d_decim; interp 1 = decimated
     int d_format;                                  // AMPS_RECC_SAMPLES_*: what one input item holds
     std::vector<amps_recc_burst_t> d_recs;
     std::vector<unsigned char> d_bursts;
@@ -27,30 +27,42 @@ class recc_subband_impl : public recc_subband {
     }
 
     // what to ask for instead of a refused (rate, decim, samples per symbol): the plan of that rate
-    static std::string refused(double rate_hz, double width_hz, int decim, int sps)
+    // -- both plans: the integer decimations and the interp / decim ratios of the rational resampler
+    static std::string refused(double rate_hz, double width_hz, int decim, int interp, int sps)
     {
         amps_recc_xlate_plan_t plan[16];
         const int n = amps_recc_xlate_shared_plan(rate_hz, width_hz, plan, 16);
+        amps_recc_resample_plan_t rplan[16];
+        const int nr = amps_recc_xlate_resample_plan(rate_hz, width_hz, rplan, 16);
         char buf[96];
-        std::snprintf(buf, sizeof buf, "; asked: %g sps / %d at %d samples per symbol; ", rate_hz, decim, sps);
+        std::snprintf(buf, sizeof buf, "; asked: %g sps x %d / %d at %d samples per symbol; ", rate_hz, interp, decim, sps);
         std::string s = buf;
-        if (n <= 0) return s + "no decimation serves this rate and transition width (decimations 1, 2, 4, 5, 6, 8, 10, 12, 16, 20; see amps_recc_xlate_shared_plan)";
-        s += "this rate admits (decim, samples per symbol, taps):";
+        if (n <= 0 && nr <= 0)
+            return s + "neither a decimation (1, 2, 4, 5, 6, 8, 10, 12, 16, 20; amps_recc_xlate_shared_plan) nor a ratio interp / decim (interp 2 ... 5, "
+                       "decim up to 64; amps_recc_xlate_resample_plan) serves this rate and transition width";
+        if (n > 0) s += "this rate admits (decim, samples per symbol, taps):";
         for (int i = 0; i < std::min(n, 16); i++) {
             std::snprintf(buf, sizeof buf, " (%u, %u, %u)", plan[i].decim, plan[i].samples_per_symbol, plan[i].ntaps);
+            s += buf;
+        }
+        if (nr > 0) s += std::string(n > 0 ? "; and" : "this rate admits") + " (interp, decim, samples per symbol, taps per phase):";
+        for (int i = 0; i < std::min(nr, 16); i++) {
+            std::snprintf(buf, sizeof buf, " (%u, %u, %u, %u)", rplan[i].interp, rplan[i].decim, rplan[i].samples_per_symbol, rplan[i].ntaps_per_phase);
             s += buf;
         }
         return s;
     }
 
 public:
-    recc_subband_impl(double rate_hz, const std::vector<double> &centers_hz, int decim, int sps, int slicer, double cutoff_hz, double width_hz, int input_format)
+    recc_subband_impl(double rate_hz, const std::vector<double> &centers_hz, int decim, int sps, int slicer, double cutoff_hz, double width_hz, int input_format,
+                      int interp)
         : gr::sync_block("recc_subband", gr::io_signature::make(1, 1, (int)std::max<size_t>(item_size(input_format), 1)), gr::io_signature::make(0, 0, 0)),
-          d_handle(nullptr), d_decim(decim), d_format(input_format), d_recs(kMaxRecs), d_bursts((size_t)kMaxRecs * AMPS_RECC_CAPTURE_SYMS)
+          d_handle(nullptr), d_decim(decim), d_interp(interp), d_format(input_format), d_recs(kMaxRecs), d_bursts((size_t)kMaxRecs * AMPS_RECC_CAPTURE_SYMS)
     {
         if (!item_size(input_format)) throw std::runtime_error("amps::recc_subband: input_format must be 0 (fc32), 1 (sc16), 2 (sc8) or 3 (cu8)");
         if (centers_hz.empty()) throw std::runtime_error("amps::recc_subband: no centres");
-        if (decim < 1) throw std::runtime_error("amps::recc_subband: decim must be 1, 2, 4, 5, 6, 8, 10, 12, 16 or 20");
+        if (decim < 1) throw std::runtime_error("amps::recc_subband: decim must be 1, 2, 4, 5, 6, 8, 10, 12, 16 or 20, or up to 64 behind an interp of 2 ... 5");
+        if (interp < 1) throw std::runtime_error("amps::recc_subband: interp must be 1 (decimation alone) or 2 ... 5");
         amps_recc_cfg_t cfg = {};
         cfg.struct_size = sizeof(cfg);
         cfg.n_channels = (uint32_t)centers_hz.size();
@@ -62,18 +74,31 @@ public:
                                                   : slicer == 2 ? AMPS_RECC_FLAG_SLICER_SINE : slicer == 3 ? AMPS_RECC_FLAG_SLICER_EXACT : 0u);
         int rc = amps_recc_create(&d_handle, &cfg);
         if (rc != 0) throw std::runtime_error(std::string("amps::recc_subband: ") + amps_recc_strerror(rc));
-        amps_recc_xlate_shared_cfg_t x = {};
-        x.struct_size = sizeof(x);
-        x.decim = (uint32_t)decim;
-        x.n_centers = (uint32_t)centers_hz.size();
-        x.rate_hz = rate_hz;
-        x.cutoff_hz = cutoff_hz;                       // 0 = the flow graph's 10 kHz / 4.5 kHz
-        x.width_hz = width_hz;
-        x.center_hz = centers_hz.data();
-        rc = amps_recc_set_xlate_shared(d_handle, &x);
+        if (interp == 1) {
+            amps_recc_xlate_shared_cfg_t x = {};
+            x.struct_size = sizeof(x);
+            x.decim = (uint32_t)decim;
+            x.n_centers = (uint32_t)centers_hz.size();
+            x.rate_hz = rate_hz;
+            x.cutoff_hz = cutoff_hz;                   // 0 = the flow graph's 10 kHz / 4.5 kHz
+            x.width_hz = width_hz;
+            x.center_hz = centers_hz.data();
+            rc = amps_recc_set_xlate_shared(d_handle, &x);
+        } else {                                       // the rational resampler: 2.048 Msps x 5/64, 2.5 Msps x 2/25, ...
+            amps_recc_xlate_resample_cfg_t x = {};
+            x.struct_size = sizeof(x);
+            x.interp = (uint32_t)interp;
+            x.decim = (uint32_t)decim;
+            x.n_centers = (uint32_t)centers_hz.size();
+            x.rate_hz = rate_hz;
+            x.cutoff_hz = cutoff_hz;
+            x.width_hz = width_hz;
+            x.center_hz = centers_hz.data();
+            rc = amps_recc_set_xlate_resampled(d_handle, &x);
+        }
         if (rc != 0) {
             amps_recc_destroy(d_handle);
-            throw std::runtime_error(std::string("amps::recc_subband (xlate): ") + amps_recc_strerror(rc) + refused(rate_hz, width_hz, decim, sps));
+            throw std::runtime_error(std::string("amps::recc_subband (xlate): ") + amps_recc_strerror(rc) + refused(rate_hz, width_hz, decim, interp, sps));
         }
         message_port_register_out(pmt::mp("bursts"));
         message_port_register_out(pmt::mp("records"));
@@ -84,7 +109,8 @@ public:
     {
         const unsigned char *in = (const unsigned char *)input_items[0];
         const size_t item = item_size(d_format);
-        const int max_push = (kMaxOut - 1) * d_decim;          // a leftover sample of the last push may complete one more output
+        // a leftover sample of the last push may complete one more output; interp outputs per decim inputs
+        const int max_push = (int)((long long)(kMaxOut - 1) * d_decim / d_interp);
         int done = 0;
         while (done < noutput_items) {
             int n = noutput_items - done;
@@ -110,9 +136,9 @@ public:
 };
 
 recc_subband::sptr recc_subband::make(double rate_hz, const std::vector<double> &centers_hz, int decim, int samples_per_symbol, int slicer,
-                                      double cutoff_hz, double width_hz, int input_format)
+                                      double cutoff_hz, double width_hz, int input_format, int interp)
 {
-    return gnuradio::get_initial_sptr(new recc_subband_impl(rate_hz, centers_hz, decim, samples_per_symbol, slicer, cutoff_hz, width_hz, input_format));
+    return gnuradio::get_initial_sptr(new recc_subband_impl(rate_hz, centers_hz, decim, samples_per_symbol, slicer, cutoff_hz, width_hz, input_format, interp));
 }
 
 } // namespace amps

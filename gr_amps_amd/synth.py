@@ -142,8 +142,9 @@ def symbol_stream(n_symbols, bursts, rng, idle="random"):
 
 def symbol_waveform(sym, sps, sym_ppm=0.0):
     """+-1 symbol values held for sps / (1 + sym_ppm 1e-6) samples each: a mobile whose bit clock runs sym_ppm parts per million
-    fast (TIA-553 allows 10 kbit/s +- 1 bit/s = +-100 ppm).  sym_ppm = 0 is np.repeat(sym, sps)."""
-    if sym_ppm == 0.0:
+    fast (TIA-553 allows 10 kbit/s +- 1 bit/s = +-100 ppm).  sym_ppm = 0 is np.repeat(sym, sps) -- at an integer sps; a sample rate
+    that is no multiple of the symbol rate (2.048 Msps: sps = 102.4) takes the sampling path below whatever sym_ppm is."""
+    if sym_ppm == 0.0 and sps == int(sps):
         return np.repeat(sym, sps)
     rate = (1.0 + sym_ppm * 1e-6) / sps                       # symbols per sample
     n = int(np.floor(len(sym) / rate))
@@ -175,7 +176,9 @@ def make_channel_block(n_samples, n_bursts, seed, sps=10, snr_db=30.0, first=400
     where truth = [(sample_offset, kind, min10, esn, dialed, words36)]."""
     rng = np.random.default_rng(seed)
     burst_len = (BURST_PREFIX_BITS + 7 + 7 * 240) * 2 * sps
-    spacing = spacing or (burst_len + (TRIGGER_SYMS + 200) * sps)
+    if burst_len != int(burst_len):                           # a non-integer sps (102.4 at 2.048 Msps): whole samples, rounded up
+        burst_len = int(burst_len) + 1
+    spacing = spacing or (burst_len + int((TRIGGER_SYMS + 200) * sps))
     truth, bursts = [], []
     off = first + (int(rng.integers(0, 997)) if jitter else 0)
     for _ in range(n_bursts):

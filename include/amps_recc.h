@@ -51,7 +51,9 @@ extern "C" {
                                      still 4, four entry points added and nothing changed: amps_recc_push_raw_shared_as / _push_raw_as /
                                      _debug_xlate_shared_as / _debug_xlate_as, the translate seams on an SDR's integer samples (AMPS_RECC_SAMPLES_*);
                                      still 4, one entry point added and nothing changed: amps_recc_xlate_shared_plan, with the shared translate seam's
-                                     decimations 5, 6, 10, 12, 16 and 20) */
+                                     decimations 5, 6, 10, 12, 16 and 20;
+                                     still 4, two entry points added and nothing changed: amps_recc_set_xlate_resampled / amps_recc_xlate_resample_plan,
+                                     the shared translate seam behind a rational L / M resampler) */
 
 /* protocol constants of the reference */
 #define AMPS_RECC_TRIGGER_SYMS 74   /* lib/recc_impl.cc:76-77: 37 bits x 2 Manchester symbols   */
@@ -348,11 +350,12 @@ int amps_recc_set_xlate_shared(amps_recc_t *h, const amps_recc_xlate_shared_cfg_
 /* "Which decimation do I ask for?"  The (decim, samples_per_symbol) pairs amps_recc_set_xlate_shared accepts for a stream at rate_hz
  * with transition width width_hz (0 = the flow graph's 4.5 kHz), ascending by decim; ntaps = the filter's length.  Returns how many
  * there are (may exceed cap, of which the first cap are written; out may be NULL with cap 0); 0 for a rate no decimation serves
- * (2.048 Msps, 2.5 Msps: there is no fractional resampler) or a width that gives fewer than 3 taps, which the configuration refuses;
+ * (2.048 Msps, 2.5 Msps: these take the rational resampler, amps_recc_set_xlate_resampled) or a width that gives fewer than 3 taps, which the configuration refuses;
  * -EINVAL for a rate that is not a positive number.  Host arithmetic only:
  * no handle and no device needed, and it asks the same function the configuration asks, so the two cannot disagree. */
 typedef struct amps_recc_xlate_plan { uint32_t decim, samples_per_symbol, ntaps, _pad; } amps_recc_xlate_plan_t;
 int amps_recc_xlate_shared_plan(double rate_hz, double width_hz, amps_recc_xlate_plan_t *out, size_t cap);
+/* For the rates it answers with nothing, ask amps_recc_xlate_resample_plan below. */
 /* iq is ONE row of nsamp samples at rate_hz.  Any nsamp <= decim * max_samples_per_push (-E2BIG beyond); leftover samples (fewer than
  * decim) wait for the next push.  Host and device blocks follow the ownership rules of amps_recc_push_raw; amps_recc_reset restarts
  * the stream; ms_xlate of amps_recc_get_timing counts the kernel.  -ESTALE as the data seams. */
@@ -360,6 +363,48 @@ int amps_recc_push_raw_shared(amps_recc_t *h, const float *iq, size_t nsamp, int
 /* test tap: run only the shared translate stage (continuing its stream); out is host [n_channels][out_ld] fc32 */
 int amps_recc_debug_xlate_shared(amps_recc_t *h, const float *iq, size_t nsamp, int mem,
                                  float *out, size_t out_ld, size_t *nout);
+
+/* translate seam, shared form behind a rational resampler: the rates no integer decimation brings to samples_per_symbol * 20 kHz --
+ * 2.048 Msps (the RTL-SDR tools' default) * 5/64 = 160 ksps, 2.5 Msps (USRP N2xx, Airspy) * 2/25 = 200 ksps, 3.0 Msps * 2/25 = 240,
+ * 1.024 Msps * 5/32, 768 ksps (Airspy HF+) * 5/24 or 5/16, 1.25 Msps * 4/25; amps_recc_xlate_resample_plan lists what a rate admits.
+ * DEFINITION.  The stream at rate_hz is resampled by interp / decim = L / M to samples_per_symbol * 20 kHz by the textbook polyphase
+ * resampler behind the per-channel mix of amps_recc_set_xlate_shared.  The prototype g = firdes.low_pass(gain * L, L * rate_hz,
+ * cutoff_hz, width_hz), the flow graph's filter designed at the up-sampled rate with its gain times L for the zero stuffing, has
+ * N_g = int(74 L rate_hz / (22 width_hz)) made odd taps.  Phase p has the taps h_p[i] = g[L i + p], zero beyond N_g:
+ * Np = ceil(N_g / L) taps per phase, zero padded to a multiple of 8 (ntp).  For output k write k M = L q_k + p_k, 0 <= p_k < L; then
+ *     y_c[k] = sum_{i = 0}^{ntp - 1} h_{p_k}[i] z_c[q_k - i],   z_c[n] = x[n] e^{-j 2 pi center_hz[c] n / rate_hz},
+ * the mix of sample n taken from its absolute index as in the integer forms, the sum one fp32 fma chain in ascending i, samples
+ * before the stream's start zero.  After N input samples in all the stream has delivered ceil(L N / M) outputs -- the k with
+ * q_k <= N - 1; a push delivers the difference to what was delivered before, and later outputs wait for their last input.  The
+ * result does not depend on push boundaries, the sample format or the other channels.
+ * interp: 2 ... 5; decim: interp < decim <= 64 with no factor in common with interp; 0 removes the stage.  rate_hz * interp / decim
+ * must equal samples_per_symbol * 20 kHz; gain / cutoff_hz / width_hz = 0 select the flow graph's 3.0 / 10 kHz / 4.5 kHz.
+ * Once configured, amps_recc_push_raw_shared, _push_raw_shared_as, _debug_xlate_shared and _debug_xlate_shared_as run this stage: any
+ * nsamp that delivers at most max_samples_per_push outputs (-E2BIG beyond).  The three translate forms exclude each other:
+ * configuring one removes the others.  Resets nothing else; call before the first push.
+ * Errors, as amps_recc_set_xlate_shared: -EINVAL (null handle or cfg, wrong struct_size, n_centers != n_channels, null center_hz,
+ * interp outside 2 ... 5, decim <= interp or > 64, a common factor, rate mismatch, a centre beyond the rate, a width_hz that gives
+ * fewer than 3 taps or a cutoff_hz above interp * rate_hz / 2); -E2BIG (more than 2400 padded taps per phase, or the interp tap
+ * sets and the mixed window of 64 decim + ntp samples beyond 80 KB of LDS: the default filter fits every ratio above, 2.048 Msps *
+ * 5/64 has 1531 taps per phase); -ENOSYS (a handle without the IQ seam, or a channel-group handle).  A configuration that is
+ * refused leaves the handle's translate stage as it was. */
+typedef struct amps_recc_xlate_resample_cfg {
+    uint32_t struct_size;
+    uint32_t interp;             /* L: 2 ... 5 */
+    uint32_t decim;              /* M: interp < M <= 64, gcd(L, M) = 1; 0 removes the stage */
+    uint32_t n_centers;          /* must equal cfg.n_channels */
+    uint32_t _pad;
+    double   rate_hz;            /* rate_hz * interp / decim == samples_per_symbol * 20 kHz */
+    double   gain, cutoff_hz, width_hz;  /* 0 = the flow graph's 3.0 / 10 kHz / 4.5 kHz, as amps_recc_set_xlate */
+    const double *center_hz;     /* [n_centers], |center| <= rate_hz; duplicates are legal */
+} amps_recc_xlate_resample_cfg_t;
+int amps_recc_set_xlate_resampled(amps_recc_t *h, const amps_recc_xlate_resample_cfg_t *x);
+/* "Which ratio do I ask for?"  The (interp, decim, samples_per_symbol) triples amps_recc_set_xlate_resampled accepts for a stream at
+ * rate_hz with transition width width_hz (0 = 4.5 kHz), ascending by (interp, decim); ntaps_per_phase = ceil(N_g / interp).  Return
+ * value, cap and errors as amps_recc_xlate_shared_plan; 0 for a rate no admitted ratio serves (2.4 Msps: integer decimation is its
+ * answer).  Host arithmetic only, and it asks the same function the configuration asks. */
+typedef struct amps_recc_resample_plan { uint32_t interp, decim, samples_per_symbol, ntaps_per_phase; } amps_recc_resample_plan_t;
+int amps_recc_xlate_resample_plan(double rate_hz, double width_hz, amps_recc_resample_plan_t *out, size_t cap);
 
 /* translate seams on an SDR's integer samples, read IN PLACE.  No SDR delivers fc32: USRP-class devices, Lime and Pluto deliver
  * interleaved int16 ("sc16"), HackRF int8 ("sc8"), RTL-SDR offset-binary uint8 ("cu8"), and their capture files hold the same. */
