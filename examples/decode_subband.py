@@ -13,6 +13,9 @@ amps.recc -> amps.recc_decode] of grc/recctest.grc.  Needs an MI355X: the librar
     python examples/decode_subband.py --rtl2048   # the same dongle at 2.048 Msps, the rate most RTL-SDR tools default to: no integer
                                                   # decimation reaches a symbol rate, so the stage resamples by 5/64 to 160 ksps, 8
                                                   # samples per symbol (Recc.set_xlate_resampled; capi.resample_plan(2.048e6))
+    python examples/decode_subband.py --rssi      # with any of the above: the mobiles arrive 0, 3, 6, 9 and 12 dB down in turn, the handle
+                                                  # keeps received power (Recc(stream_power=True)) and every decoded MIN is printed with
+                                                  # its burst power in dB relative to the strongest (Recc.burst_power)
 """
 import os
 import sys
@@ -24,6 +27,7 @@ from gr_amps_amd import capi, synth
 
 RTL2048 = "--rtl2048" in sys.argv[1:]
 RTL = "--rtl" in sys.argv[1:] or RTL2048
+RSSI = "--rssi" in sys.argv[1:]
 INTERP, SPS = 1, 10
 if RTL2048:
     RATE, INTERP, DECIM, SPS, NSAMP = 2.048e6, 5, 64, 8, 1_024_000   # 0.5 s of signal; 2.048 Msps x 5/64 = 160 ksps per channel
@@ -44,7 +48,8 @@ else:
     FIRST, GAP = 4000, 11000
 
 try:
-    rx = capi.Recc(n_channels=len(centres), sps=SPS, max_samples=NSAMP // DECIM if INTERP == 1 else NSAMP * INTERP // DECIM + 1, max_bursts=64)
+    rx = capi.Recc(n_channels=len(centres), sps=SPS, max_samples=NSAMP // DECIM if INTERP == 1 else NSAMP * INTERP // DECIM + 1, max_bursts=64,
+                   stream_power=RSSI)
 except capi.AmpsError as e:
     sys.exit("no MI355X here (%s): the library has no CPU fallback" % e)
 
@@ -54,6 +59,8 @@ x = np.zeros(NSAMP, np.complex128)
 sent = {}
 for c, fc in enumerate(centres):                  # one seizure burst per channel, at its own time
     iq, truth = synth.make_channel_block(NSAMP, 1, seed=7000 + c, sps=RATE / 20e3 if INTERP > 1 else 10 * DECIM, snr_db=40.0, first=FIRST + GAP * c)
+    if RSSI:
+        iq = iq * 10.0 ** (-3.0 * (c % 5) / 20.0)
     x += iq * np.exp(2j * np.pi * fc * k / RATE)
     sent[c] = truth[0][2]
 x = x.astype(np.complex64)
@@ -78,10 +85,17 @@ with rx:
             rx.push_raw_shared(x[pos:pos + n])
         pos += n
     recs = rx.drain()
+    power, nblk = rx.burst_power(recs) if RSSI else (None, None)
 print("%d bursts sent, %d decoded" % (len(sent), len(recs)))
 for r in recs:
     ch, got = int(r["channel"]), r["min"].decode()
     print("  channel %3d (AMPS %d, %.2f MHz)  MIN %s  class %d  words valid %s  %s"
           % (ch, 313 + ch, (TUNED + centres[ch]) / 1e6, got, int(r["msg_class"]), "".join(str(int(v)) for v in r["valid"]),
              "ok" if sent.get(ch) == got else "MISMATCH"))
+if RSSI and len(recs):
+    print("burst power, dB relative to the strongest (sent 0, -3, -6, -9, -12 dB in turn):")
+    for r, p, nb in zip(recs, power, nblk):
+        ch = int(r["channel"])
+        rel = "%6.1f dB" % (10.0 * np.log10(p / power.max())) if nb else "  (not held)"
+        print("  channel %3d  MIN %s  %s  over %d blocks of 256 samples (sent %d dB)" % (ch, r["min"].decode(), rel, int(nb), -3 * (ch % 5)))
 sys.exit(0 if len(recs) == len(sent) and all(sent.get(int(r["channel"])) == r["min"].decode() for r in recs) else 1)

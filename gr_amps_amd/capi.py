@@ -25,7 +25,8 @@ FLAG_SLICER_ATAN = 64
 FLAG_SLICER_EXACT = 128
 FLAG_FIXED_TIMING = 256
 FLAG_CHANNEL_POWER = 512
-POWER_STRIDE = 256                       # AMPS_RECC_POWER_STRIDE: channel-rate samples between two power snapshots
+FLAG_STREAM_POWER = 0x400                # received power on the IQ and translate seams (block means; channel_power: the wideband seam's snapshots)
+POWER_STRIDE = 256                       # AMPS_RECC_POWER_STRIDE: channel-rate samples between two power snapshots / in one power block
 
 # slicer names accepted by Recc(slicer=...): numeric spec of include/amps_recc_numerics.h -> cfg flag
 _SLICER_FLAGS = {None: 0, "default": 0, "atan": FLAG_SLICER_ATAN, 0: FLAG_SLICER_ATAN, "A": FLAG_SLICER_ATAN,
@@ -339,7 +340,7 @@ class Recc:
 
     def __init__(self, n_channels=1, sps=None, max_samples=0, max_bursts=1024, device=-1, time_kernels=False,
                  stream=None, wideband=None, majority=False, unfused_wideband=False, sync_tolerance=0, slicer="default",
-                 sync_torch=True, keep_bursts=False, fixed_timing=False, channel_power=False):
+                 sync_torch=True, keep_bursts=False, fixed_timing=False, channel_power=False, stream_power=False):
         L = load()
         if isinstance(slicer, bool) or slicer not in _SLICER_FLAGS:        # a typo must not run a different numeric spec silently
             raise ValueError("slicer must be one of %r" % sorted(map(str, _SLICER_FLAGS)))
@@ -366,7 +367,7 @@ class Recc:
                      | (FLAG_UNFUSED_WIDEBAND if unfused_wideband else 0)
                      | _SLICER_FLAGS[slicer]
                      | (FLAG_KEEP_BURSTS if keep_bursts else 0) | (FLAG_FIXED_TIMING if fixed_timing else 0)
-                     | (FLAG_CHANNEL_POWER if channel_power else 0))
+                     | (FLAG_CHANNEL_POWER if channel_power else 0) | (FLAG_STREAM_POWER if stream_power else 0))
         cfg.stream = stream
         cfg.sync_tolerance = sync_tolerance
         if wideband:
@@ -853,16 +854,20 @@ class Recc:
                 raise AmpsError(rc, "amps_recc_debug_slicer_bits")
         return out, produced.value
 
-    # ---- received power of the wideband seam (handles created with channel_power=True)
+    # ---- received power: of the wideband seam (handles created with channel_power=True: one snapshot every 256 frames) and of the IQ
+    # and translate seams (stream_power=True: the mean of every block of 256 channel-rate samples)
     @property
     def power_ring_snaps(self):
-        """snapshots the handle keeps per row (the slicer-bit ring's span / 256); 0 without channel_power"""
+        """snapshots / blocks the handle keeps per row (the slicer-bit ring's span / 256); 0 without channel_power or stream_power"""
         return int(load().amps_recc_power_ring_snaps(self._h))
 
     def channel_power(self, first=None, n=None):
-        """(float32 [rows][n], first): P[row][first + i] = |filter-bank output|^2 of the frame at channel-rate sample 256 (first + i),
-        linear and unscaled, once the pushes so far have finished (amps_recc_channel_power).  Default: everything currently held;
-        `first` alone: from there to the newest snapshot."""
+        """(float32 [rows][n], first): P[row][first + i], linear and unscaled, once the pushes so far have finished
+        (amps_recc_channel_power).  Wideband seam (channel_power): |filter-bank output|^2 of the frame at channel-rate sample
+        256 (first + i).  IQ and translate seams (stream_power): the mean of |y|^2 over the channel-rate samples [256 (first + i),
+        256 (first + i + 1)), which exists once the whole block has been sliced.  Default: everything currently held -- on either seam
+        [max(ceil(origin / 256), produced - ring), produced), `produced` as the library reports it; `first` alone: from there to the
+        newest."""
         L = load()
         rows, prod = C.c_uint32(0), C.c_uint64(0)
         rc = L.amps_recc_channel_power(self._h, 0, 0, None, 0, C.byref(rows), C.byref(prod))
@@ -880,8 +885,9 @@ class Recc:
         return out, int(first)
 
     def burst_power(self, records):
-        """(mean float32 [n], count uint32 [n]) for records as drain() returns them: the mean power snapshot of each record's channel over
-        its capture and the number of snapshots averaged, (0.0, 0) where the ring no longer (or not yet) holds them (amps_recc_burst_power)"""
+        """(mean float32 [n], count uint32 [n]) for records as drain() returns them: the mean power snapshot (wideband seam) or power
+        block (IQ and translate seams) of each record's channel over its capture and the number averaged, (0.0, 0) where the ring no
+        longer (or not yet) holds them (amps_recc_burst_power)"""
         recs = np.ascontiguousarray(records, BURST_DTYPE).reshape(-1)
         mean, cnt = np.zeros(recs.size, np.float32), np.zeros(recs.size, np.uint32)
         rc = load().amps_recc_burst_power(self._h, _hostptr(recs), recs.size, _hostptr(mean), _hostptr(cnt))

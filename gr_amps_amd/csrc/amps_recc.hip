@@ -46,6 +46,7 @@ struct amps_recc {
     BchScratch bch;                   // amps_bch_*
     ChannelizerState chz;             // wideband seam: the filter bank
     PowerState pow;                   // received power (AMPS_RECC_FLAG_CHANNEL_POWER; the ring itself is chz.pow_ring)
+    StreamPowerState spow;            // received power of the IQ and translate seams (AMPS_RECC_FLAG_STREAM_POWER)
     XlateState xl;                    // the translate stage in the form configured last (amps_recc_set_xlate / _set_xlate_shared)
     RefState ref;                     // reference-timing seam (G2 -> G3 -> G4 as the flow graph wires them; created on first use)
     RcclState rccl;                   // one band over several GPUs: amps_recc_rccl_init / amps_recc_push_wideband_bcast
@@ -74,10 +75,14 @@ int sync_event(amps_recc *h, hipEvent_t e)
 // nothing on the other seams
 bool is_group_handle(const amps_recc *h) { return h->chz.enabled && h->chz.groups > 1; }
 
+// what capture_run_iq is handed: the power ring of a handle that keeps one
+const StreamPowerState *stream_power_of(const amps_recc *h) { return h->spow.ring ? &h->spow : nullptr; }
+
 int reset_state(amps_recc *h)
 {
     hipStream_t s = h->stream.get();
     if (int rc = capture_reset(h->cap, s)) return rc;
+    if (int rc = stream_power_reset(h->spow, s)) return rc;
     if (int rc = records_reset(h->lists, s)) return rc;
     if (int rc = symbols_reset(h->sym, s)) return rc;
     if (int rc = channelizer_reset(h->chz, s)) return rc;
@@ -144,6 +149,10 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
     if (cfg->n_channels >= (1u << (64 - CAPQ_POS_BITS))) return -EINVAL;
     // received power exists where the fused filter bank runs: the snapshot kernel re-reads that launch's block and carry
     if ((cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER) && (!cfg->wideband_channels || (cfg->flags & AMPS_RECC_FLAG_UNFUSED_WIDEBAND))) return -EINVAL;
+    // on the IQ and translate seams the channel-rate stream itself is read once more: a flag of its own, for handles with the IQ seam
+    // and no filter bank
+    if ((cfg->flags & AMPS_RECC_FLAG_STREAM_POWER) &&
+        (cfg->wideband_channels || cfg->max_samples_per_push == 0 || (cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER))) return -EINVAL;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return -ENODEV;
     int dev = cfg->device;
@@ -182,6 +191,7 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
     step("pinned record lists mapped");
     if (!rc && cfg->max_samples_per_push) rc = capture_create(h->cap, *cfg, h->C, h->slicer, cfg->wideband_channels != 0, dev);
     step("IQ seam buffers allocated");
+    if (!rc && (cfg->flags & AMPS_RECC_FLAG_STREAM_POWER)) rc = stream_power_create(h->spow, h->C, h->cap.ring_words);
     if (!rc && cfg->wideband_channels) rc = channelizer_create(h->chz, *cfg);
     step("channelizer created");
     if (!rc && (cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER)) rc = power_create(h->pow, h->chz, cfg->n_channels, h->cap.ring_words);
@@ -273,7 +283,7 @@ int amps_recc_push_iq(amps_recc_t *h, const float *iq, size_t ld, size_t nsamp, 
     if (mem == AMPS_MEM_HOST) {
         if (int rc = h->cap.stage_iq.stage(d, ld, nsamp, h->C, (size_t)h->C * h->cfg.max_samples_per_push, &d, &dld)) return rc;
     }
-    int rc = capture_run_iq(h->cap, h->lists, h->tm, h->stream.get(), d, dld, (uint32_t)nsamp);
+    int rc = capture_run_iq(h->cap, h->lists, h->tm, h->stream.get(), d, dld, (uint32_t)nsamp, stream_power_of(h));
     if (!rc && mem == AMPS_MEM_HOST) rc = h->cap.stage_iq.arm(h->stream.get());
     return rc;
 }
@@ -487,7 +497,7 @@ static int xlate_push(amps_recc *h, const void *iq, size_t ld, size_t nsamp, int
     if (rc) return rc;
     if (int rc2 = debug_sync(h->stream.get(), what)) return rc2;
     if (nout == 0) return 0;
-    return capture_run_iq(h->cap, h->lists, h->tm, h->stream.get(), f, fld, nout);
+    return capture_run_iq(h->cap, h->lists, h->tm, h->stream.get(), f, fld, nout, stream_power_of(h));
 }
 
 // test tap: run the translate stage alone and copy its rows out
@@ -830,25 +840,28 @@ int amps_recc_debug_slicer_bits(amps_recc_t *h, uint64_t first, size_t n, uint8_
 int amps_recc_channel_power(amps_recc_t *h, uint64_t first_snap, size_t n, float *out, size_t out_ld, uint32_t *rows, uint64_t *produced_snaps)
 {
     if (!h || (n && (!out || out_ld < n))) return -EINVAL;
-    if (!h->chz.pow_ring) return -ENOSYS;
+    if (!h->chz.pow_ring && !h->spow.ring) return -ENOSYS;
     STALE_CHECK(h);
     HIP_TRY(hipSetDevice(h->device));
     if (int rc = sync_stream(h, h->stream.get())) return rc;
+    if (h->spow.ring) return stream_power_channels(h->spow, h->cap.n_done, h->cap.origin, h->stream.get(), first_snap, n, out, out_ld, rows, produced_snaps);
     return power_channels(h->chz, h->cap.n_done, h->cap.origin, h->stream.get(), first_snap, n, out, out_ld, rows, produced_snaps);
 }
 
 int amps_recc_burst_power(amps_recc_t *h, const amps_recc_burst_t *recs, size_t n, float *mean_power, uint32_t *n_snaps)
 {
     if (!h || (n && (!recs || !mean_power || !n_snaps))) return -EINVAL;
-    if (!h->chz.pow_ring) return -ENOSYS;
+    if (!h->chz.pow_ring && !h->spow.ring) return -ENOSYS;
     STALE_CHECK(h);
     if (n == 0) return 0;
     if (n > 0xffffffffull) return -E2BIG;
     auto idle = [h]() -> int { HIP_TRY(hipSetDevice(h->device)); return sync_stream(h, h->stream.get()); };
+    if (h->spow.ring)
+        return stream_power_bursts(h->spow, h->cap.n_done, h->cap.origin, (uint32_t)AMPS_RECC_CAPTURE_SYMS * h->sps, h->stream.get(), idle, recs, n, mean_power, n_snaps);
     return power_bursts(h->pow, h->chz, h->cap.n_done, h->cap.origin, (uint32_t)AMPS_RECC_CAPTURE_SYMS * h->sps, h->stream.get(), idle, recs, n, mean_power, n_snaps);
 }
 
-uint32_t amps_recc_power_ring_snaps(const amps_recc_t *h) { return h && h->chz.pow_ring ? h->chz.pow_slots : 0u; }
+uint32_t amps_recc_power_ring_snaps(const amps_recc_t *h) { return !h ? 0u : h->chz.pow_ring ? h->chz.pow_slots : h->spow.ring ? h->spow.slots : 0u; }
 
 int amps_recc_set_origin(amps_recc_t *h, uint64_t first_sample)
 {

@@ -10,6 +10,10 @@
 // xlate_cutoff_hz / xlate_width_hz = 0 keep the flow graph's 10 kHz / 4.5 kHz.  A mobile whose carrier is off by 2 kHz loses half its
 // bursts at 12 dB C/N behind THAT filter (it cuts into a signal it no longer centres) and none behind a 14 kHz one of the same length
 // (profiles/r06/cfo_filter_width.txt): a receiver that expects carrier offsets sets xlate_cutoff_hz = 14e3.
+// channel_power = true keeps received power (AMPS_RECC_FLAG_STREAM_POWER) and adds the port "power": behind each "records" message
+// pmt::cons(from_long(0), blob{ float mean_power; uint32_t n_snaps }), the mean |sample|^2 of what the kernel sliced (the input, or the
+// channel filter's output) over the record's capture and the number of 256-sample blocks averaged, as gr::amps::recc_wideband and
+// gr::amps::recc_subband publish it.
 #pragma once
 #include <amps/api.h>
 
@@ -20,7 +24,7 @@ class AMPS_API recc_fused : virtual public gr::sync_block {
 public:
     typedef AMPS_SPTR<recc_fused> sptr;
     static sptr make(int samples_per_symbol = 10, double xlate_rate_hz = 0.0, double xlate_center_hz = 0.0, int xlate_decim = 2,
-                     double xlate_cutoff_hz = 0.0, double xlate_width_hz = 0.0);
+                     double xlate_cutoff_hz = 0.0, double xlate_width_hz = 0.0, bool channel_power = false);
 };
 
 } // namespace amps

@@ -8,6 +8,11 @@
 // digital_binary_slicer_fb -> amps_recc (:458, 846-874, 807, 310) once per channel.
 // Message ports:  "bursts"  pmt::cons(from_long(channel), blob(3374)) -- cdr = what amps_recc publishes (lib/recc_impl.cc:126);
 //                 "records" pmt::cons(from_long(channel), blob(amps_recc_burst_t)) -- the burst already decoded;
+//                 "power"   (blocks made with channel_power = true only) pmt::cons(from_long(channel), blob(8)) for every record, behind
+//                           its "records" message: the 8 bytes are { float mean_power; uint32_t n_snaps; } in host byte order, as
+//                           amps_recc_burst_power returns them -- the mean |channel filter output|^2 over the record's capture, linear and
+//                           unscaled (RSSI up to a constant), and the number of 256-sample power blocks averaged (130 / 131 at 10 samples
+//                           per symbol; 0 with power 0.0 if the handle no longer holds them);
 // as gr::amps::recc_wideband publishes them.  channel c = the channel at centers_hz[c] relative to the stream's centre.
 #pragma once
 #include <amps/api.h>
@@ -30,8 +35,9 @@ public:
     //         to sc16 or an "interleaved short" file source delivers; 2 (sc8) = two signed bytes (HackRF); 3 (cu8) = two offset-binary
     //         unsigned bytes (RTL-SDR).  The block pushes the items as they are (amps_recc_push_raw_shared_as: 4 or 2 bytes per sample
     //         to the device, no float copy on the host); the records are those of the plainly converted stream.
+    // channel_power: keep per-channel received power (AMPS_RECC_FLAG_STREAM_POWER) and publish every record's burst power on "power"
     static sptr make(double rate_hz, const std::vector<double> &centers_hz, int decim = 4, int samples_per_symbol = 10, int slicer = -1,
-                     double cutoff_hz = 0.0, double width_hz = 0.0, int input_format = 0, int interp = 1);
+                     double cutoff_hz = 0.0, double width_hz = 0.0, int input_format = 0, int interp = 1, bool channel_power = false);
 };
 
 } // namespace amps

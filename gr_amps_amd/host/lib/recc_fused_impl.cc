@@ -15,14 +15,15 @@ namespace amps {
 class recc_fused_impl : public recc_fused {
     amps_recc_t *d_handle;
     bool d_raw;
+    bool d_power;                                  // AMPS_RECC_FLAG_STREAM_POWER: every record's burst power goes out on "power"
     std::vector<unsigned char> d_bursts;
     static const int kMaxPush = 1 << 20;
     static const int kMaxRecs = 64;
 
 public:
-    recc_fused_impl(int sps, double xlate_rate, double xlate_center, int xlate_decim, double xlate_cutoff, double xlate_width)
+    recc_fused_impl(int sps, double xlate_rate, double xlate_center, int xlate_decim, double xlate_cutoff, double xlate_width, bool channel_power)
         : gr::sync_block("recc_fused", gr::io_signature::make(1, 1, 2 * sizeof(float)), gr::io_signature::make(0, 0, 0)), d_handle(nullptr),
-          d_raw(xlate_rate > 0.0), d_bursts((size_t)kMaxRecs * AMPS_RECC_CAPTURE_SYMS)
+          d_raw(xlate_rate > 0.0), d_power(channel_power), d_bursts((size_t)kMaxRecs * AMPS_RECC_CAPTURE_SYMS)
     {
         amps_recc_cfg_t cfg = {};
         cfg.struct_size = sizeof(cfg);
@@ -31,7 +32,7 @@ public:
         cfg.max_samples_per_push = kMaxPush;
         cfg.max_bursts = kMaxRecs;
         cfg.device = -1;
-        cfg.flags = AMPS_RECC_FLAG_KEEP_BURSTS;               // the captured symbols travel with the record
+        cfg.flags = AMPS_RECC_FLAG_KEEP_BURSTS | (channel_power ? AMPS_RECC_FLAG_STREAM_POWER : 0u);   // the captured symbols travel with the record
         int rc = amps_recc_create(&d_handle, &cfg);
         if (rc != 0) throw std::runtime_error(std::string("amps::recc_fused: ") + amps_recc_strerror(rc));
         if (d_raw) {
@@ -50,6 +51,7 @@ public:
         }
         message_port_register_out(pmt::mp("bursts"));          // what amps_recc publishes: connects to amps_recc_decode unchanged
         message_port_register_out(pmt::mp("records"));         // the same burst already decoded (recc_decode accepts it too)
+        if (d_power) message_port_register_out(pmt::mp("power"));
     }
     ~recc_fused_impl() { amps_recc_destroy(d_handle); }
 
@@ -70,9 +72,21 @@ public:
             // next push -- a recoverable condition must not end the flow graph
             if (rc == -ENOSPC) std::fprintf(stderr, "amps::recc_fused: %s (bursts dropped, continuing)\n", amps_recc_strerror(rc));
             else if (rc != 0) { std::fprintf(stderr, "amps::recc_fused: %s\n", amps_recc_strerror(rc)); return WORK_DONE; }
+            // the push that found a record has just been drained: its capture is inside the power ring's window
+            float pow[kMaxRecs];
+            uint32_t nsnap[kMaxRecs];
+            if (d_power && nrec) {
+                rc = amps_recc_burst_power(d_handle, recs, nrec, pow, nsnap);
+                if (rc != 0) { std::fprintf(stderr, "amps::recc_fused: burst power: %s\n", amps_recc_strerror(rc)); return WORK_DONE; }
+            }
             for (size_t i = 0; i < nrec; i++) {
                 message_port_pub(pmt::mp("bursts"), pmt::mp(d_bursts.data() + i * AMPS_RECC_CAPTURE_SYMS, AMPS_RECC_CAPTURE_SYMS));
                 message_port_pub(pmt::mp("records"), pmt::mp(&recs[i], sizeof(recs[i])));
+                if (d_power) {
+                    struct { float mean_power; uint32_t n_snaps; } p = { pow[i], nsnap[i] };
+                    static_assert(sizeof(p) == 8, "payload of the power port");
+                    message_port_pub(pmt::mp("power"), pmt::cons(pmt::from_long((long)recs[i].channel), pmt::mp(&p, sizeof(p))));
+                }
             }
             done += n;
         }
@@ -81,9 +95,11 @@ public:
     }
 };
 
-recc_fused::sptr recc_fused::make(int samples_per_symbol, double xlate_rate_hz, double xlate_center_hz, int xlate_decim, double xlate_cutoff_hz, double xlate_width_hz)
+recc_fused::sptr recc_fused::make(int samples_per_symbol, double xlate_rate_hz, double xlate_center_hz, int xlate_decim, double xlate_cutoff_hz, double xlate_width_hz,
+                                  bool channel_power)
 {
-    return gnuradio::get_initial_sptr(new recc_fused_impl(samples_per_symbol, xlate_rate_hz, xlate_center_hz, xlate_decim, xlate_cutoff_hz, xlate_width_hz));
+    return gnuradio::get_initial_sptr(new recc_fused_impl(samples_per_symbol, xlate_rate_hz, xlate_center_hz, xlate_decim, xlate_cutoff_hz, xlate_width_hz,
+                                                          channel_power));
 }
 
 } // namespace amps

@@ -17,6 +17,9 @@ class recc_subband_impl : public recc_subband {
     int d_format;                                  // AMPS_RECC_SAMPLES_*: what one input item holds
     std::vector<amps_recc_burst_t> d_recs;
     std::vector<unsigned char> d_bursts;
+    bool d_power = false;                          // AMPS_RECC_FLAG_STREAM_POWER: every record's burst power goes out on "power"
+    std::vector<float> d_pow;
+    std::vector<uint32_t> d_nsnap;
     static const int kMaxOut = 1 << 18;            // channel-rate samples per push: 1.3 s at 200 ksps
     static const int kMaxRecs = 1024;
     // bytes of one input item: two floats, two shorts or two bytes; 0 = no such format
@@ -55,9 +58,10 @@ class recc_subband_impl : public recc_subband {
 
 public:
     recc_subband_impl(double rate_hz, const std::vector<double> &centers_hz, int decim, int sps, int slicer, double cutoff_hz, double width_hz, int input_format,
-                      int interp)
+                      int interp, bool channel_power)
         : gr::sync_block("recc_subband", gr::io_signature::make(1, 1, (int)std::max<size_t>(item_size(input_format), 1)), gr::io_signature::make(0, 0, 0)),
-          d_handle(nullptr), d_decim(decim), d_interp(interp), d_format(input_format), d_recs(kMaxRecs), d_bursts((size_t)kMaxRecs * AMPS_RECC_CAPTURE_SYMS)
+          d_handle(nullptr), d_decim(decim), d_interp(interp), d_format(input_format), d_recs(kMaxRecs), d_bursts((size_t)kMaxRecs * AMPS_RECC_CAPTURE_SYMS),
+          d_power(channel_power), d_pow(channel_power ? kMaxRecs : 0), d_nsnap(channel_power ? kMaxRecs : 0)
     {
         if (!item_size(input_format)) throw std::runtime_error("amps::recc_subband: input_format must be 0 (fc32), 1 (sc16), 2 (sc8) or 3 (cu8)");
         if (centers_hz.empty()) throw std::runtime_error("amps::recc_subband: no centres");
@@ -70,7 +74,7 @@ public:
         cfg.max_samples_per_push = kMaxOut;
         cfg.max_bursts = kMaxRecs;
         cfg.device = -1;
-        cfg.flags = AMPS_RECC_FLAG_KEEP_BURSTS | (slicer == 0 ? AMPS_RECC_FLAG_SLICER_ATAN : slicer == 1 ? AMPS_RECC_FLAG_SLICER_PRODUCT
+        cfg.flags = AMPS_RECC_FLAG_KEEP_BURSTS | (channel_power ? AMPS_RECC_FLAG_STREAM_POWER : 0u) | (slicer == 0 ? AMPS_RECC_FLAG_SLICER_ATAN : slicer == 1 ? AMPS_RECC_FLAG_SLICER_PRODUCT
                                                   : slicer == 2 ? AMPS_RECC_FLAG_SLICER_SINE : slicer == 3 ? AMPS_RECC_FLAG_SLICER_EXACT : 0u);
         int rc = amps_recc_create(&d_handle, &cfg);
         if (rc != 0) throw std::runtime_error(std::string("amps::recc_subband: ") + amps_recc_strerror(rc));
@@ -102,6 +106,7 @@ public:
         }
         message_port_register_out(pmt::mp("bursts"));
         message_port_register_out(pmt::mp("records"));
+        if (d_power) message_port_register_out(pmt::mp("power"));
     }
     ~recc_subband_impl() { amps_recc_destroy(d_handle); }
 
@@ -123,10 +128,20 @@ public:
             // next push -- a recoverable condition must not end the flow graph
             if (rc == -ENOSPC) std::fprintf(stderr, "amps::recc_subband: %s (bursts dropped, continuing)\n", amps_recc_strerror(rc));
             else if (rc != 0) { std::fprintf(stderr, "amps::recc_subband: %s\n", amps_recc_strerror(rc)); return WORK_DONE; }
+            // the push that found a record has just been drained: its capture is inside the power ring's window
+            if (d_power && nrec) {
+                rc = amps_recc_burst_power(d_handle, d_recs.data(), nrec, d_pow.data(), d_nsnap.data());
+                if (rc != 0) { std::fprintf(stderr, "amps::recc_subband: burst power: %s\n", amps_recc_strerror(rc)); return WORK_DONE; }
+            }
             for (size_t i = 0; i < nrec; i++) {
                 const pmt::pmt_t ch = pmt::from_long((long)d_recs[i].channel);
                 message_port_pub(pmt::mp("bursts"), pmt::cons(ch, pmt::mp(d_bursts.data() + i * AMPS_RECC_CAPTURE_SYMS, AMPS_RECC_CAPTURE_SYMS)));
                 message_port_pub(pmt::mp("records"), pmt::cons(ch, pmt::mp(&d_recs[i], sizeof(d_recs[i]))));
+                if (d_power) {
+                    struct { float mean_power; uint32_t n_snaps; } p = { d_pow[i], d_nsnap[i] };
+                    static_assert(sizeof(p) == 8, "payload of the power port");
+                    message_port_pub(pmt::mp("power"), pmt::cons(ch, pmt::mp(&p, sizeof(p))));
+                }
             }
             done += n;
         }
@@ -136,9 +151,10 @@ public:
 };
 
 recc_subband::sptr recc_subband::make(double rate_hz, const std::vector<double> &centers_hz, int decim, int samples_per_symbol, int slicer,
-                                      double cutoff_hz, double width_hz, int input_format, int interp)
+                                      double cutoff_hz, double width_hz, int input_format, int interp, bool channel_power)
 {
-    return gnuradio::get_initial_sptr(new recc_subband_impl(rate_hz, centers_hz, decim, samples_per_symbol, slicer, cutoff_hz, width_hz, input_format, interp));
+    return gnuradio::get_initial_sptr(new recc_subband_impl(rate_hz, centers_hz, decim, samples_per_symbol, slicer, cutoff_hz, width_hz, input_format, interp,
+                                                            channel_power));
 }
 
 } // namespace amps

@@ -53,7 +53,9 @@ extern "C" {
                                      still 4, one entry point added and nothing changed: amps_recc_xlate_shared_plan, with the shared translate seam's
                                      decimations 5, 6, 10, 12, 16 and 20;
                                      still 4, two entry points added and nothing changed: amps_recc_set_xlate_resampled / amps_recc_xlate_resample_plan,
-                                     the shared translate seam behind a rational L / M resampler) */
+                                     the shared translate seam behind a rational L / M resampler;
+                                     still 4, a flag added and nothing changed: AMPS_RECC_FLAG_STREAM_POWER, received power on the IQ and
+                                     translate seams through amps_recc_channel_power / _burst_power / _power_ring_snaps) */
 
 /* protocol constants of the reference */
 #define AMPS_RECC_TRIGGER_SYMS 74   /* lib/recc_impl.cc:76-77: 37 bits x 2 Manchester symbols   */
@@ -92,7 +94,12 @@ extern "C" {
 #define AMPS_RECC_FLAG_CHANNEL_POWER 0x200u /* wideband seam, fused form: keep per-channel received power (amps_recc_channel_power,
                                                amps_recc_burst_power below).  Off by default; with it off nothing is allocated or launched for it.
                                                With AMPS_RECC_FLAG_UNFUSED_WIDEBAND, or on a handle without wideband_channels: -EINVAL */
-#define AMPS_RECC_FLAG_MAJORITY     0x2u /* decode mode "majority" instead of "reference" (SURVEY.md 8f.2), see below */
+#define AMPS_RECC_FLAG_STREAM_POWER 0x400u /* IQ and translate seams: keep per-channel received power (the same three entry points; the
+                                               definition for these seams stands below theirs).  Off by default; with it off nothing is
+                                               allocated or launched for it and no record changes.  On a handle with wideband_channels
+                                               (fused or not), with max_samples_per_push == 0 (symbol seam only), or together with
+                                               AMPS_RECC_FLAG_CHANNEL_POWER: -EINVAL */
+#define AMPS_RECC_FLAG_MAJORITY    0x2u /* decode mode "majority" instead of "reference" (SURVEY.md 8f.2), see below */
 
 /* message classes, the branches of lib/recc_decode_impl.cc:108-168 */
 enum amps_recc_msg_class {
@@ -485,7 +492,7 @@ int amps_recc_debug_demod(amps_recc_t *h, const float *iq, size_t nsamp, int mem
 int amps_recc_debug_slicer_bits(amps_recc_t *h, uint64_t first, size_t n, uint8_t *out, size_t out_ld,
                                 uint32_t *rows, uint64_t *produced);
 
-/* ---- received power of the wideband seam (handles created with AMPS_RECC_FLAG_CHANNEL_POWER; -ENOSYS on every other handle) ----
+/* ---- received power of the wideband seam (handles created with AMPS_RECC_FLAG_CHANNEL_POWER; -ENOSYS on a handle with neither power flag) ----
  * A POWER SNAPSHOT is taken at every channel-rate sample index s with s % AMPS_RECC_POWER_STRIDE == 0, s in the numbering of
  * amps_recc_debug_slicer_bits and of amps_recc_burst_t.position (absolute, amps_recc_set_origin counted: frame m of the stream is
  * s = origin + m).  Snapshot j = s / 256 of row r is P[r][j] = |Y_k[m]|^2, Y_k[m] the filter-bank output of the row's FFT bin for that
@@ -512,6 +519,34 @@ int amps_recc_channel_power(amps_recc_t *h, uint64_t first_snap, size_t n, float
 int amps_recc_burst_power(amps_recc_t *h, const amps_recc_burst_t *recs, size_t n, float *mean_power, uint32_t *n_snaps);
 /* snapshots the handle keeps per row, R / 256; 0 on a handle without the flag (or a null handle) */
 uint32_t amps_recc_power_ring_snaps(const amps_recc_t *h);
+
+/* ---- received power of the IQ and translate seams (handles created with AMPS_RECC_FLAG_STREAM_POWER) ----
+ * The three entry points above answer on such a handle too, with the same arguments and errors, for a BLOCK MEAN instead of a snapshot:
+ * on these seams the channel-rate stream is in device memory for the length of a push, so all of it is read, not one sample in 256.
+ * Numbering.  y_c[s] is the channel-rate sample of row c at absolute index s, the numbering of amps_recc_burst_t.position and of
+ *   amps_recc_debug_slicer_bits (amps_recc_set_origin counted): the sample the streaming kernel slices -- the caller's IQ on
+ *   amps_recc_push_iq, the translate stage's output on amps_recc_push_raw[_as] and amps_recc_push_raw_shared[_as] (integer, wide and
+ *   rational forms).  Row = channel: rows = n_channels.
+ * Block j of row c is  P[c][j] = (1 / 256) * sum over s = 256 j ... 256 j + 255 of |y_c[s]|^2 : linear, fp32, unscaled,
+ *   AMPS_RECC_POWER_STRIDE the block length.  An unmodulated carrier of amplitude a reads a^2 on amps_recc_push_iq and (gain * a)^2 at a
+ *   centre of a translate seam once the filter has filled.
+ * Summation order, ONE and fixed: the terms are t(s) = fma(im, im, re * re) in fp32.  Lane l = 0 ... 63 adds
+ *   ((t(256 j + l) + t(256 j + l + 64)) + t(256 j + l + 128)) + t(256 j + l + 192); the 64 lane sums are added by the butterfly
+ *   a_l = a_l + a_(l xor o) for o = 32, 16, 8, 4, 2, 1; the result times 2^-8, which is exact.  Every term is non-negative, so
+ *   |P - exact| <= 257 * 2^-24 * exact.
+ * Existence.  Block j exists once 256 (j + 1) <= produced, `produced` as amps_recc_debug_slicer_bits reports it (the seam holds back
+ *   fewer than 64 samples); *produced_snaps = floor(produced / 256).
+ * Held window.  [max(ceil(origin / 256), produced_snaps - R / 256), produced_snaps), R the span of the slicer-bit ring; anything outside
+ *   it is -ERANGE.  A block that would begin before the origin is never reported.  Every record found by a push still has its whole
+ *   capture inside the window when that push is drained.
+ * Independence.  Values depend on the stream only: not on how it was cut into pushes, on ld, on host or device residence, or on the
+ *   integer format a translate push arrived in (bit-identical in each case).  amps_recc_reset empties the window; the debug taps
+ *   amps_recc_debug_xlate* leave it alone, as they leave the slicer alone.
+ * Burst power.  The arithmetic mean of P[channel][j] over the blocks that lie wholly inside the capture,
+ *   j0 = ceil(position / 256) ... j1 = floor((position + AMPS_RECC_CAPTURE_SYMS * samples_per_symbol) / 256) - 1, n_snaps = j1 - j0 + 1
+ *   (130 or 131 at 10 samples per symbol, 38 or 39 at 3).  If any of those blocks is not held: {0.0f, 0}, which is not an error.
+ *   channel >= n_channels: -EINVAL.
+ * Cost: one short kernel behind the streaming kernel per push, one more read of the push's samples. */
 
 /* ---- one band over the GPUs of a node (BASELINE configs[4]: "RCCL broadcast of wideband IQ over xGMI") ----
  * One process and one handle per GPU, every handle created with cfg.wideband_groups = N, wideband_group = its rank (the reference's
