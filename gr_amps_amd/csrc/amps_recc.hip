@@ -18,7 +18,6 @@
 #include "recc_capture.hip.h"
 #include "recc_symbols.hip.h"
 #include "recc_channelizer.hip.h"
-#include "recc_power.hip.h"
 #include "recc_rccl.hip.h"
 #include "recc_xlate.hip.h"
 #include "recc_refchain.hip.h"
@@ -45,8 +44,7 @@ struct amps_recc {
     SymbolsState sym;
     BchScratch bch;                   // amps_bch_*
     ChannelizerState chz;             // wideband seam: the filter bank
-    PowerState pow;                   // received power (AMPS_RECC_FLAG_CHANNEL_POWER; the ring itself is chz.pow_ring)
-    StreamPowerState spow;            // received power of the IQ and translate seams (AMPS_RECC_FLAG_STREAM_POWER)
+    PowerRing power;                  // received power (AMPS_RECC_FLAG_CHANNEL_POWER or AMPS_RECC_FLAG_STREAM_POWER: one ring, filled by that seam's producer)
     XlateState xl;                    // the translate stage in the form configured last (amps_recc_set_xlate / _set_xlate_shared)
     RefState ref;                     // reference-timing seam (G2 -> G3 -> G4 as the flow graph wires them; created on first use)
     RcclState rccl;                   // one band over several GPUs: amps_recc_rccl_init / amps_recc_push_wideband_bcast
@@ -75,14 +73,14 @@ int sync_event(amps_recc *h, hipEvent_t e)
 // nothing on the other seams
 bool is_group_handle(const amps_recc *h) { return h->chz.enabled && h->chz.groups > 1; }
 
-// what capture_run_iq is handed: the power ring of a handle that keeps one
-const StreamPowerState *stream_power_of(const amps_recc *h) { return h->spow.ring ? &h->spow : nullptr; }
+// what capture_run_iq and channelizer_run are handed: the power ring of a handle that keeps one
+const PowerRing *power_of(const amps_recc *h) { return h->power.ring ? &h->power : nullptr; }
 
 int reset_state(amps_recc *h)
 {
     hipStream_t s = h->stream.get();
     if (int rc = capture_reset(h->cap, s)) return rc;
-    if (int rc = stream_power_reset(h->spow, s)) return rc;
+    if (int rc = power_ring_reset(h->power, s)) return rc;
     if (int rc = records_reset(h->lists, s)) return rc;
     if (int rc = symbols_reset(h->sym, s)) return rc;
     if (int rc = channelizer_reset(h->chz, s)) return rc;
@@ -191,10 +189,10 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
     step("pinned record lists mapped");
     if (!rc && cfg->max_samples_per_push) rc = capture_create(h->cap, *cfg, h->C, h->slicer, cfg->wideband_channels != 0, dev);
     step("IQ seam buffers allocated");
-    if (!rc && (cfg->flags & AMPS_RECC_FLAG_STREAM_POWER)) rc = stream_power_create(h->spow, h->C, h->cap.ring_words);
+    if (!rc && (cfg->flags & AMPS_RECC_FLAG_STREAM_POWER)) rc = power_ring_create(h->power, PowerRule::BLOCK, h->C, h->cap.ring_words);
     if (!rc && cfg->wideband_channels) rc = channelizer_create(h->chz, *cfg);
     step("channelizer created");
-    if (!rc && (cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER)) rc = power_create(h->pow, h->chz, cfg->n_channels, h->cap.ring_words);
+    if (!rc && (cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER)) rc = power_ring_create(h->power, PowerRule::SNAPSHOT, h->chz.C, h->cap.ring_words, &h->chz.row2chan, cfg->n_channels);
     if (!rc) rc = reset_state(h);
     step("state reset");
     if (rc) { amps_recc_destroy(h); return rc; }
@@ -283,7 +281,7 @@ int amps_recc_push_iq(amps_recc_t *h, const float *iq, size_t ld, size_t nsamp, 
     if (mem == AMPS_MEM_HOST) {
         if (int rc = h->cap.stage_iq.stage(d, ld, nsamp, h->C, (size_t)h->C * h->cfg.max_samples_per_push, &d, &dld)) return rc;
     }
-    int rc = capture_run_iq(h->cap, h->lists, h->tm, h->stream.get(), d, dld, (uint32_t)nsamp, stream_power_of(h));
+    int rc = capture_run_iq(h->cap, h->lists, h->tm, h->stream.get(), d, dld, (uint32_t)nsamp, power_of(h));
     if (!rc && mem == AMPS_MEM_HOST) rc = h->cap.stage_iq.arm(h->stream.get());
     return rc;
 }
@@ -310,6 +308,7 @@ static int push_wideband_block(amps_recc_t *h, const void *iq, size_t nsamp, int
         ChzRunIn in;
         in.iq = iq; in.nsamp = nsamp; in.mem = mem; in.sc16 = sc16; in.fused = fused;
         in.gring = h->cap.gring.get(); in.ring_words = h->cap.ring_words; in.n_done = h->cap.n_done; in.slicer = h->slicer;
+        in.power = power_of(h);
         in.after_main = SpanGuard::end_cb; in.after_ctx = &g;
         rc = channelizer_run(h->chz, in, h->stream.get(), &chan_iq, &ld, &nout);
     }
@@ -497,7 +496,7 @@ static int xlate_push(amps_recc *h, const void *iq, size_t ld, size_t nsamp, int
     if (rc) return rc;
     if (int rc2 = debug_sync(h->stream.get(), what)) return rc2;
     if (nout == 0) return 0;
-    return capture_run_iq(h->cap, h->lists, h->tm, h->stream.get(), f, fld, nout, stream_power_of(h));
+    return capture_run_iq(h->cap, h->lists, h->tm, h->stream.get(), f, fld, nout, power_of(h));
 }
 
 // test tap: run the translate stage alone and copy its rows out
@@ -840,28 +839,25 @@ int amps_recc_debug_slicer_bits(amps_recc_t *h, uint64_t first, size_t n, uint8_
 int amps_recc_channel_power(amps_recc_t *h, uint64_t first_snap, size_t n, float *out, size_t out_ld, uint32_t *rows, uint64_t *produced_snaps)
 {
     if (!h || (n && (!out || out_ld < n))) return -EINVAL;
-    if (!h->chz.pow_ring && !h->spow.ring) return -ENOSYS;
+    if (!h->power.ring) return -ENOSYS;
     STALE_CHECK(h);
     HIP_TRY(hipSetDevice(h->device));
     if (int rc = sync_stream(h, h->stream.get())) return rc;
-    if (h->spow.ring) return stream_power_channels(h->spow, h->cap.n_done, h->cap.origin, h->stream.get(), first_snap, n, out, out_ld, rows, produced_snaps);
-    return power_channels(h->chz, h->cap.n_done, h->cap.origin, h->stream.get(), first_snap, n, out, out_ld, rows, produced_snaps);
+    return power_ring_channels(h->power, h->cap.n_done, h->cap.origin, h->stream.get(), first_snap, n, out, out_ld, rows, produced_snaps);
 }
 
 int amps_recc_burst_power(amps_recc_t *h, const amps_recc_burst_t *recs, size_t n, float *mean_power, uint32_t *n_snaps)
 {
     if (!h || (n && (!recs || !mean_power || !n_snaps))) return -EINVAL;
-    if (!h->chz.pow_ring && !h->spow.ring) return -ENOSYS;
+    if (!h->power.ring) return -ENOSYS;
     STALE_CHECK(h);
     if (n == 0) return 0;
     if (n > 0xffffffffull) return -E2BIG;
     auto idle = [h]() -> int { HIP_TRY(hipSetDevice(h->device)); return sync_stream(h, h->stream.get()); };
-    if (h->spow.ring)
-        return stream_power_bursts(h->spow, h->cap.n_done, h->cap.origin, (uint32_t)AMPS_RECC_CAPTURE_SYMS * h->sps, h->stream.get(), idle, recs, n, mean_power, n_snaps);
-    return power_bursts(h->pow, h->chz, h->cap.n_done, h->cap.origin, (uint32_t)AMPS_RECC_CAPTURE_SYMS * h->sps, h->stream.get(), idle, recs, n, mean_power, n_snaps);
+    return power_ring_bursts(h->power, h->cap.n_done, h->cap.origin, (uint32_t)AMPS_RECC_CAPTURE_SYMS * h->sps, h->stream.get(), idle, recs, n, mean_power, n_snaps);
 }
 
-uint32_t amps_recc_power_ring_snaps(const amps_recc_t *h) { return !h ? 0u : h->chz.pow_ring ? h->chz.pow_slots : h->spow.ring ? h->spow.slots : 0u; }
+uint32_t amps_recc_power_ring_snaps(const amps_recc_t *h) { return h && h->power.ring ? h->power.slots : 0u; }
 
 int amps_recc_set_origin(amps_recc_t *h, uint64_t first_sample)
 {

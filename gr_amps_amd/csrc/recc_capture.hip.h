@@ -244,7 +244,7 @@ inline FrontArgs front_args(const CaptureState &c, RecordLists &L, const FrontGe
 // pw: the handle keeps received power (AMPS_RECC_FLAG_STREAM_POWER): its block means are taken behind the streaming kernel, from the
 // block and the carry that launch read
 inline int capture_run_iq(CaptureState &c, RecordLists &L, TimingState &tm, hipStream_t s, const float2 *iq, uint64_t ld, uint32_t nsamp,
-                          const StreamPowerState *pw = nullptr)
+                          const PowerRing *pw = nullptr)
 {
     c.origin_locked = true;
     if (nsamp == 0) return 0;

@@ -39,6 +39,7 @@
 #include "recc_chz_fft.hip.h"
 #include "recc_chz_fold.hip.h"
 #include "recc_chz_slicer.hip.h"
+#include "recc_power.hip.h"       // chz_power_launch: the power snapshots behind a fused launch
 
 namespace amps {
 
@@ -157,11 +158,7 @@ struct ChannelizerState {
     HostStage stage;                // host-resident wideband input as the caller's samples (fc32 or sc16), sized in bytes: the largest block so far
     DevBuf<float2> cvt;             // an sc16 block expanded to fc32: the checking modes and the pre-pass experiment only
     bool short_prepass = false;     // AMPS_RECC_SHORT_PREPASS=1 at create: sc16 blocks go through chz_short_to_float_kernel + the fc32 kernel
-    DevBuf<float> pow_ring;         // AMPS_RECC_FLAG_CHANNEL_POWER: [pow_slots][C] power snapshots (recc_power.hip.h), else null
-    uint32_t pow_slots = 0;         // snapshots held per row: the bit ring's span / AMPS_RECC_POWER_STRIDE (a power of two)
 };
-// recc_power.hip.h: the snapshot frames of a fused filter-bank launch, from that launch's own arguments
-inline void chz_power_launch(const ChannelizerState &z, const ChzArgs &a, bool sc16, hipStream_t s);
 
 inline double bessel_i0(double x)
 {
@@ -204,7 +201,6 @@ inline int channelizer_reset(ChannelizerState &z, hipStream_t s)
     const size_t cap = chz_carry_cap(z.P, z.D);
     if (hipMemsetAsync(z.carry[0].get(), 0, sizeof(float2) * cap, s) != hipSuccess) return -EIO;
     if (hipMemsetAsync(z.carry[1].get(), 0, sizeof(float2) * cap, s) != hipSuccess) return -EIO;
-    if (z.pow_ring) HIP_TRY(hipMemsetAsync(z.pow_ring.get(), 0, sizeof(float) * (size_t)z.pow_slots * z.C, s));   // the stream starts again: no snapshot is held
     z.carry_cur = 0;
     z.carry_len = chz_hist(z.P, z.D);                // all-zero history, no leftover
     z.frames_done = 0;
@@ -305,6 +301,7 @@ struct ChzRunIn {
     uint32_t ring_words = 0;
     uint64_t n_done = 0;
     int slicer = AMPS_SLICER_ATAN_BOXCAR;
+    const PowerRing *power = nullptr;        // fused: the power ring of a handle that keeps one (AMPS_RECC_FLAG_CHANNEL_POWER)
     void (*after_main)(void *) = nullptr;    // called behind the filter-bank launch, in front of the carry and power launches (timing)
     void *after_ctx = nullptr;
 };
@@ -370,7 +367,7 @@ inline int channelizer_run(ChannelizerState &z, const ChzRunIn &in, hipStream_t 
     }
     if (in.after_main) in.after_main(in.after_ctx);                            // timing: the span ends behind the filter-bank kernel, before the carry copy
     // power snapshots (opt-in): behind the filter bank, from the block and the carry it read -- the carry buffers swap below
-    if (fused && z.pow_ring && nframes) chz_power_launch(z, a, sc16, s);
+    if (fused && in.power && nframes) chz_power_launch(*in.power, z.D, a, sc16, s);
 #ifdef CHZ_TIMELINE
     if (a.tl) chz_timeline().dump("AMPS_RECC_CHZ_TIMELINE", CHZ_TL_STAMPS, s);   // the last launch's stamps
 #endif

@@ -8,6 +8,7 @@
 #include <stdexcept>
 #include <vector>
 #include "amps_recc.h"
+#include "recc_publish.h"
 
 namespace gr {
 namespace amps {
@@ -66,28 +67,10 @@ public:
                            : amps_recc_push_iq(d_handle, in + 2 * (size_t)done, (size_t)n, (size_t)n, AMPS_MEM_HOST);
             if (rc != 0) { std::fprintf(stderr, "amps::recc_fused: %s\n", amps_recc_strerror(rc)); return WORK_DONE; }
             amps_recc_burst_t recs[kMaxRecs];
-            size_t nrec = 0;
-            rc = amps_recc_drain_bursts(d_handle, recs, d_bursts.data(), kMaxRecs, &nrec);
-            // -ENOSPC: more bursts than the list holds were found; the ones that fit are returned and the list recovers on the
-            // next push -- a recoverable condition must not end the flow graph
-            if (rc == -ENOSPC) std::fprintf(stderr, "amps::recc_fused: %s (bursts dropped, continuing)\n", amps_recc_strerror(rc));
-            else if (rc != 0) { std::fprintf(stderr, "amps::recc_fused: %s\n", amps_recc_strerror(rc)); return WORK_DONE; }
-            // the push that found a record has just been drained: its capture is inside the power ring's window
             float pow[kMaxRecs];
             uint32_t nsnap[kMaxRecs];
-            if (d_power && nrec) {
-                rc = amps_recc_burst_power(d_handle, recs, nrec, pow, nsnap);
-                if (rc != 0) { std::fprintf(stderr, "amps::recc_fused: burst power: %s\n", amps_recc_strerror(rc)); return WORK_DONE; }
-            }
-            for (size_t i = 0; i < nrec; i++) {
-                message_port_pub(pmt::mp("bursts"), pmt::mp(d_bursts.data() + i * AMPS_RECC_CAPTURE_SYMS, AMPS_RECC_CAPTURE_SYMS));
-                message_port_pub(pmt::mp("records"), pmt::mp(&recs[i], sizeof(recs[i])));
-                if (d_power) {
-                    struct { float mean_power; uint32_t n_snaps; } p = { pow[i], nsnap[i] };
-                    static_assert(sizeof(p) == 8, "payload of the power port");
-                    message_port_pub(pmt::mp("power"), pmt::cons(pmt::from_long((long)recs[i].channel), pmt::mp(&p, sizeof(p))));
-                }
-            }
+            if (!recc_drain_and_publish(*this, "recc_fused", false, d_handle, recs, d_bursts.data(), kMaxRecs, d_power ? pow : nullptr, d_power ? nsnap : nullptr))
+                return WORK_DONE;
             done += n;
         }
         consume_each(noutput_items);

@@ -1,0 +1,48 @@
+// recc_publish.h -- what recc_wideband, recc_subband and recc_fused do behind every push: drain the records with their bursts, ask for
+// their burst power where the block keeps power, and publish on "bursts", "records" and "power".  Internal to lib/.
+#pragma once
+#include <amps/api.h>
+#include <cerrno>
+#include <cstdint>
+#include <cstdio>
+#include "amps_recc.h"
+
+namespace gr {
+namespace amps {
+
+// payload of the "power" port, behind the record's channel number
+struct recc_power_payload { float mean_power; uint32_t n_snaps; };
+static_assert(sizeof(recc_power_payload) == 8, "payload of the power port");
+
+// What differs between the blocks: the name in the stderr lines, and whether "bursts" and "records" carry (channel, blob) pairs
+// or the bare blob (recc_fused: one channel, and what gr::amps::recc publishes).  recs / bursts hold `cap` records; pow / nsnap hold as
+// many, or are null on a block that keeps no power.  false = stop the flow graph (the caller knows what that takes).
+inline bool recc_drain_and_publish(gr::basic_block &blk, const char *name, bool channel_pairs, amps_recc_t *h, amps_recc_burst_t *recs,
+                                   unsigned char *bursts, size_t cap, float *pow, uint32_t *nsnap)
+{
+    size_t nrec = 0;
+    int rc = amps_recc_drain_bursts(h, recs, bursts, cap, &nrec);
+    // -ENOSPC: more bursts than the list holds were found; the ones that fit are returned and the list recovers on the
+    // next push -- a recoverable condition must not end the flow graph
+    if (rc == -ENOSPC) std::fprintf(stderr, "amps::%s: %s (bursts dropped, continuing)\n", name, amps_recc_strerror(rc));
+    else if (rc != 0) { std::fprintf(stderr, "amps::%s: %s\n", name, amps_recc_strerror(rc)); return false; }
+    // the push that found a record has just been drained: its capture is inside the power ring's window
+    if (pow && nrec) {
+        rc = amps_recc_burst_power(h, recs, nrec, pow, nsnap);
+        if (rc != 0) { std::fprintf(stderr, "amps::%s: burst power: %s\n", name, amps_recc_strerror(rc)); return false; }
+    }
+    for (size_t i = 0; i < nrec; i++) {
+        const pmt::pmt_t ch = pmt::from_long((long)recs[i].channel);
+        const pmt::pmt_t burst = pmt::mp(bursts + i * AMPS_RECC_CAPTURE_SYMS, AMPS_RECC_CAPTURE_SYMS), rec = pmt::mp(&recs[i], sizeof(recs[i]));
+        blk.message_port_pub(pmt::mp("bursts"), channel_pairs ? pmt::cons(ch, burst) : burst);
+        blk.message_port_pub(pmt::mp("records"), channel_pairs ? pmt::cons(ch, rec) : rec);
+        if (pow) {
+            const recc_power_payload p = { pow[i], nsnap[i] };
+            blk.message_port_pub(pmt::mp("power"), pmt::cons(ch, pmt::mp(&p, sizeof(p))));
+        }
+    }
+    return true;
+}
+
+} // namespace amps
+} // namespace gr

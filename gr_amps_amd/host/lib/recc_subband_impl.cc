@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 #include "amps_recc.h"
+#include "recc_publish.h"
 
 namespace gr {
 namespace amps {
@@ -122,27 +123,8 @@ public:
             if (n > max_push) n = max_push;
             int rc = amps_recc_push_raw_shared_as(d_handle, in + item * (size_t)done, (size_t)n, d_format, AMPS_MEM_HOST);
             if (rc != 0) { std::fprintf(stderr, "amps::recc_subband: %s\n", amps_recc_strerror(rc)); return WORK_DONE; }
-            size_t nrec = 0;
-            rc = amps_recc_drain_bursts(d_handle, d_recs.data(), d_bursts.data(), kMaxRecs, &nrec);
-            // -ENOSPC: more bursts than the list holds were found; the ones that fit are returned and the list recovers on the
-            // next push -- a recoverable condition must not end the flow graph
-            if (rc == -ENOSPC) std::fprintf(stderr, "amps::recc_subband: %s (bursts dropped, continuing)\n", amps_recc_strerror(rc));
-            else if (rc != 0) { std::fprintf(stderr, "amps::recc_subband: %s\n", amps_recc_strerror(rc)); return WORK_DONE; }
-            // the push that found a record has just been drained: its capture is inside the power ring's window
-            if (d_power && nrec) {
-                rc = amps_recc_burst_power(d_handle, d_recs.data(), nrec, d_pow.data(), d_nsnap.data());
-                if (rc != 0) { std::fprintf(stderr, "amps::recc_subband: burst power: %s\n", amps_recc_strerror(rc)); return WORK_DONE; }
-            }
-            for (size_t i = 0; i < nrec; i++) {
-                const pmt::pmt_t ch = pmt::from_long((long)d_recs[i].channel);
-                message_port_pub(pmt::mp("bursts"), pmt::cons(ch, pmt::mp(d_bursts.data() + i * AMPS_RECC_CAPTURE_SYMS, AMPS_RECC_CAPTURE_SYMS)));
-                message_port_pub(pmt::mp("records"), pmt::cons(ch, pmt::mp(&d_recs[i], sizeof(d_recs[i]))));
-                if (d_power) {
-                    struct { float mean_power; uint32_t n_snaps; } p = { d_pow[i], d_nsnap[i] };
-                    static_assert(sizeof(p) == 8, "payload of the power port");
-                    message_port_pub(pmt::mp("power"), pmt::cons(ch, pmt::mp(&p, sizeof(p))));
-                }
-            }
+            if (!recc_drain_and_publish(*this, "recc_subband", true, d_handle, d_recs.data(), d_bursts.data(), kMaxRecs, d_power ? d_pow.data() : nullptr,
+                                        d_power ? d_nsnap.data() : nullptr)) return WORK_DONE;
             done += n;
         }
         consume_each(noutput_items);

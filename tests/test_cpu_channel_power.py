@@ -1,5 +1,6 @@
 """not gpu: the received-power feature of the wideband seam (AMPS_RECC_FLAG_CHANNEL_POWER, include/amps_recc.h) as far as it can be
-checked without a device -- the declarations, the argument validation, the resources of the two new kernels, and the float64 model
+checked without a device -- the declarations, the argument validation, the resources of the snapshot kernel and of the gather kernel
+(the one both received-power flags share), and the float64 model
 tests/powerref.py that the GPU tests compare against."""
 import ctypes as C
 import os
@@ -58,7 +59,7 @@ def res():
 def test_power_kernels_need_no_scratch_and_little_lds(res):
     snap = {k: v for k, v in res.items() if "amps::chz_power_kernel<" in k}
     assert len(snap) == 4, sorted(snap)                               # fc32 and sc16 blocks at either decimation
-    gather = {k: v for k, v in res.items() if "amps::chz_power_gather_kernel(" in k}
+    gather = {k: v for k, v in res.items() if "amps::power_ring_gather_kernel(" in k}
     assert len(gather) == 1, sorted(gather)
     for name, r in {**snap, **gather}.items():
         assert r["scratch_bytes_per_lane"] == 0 and r["vgpr_spill"] == 0 and r["sgpr_spill"] == 0, (name, r)
@@ -66,6 +67,8 @@ def test_power_kernels_need_no_scratch_and_little_lds(res):
     # the names do not collide with the prefixes other tests count instantiations by
     for name in list(snap) + list(gather):
         assert not re.search(r"amps::(chz12_kernel|recc_front_kernel|recc_resolve_kernel)<", name), name
+    for name in gather:
+        assert not re.search(r"amps::(chz_power_kernel<|stream_power_kernel\()", name), name
 
 
 @pytest.mark.parametrize("D", [512, 768])

@@ -1,5 +1,6 @@
 """not gpu: received power of the IQ and translate seams (AMPS_RECC_FLAG_STREAM_POWER, include/amps_recc.h) as far as it can be
-checked without a device -- the flag in the header and the binding, the resources of the two new kernels, and the float64 model
+checked without a device -- the flag in the header and the binding, the resources of the block kernel and of the gather
+kernel (the one both received-power flags share), and the float64 model
 tests/streampowerref.py that the GPU tests compare against."""
 import inspect
 import os
@@ -48,14 +49,17 @@ def res():
 
 def test_stream_power_kernels_need_no_scratch_and_no_lds(res):
     block = {k: v for k, v in res.items() if "amps::stream_power_kernel(" in k}
-    gather = {k: v for k, v in res.items() if "amps::stream_power_gather_kernel(" in k}
+    gather = {k: v for k, v in res.items() if "amps::power_ring_gather_kernel(" in k}
     assert len(block) == 1 and len(gather) == 1, (sorted(block), sorted(gather))
     for name, r in {**block, **gather}.items():
         assert r["scratch_bytes_per_lane"] == 0 and r["vgpr_spill"] == 0 and r["sgpr_spill"] == 0, (name, r)
     assert list(block.values())[0]["lds_bytes"] == 0
+    assert list(gather.values())[0]["lds_bytes"] <= 24 * 1024
     # the names do not collide with the prefixes other tests count instantiations by
     for name in list(block) + list(gather):
-        assert not re.search(r"amps::(chz12_kernel<|recc_front_kernel<|recc_resolve_kernel<|chz_power_kernel<|chz_power_gather_kernel\()", name), name
+        assert not re.search(r"amps::(chz12_kernel<|recc_front_kernel<|recc_resolve_kernel<|chz_power_kernel<)", name), name
+    for name in gather:
+        assert "amps::stream_power_kernel(" not in name, name
 
 
 def test_model_constant_amplitude_tone_reads_its_amplitude_squared():

@@ -7,6 +7,7 @@ other number is used.  A wrong tap, bin, frame or row gives errors of order S^2.
 import numpy as np
 import pytest
 
+import gatherref
 import powerref
 from gr_amps_amd import capi, synth_wideband as sw
 from conftest import wb_cfg
@@ -274,3 +275,68 @@ def test_channel_group_rows_equal_the_whole_band_rows(gpu, decim, tones):
         assert e.value.code == -22
     assert f0 == f1 == 0 and part.shape == (len(mine), whole.shape[1]) and len(mine) == C // 2
     assert np.array_equal(part.view(np.uint32), whole[mine].view(np.uint32))
+
+
+# The burst mean is the stated reduction of the ring, bit for bit (tests/gatherref.py), on the very floats amps_recc_channel_power
+# returns: no tolerance.  The gather kernel is the one the IQ and translate seams use, so the wrap of its loop round the ring's end is
+# covered once, in tests/test_gpu_stream_power.py; here it would cost a ring's span of frames, and test_ring_keeps_the_newest_window
+# turns this ring already.  64 channels: the fewest at which a wideband handle takes the capture form every other test of this seam
+# runs (below 64 a handle queues its captures, recc_resolve.hip.h); the gather does not depend on the count.
+GATHER_FRAMES = {512: 10560, 768: 7232}                              # the smallest multiples of 64 at which snapshot 41 / 28 exists
+GATHER_COUNTS = {512: (40, 39), 768: (27, 26)}                       # at position 512 (j0 = 2) and 513 (j0 = 3)
+
+
+@pytest.fixture(scope="module")
+def gather_noise():
+    cache = {}
+
+    def get(D):
+        if D not in cache:
+            cache[D] = _noise(GATHER_FRAMES[D] * D, 13)
+            cache[D].setflags(write=False)
+        return cache[D]
+    return get
+
+
+def _gather_check(r, x, D, channels, row_of, foreign=None):
+    for off in range(0, GATHER_FRAMES[D], 2048):
+        r.push_wideband(x[off * D:(off + 2048) * D])
+    ring, lo = r.channel_power()
+    assert lo == 0 and ring.shape[1] == -(-GATHER_FRAMES[D] // 256) == GATHER_COUNTS[D][0] + 2
+    cases = {512: (2, GATHER_COUNTS[D][0]), 256 * 60: (60, 0), 513: (3, GATHER_COUNTS[D][1])}
+    recs = np.zeros(len(cases) * len(channels), capi.BURST_DTYPE)
+    recs["position"] = np.repeat(list(cases), len(channels))
+    recs["channel"] = np.tile(channels, len(cases))
+    mean, cnt = r.burst_power(recs)
+    for g, m, c in zip(recs, mean, cnt):
+        j0, count = cases[int(g["position"])]
+        assert int(c) == count, (int(g["position"]), int(c))
+        if count == 0:
+            assert gatherref.bits(m) == 0                            # beyond what is produced
+            continue
+        assert (j0, count) == powerref.burst_window(int(g["position"]), 1536 // D)
+        want = gatherref.gather_mean(ring[row_of(int(g["channel"])), j0:j0 + count])
+        print("\nchannel %d at %d: %d snapshots, mean %.9g, stated reduction %.9g" % (g["channel"], g["position"], count, m, want))
+        assert gatherref.bits(m) == gatherref.bits(want)
+    if foreign is not None:                                          # a channel of the other group in the same call
+        recs["channel"][1] = foreign
+        with pytest.raises(capi.AmpsError) as e:
+            r.burst_power(recs)
+        assert e.value.code == -22
+
+
+def test_burst_means_are_the_stated_reduction_of_the_ring_bit_for_bit(gpu, decim, gather_noise):
+    D = decim
+    first, C = 96, 64
+    with _handle(D, C, first, 2048) as r:
+        _gather_check(r, gather_noise(D), D, [0, 31, C - 1], lambda ch: ch)
+
+
+def test_burst_means_of_a_channel_group_bit_for_bit(gpu, gather_noise):
+    D = 768
+    first, C = 96, 64
+    with _handle(D, C, first, 2048, groups=2, group=1) as r:
+        mine = [c for c in range(C) if ((first + c) % 64) // 32 == 1]
+        other = [c for c in range(C) if c not in set(mine)][0]
+        assert len(mine) == C // 2
+        _gather_check(r, gather_noise(D), D, [mine[0], mine[7], mine[-1]], mine.index, foreign=other)

@@ -13,6 +13,7 @@ import functools
 import numpy as np
 import pytest
 
+import gatherref
 import oracle
 import streampowerref as spr
 from gr_amps_amd import capi, synth
@@ -391,3 +392,39 @@ def test_a_record_drained_behind_later_pushes_still_has_its_power(gpu):
         _, first = r.channel_power()
         assert first == n // 64 * 64 // 256 - snaps > 0
         _burst_checks(r, recs, model[:, first:], first=first)
+
+
+# ---- 8. the burst mean is the stated reduction of the ring, bit for bit, across the ring's wrap
+def test_burst_means_are_the_stated_reduction_of_the_ring_bit_for_bit(gpu):
+    """amps_recc_burst_power against tests/gatherref.py on the very floats amps_recc_channel_power returns: no tolerance.  The records
+    are fabricated (the entry point takes any channel and position); held and unheld ones alternate in one call."""
+    C, sps, push, pushes = 3, 12, 4096, 27
+    y = _noise(48, (C, push * pushes))
+    with _iq(C, push, sps=sps) as r:
+        snaps = r.power_ring_snaps
+        assert snaps == 256                                          # R = 65536: the smallest power of two >= 4096 + 12 * 3586 + 1024
+        for a in range(0, y.shape[1], push):
+            r.push_iq(np.ascontiguousarray(y[:, a:a + push]))
+        ring, lo = r.channel_power()
+        # position -> (first block, blocks): 158 blocks from 200 cross slot 255 -> 0 and give three values to the first lanes; 157 is
+        # the other count class; block 172 has left the window; block 469 is not produced yet
+        cases = {51200: (200, 158), 44000: (172, 0), 51201: (201, 157), 80000: (313, 0)}
+        recs = np.zeros(len(cases) * C, capi.BURST_DTYPE)
+        recs["position"] = np.repeat(list(cases), C)
+        recs["channel"] = np.tile(np.arange(C), len(cases))
+        mean, cnt = r.burst_power(recs)
+    assert lo == 176 and ring.shape == (C, 256)                      # 110 592 samples: blocks [176, 432) are held
+    assert (44000 + 255) // 256 < lo and (80000 + 3374 * sps) // 256 > lo + 256
+    held = 0
+    for g, m, c in zip(recs, mean, cnt):
+        j0, count = cases[int(g["position"])]
+        assert j0 == (int(g["position"]) + 255) // 256 and int(c) == count, (g["position"], int(c))
+        if count == 0:
+            assert gatherref.bits(m) == 0
+            continue
+        assert count == spr.burst_window(int(g["position"]), sps)[1] and j0 < 256 < j0 + count
+        want = gatherref.gather_mean(ring[int(g["channel"]), j0 - lo:j0 - lo + count])
+        print("\nchannel %d at %d: %d blocks, mean %.9g, stated reduction %.9g" % (g["channel"], g["position"], count, m, want))
+        assert gatherref.bits(m) == gatherref.bits(want)
+        held += 1
+    assert held == 2 * C
