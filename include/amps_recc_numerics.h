@@ -32,6 +32,14 @@
  *
  * Samples before the start of the stream are zero (x = 0 -> d = 0 -> g = 1).
  *
+ * Non-finite input (all four specs).  Every spec takes finite samples with |x| < 2^60; the product of two of them then stays finite,
+ * and down to zero -- through the subnormal range, which is not flushed -- the bits are the ones this arithmetic gives.  A NaN, an
+ * infinity or a sample whose products overflow is outside the contract and the bits it touches are unspecified, but it is
+ * contained: the slicer of sample n reads x[n-sps .. n] of its own channel and keeps no other state, so such a sample has no effect
+ * on the bits of its channel more than sps samples behind it, none on the records of bursts that lie outside that stretch, and none
+ * on any other channel (tests/test_gpu_sample_values.py).  (x is the slicer's own input.  Behind a translate stage or the filter bank
+ * a non-finite input sample first spreads over the filter's length -- and in the filter bank over every channel -- before it gets here.)
+ *
  * ---- slicer spec B, "product detector" (AMPS_RECC_FLAG_SLICER_PRODUCT) ----
  * The boxcar of spec A sums the sps phase increments that end at n; that sum telescopes:
  *     S[n] = sum_{k=n-sps+1..n} arg(x[k] conj(x[k-1]))  ==  arg(x[n] conj(x[n-sps]))   (mod 2 pi)
