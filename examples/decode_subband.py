@@ -16,6 +16,11 @@ amps.recc -> amps.recc_decode] of grc/recctest.grc.  Needs an MI355X: the librar
     python examples/decode_subband.py --rssi      # with any of the above: the mobiles arrive 0, 3, 6, 9 and 12 dB down in turn, the handle
                                                   # keeps received power (Recc(stream_power=True)) and every decoded MIN is printed with
                                                   # its burst power in dB relative to the strongest (Recc.burst_power)
+    python examples/decode_subband.py --cfo       # with any of the above: the tuner's crystal is 1.4 ppm off (+1200 Hz at 835 MHz) and every
+                                                  # mobile a little off on its own (-300 .. +300 Hz); the handle measures carrier offsets
+                                                  # (Recc(stream_offset=True)) behind a channel filter opened to 16 kHz -- behind the default
+                                                  # 10 kHz one the figure is not usable -- and every decoded MIN is printed
+                                                  # with the offset sent and read (Recc.burst_offset); the median is the tuner's error
 """
 import os
 import sys
@@ -28,6 +33,9 @@ from gr_amps_amd import capi, synth
 RTL2048 = "--rtl2048" in sys.argv[1:]
 RTL = "--rtl" in sys.argv[1:] or RTL2048
 RSSI = "--rssi" in sys.argv[1:]
+CFO = "--cfo" in sys.argv[1:]
+TUNER_HZ = 1200.0                                 # --cfo: what every channel is off by; mobile c adds (c % 5 - 2) * 150 Hz of its own
+CFO_CUTOFF = 16e3                                 # --cfo: the channel filter's cut-off (0 = the flow graph's 10 kHz otherwise)
 INTERP, SPS = 1, 10
 if RTL2048:
     RATE, INTERP, DECIM, SPS, NSAMP = 2.048e6, 5, 64, 8, 1_024_000   # 0.5 s of signal; 2.048 Msps x 5/64 = 160 ksps per channel
@@ -49,16 +57,18 @@ else:
 
 try:
     rx = capi.Recc(n_channels=len(centres), sps=SPS, max_samples=NSAMP // DECIM if INTERP == 1 else NSAMP * INTERP // DECIM + 1, max_bursts=64,
-                   stream_power=RSSI)
+                   stream_power=RSSI, stream_offset=CFO)
 except capi.AmpsError as e:
     sys.exit("no MI355X here (%s): the library has no CPU fallback" % e)
 
 rng = np.random.default_rng(7)
 k = np.arange(NSAMP)
 x = np.zeros(NSAMP, np.complex128)
-sent = {}
+sent, sent_hz = {}, {}
 for c, fc in enumerate(centres):                  # one seizure burst per channel, at its own time
-    iq, truth = synth.make_channel_block(NSAMP, 1, seed=7000 + c, sps=RATE / 20e3 if INTERP > 1 else 10 * DECIM, snr_db=40.0, first=FIRST + GAP * c)
+    iq, truth = synth.make_channel_block(NSAMP, 1, seed=7000 + c, sps=RATE / 20e3 if INTERP > 1 else 10 * DECIM, snr_db=40.0, first=FIRST + GAP * c,
+                                          **({"cfo_hz": TUNER_HZ + 150.0 * (c % 5 - 2)} if CFO else {}))
+    sent_hz[c] = TUNER_HZ + 150.0 * (c % 5 - 2)
     if RSSI:
         iq = iq * 10.0 ** (-3.0 * (c % 5) / 20.0)
     x += iq * np.exp(2j * np.pi * fc * k / RATE)
@@ -73,9 +83,9 @@ if RTL:                                           # the dongle's converter: 8 bi
 
 with rx:
     if INTERP > 1:
-        rx.set_xlate_resampled(RATE, centres, INTERP, DECIM)
+        rx.set_xlate_resampled(RATE, centres, INTERP, DECIM, cutoff_hz=CFO_CUTOFF if CFO else 0.0)
     else:
-        rx.set_xlate_shared(RATE, centres, DECIM)
+        rx.set_xlate_shared(RATE, centres, DECIM, cutoff_hz=CFO_CUTOFF if CFO else 0.0)
     pos = 0
     while pos < NSAMP:                            # blocks of any size: samples short of a decimation step wait in the handle
         n = min(int(rng.integers(10_000, 150_000)), NSAMP - pos)
@@ -86,6 +96,7 @@ with rx:
         pos += n
     recs = rx.drain()
     power, nblk = rx.burst_power(recs) if RSSI else (None, None)
+    read_hz, nblk_hz = rx.burst_offset(recs) if CFO else (None, None)
 print("%d bursts sent, %d decoded" % (len(sent), len(recs)))
 for r in recs:
     ch, got = int(r["channel"]), r["min"].decode()
@@ -98,4 +109,11 @@ if RSSI and len(recs):
         ch = int(r["channel"])
         rel = "%6.1f dB" % (10.0 * np.log10(p / power.max())) if nb else "  (not held)"
         print("  channel %3d  MIN %s  %s  over %d blocks of 256 samples (sent %d dB)" % (ch, r["min"].decode(), rel, int(nb), -3 * (ch % 5)))
+if CFO and len(recs):
+    print("carrier offset, Hz from the channel centre (the tuner %+.0f Hz off, every mobile up to 300 Hz on its own):" % TUNER_HZ)
+    for r, hz, nb in zip(recs, read_hz, nblk_hz):
+        ch = int(r["channel"])
+        print("  channel %3d  MIN %s  sent %+7.1f Hz  read %s  over %d blocks of 256 samples"
+              % (ch, r["min"].decode(), sent_hz[ch], "%+7.1f Hz" % hz if nb else "(not held)", int(nb)))
+    print("tuner error (median of %d): %+.1f Hz" % (int(np.count_nonzero(nblk_hz)), float(np.median(read_hz[nblk_hz > 0]))))
 sys.exit(0 if len(recs) == len(sent) and all(sent.get(int(r["channel"])) == r["min"].decode() for r in recs) else 1)

@@ -26,6 +26,7 @@ FLAG_SLICER_EXACT = 128
 FLAG_FIXED_TIMING = 256
 FLAG_CHANNEL_POWER = 512
 FLAG_STREAM_POWER = 0x400                # received power on the IQ and translate seams (block means; channel_power: the wideband seam's snapshots)
+FLAG_STREAM_OFFSET = 0x800               # carrier offset on the IQ and translate seams (lag-one autocorrelation sums per block)
 POWER_STRIDE = 256                       # AMPS_RECC_POWER_STRIDE: channel-rate samples between two power snapshots / in one power block
 
 # slicer names accepted by Recc(slicer=...): numeric spec of include/amps_recc_numerics.h -> cfg flag
@@ -144,11 +145,13 @@ EXPORTS = (
     "amps_recc_push_raw_shared_as", "amps_recc_push_raw_as", "amps_recc_debug_xlate_shared_as", "amps_recc_debug_xlate_as",
     "amps_recc_xlate_shared_plan",
     "amps_recc_set_xlate_resampled", "amps_recc_xlate_resample_plan",
+    "amps_recc_channel_autocorr", "amps_recc_burst_autocorr", "amps_recc_burst_offset",
 )
 _XLATE_RESAMPLED = ("amps_recc_set_xlate_resampled", "amps_recc_xlate_resample_plan")
 _XLATE_AS = ("amps_recc_push_raw_shared_as", "amps_recc_push_raw_as", "amps_recc_debug_xlate_shared_as", "amps_recc_debug_xlate_as")
 _XLATE_SHARED = ("amps_recc_set_xlate_shared", "amps_recc_push_raw_shared", "amps_recc_debug_xlate_shared")
 _POWER = ("amps_recc_channel_power", "amps_recc_burst_power", "amps_recc_power_ring_snaps")
+_OFFSET = ("amps_recc_channel_autocorr", "amps_recc_burst_autocorr", "amps_recc_burst_offset")
 _NEW_IN_ABI4 = ("amps_recc_push_wideband_dist", "amps_recc_rccl_info", "amps_recc_rccl_abort", "amps_recc_rccl_set_timeout")
 DIST_BROADCAST, DIST_SCATTER_ALLGATHER = 0, 1
 # sample formats of the translate seams' _as entry points (AMPS_RECC_SAMPLES_*): the element dtype of a block, two per sample
@@ -224,6 +227,10 @@ def load():
         L.amps_recc_channel_power.argtypes = [vp, C.c_uint64, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
         L.amps_recc_burst_power.argtypes = [vp, vp, C.c_size_t, vp, vp]
         L.amps_recc_power_ring_snaps.argtypes = [vp]
+    if hasattr(L, "amps_recc_channel_autocorr"):      # likewise
+        L.amps_recc_channel_autocorr.argtypes = [vp, C.c_uint64, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+        L.amps_recc_burst_autocorr.argtypes = [vp, vp, C.c_size_t, vp, vp]
+        L.amps_recc_burst_offset.argtypes = [vp, vp, C.c_size_t, vp, vp]
     L.amps_recc_reply_words.argtypes = [vp, C.POINTER(Reply)]
     L.amps_recc_set_xlate.argtypes = [vp, C.POINTER(XlateCfg)]
     L.amps_recc_push_raw.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int]
@@ -247,7 +254,7 @@ def load():
     for name in EXPORTS:
         if name in ("amps_recc_default_slicer", "amps_recc_default_wideband_decim", "amps_recc_debug_exact_slice", "amps_recc_rccl_unique_id", "amps_recc_rccl_init",
                     "amps_recc_push_wideband_bcast", "amps_recc_drain_gather", "amps_recc_debug_slicer_bits",
-                    "amps_recc_push_wideband_short", "amps_recc_xlate_shared_plan") + _NEW_IN_ABI4 + _POWER + _XLATE_SHARED + _XLATE_AS + _XLATE_RESAMPLED and not hasattr(L, name):
+                    "amps_recc_push_wideband_short", "amps_recc_xlate_shared_plan") + _NEW_IN_ABI4 + _POWER + _OFFSET + _XLATE_SHARED + _XLATE_AS + _XLATE_RESAMPLED and not hasattr(L, name):
             continue
         if name not in ("amps_recc_strerror", "amps_recc_burst_size", "amps_recc_destroy"):   # every other entry point returns int
             getattr(L, name).restype = C.c_uint32 if name == "amps_recc_power_ring_snaps" else C.c_int
@@ -340,7 +347,7 @@ class Recc:
 
     def __init__(self, n_channels=1, sps=None, max_samples=0, max_bursts=1024, device=-1, time_kernels=False,
                  stream=None, wideband=None, majority=False, unfused_wideband=False, sync_tolerance=0, slicer="default",
-                 sync_torch=True, keep_bursts=False, fixed_timing=False, channel_power=False, stream_power=False):
+                 sync_torch=True, keep_bursts=False, fixed_timing=False, channel_power=False, stream_power=False, stream_offset=False):
         L = load()
         if isinstance(slicer, bool) or slicer not in _SLICER_FLAGS:        # a typo must not run a different numeric spec silently
             raise ValueError("slicer must be one of %r" % sorted(map(str, _SLICER_FLAGS)))
@@ -367,7 +374,8 @@ class Recc:
                      | (FLAG_UNFUSED_WIDEBAND if unfused_wideband else 0)
                      | _SLICER_FLAGS[slicer]
                      | (FLAG_KEEP_BURSTS if keep_bursts else 0) | (FLAG_FIXED_TIMING if fixed_timing else 0)
-                     | (FLAG_CHANNEL_POWER if channel_power else 0) | (FLAG_STREAM_POWER if stream_power else 0))
+                     | (FLAG_CHANNEL_POWER if channel_power else 0) | (FLAG_STREAM_POWER if stream_power else 0)
+                     | (FLAG_STREAM_OFFSET if stream_offset else 0))
         cfg.stream = stream
         cfg.sync_tolerance = sync_tolerance
         if wideband:
@@ -894,6 +902,57 @@ class Recc:
         if rc:
             raise AmpsError(rc, "amps_recc_burst_power")
         return mean, cnt
+
+    # ---- carrier offset of the IQ and translate seams (handles created with stream_offset=True): the lag-one autocorrelation sum of
+    # every block of 256 channel-rate samples, and its sum and argument over a record's capture
+    @property
+    def autocorr_ring_blocks(self):
+        """blocks the handle keeps per row: the slicer-bit ring's span R / 256, R the smallest power of two >= max_samples + sps * 3586
+        + 1024 (include/amps_recc.h: amps_recc_debug_slicer_bits)"""
+        need, span = self.max_samples + self.sps * 3586 + 1024, 1
+        while span < need:
+            span <<= 1
+        return span // POWER_STRIDE
+
+    def channel_autocorr(self, first=None, n=None):
+        """(complex64 [rows][n], first): A[row][first + i] = 2^-8 sum of y[s] conj(y[s - 1]) over the channel-rate samples
+        [256 (first + i), 256 (first + i + 1)), once the pushes so far have finished (amps_recc_channel_autocorr).  Default: everything
+        currently held, as channel_power on a stream_power handle"""
+        L = load()
+        rows, prod = C.c_uint32(0), C.c_uint64(0)
+        rc = L.amps_recc_channel_autocorr(self._h, 0, 0, None, 0, C.byref(rows), C.byref(prod))
+        if rc:
+            raise AmpsError(rc, "amps_recc_channel_autocorr")
+        if first is None:
+            first = max(-(-self._origin // POWER_STRIDE), prod.value - self.autocorr_ring_blocks)   # the held window's first block
+        if n is None:
+            n = max(0, prod.value - first)
+        out = np.zeros((rows.value, n), np.complex64)
+        if n:
+            rc = L.amps_recc_channel_autocorr(self._h, first, n, _hostptr(out), n, None, None)
+            if rc:
+                raise AmpsError(rc, "amps_recc_channel_autocorr")
+        return out, int(first)
+
+    def burst_autocorr(self, records):
+        """(sum complex64 [n], count uint32 [n]) for records as drain() returns them: the sum of A over the blocks wholly inside each
+        record's capture and their number, (0, 0) where the ring no longer (or not yet) holds them (amps_recc_burst_autocorr)"""
+        recs = np.ascontiguousarray(records, BURST_DTYPE).reshape(-1)
+        total, cnt = np.zeros(recs.size, np.complex64), np.zeros(recs.size, np.uint32)
+        rc = load().amps_recc_burst_autocorr(self._h, _hostptr(recs), recs.size, _hostptr(total), _hostptr(cnt))
+        if rc:
+            raise AmpsError(rc, "amps_recc_burst_autocorr")
+        return total, cnt
+
+    def burst_offset(self, records):
+        """(offset in Hz float32 [n], count uint32 [n]): the argument of burst_autocorr's sums times fs / 2 pi, fs = 20000 * sps; 0.0
+        where nothing is held (amps_recc_burst_offset).  Positive: the mobile is above the channel centre"""
+        recs = np.ascontiguousarray(records, BURST_DTYPE).reshape(-1)
+        hz, cnt = np.zeros(recs.size, np.float32), np.zeros(recs.size, np.uint32)
+        rc = load().amps_recc_burst_offset(self._h, _hostptr(recs), recs.size, _hostptr(hz), _hostptr(cnt))
+        if rc:
+            raise AmpsError(rc, "amps_recc_burst_offset")
+        return hz, cnt
 
     def set_timing(self, mode):
         """mode: "off" | "all" | "dominant" (only the streaming kernel of the seam in use is bracketed by HIP events) |

@@ -45,6 +45,7 @@ struct amps_recc {
     BchScratch bch;                   // amps_bch_*
     ChannelizerState chz;             // wideband seam: the filter bank
     PowerRing power;                  // received power (AMPS_RECC_FLAG_CHANNEL_POWER or AMPS_RECC_FLAG_STREAM_POWER: one ring, filled by that seam's producer)
+    AutocorrRing offset;              // carrier offset (AMPS_RECC_FLAG_STREAM_OFFSET: the lag-one autocorrelation sums of the IQ and translate seams)
     XlateState xl;                    // the translate stage in the form configured last (amps_recc_set_xlate / _set_xlate_shared)
     RefState ref;                     // reference-timing seam (G2 -> G3 -> G4 as the flow graph wires them; created on first use)
     RcclState rccl;                   // one band over several GPUs: amps_recc_rccl_init / amps_recc_push_wideband_bcast
@@ -75,12 +76,14 @@ bool is_group_handle(const amps_recc *h) { return h->chz.enabled && h->chz.group
 
 // what capture_run_iq and channelizer_run are handed: the power ring of a handle that keeps one
 const PowerRing *power_of(const amps_recc *h) { return h->power.ring ? &h->power : nullptr; }
+const AutocorrRing *offset_of(const amps_recc *h) { return h->offset.ring ? &h->offset : nullptr; }
 
 int reset_state(amps_recc *h)
 {
     hipStream_t s = h->stream.get();
     if (int rc = capture_reset(h->cap, s)) return rc;
     if (int rc = power_ring_reset(h->power, s)) return rc;
+    if (int rc = autocorr_ring_reset(h->offset, s)) return rc;
     if (int rc = records_reset(h->lists, s)) return rc;
     if (int rc = symbols_reset(h->sym, s)) return rc;
     if (int rc = channelizer_reset(h->chz, s)) return rc;
@@ -151,6 +154,9 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
     // and no filter bank
     if ((cfg->flags & AMPS_RECC_FLAG_STREAM_POWER) &&
         (cfg->wideband_channels || cfg->max_samples_per_push == 0 || (cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER))) return -EINVAL;
+    // the carrier offset is measured on the same stream, under the same conditions; it combines with AMPS_RECC_FLAG_STREAM_POWER
+    if ((cfg->flags & AMPS_RECC_FLAG_STREAM_OFFSET) &&
+        (cfg->wideband_channels || cfg->max_samples_per_push == 0 || (cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER))) return -EINVAL;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return -ENODEV;
     int dev = cfg->device;
@@ -190,6 +196,7 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
     if (!rc && cfg->max_samples_per_push) rc = capture_create(h->cap, *cfg, h->C, h->slicer, cfg->wideband_channels != 0, dev);
     step("IQ seam buffers allocated");
     if (!rc && (cfg->flags & AMPS_RECC_FLAG_STREAM_POWER)) rc = power_ring_create(h->power, PowerRule::BLOCK, h->C, h->cap.ring_words);
+    if (!rc && (cfg->flags & AMPS_RECC_FLAG_STREAM_OFFSET)) rc = autocorr_ring_create(h->offset, h->C, h->cap.ring_words);
     if (!rc && cfg->wideband_channels) rc = channelizer_create(h->chz, *cfg);
     step("channelizer created");
     if (!rc && (cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER)) rc = power_ring_create(h->power, PowerRule::SNAPSHOT, h->chz.C, h->cap.ring_words, &h->chz.row2chan, cfg->n_channels);
@@ -281,7 +288,7 @@ int amps_recc_push_iq(amps_recc_t *h, const float *iq, size_t ld, size_t nsamp, 
     if (mem == AMPS_MEM_HOST) {
         if (int rc = h->cap.stage_iq.stage(d, ld, nsamp, h->C, (size_t)h->C * h->cfg.max_samples_per_push, &d, &dld)) return rc;
     }
-    int rc = capture_run_iq(h->cap, h->lists, h->tm, h->stream.get(), d, dld, (uint32_t)nsamp, power_of(h));
+    int rc = capture_run_iq(h->cap, h->lists, h->tm, h->stream.get(), d, dld, (uint32_t)nsamp, power_of(h), offset_of(h));
     if (!rc && mem == AMPS_MEM_HOST) rc = h->cap.stage_iq.arm(h->stream.get());
     return rc;
 }
@@ -496,7 +503,7 @@ static int xlate_push(amps_recc *h, const void *iq, size_t ld, size_t nsamp, int
     if (rc) return rc;
     if (int rc2 = debug_sync(h->stream.get(), what)) return rc2;
     if (nout == 0) return 0;
-    return capture_run_iq(h->cap, h->lists, h->tm, h->stream.get(), f, fld, nout, power_of(h));
+    return capture_run_iq(h->cap, h->lists, h->tm, h->stream.get(), f, fld, nout, power_of(h), offset_of(h));
 }
 
 // test tap: run the translate stage alone and copy its rows out
@@ -858,6 +865,37 @@ int amps_recc_burst_power(amps_recc_t *h, const amps_recc_burst_t *recs, size_t 
 }
 
 uint32_t amps_recc_power_ring_snaps(const amps_recc_t *h) { return h && h->power.ring ? h->power.slots : 0u; }
+
+int amps_recc_channel_autocorr(amps_recc_t *h, uint64_t first_block, size_t n, float *out, size_t out_ld, uint32_t *rows, uint64_t *produced_blocks)
+{
+    if (!h || (n && (!out || out_ld < n))) return -EINVAL;
+    if (!h->offset.ring) return -ENOSYS;
+    STALE_CHECK(h);
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = sync_stream(h, h->stream.get())) return rc;
+    return autocorr_ring_channels(h->offset, h->cap.n_done, h->cap.origin, h->stream.get(), first_block, n, out, out_ld, rows, produced_blocks);
+}
+
+int amps_recc_burst_autocorr(amps_recc_t *h, const amps_recc_burst_t *recs, size_t n, float *sum, uint32_t *n_blocks)
+{
+    if (!h || (n && (!recs || !sum || !n_blocks))) return -EINVAL;
+    if (!h->offset.ring) return -ENOSYS;
+    STALE_CHECK(h);
+    if (n == 0) return 0;
+    if (n > 0xffffffffull) return -E2BIG;
+    auto idle = [h]() -> int { HIP_TRY(hipSetDevice(h->device)); return sync_stream(h, h->stream.get()); };
+    return autocorr_ring_bursts(h->offset, h->cap.n_done, h->cap.origin, (uint32_t)AMPS_RECC_CAPTURE_SYMS * h->sps, h->stream.get(), idle, recs, n, sum, n_blocks);
+}
+
+int amps_recc_burst_offset(amps_recc_t *h, const amps_recc_burst_t *recs, size_t n, float *offset_hz, uint32_t *n_blocks)
+{
+    if (!h || (n && (!recs || !offset_hz || !n_blocks))) return -EINVAL;
+    if (!h->offset.ring) return -ENOSYS;
+    std::vector<float> sum(2 * n);
+    if (int rc = amps_recc_burst_autocorr(h, recs, n, sum.data(), n_blocks)) return rc;
+    for (size_t i = 0; i < n; i++) offset_hz[i] = autocorr_offset_hz(sum[2 * i], sum[2 * i + 1], n_blocks[i], h->sps);
+    return 0;
+}
 
 int amps_recc_set_origin(amps_recc_t *h, uint64_t first_sample)
 {

@@ -8,6 +8,7 @@
 #include "recc_records.hip.h"
 #include "recc_timing.hip.h"
 #include "recc_stream_power.hip.h"
+#include "recc_stream_offset.hip.h"
 
 namespace amps {
 
@@ -242,9 +243,9 @@ inline FrontArgs front_args(const CaptureState &c, RecordLists &L, const FrontGe
 // the fused chain on channel-major device IQ: front -> carry -> resolve -> capture/decode
 // one workgroup per channel; wide groups when a channel spans more wave segments than 256 lanes cover in one batch.
 // pw: the handle keeps received power (AMPS_RECC_FLAG_STREAM_POWER): its block means are taken behind the streaming kernel, from the
-// block and the carry that launch read
+// block and the carry that launch read; ac: likewise its lag-one autocorrelation sums (AMPS_RECC_FLAG_STREAM_OFFSET)
 inline int capture_run_iq(CaptureState &c, RecordLists &L, TimingState &tm, hipStream_t s, const float2 *iq, uint64_t ld, uint32_t nsamp,
-                          const PowerRing *pw = nullptr)
+                          const PowerRing *pw = nullptr, const AutocorrRing *ac = nullptr)
 {
     c.origin_locked = true;
     if (nsamp == 0) return 0;
@@ -266,7 +267,9 @@ inline int capture_run_iq(CaptureState &c, RecordLists &L, TimingState &tm, hipS
         const front_kernel_t k = front_kernel_for(c.sps, c.slicer, fa.tol != 0);
         if (!k) return -EINVAL;
         hipLaunchKernelGGL(k, dim3((nwaves + 3) / 4), dim3(256), 0, s, fa);
-        if (pw) { g.end(); stream_power_launch(*pw, fa, s); }     // outside the streaming kernel's span: T_FRONT times what it always timed
+        if (pw || ac) g.end();                                    // outside the streaming kernel's span: T_FRONT times what it always timed
+        if (pw) stream_power_launch(*pw, fa, s);
+        if (ac) stream_autocorr_launch(*ac, fa, s);
     }
     if (int rc = debug_sync(s, "front")) return rc;
     if (!P) {                                              // a push too short for a 64-sample word only moves the carry

@@ -20,7 +20,9 @@
 //                                      channel at center_hz (default +160 kHz, :889-937) -> channel filter + fused chain on the GPU;
 //                                      cutoff_hz (default 0 = the flow graph's 10 kHz) widens the channel filter for mobiles off their carrier.
 //                                      A last argument `power` makes the block keep received power: every burst's lines are followed by
-//                                      `MSG power channel 0 <10 log10(mean power)> dB n=<blocks>`, as `wide ... power` prints them
+//                                      `MSG power channel 0 <10 log10(mean power)> dB n=<blocks>`, as `wide ... power` prints them; a last
+//                                      argument `offset` makes it measure the carrier offset: `MSG offset channel 0 <Hz> Hz n=<blocks>` behind
+//                                      every burst's lines.  Both may be given, in either order
 //   recctest sub  <file.raw> <chunk> <rate_hz> <decim> <c0,c1,...>   one narrowband fc32 capture at rate_hz holding several channels -> gr::amps::recc_subband
 //                 (<decim> may be L/M, e.g. 5/64 for a 2.048 Msps capture: the rational resampler)
 //                                      (the channel filter per centre c0, c1, ... in Hz relative to the capture's centre, decimation `decim` -- 1, 2, 4,
@@ -30,7 +32,9 @@
 //                                      interleaved int16, .sc8 / .cs8 int8, .cu8 offset-binary uint8 (what USRP-class, HackRF and RTL-SDR tools
 //                                      write), read as they are through the block's input format; anything else is fc32.  A last argument
 //                                      `power` (behind the centres) adds `MSG power channel <c> <10 log10(mean power)> dB n=<blocks>` behind
-//                                      every burst's lines; without it the output is what it always was
+//                                      every burst's lines, a last argument `offset` `MSG offset channel <c> <Hz> Hz n=<blocks>` (the burst's
+//                                      carrier offset from its centre, amps_recc_burst_offset); both may be given, in either order; without
+//                                      them the output is what it always was
 // Every message published on recc_decode's output ports is printed as one text line, which is what
 // tests/test_gpu_host_blocks.py compares with the oracle.
 #include <amps/recc.h>
@@ -95,11 +99,23 @@ void print_power(const pmt::pmt_t &m)
     std::memcpy(&n, b + 4, 4);
     std::printf("MSG power channel %ld %.2f dB n=%u\n", pmt::to_long(pmt::car(m)), 10.0 * std::log10((double)p), (unsigned)n);
 }
-struct power_sink : gr::block {   // the "power" port of a block whose other ports go to recc_decode directly
+// a message of a block's "offset" port: pmt::cons(channel, blob{ float offset_hz; uint32_t n_blocks; }) (amps/recc_subband.h)
+void print_offset(const pmt::pmt_t &m)
+{
+    float hz = 0.f;
+    uint32_t n = 0;
+    const uint8_t *b = (const uint8_t *)pmt::blob_data(pmt::cdr(m));
+    std::memcpy(&hz, b, 4);
+    std::memcpy(&n, b + 4, 4);
+    std::printf("MSG offset channel %ld %.1f Hz n=%u\n", pmt::to_long(pmt::car(m)), (double)hz, (unsigned)n);
+}
+struct power_sink : gr::block {   // the "power" and "offset" ports of a block whose other ports go to recc_decode directly
     power_sink() : gr::block("power_sink", gr::io_signature::make(0, 0, 0), gr::io_signature::make(0, 0, 0))
     {
         message_port_register_in(pmt::mp("power"));
         set_msg_handler(pmt::mp("power"), [](pmt::pmt_t m) { print_power(m); });
+        message_port_register_in(pmt::mp("offset"));
+        set_msg_handler(pmt::mp("offset"), [](pmt::pmt_t m) { print_offset(m); });
     }
     int general_work(int n, gr_vector_int &, gr_vector_const_void_star &, gr_vector_void_star &) override { return n; }
 };
@@ -110,8 +126,15 @@ int main(int argc, char **argv)
     if (argc < 3) { std::fprintf(stderr, "usage: %s syms|iq|iqb|raw|bank|wide|sub <file> [chunk] [center_hz | C | slicer | rate_hz decim c0,c1,...]\n", argv[0]); return 2; }
     const std::string mode = argv[1];
     // sub and raw: a last argument `power` asks for received power (wide finds its own further down, behind its positional arguments)
-    const bool power_last = (mode == "sub" || mode == "raw") && argc > 3 && std::string(argv[argc - 1]) == "power";
-    if (power_last) argc--;
+    // and `offset` for the carrier offset; the two may come in either order
+    bool power_last = false, offset_last = false;
+    while ((mode == "sub" || mode == "raw") && argc > 3) {
+        const std::string last = argv[argc - 1];
+        if (last == "power" && !power_last) power_last = true;
+        else if (last == "offset" && !offset_last) offset_last = true;
+        else break;
+        argc--;
+    }
     const int chunk = argc > 3 ? std::atoi(argv[3]) : 4096;
     std::ifstream f(argv[2], std::ios::binary);
     if (!f) { std::perror(argv[2]); return 2; }
@@ -232,7 +255,7 @@ int main(int argc, char **argv)
             const int interp = slash ? std::atoi(argv[5]) : 1, decim = std::atoi(slash ? slash + 1 : argv[5]);
             const double rate = std::atof(argv[4]);
             const int sps = decim > 0 && interp > 0 ? (int)std::lround(rate * interp / decim / 20e3) : 10;
-            auto src = gr::amps::recc_subband::make(rate, centers, decim, sps, -1, 0.0, 0.0, format, interp, power_last);
+            auto src = gr::amps::recc_subband::make(rate, centers, decim, sps, -1, 0.0, 0.0, format, interp, power_last, offset_last);
             struct demux : gr::block {
                 std::shared_ptr<gr::basic_block> dec;
                 demux() : gr::block("demux", gr::io_signature::make(0, 0, 0), gr::io_signature::make(0, 0, 0))
@@ -244,6 +267,8 @@ int main(int argc, char **argv)
                     });
                     message_port_register_in(pmt::mp("power"));
                     set_msg_handler(pmt::mp("power"), [](pmt::pmt_t m) { print_power(m); });
+                    message_port_register_in(pmt::mp("offset"));
+                    set_msg_handler(pmt::mp("offset"), [](pmt::pmt_t m) { print_offset(m); });
                 }
                 int general_work(int n, gr_vector_int &, gr_vector_const_void_star &, gr_vector_void_star &) override { return n; }
             };
@@ -251,6 +276,7 @@ int main(int argc, char **argv)
             dm->dec = dec;
             gr::msg_connect(src, "bursts", dm, "bursts");
             if (power_last) gr::msg_connect(src, "power", dm, "power");
+            if (offset_last) gr::msg_connect(src, "offset", dm, "offset");
             const size_t ns = data.size() / item;
             for (size_t off = 0; off < ns; off += (size_t)chunk) {
                 int n = (int)std::min<size_t>((size_t)chunk, ns - off);
@@ -268,10 +294,11 @@ int main(int argc, char **argv)
         } else {
             const double center = argc > 4 ? std::atof(argv[4]) : 160e3;
             const double cutoff = argc > 5 ? std::atof(argv[5]) : 0.0;
-            auto src = mode == "raw" ? gr::amps::recc_fused::make(10, 400e3, center, 2, cutoff, 0.0, power_last) : gr::amps::recc_fused::make(10);
+            auto src = mode == "raw" ? gr::amps::recc_fused::make(10, 400e3, center, 2, cutoff, 0.0, power_last, offset_last) : gr::amps::recc_fused::make(10);
             if (mode == "iqb") gr::msg_connect(src, "bursts", dec, "bursts"); else gr::msg_connect(src, "records", dec, "records");
             auto ps = std::make_shared<power_sink>();
             if (power_last) gr::msg_connect(src, "power", ps, "power");
+            if (offset_last) gr::msg_connect(src, "offset", ps, "offset");
             const size_t ns = data.size() / 8;
             for (size_t off = 0; off < ns; off += (size_t)chunk) {
                 int n = (int)std::min<size_t>((size_t)chunk, ns - off);

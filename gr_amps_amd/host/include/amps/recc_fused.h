@@ -14,6 +14,11 @@
 // pmt::cons(from_long(0), blob{ float mean_power; uint32_t n_snaps }), the mean |sample|^2 of what the kernel sliced (the input, or the
 // channel filter's output) over the record's capture and the number of 256-sample blocks averaged, as gr::amps::recc_wideband and
 // gr::amps::recc_subband publish it.
+// channel_offset = true measures the carrier offset (AMPS_RECC_FLAG_STREAM_OFFSET) and adds the port "offset": behind each "records"
+// message pmt::cons(from_long(0), blob{ float offset_hz; uint32_t n_blocks }), amps_recc_burst_offset of the record: how far the mobile's
+// carrier stands from the channel centre, and the 256-sample blocks it was read from.  Behind the default 10 kHz channel filter the
+// figure is not usable (the filter cuts the side of the signal the offset moved outwards and the estimate leans the other way); set
+// xlate_cutoff_hz = 16e3 to steer by it.
 #pragma once
 #include <amps/api.h>
 
@@ -24,7 +29,7 @@ class AMPS_API recc_fused : virtual public gr::sync_block {
 public:
     typedef AMPS_SPTR<recc_fused> sptr;
     static sptr make(int samples_per_symbol = 10, double xlate_rate_hz = 0.0, double xlate_center_hz = 0.0, int xlate_decim = 2,
-                     double xlate_cutoff_hz = 0.0, double xlate_width_hz = 0.0, bool channel_power = false);
+                     double xlate_cutoff_hz = 0.0, double xlate_width_hz = 0.0, bool channel_power = false, bool channel_offset = false);
 };
 
 } // namespace amps

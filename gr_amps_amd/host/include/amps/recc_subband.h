@@ -13,6 +13,12 @@
 //                           amps_recc_burst_power returns them -- the mean |channel filter output|^2 over the record's capture, linear and
 //                           unscaled (RSSI up to a constant), and the number of 256-sample power blocks averaged (130 / 131 at 10 samples
 //                           per symbol; 0 with power 0.0 if the handle no longer holds them);
+//                 "offset"  (blocks made with channel_offset = true only) pmt::cons(from_long(channel), blob(8)) for every record, behind
+//                           its "records" (and "power") message: { float offset_hz; uint32_t n_blocks; } as amps_recc_burst_offset returns
+//                           them -- how far the mobile's carrier stands from centers_hz[channel], positive above it, and the number of
+//                           256-sample blocks it was read from (0 with 0.0 Hz if the handle no longer holds them).  Behind the default
+//                           10 kHz cut-off the figure is not usable -- the filter cuts the side of the signal the offset moved outwards,
+//                           and the estimate leans the other way; with cutoff_hz = 16e3 it reads about 5 % low;
 // as gr::amps::recc_wideband publishes them.  channel c = the channel at centers_hz[c] relative to the stream's centre.
 #pragma once
 #include <amps/api.h>
@@ -36,8 +42,10 @@ public:
     //         unsigned bytes (RTL-SDR).  The block pushes the items as they are (amps_recc_push_raw_shared_as: 4 or 2 bytes per sample
     //         to the device, no float copy on the host); the records are those of the plainly converted stream.
     // channel_power: keep per-channel received power (AMPS_RECC_FLAG_STREAM_POWER) and publish every record's burst power on "power"
+    // channel_offset: measure the carrier offset (AMPS_RECC_FLAG_STREAM_OFFSET) and publish every record's on "offset"
     static sptr make(double rate_hz, const std::vector<double> &centers_hz, int decim = 4, int samples_per_symbol = 10, int slicer = -1,
-                     double cutoff_hz = 0.0, double width_hz = 0.0, int input_format = 0, int interp = 1, bool channel_power = false);
+                     double cutoff_hz = 0.0, double width_hz = 0.0, int input_format = 0, int interp = 1, bool channel_power = false,
+                     bool channel_offset = false);
 };
 
 } // namespace amps

@@ -17,14 +17,15 @@ class recc_fused_impl : public recc_fused {
     amps_recc_t *d_handle;
     bool d_raw;
     bool d_power;                                  // AMPS_RECC_FLAG_STREAM_POWER: every record's burst power goes out on "power"
+    bool d_offset;                                 // AMPS_RECC_FLAG_STREAM_OFFSET: every record's carrier offset goes out on "offset"
     std::vector<unsigned char> d_bursts;
     static const int kMaxPush = 1 << 20;
     static const int kMaxRecs = 64;
 
 public:
-    recc_fused_impl(int sps, double xlate_rate, double xlate_center, int xlate_decim, double xlate_cutoff, double xlate_width, bool channel_power)
+    recc_fused_impl(int sps, double xlate_rate, double xlate_center, int xlate_decim, double xlate_cutoff, double xlate_width, bool channel_power, bool channel_offset)
         : gr::sync_block("recc_fused", gr::io_signature::make(1, 1, 2 * sizeof(float)), gr::io_signature::make(0, 0, 0)), d_handle(nullptr),
-          d_raw(xlate_rate > 0.0), d_power(channel_power), d_bursts((size_t)kMaxRecs * AMPS_RECC_CAPTURE_SYMS)
+          d_raw(xlate_rate > 0.0), d_power(channel_power), d_offset(channel_offset), d_bursts((size_t)kMaxRecs * AMPS_RECC_CAPTURE_SYMS)
     {
         amps_recc_cfg_t cfg = {};
         cfg.struct_size = sizeof(cfg);
@@ -33,7 +34,7 @@ public:
         cfg.max_samples_per_push = kMaxPush;
         cfg.max_bursts = kMaxRecs;
         cfg.device = -1;
-        cfg.flags = AMPS_RECC_FLAG_KEEP_BURSTS | (channel_power ? AMPS_RECC_FLAG_STREAM_POWER : 0u);   // the captured symbols travel with the record
+        cfg.flags = AMPS_RECC_FLAG_KEEP_BURSTS | (channel_power ? AMPS_RECC_FLAG_STREAM_POWER : 0u) | (channel_offset ? AMPS_RECC_FLAG_STREAM_OFFSET : 0u);   // the captured symbols travel with the record
         int rc = amps_recc_create(&d_handle, &cfg);
         if (rc != 0) throw std::runtime_error(std::string("amps::recc_fused: ") + amps_recc_strerror(rc));
         if (d_raw) {
@@ -53,6 +54,7 @@ public:
         message_port_register_out(pmt::mp("bursts"));          // what amps_recc publishes: connects to amps_recc_decode unchanged
         message_port_register_out(pmt::mp("records"));         // the same burst already decoded (recc_decode accepts it too)
         if (d_power) message_port_register_out(pmt::mp("power"));
+        if (d_offset) message_port_register_out(pmt::mp("offset"));
     }
     ~recc_fused_impl() { amps_recc_destroy(d_handle); }
 
@@ -69,7 +71,10 @@ public:
             amps_recc_burst_t recs[kMaxRecs];
             float pow[kMaxRecs];
             uint32_t nsnap[kMaxRecs];
-            if (!recc_drain_and_publish(*this, "recc_fused", false, d_handle, recs, d_bursts.data(), kMaxRecs, d_power ? pow : nullptr, d_power ? nsnap : nullptr))
+            float off[kMaxRecs];
+            uint32_t offn[kMaxRecs];
+            if (!recc_drain_and_publish(*this, "recc_fused", false, d_handle, recs, d_bursts.data(), kMaxRecs, d_power ? pow : nullptr, d_power ? nsnap : nullptr,
+                                        d_offset ? off : nullptr, d_offset ? offn : nullptr))
                 return WORK_DONE;
             done += n;
         }
@@ -79,10 +84,10 @@ public:
 };
 
 recc_fused::sptr recc_fused::make(int samples_per_symbol, double xlate_rate_hz, double xlate_center_hz, int xlate_decim, double xlate_cutoff_hz, double xlate_width_hz,
-                                  bool channel_power)
+                                  bool channel_power, bool channel_offset)
 {
     return gnuradio::get_initial_sptr(new recc_fused_impl(samples_per_symbol, xlate_rate_hz, xlate_center_hz, xlate_decim, xlate_cutoff_hz, xlate_width_hz,
-                                                          channel_power));
+                                                          channel_power, channel_offset));
 }
 
 } // namespace amps

@@ -1,5 +1,6 @@
 // recc_publish.h -- what recc_wideband, recc_subband and recc_fused do behind every push: drain the records with their bursts, ask for
-// their burst power where the block keeps power, and publish on "bursts", "records" and "power".  Internal to lib/.
+// their burst power where the block keeps power and for their carrier offset where it measures that, and publish on "bursts",
+// "records", "power" and "offset".  Internal to lib/.
 #pragma once
 #include <amps/api.h>
 #include <cerrno>
@@ -13,12 +14,17 @@ namespace amps {
 // payload of the "power" port, behind the record's channel number
 struct recc_power_payload { float mean_power; uint32_t n_snaps; };
 static_assert(sizeof(recc_power_payload) == 8, "payload of the power port");
+// payload of the "offset" port, behind the record's channel number (amps_recc_burst_offset)
+struct recc_offset_payload { float offset_hz; uint32_t n_blocks; };
+static_assert(sizeof(recc_offset_payload) == 8, "payload of the offset port");
 
 // What differs between the blocks: the name in the stderr lines, and whether "bursts" and "records" carry (channel, blob) pairs
 // or the bare blob (recc_fused: one channel, and what gr::amps::recc publishes).  recs / bursts hold `cap` records; pow / nsnap hold as
-// many, or are null on a block that keeps no power.  false = stop the flow graph (the caller knows what that takes).
+// many, or are null on a block that keeps no power; off_hz / off_n likewise on a block that measures no carrier offset.  false = stop
+// the flow graph (the caller knows what that takes).
 inline bool recc_drain_and_publish(gr::basic_block &blk, const char *name, bool channel_pairs, amps_recc_t *h, amps_recc_burst_t *recs,
-                                   unsigned char *bursts, size_t cap, float *pow, uint32_t *nsnap)
+                                   unsigned char *bursts, size_t cap, float *pow, uint32_t *nsnap, float *off_hz = nullptr,
+                                   uint32_t *off_n = nullptr)
 {
     size_t nrec = 0;
     int rc = amps_recc_drain_bursts(h, recs, bursts, cap, &nrec);
@@ -31,6 +37,10 @@ inline bool recc_drain_and_publish(gr::basic_block &blk, const char *name, bool 
         rc = amps_recc_burst_power(h, recs, nrec, pow, nsnap);
         if (rc != 0) { std::fprintf(stderr, "amps::%s: burst power: %s\n", name, amps_recc_strerror(rc)); return false; }
     }
+    if (off_hz && nrec) {                          // likewise the window of the autocorrelation sums
+        rc = amps_recc_burst_offset(h, recs, nrec, off_hz, off_n);
+        if (rc != 0) { std::fprintf(stderr, "amps::%s: burst offset: %s\n", name, amps_recc_strerror(rc)); return false; }
+    }
     for (size_t i = 0; i < nrec; i++) {
         const pmt::pmt_t ch = pmt::from_long((long)recs[i].channel);
         const pmt::pmt_t burst = pmt::mp(bursts + i * AMPS_RECC_CAPTURE_SYMS, AMPS_RECC_CAPTURE_SYMS), rec = pmt::mp(&recs[i], sizeof(recs[i]));
@@ -39,6 +49,10 @@ inline bool recc_drain_and_publish(gr::basic_block &blk, const char *name, bool 
         if (pow) {
             const recc_power_payload p = { pow[i], nsnap[i] };
             blk.message_port_pub(pmt::mp("power"), pmt::cons(ch, pmt::mp(&p, sizeof(p))));
+        }
+        if (off_hz) {
+            const recc_offset_payload p = { off_hz[i], off_n[i] };
+            blk.message_port_pub(pmt::mp("offset"), pmt::cons(ch, pmt::mp(&p, sizeof(p))));
         }
     }
     return true;

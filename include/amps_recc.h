@@ -55,7 +55,9 @@ extern "C" {
                                      still 4, two entry points added and nothing changed: amps_recc_set_xlate_resampled / amps_recc_xlate_resample_plan,
                                      the shared translate seam behind a rational L / M resampler;
                                      still 4, a flag added and nothing changed: AMPS_RECC_FLAG_STREAM_POWER, received power on the IQ and
-                                     translate seams through amps_recc_channel_power / _burst_power / _power_ring_snaps) */
+                                     translate seams through amps_recc_channel_power / _burst_power / _power_ring_snaps;
+                                     still 4, a flag and three entry points added and nothing changed: AMPS_RECC_FLAG_STREAM_OFFSET, carrier offset
+                                     on the IQ and translate seams through amps_recc_channel_autocorr / _burst_autocorr / _burst_offset) */
 
 /* protocol constants of the reference */
 #define AMPS_RECC_TRIGGER_SYMS 74   /* lib/recc_impl.cc:76-77: 37 bits x 2 Manchester symbols   */
@@ -99,6 +101,12 @@ extern "C" {
                                                allocated or launched for it and no record changes.  On a handle with wideband_channels
                                                (fused or not), with max_samples_per_push == 0 (symbol seam only), or together with
                                                AMPS_RECC_FLAG_CHANNEL_POWER: -EINVAL */
+#define AMPS_RECC_FLAG_STREAM_OFFSET 0x800u /* IQ and translate seams: keep the per-channel lag-one autocorrelation sums from which a burst's
+                                               carrier offset is read (amps_recc_channel_autocorr, amps_recc_burst_autocorr,
+                                               amps_recc_burst_offset below).  Off by default; with it off nothing is allocated or launched
+                                               for it and no record changes.  Combines freely with AMPS_RECC_FLAG_STREAM_POWER.  On a handle
+                                               with wideband_channels (fused or not), with max_samples_per_push == 0 (symbol seam only), or
+                                               together with AMPS_RECC_FLAG_CHANNEL_POWER: -EINVAL */
 #define AMPS_RECC_FLAG_MAJORITY    0x2u /* decode mode "majority" instead of "reference" (SURVEY.md 8f.2), see below */
 
 /* message classes, the branches of lib/recc_decode_impl.cc:108-168 */
@@ -547,6 +555,52 @@ uint32_t amps_recc_power_ring_snaps(const amps_recc_t *h);
  *   (130 or 131 at 10 samples per symbol, 38 or 39 at 3).  If any of those blocks is not held: {0.0f, 0}, which is not an error.
  *   channel >= n_channels: -EINVAL.
  * Cost: one short kernel behind the streaming kernel per push, one more read of the push's samples. */
+
+/* ---- carrier offset of the IQ and translate seams (handles created with AMPS_RECC_FLAG_STREAM_OFFSET; -ENOSYS without it) ----
+ * How far a mobile's carrier stands from the centre of its channel, from the lag-one autocorrelation (pulse-pair) sum of the stream:
+ * Manchester FM is balanced over every bit, so over a burst at offset f the products y[s] conj(y[s - 1]) sum to
+ * e^(j 2 pi f / fs) (N+ e^(jd) + N- e^(-jd)) with N+ = N-, whose argument is 2 pi f / fs.  The sum is amplitude-weighted: noise-only
+ * blocks add little.  Behind a channel filter that cuts into the offset signal the estimate reads low, because the filter takes
+ * amplitude from the side of the spectrum the offset moved outwards and the sum leans to the other: 4 - 5 % low behind a translate
+ * seam's filter with cutoff_hz = 16e3, and behind the default 10 kHz cut-off so far that it comes out with the WRONG SIGN -- measure
+ * behind 16 kHz, or on amps_recc_push_iq (DESIGN.md 4.7g has the measured table).
+ * Numbering, rows and blocks are those of AMPS_RECC_FLAG_STREAM_POWER above: y_c[s] the channel-rate sample the streaming kernel slices,
+ *   s absolute (amps_recc_set_origin counted), row = channel, a block AMPS_RECC_POWER_STRIDE = 256 samples.
+ * Block j of row c is  A[c][j] = 2^-8 * sum over s = 256 j ... 256 j + 255 of y_c[s] * conj(y_c[s - 1]) : complex, an fp32 pair
+ *   (re, im), unscaled.  y_c[origin - 1] = 0: the sample in front of the stream is zero, so the first product of a block that begins at
+ *   the origin is zero.  An unmodulated carrier a e^(j 2 pi f s / fs) reads a^2 e^(j 2 pi f / fs).
+ * Summation order, ONE and fixed.  With a = y[s] and b = y[s - 1] the terms are, in fp32,
+ *   re(s) = fma(a.re, b.re, a.im * b.im)   and   im(s) = fma(a.im, b.re, -(a.re * b.im)).
+ *   Re and im are summed separately and alike: lane l = 0 ... 63 adds ((t(256 j + l) + t(256 j + l + 64)) + t(256 j + l + 128)) +
+ *   t(256 j + l + 192); the 64 lane sums are added by the butterfly a_l = a_l + a_(l xor o) for o = 32, 16, 8, 4, 2, 1; the result times
+ *   2^-8, which is exact.  Error: a term carries at most 2 u |a| |b| (the product's rounding and the fma's; |a.re b.re| + |a.im b.im| <=
+ *   |a| |b|), u = 2^-24, and the 255 additions at most 255 u times the sum of the |terms| whatever the order, so each component lies
+ *   within 257 * 2^-24 * 2^-8 * sum |y[s]| |y[s - 1]| of the exact value.  The terms cancel, so the bound is relative to that sum, not to |A|.
+ * Existence, held window, independence: exactly as for the block means above -- block j exists once 256 (j + 1) <= produced,
+ *   *produced_blocks = floor(produced / 256); the window is [max(ceil(origin / 256), produced_blocks - R / 256), produced_blocks),
+ *   R the span of the slicer-bit ring (amps_recc_debug_slicer_bits), and anything outside it is -ERANGE; every record found by a
+ *   push still has its whole capture inside the window when that push is drained; values depend on the stream only (not on the cut
+ *   into pushes, ld, residence or integer format: bit-identical in each case); amps_recc_reset empties the window, the debug taps leave it
+ *   alone.  With both flags on nothing of either changes: the power values are those of a handle with AMPS_RECC_FLAG_STREAM_POWER alone.
+ * Cost: one short kernel behind the streaming kernel per push, one more read of the push's samples. */
+/* out[(row * out_ld + i) * 2 + {0, 1}] = {re, im} of A[row][first_block + i], i < n, into host memory out[rows][out_ld][2], once the
+ * pushes enqueued so far have finished; *rows = n_channels, *produced_blocks = one past the newest block (either may be NULL).  n = 0
+ * only reports.  -ERANGE outside the held window; -EINVAL for a null handle, or out == NULL / out_ld < n with n > 0; -ESTALE as the
+ * data seams.  Changes nothing. */
+int amps_recc_channel_autocorr(amps_recc_t *h, uint64_t first_block, size_t n, float *out, size_t out_ld,
+                               uint32_t *rows, uint64_t *produced_blocks);
+/* Burst sum: for each of the n records (host array; only `channel` and `position` are read) the fp32 sum of A[channel][j] over the
+ * blocks that lie wholly inside the capture -- j0 = ceil(position / 256) ... j1 = floor((position + AMPS_RECC_CAPTURE_SYMS *
+ * samples_per_symbol) / 256) - 1, the blocks of burst power -- into sum[2 i] (re) and sum[2 i + 1] (im), and their number j1 - j0 + 1
+ * into n_blocks[i].  Order, each component alone: lane l adds 0 + A[j0 + l] + A[j0 + l + 64] + ... ascending, then the butterfly
+ * o = 32 ... 1 as above; no division.  If any of those blocks is not held: {0.0f, 0.0f} and 0, which is not an error.
+ * channel >= n_channels: -EINVAL, before any wait (as for a null handle or null arrays with n > 0). */
+int amps_recc_burst_autocorr(amps_recc_t *h, const amps_recc_burst_t *recs, size_t n, float *sum, uint32_t *n_blocks);
+/* Burst offset in Hz: of the same sums, offset_hz[i] = (float)(atan2((double)im, (double)re) * fs / (2 pi)), fs = 20000 *
+ * samples_per_symbol, computed on the host in double and rounded to float once; n_blocks[i] as above.  0.0f when n_blocks[i] == 0 or
+ * both sums are zero.  Positive: the mobile is above the channel centre.  Unambiguous within +- fs / 2.  Errors as
+ * amps_recc_burst_autocorr. */
+int amps_recc_burst_offset(amps_recc_t *h, const amps_recc_burst_t *recs, size_t n, float *offset_hz, uint32_t *n_blocks);
 
 /* ---- one band over the GPUs of a node (BASELINE configs[4]: "RCCL broadcast of wideband IQ over xGMI") ----
  * One process and one handle per GPU, every handle created with cfg.wideband_groups = N, wideband_group = its rank (the reference's
