@@ -27,6 +27,7 @@ FLAG_FIXED_TIMING = 256
 FLAG_CHANNEL_POWER = 512
 FLAG_STREAM_POWER = 0x400                # received power on the IQ and translate seams (block means; channel_power: the wideband seam's snapshots)
 FLAG_STREAM_OFFSET = 0x800               # carrier offset on the IQ and translate seams (lag-one autocorrelation sums per block)
+FLAG_STREAM_OFFSET_UNIT = 0x1000         # the same ring and entry points with the unit-amplitude statistic (the one to use behind a channel filter)
 POWER_STRIDE = 256                       # AMPS_RECC_POWER_STRIDE: channel-rate samples between two power snapshots / in one power block
 
 # slicer names accepted by Recc(slicer=...): numeric spec of include/amps_recc_numerics.h -> cfg flag
@@ -146,12 +147,14 @@ EXPORTS = (
     "amps_recc_xlate_shared_plan",
     "amps_recc_set_xlate_resampled", "amps_recc_xlate_resample_plan",
     "amps_recc_channel_autocorr", "amps_recc_burst_autocorr", "amps_recc_burst_offset",
+    "amps_recc_retune_xlate",
 )
 _XLATE_RESAMPLED = ("amps_recc_set_xlate_resampled", "amps_recc_xlate_resample_plan")
 _XLATE_AS = ("amps_recc_push_raw_shared_as", "amps_recc_push_raw_as", "amps_recc_debug_xlate_shared_as", "amps_recc_debug_xlate_as")
 _XLATE_SHARED = ("amps_recc_set_xlate_shared", "amps_recc_push_raw_shared", "amps_recc_debug_xlate_shared")
 _POWER = ("amps_recc_channel_power", "amps_recc_burst_power", "amps_recc_power_ring_snaps")
 _OFFSET = ("amps_recc_channel_autocorr", "amps_recc_burst_autocorr", "amps_recc_burst_offset")
+_RETUNE = ("amps_recc_retune_xlate",)
 _NEW_IN_ABI4 = ("amps_recc_push_wideband_dist", "amps_recc_rccl_info", "amps_recc_rccl_abort", "amps_recc_rccl_set_timeout")
 DIST_BROADCAST, DIST_SCATTER_ALLGATHER = 0, 1
 # sample formats of the translate seams' _as entry points (AMPS_RECC_SAMPLES_*): the element dtype of a block, two per sample
@@ -231,6 +234,8 @@ def load():
         L.amps_recc_channel_autocorr.argtypes = [vp, C.c_uint64, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
         L.amps_recc_burst_autocorr.argtypes = [vp, vp, C.c_size_t, vp, vp]
         L.amps_recc_burst_offset.argtypes = [vp, vp, C.c_size_t, vp, vp]
+    if hasattr(L, "amps_recc_retune_xlate"):          # likewise
+        L.amps_recc_retune_xlate.argtypes = [vp, C.POINTER(C.c_double), C.c_size_t]
     L.amps_recc_reply_words.argtypes = [vp, C.POINTER(Reply)]
     L.amps_recc_set_xlate.argtypes = [vp, C.POINTER(XlateCfg)]
     L.amps_recc_push_raw.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int]
@@ -254,7 +259,7 @@ def load():
     for name in EXPORTS:
         if name in ("amps_recc_default_slicer", "amps_recc_default_wideband_decim", "amps_recc_debug_exact_slice", "amps_recc_rccl_unique_id", "amps_recc_rccl_init",
                     "amps_recc_push_wideband_bcast", "amps_recc_drain_gather", "amps_recc_debug_slicer_bits",
-                    "amps_recc_push_wideband_short", "amps_recc_xlate_shared_plan") + _NEW_IN_ABI4 + _POWER + _OFFSET + _XLATE_SHARED + _XLATE_AS + _XLATE_RESAMPLED and not hasattr(L, name):
+                    "amps_recc_push_wideband_short", "amps_recc_xlate_shared_plan") + _NEW_IN_ABI4 + _POWER + _OFFSET + _RETUNE + _XLATE_SHARED + _XLATE_AS + _XLATE_RESAMPLED and not hasattr(L, name):
             continue
         if name not in ("amps_recc_strerror", "amps_recc_burst_size", "amps_recc_destroy"):   # every other entry point returns int
             getattr(L, name).restype = C.c_uint32 if name == "amps_recc_power_ring_snaps" else C.c_int
@@ -349,6 +354,8 @@ class Recc:
                  stream=None, wideband=None, majority=False, unfused_wideband=False, sync_tolerance=0, slicer="default",
                  sync_torch=True, keep_bursts=False, fixed_timing=False, channel_power=False, stream_power=False, stream_offset=False):
         L = load()
+        if stream_offset not in (False, True, "unit"):                     # True: the amplitude-weighted sums; "unit": the unit-amplitude ones
+            raise ValueError("stream_offset must be False, True or 'unit'")
         if isinstance(slicer, bool) or slicer not in _SLICER_FLAGS:        # a typo must not run a different numeric spec silently
             raise ValueError("slicer must be one of %r" % sorted(map(str, _SLICER_FLAGS)))
         self.slicer = SLICER_NAMES[L.amps_recc_default_slicer() if hasattr(L, "amps_recc_default_slicer") else 0] if _SLICER_FLAGS[slicer] == 0 else \
@@ -375,7 +382,7 @@ class Recc:
                      | _SLICER_FLAGS[slicer]
                      | (FLAG_KEEP_BURSTS if keep_bursts else 0) | (FLAG_FIXED_TIMING if fixed_timing else 0)
                      | (FLAG_CHANNEL_POWER if channel_power else 0) | (FLAG_STREAM_POWER if stream_power else 0)
-                     | (FLAG_STREAM_OFFSET if stream_offset else 0))
+                     | (FLAG_STREAM_OFFSET_UNIT if stream_offset == "unit" else FLAG_STREAM_OFFSET if stream_offset else 0))
         cfg.stream = stream
         cfg.sync_tolerance = sync_tolerance
         if wideband:
@@ -508,6 +515,15 @@ class Recc:
         rc = load().amps_recc_set_xlate_shared(self._h, C.byref(x))
         if rc:
             raise AmpsError(rc, "amps_recc_set_xlate_shared")
+
+    def retune_xlate(self, centers_hz):
+        """Replace the centres of the configured translate form in mid-stream (amps_recc_retune_xlate): n_channels centres for the
+        shared and the resampled form, one for the per-row form.  Takes effect with the next push; from then on the stage delivers,
+        bit for bit, what a handle configured with these centres from the start would.  Nothing is reset and the host does not wait."""
+        cen = np.ascontiguousarray(centers_hz, np.float64).reshape(-1)
+        rc = load().amps_recc_retune_xlate(self._h, cen.ctypes.data_as(C.POINTER(C.c_double)), cen.size)
+        if rc:
+            raise AmpsError(rc, "amps_recc_retune_xlate")
 
     def set_xlate_resampled(self, rate_hz, centers_hz, interp, decim, gain=0.0, cutoff_hz=0.0, width_hz=0.0):
         """set_xlate_shared for the rates no integer decimation serves: the shared stream is resampled by interp / decim (2.048 Msps
@@ -903,7 +919,8 @@ class Recc:
             raise AmpsError(rc, "amps_recc_burst_power")
         return mean, cnt
 
-    # ---- carrier offset of the IQ and translate seams (handles created with stream_offset=True): the lag-one autocorrelation sum of
+    # ---- carrier offset of the IQ and translate seams (handles created with stream_offset=True, or "unit" for the unit-amplitude
+    # statistic, which is the one to use behind a channel filter): the lag-one autocorrelation sum of
     # every block of 256 channel-rate samples, and its sum and argument over a record's capture
     @property
     def autocorr_ring_blocks(self):
@@ -915,7 +932,8 @@ class Recc:
         return span // POWER_STRIDE
 
     def channel_autocorr(self, first=None, n=None):
-        """(complex64 [rows][n], first): A[row][first + i] = 2^-8 sum of y[s] conj(y[s - 1]) over the channel-rate samples
+        """(complex64 [rows][n], first): A[row][first + i] = 2^-8 sum of y[s] conj(y[s - 1]) (stream_offset="unit": of those products
+        brought to unit amplitude, U) over the channel-rate samples
         [256 (first + i), 256 (first + i + 1)), once the pushes so far have finished (amps_recc_channel_autocorr).  Default: everything
         currently held, as channel_power on a stream_power handle"""
         L = load()

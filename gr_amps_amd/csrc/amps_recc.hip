@@ -45,7 +45,7 @@ struct amps_recc {
     BchScratch bch;                   // amps_bch_*
     ChannelizerState chz;             // wideband seam: the filter bank
     PowerRing power;                  // received power (AMPS_RECC_FLAG_CHANNEL_POWER or AMPS_RECC_FLAG_STREAM_POWER: one ring, filled by that seam's producer)
-    AutocorrRing offset;              // carrier offset (AMPS_RECC_FLAG_STREAM_OFFSET: the lag-one autocorrelation sums of the IQ and translate seams)
+    AutocorrRing offset;              // carrier offset (AMPS_RECC_FLAG_STREAM_OFFSET or _OFFSET_UNIT: the lag-one autocorrelation sums of the IQ and translate seams)
     XlateState xl;                    // the translate stage in the form configured last (amps_recc_set_xlate / _set_xlate_shared)
     RefState ref;                     // reference-timing seam (G2 -> G3 -> G4 as the flow graph wires them; created on first use)
     RcclState rccl;                   // one band over several GPUs: amps_recc_rccl_init / amps_recc_push_wideband_bcast
@@ -155,8 +155,11 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
     if ((cfg->flags & AMPS_RECC_FLAG_STREAM_POWER) &&
         (cfg->wideband_channels || cfg->max_samples_per_push == 0 || (cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER))) return -EINVAL;
     // the carrier offset is measured on the same stream, under the same conditions; it combines with AMPS_RECC_FLAG_STREAM_POWER
-    if ((cfg->flags & AMPS_RECC_FLAG_STREAM_OFFSET) &&
+    // in either statistic, and a handle keeps one ring with one of them
+    constexpr uint32_t OFFSET_FLAGS = AMPS_RECC_FLAG_STREAM_OFFSET | AMPS_RECC_FLAG_STREAM_OFFSET_UNIT;
+    if ((cfg->flags & OFFSET_FLAGS) &&
         (cfg->wideband_channels || cfg->max_samples_per_push == 0 || (cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER))) return -EINVAL;
+    if ((cfg->flags & OFFSET_FLAGS) == OFFSET_FLAGS) return -EINVAL;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return -ENODEV;
     int dev = cfg->device;
@@ -196,7 +199,7 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
     if (!rc && cfg->max_samples_per_push) rc = capture_create(h->cap, *cfg, h->C, h->slicer, cfg->wideband_channels != 0, dev);
     step("IQ seam buffers allocated");
     if (!rc && (cfg->flags & AMPS_RECC_FLAG_STREAM_POWER)) rc = power_ring_create(h->power, PowerRule::BLOCK, h->C, h->cap.ring_words);
-    if (!rc && (cfg->flags & AMPS_RECC_FLAG_STREAM_OFFSET)) rc = autocorr_ring_create(h->offset, h->C, h->cap.ring_words);
+    if (!rc && (cfg->flags & OFFSET_FLAGS)) rc = autocorr_ring_create(h->offset, h->C, h->cap.ring_words, (cfg->flags & AMPS_RECC_FLAG_STREAM_OFFSET_UNIT) != 0);
     if (!rc && cfg->wideband_channels) rc = channelizer_create(h->chz, *cfg);
     step("channelizer created");
     if (!rc && (cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER)) rc = power_ring_create(h->power, PowerRule::SNAPSHOT, h->chz.C, h->cap.ring_words, &h->chz.row2chan, cfg->n_channels);
@@ -600,6 +603,15 @@ int amps_recc_set_xlate_resampled(amps_recc_t *h, const amps_recc_xlate_resample
     if (xlate_resample_admit(x->interp, x->decim, h->sps, x->rate_hz, cutoff, width, &npp) == -EINVAL) return -EINVAL;
     return xlate_create(h->xl, true, h->C, x->decim, h->cfg.max_samples_per_push, x->rate_hz, x->center_hz,
                         xlate_design_taps(gain * x->interp, x->interp * x->rate_hz, cutoff, width), h->stream.get(), x->interp);
+}
+
+int amps_recc_retune_xlate(amps_recc_t *h, const double *center_hz, size_t n)
+{
+    if (!h || !center_hz) return -EINVAL;
+    STALE_CHECK(h);
+    if (!h->xl.enabled) return -ENOSYS;
+    HIP_TRY(hipSetDevice(h->device));
+    return xlate_retune(h->xl, center_hz, n, h->stream.get());
 }
 
 int amps_recc_xlate_resample_plan(double rate_hz, double width_hz, amps_recc_resample_plan_t *out, size_t cap)

@@ -10,6 +10,9 @@
 // the mobile's carrier from the channel centre; the ring keeps the complex sums and never an angle: they add correctly across blocks.
 //
 //   stream_autocorr_kernel       one wave per (block, channel), the four waves of a workgroup on neighbouring channels; no LDS
+//   stream_unit_autocorr_kernel  the same body with every product brought to unit amplitude first (AMPS_RECC_FLAG_STREAM_OFFSET_UNIT:
+//                                U[c][j] = 2^-8 * sum of p / |p|, the statistic that survives a narrow channel filter); a handle keeps
+//                                one ring with one of the two statistics
 //   autocorr_ring_gather_kernel  the complex twin of power_ring_gather_kernel: one wave per record, the sum over a capture's blocks
 //
 // Which blocks exist and which a capture takes is recc_power_ring.hip.h under PowerRule::BLOCK (power_ring_window, power_ring_range):
@@ -51,6 +54,22 @@ struct StreamAutocorrArgs {
     uint32_t groups;         // ceil(n_channels / 4): workgroups per block
 };
 
+// AMPS_RECC_FLAG_STREAM_OFFSET_UNIT: a product (re, im) to unit amplitude, in the sequence include/amps_recc.h states.  e = the binary
+// exponent of the larger magnitude (frexp: that magnitude = f 2^e, 0.5 <= f < 1); both components times 2^-e, which is exact (a
+// component more than 2^100 times smaller than the other may lose bits or vanish below the subnormals: far below u); m = fma(im', im',
+// re' re') lies in [0.25, 2), so nothing overflows or underflows whatever |p| was; one v_rsq_f32 (1 ulp); two multiplies.  A product that
+// is (0, 0) or has a component that is not finite gives (0, 0).
+__device__ __forceinline__ void unit_phasor(float &re, float &im)
+{
+    const float big = fmaxf(fabsf(re), fabsf(im));                // a NaN in one component leaves the other: the test below sees it
+    const bool live = fabsf(re) < INFINITY && fabsf(im) < INFINITY && big > 0.f;
+    const int e = __builtin_amdgcn_frexp_expf(big);
+    const float sr = __builtin_ldexpf(re, -e), si = __builtin_ldexpf(im, -e);
+    const float r = __builtin_amdgcn_rsqf(__builtin_fmaf(si, si, sr * sr));
+    re = live ? sr * r : 0.f;
+    im = live ? si * r : 0.f;
+}
+
 // grid: blocks of the launch x ceil(C / 4), channel groups fastest (one dimension: neither factor is bounded by 65535).
 // Launch-relative sample i (absolute n_done + i) is carry[HALO + i] for i < r_prev and block[i - r_prev] from there on
 // (recc_front_kernel's `fetch`); the select is made per sample: sample s can be the block's first while s - 1 is the carry's last.
@@ -91,6 +110,45 @@ __global__ __launch_bounds__(256) void stream_autocorr_kernel(StreamAutocorrArgs
         a.ring[(size_t)((uint32_t)j & a.slot_mask) * a.n_channels + c] = make_float2(re * (1.0f / AMPS_RECC_POWER_STRIDE), im * (1.0f / AMPS_RECC_POWER_STRIDE));
 }
 
+// The unit-amplitude twin: stream_autocorr_kernel line for line but for unit_phasor on every product.  A kernel of its own and not the
+// same body behind a template switch: with the body shared, the compiler scheduled stream_autocorr_kernel's scalar loads in another
+// order, and that kernel has to stay instruction for instruction what it was (profiles/stream_offset_unit/isa_identity.txt).
+__global__ __launch_bounds__(256) void stream_unit_autocorr_kernel(StreamAutocorrArgs a)
+{
+    const uint32_t b = blockIdx.x / a.groups, g = blockIdx.x - b * a.groups;
+    const uint32_t c = g * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (c >= a.n_channels) return;                                // wave-uniform
+    const uint64_t j = a.first_block + b;
+    const int64_t i0 = (int64_t)(j * AMPS_RECC_POWER_STRIDE) - (int64_t)a.n_done + lane;
+    const float2 *car = a.carry + (uint64_t)c * CARRY_CAP + HALO;
+    const float2 *blk = a.block + (uint64_t)c * a.ld - a.r_prev;
+    float2 x[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {                                 // four independent loads, consecutive lanes on consecutive samples
+        const int64_t i = i0 + 64 * k;
+        x[k] = i < (int64_t)a.r_prev ? car[i] : blk[i];
+    }
+    float2 before = make_float2(0.f, 0.f);                        // sample 256 j - 1: lane 0 only
+    if (lane == 0) before = i0 - 1 < (int64_t)a.r_prev ? car[i0 - 1] : blk[i0 - 1];
+    float re = 0.f, im = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        float2 p = make_float2(__shfl_up(x[k].x, 1), __shfl_up(x[k].y, 1));           // lane l - 1's sample of this quarter
+        const int kq = k ? k - 1 : 0;
+        const float2 last = k ? make_float2(__shfl(x[kq].x, 63), __shfl(x[kq].y, 63)) : before;
+        if (lane == 0) p = last;                                                       // lane 63's sample of the quarter before
+        float tr = __builtin_fmaf(x[k].x, p.x, x[k].y * p.y);
+        float ti = __builtin_fmaf(x[k].y, p.x, -(x[k].x * p.y));
+        unit_phasor(tr, ti);
+        re = k ? re + tr : tr;
+        im = k ? im + ti : ti;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { re += __shfl_xor(re, o); im += __shfl_xor(im, o); }
+    if (lane == 0)
+        a.ring[(size_t)((uint32_t)j & a.slot_mask) * a.n_channels + c] = make_float2(re * (1.0f / AMPS_RECC_POWER_STRIDE), im * (1.0f / AMPS_RECC_POWER_STRIDE));
+}
+
 // Burst sums: record i asks for `count` entries of ring row `row` from entry j0 on (the host has found them held; count = 0: one of
 // them is not); the answer is {re, im, count}.  The summation order is stated at the top of this file.
 struct AutocorrBurstSum { float re, im; uint32_t count; };
@@ -115,13 +173,15 @@ __global__ __launch_bounds__(256) void autocorr_ring_gather_kernel(const float2 
 struct AutocorrRing {
     DevBuf<float2> ring;                      // [slots][rows] complex sums; null: the handle was created without the flag
     uint32_t slots = 0, rows = 0;             // slots: a power of two; row = channel
+    bool unit = false;                        // the ring's one statistic: U (AMPS_RECC_FLAG_STREAM_OFFSET_UNIT) instead of A
     DevBuf<PowerBurstQuery> q_dev;            // amps_recc_burst_autocorr / _burst_offset scratch (grow-only)
     DevBuf<AutocorrBurstSum> q_out;
 };
 
 // ring_words: of the slicer-bit ring, whose window the ring shares (a power of two, >= 32)
-inline int autocorr_ring_create(AutocorrRing &p, uint32_t rows, uint32_t ring_words)
+inline int autocorr_ring_create(AutocorrRing &p, uint32_t rows, uint32_t ring_words, bool unit)
 {
+    p.unit = unit;
     p.slots = 64u * ring_words / AMPS_RECC_POWER_STRIDE;
     p.rows = rows;
     return p.ring.alloc((size_t)p.slots * rows);
@@ -143,7 +203,7 @@ inline void stream_autocorr_launch(const AutocorrRing &p, const FrontArgs &fa, h
     if (nblk == 0) return;                                        // e.g. a 64-sample launch that ends at s = 128 mod 256
     const uint32_t groups = (fa.n_channels + 3) / 4;
     const StreamAutocorrArgs a{ fa.block, fa.carry, fa.ld, fa.n_done, fa.r_prev, fa.n_channels, first, p.ring.get(), p.slots - 1, groups };
-    hipLaunchKernelGGL(stream_autocorr_kernel, dim3((uint32_t)(nblk * groups)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(p.unit ? stream_unit_autocorr_kernel : stream_autocorr_kernel, dim3((uint32_t)(nblk * groups)), dim3(256), 0, s, a);
 }
 
 // amps_recc_channel_autocorr on an idle stream at position n_done: out is [rows][out_ld][2]

@@ -53,6 +53,7 @@
 #include "amps_recc.h"              // AMPS_RECC_SAMPLES_*
 #include "recc_chz_common.hip.h"    // cf2, cmul, chz_sc16
 #include "recc_devmem.hip.h"
+#include "recc_xlate_steps.h"
 
 namespace amps {
 
@@ -447,6 +448,7 @@ struct XlateState {
     int cur = 0;
     uint64_t n_abs = 0;
     uint64_t k_abs = 0;              // rational form: absolute index of the next output
+    double rate_hz = 0.0;            // of the input stream: what xlate_retune turns new centres into steps by
     DevBuf<float> taps;
     DevBuf<uint64_t> steps;          // [C]
     DevBuf<float2> carry[2];         // [rows][carry_cap] (hist + D samples a row; hist + 1 of the rational form), double-buffered
@@ -539,18 +541,13 @@ inline int xlate_create(XlateState &x, bool shared, uint32_t C, uint32_t D, uint
     if (rational ? !shared || xlr_limits(L, D, 8, 1) == -EINVAL : !xlate_kernel_for(shared, D)) return -EINVAL;
     if (C == 0 || !center_hz || taps.empty() || !(rate_hz > 0.0)) return -EINVAL;
     std::vector<uint64_t> steps(C);
-    for (uint32_t c = 0; c < C; c++) {
-        if (!(std::fabs(center_hz[c]) <= rate_hz)) return -EINVAL;   // a NaN included
-        // fraction of a turn per input sample, two's complement for negative offsets
-        const long double f = (long double)center_hz[c] / (long double)rate_hz;
-        const long double fr = f - std::floor(f);
-        steps[c] = (uint64_t)(fr * 18446744073709551616.0L);
-    }
+    if (xlate_steps_from(rate_hz, center_hz, C, steps.data())) return -EINVAL;   // a centre beyond +-rate_hz, a NaN included
     if (taps.size() > 1000000u) return -E2BIG;
     const uint32_t ntp = (uint32_t)(((taps.size() + L - 1) / L + 7) / 8 * 8);   // per phase
     if (rational ? xlr_limits(L, D, ntp, 1) != 0 : ntp > xlate_max_taps(shared, D)) return -E2BIG;
     xlate_destroy(x);
     x.shared = shared; x.C = C; x.rows = shared ? 1 : C; x.D = D; x.L = L; x.ntp = ntp; x.hist = ntp - 1; x.max_out = max_out;
+    x.rate_hz = rate_hz;
     // the rational form's next output never sits before the stream's end (xlate_run): its carry is the history alone
     x.carry_cap = rational ? ntp : ntp + D;
     std::vector<float> padded((size_t)L * ntp, 0.0f);             // phase p, tap i = taps[L i + p], zero beyond
@@ -562,6 +559,29 @@ inline int xlate_create(XlateState &x, bool shared, uint32_t C, uint32_t D, uint
     if (rc) { xlate_destroy(x); return rc; }
     x.enabled = true;
     return xlate_reset(x, s);
+}
+
+// Retune (amps_recc_retune_xlate): new steps for the configured form, everything else kept.  The steps travel as kernel arguments, a
+// chunk a launch, so the update is ordered on the stream behind the kernels already queued, the host waits for nothing and no host
+// buffer is read after the call.  The kernels in front read the old steps, those behind the new ones: a sample's phasor comes from
+// its absolute index, so the stage then delivers what a stage created with these centres would.
+struct XlateStepChunk { uint64_t v[128]; };
+__global__ __launch_bounds__(128) void xlate_steps_store_kernel(uint64_t *steps, uint32_t first, uint32_t n, XlateStepChunk c)
+{
+    if (threadIdx.x < n) steps[first + threadIdx.x] = c.v[threadIdx.x];
+}
+inline int xlate_retune(XlateState &x, const double *center_hz, size_t n, hipStream_t s)
+{
+    if (!x.enabled) return -ENOSYS;
+    std::vector<uint64_t> steps(x.C);
+    if (int rc = xlate_retune_steps(x.shared, x.C, x.rate_hz, center_hz, n, steps.data())) return rc;
+    for (uint32_t first = 0; first < x.C; first += 128) {
+        XlateStepChunk c{};
+        const uint32_t m = std::min<uint32_t>(128, x.C - first);
+        std::copy(steps.begin() + first, steps.begin() + first + m, c.v);
+        hipLaunchKernelGGL(xlate_steps_store_kernel, dim3(1), dim3(128), 0, s, x.steps.get(), first, m, c);
+    }
+    return hipGetLastError() != hipSuccess ? -EIO : 0;
 }
 
 // channels per workgroup of the shared form: as many groups of as few channels as it takes to reach WANT workgroups; one group (the

@@ -22,7 +22,9 @@
 //                                      A last argument `power` makes the block keep received power: every burst's lines are followed by
 //                                      `MSG power channel 0 <10 log10(mean power)> dB n=<blocks>`, as `wide ... power` prints them; a last
 //                                      argument `offset` makes it measure the carrier offset: `MSG offset channel 0 <Hz> Hz n=<blocks>` behind
-//                                      every burst's lines.  Both may be given, in either order
+//                                      every burst's lines.  Both may be given, in either order; `offset unit` selects the unit-amplitude
+//                                      statistic, which is right behind the default 10 kHz filter too.  Behind them `retune=<sample>:<hz>`
+//                                      moves the centre by <hz> before the first chunk at or beyond input sample <sample> (recc_fused::retune)
 //   recctest sub  <file.raw> <chunk> <rate_hz> <decim> <c0,c1,...>   one narrowband fc32 capture at rate_hz holding several channels -> gr::amps::recc_subband
 //                 (<decim> may be L/M, e.g. 5/64 for a 2.048 Msps capture: the rational resampler)
 //                                      (the channel filter per centre c0, c1, ... in Hz relative to the capture's centre, decimation `decim` -- 1, 2, 4,
@@ -33,7 +35,9 @@
 //                                      write), read as they are through the block's input format; anything else is fc32.  A last argument
 //                                      `power` (behind the centres) adds `MSG power channel <c> <10 log10(mean power)> dB n=<blocks>` behind
 //                                      every burst's lines, a last argument `offset` `MSG offset channel <c> <Hz> Hz n=<blocks>` (the burst's
-//                                      carrier offset from its centre, amps_recc_burst_offset); both may be given, in either order; without
+//                                      carrier offset from its centre, amps_recc_burst_offset; `offset unit`: of the unit-amplitude
+//                                      statistic); both may be given, in either order; behind them `retune=<sample>:<hz>` moves every centre
+//                                      by <hz> before the first chunk at or beyond input sample <sample> (recc_subband::retune); without
 //                                      them the output is what it always was
 // Every message published on recc_decode's output ports is printed as one text line, which is what
 // tests/test_gpu_host_blocks.py compares with the oracle.
@@ -127,11 +131,23 @@ int main(int argc, char **argv)
     const std::string mode = argv[1];
     // sub and raw: a last argument `power` asks for received power (wide finds its own further down, behind its positional arguments)
     // and `offset` for the carrier offset; the two may come in either order
-    bool power_last = false, offset_last = false;
+    // `offset unit` selects the unit-amplitude statistic (the one that is right behind the default channel filter).  Behind all of
+    // them `retune=<sample>:<hz>` moves every centre by <hz> before the first chunk that begins at or beyond input sample <sample>
+    bool power_last = false, offset_last = false, unit_last = false;
+    long long retune_at = -1;
+    double retune_hz = 0.0;
+    if ((mode == "sub" || mode == "raw") && argc > 3 && std::strncmp(argv[argc - 1], "retune=", 7) == 0) {
+        char *end = nullptr;
+        retune_at = std::strtoll(argv[argc - 1] + 7, &end, 10);
+        if (retune_at < 0 || *end != ':') { std::fprintf(stderr, "%s: retune=<sample>:<hz>\n", argv[argc - 1]); return 2; }
+        retune_hz = std::atof(end + 1);
+        argc--;
+    }
     while ((mode == "sub" || mode == "raw") && argc > 3) {
         const std::string last = argv[argc - 1];
         if (last == "power" && !power_last) power_last = true;
         else if (last == "offset" && !offset_last) offset_last = true;
+        else if (last == "unit" && !offset_last && argc > 4 && std::string(argv[argc - 2]) == "offset") { offset_last = unit_last = true; argc--; }
         else break;
         argc--;
     }
@@ -255,7 +271,7 @@ int main(int argc, char **argv)
             const int interp = slash ? std::atoi(argv[5]) : 1, decim = std::atoi(slash ? slash + 1 : argv[5]);
             const double rate = std::atof(argv[4]);
             const int sps = decim > 0 && interp > 0 ? (int)std::lround(rate * interp / decim / 20e3) : 10;
-            auto src = gr::amps::recc_subband::make(rate, centers, decim, sps, -1, 0.0, 0.0, format, interp, power_last, offset_last);
+            auto src = gr::amps::recc_subband::make(rate, centers, decim, sps, -1, 0.0, 0.0, format, interp, power_last, offset_last, unit_last);
             struct demux : gr::block {
                 std::shared_ptr<gr::basic_block> dec;
                 demux() : gr::block("demux", gr::io_signature::make(0, 0, 0), gr::io_signature::make(0, 0, 0))
@@ -280,6 +296,11 @@ int main(int argc, char **argv)
             const size_t ns = data.size() / item;
             for (size_t off = 0; off < ns; off += (size_t)chunk) {
                 int n = (int)std::min<size_t>((size_t)chunk, ns - off);
+                if (retune_at >= 0 && off >= (size_t)retune_at) {
+                    for (double &c : centers) c += retune_hz;
+                    src->retune(centers);
+                    retune_at = -1;
+                }
                 gr_vector_const_void_star ins = { data.data() + item * off };
                 if (src->work(n, ins, outs) != 0) return 1;
             }
@@ -294,7 +315,7 @@ int main(int argc, char **argv)
         } else {
             const double center = argc > 4 ? std::atof(argv[4]) : 160e3;
             const double cutoff = argc > 5 ? std::atof(argv[5]) : 0.0;
-            auto src = mode == "raw" ? gr::amps::recc_fused::make(10, 400e3, center, 2, cutoff, 0.0, power_last, offset_last) : gr::amps::recc_fused::make(10);
+            auto src = mode == "raw" ? gr::amps::recc_fused::make(10, 400e3, center, 2, cutoff, 0.0, power_last, offset_last, unit_last) : gr::amps::recc_fused::make(10);
             if (mode == "iqb") gr::msg_connect(src, "bursts", dec, "bursts"); else gr::msg_connect(src, "records", dec, "records");
             auto ps = std::make_shared<power_sink>();
             if (power_last) gr::msg_connect(src, "power", ps, "power");
@@ -302,6 +323,10 @@ int main(int argc, char **argv)
             const size_t ns = data.size() / 8;
             for (size_t off = 0; off < ns; off += (size_t)chunk) {
                 int n = (int)std::min<size_t>((size_t)chunk, ns - off);
+                if (retune_at >= 0 && off >= (size_t)retune_at) {
+                    src->retune(center + retune_hz);
+                    retune_at = -1;
+                }
                 gr_vector_const_void_star ins = { data.data() + 8 * off };
                 if (src->work(n, ins, outs) != 0) return 1;
             }

@@ -18,7 +18,12 @@
 // message pmt::cons(from_long(0), blob{ float offset_hz; uint32_t n_blocks }), amps_recc_burst_offset of the record: how far the mobile's
 // carrier stands from the channel centre, and the 256-sample blocks it was read from.  Behind the default 10 kHz channel filter the
 // figure is not usable (the filter cuts the side of the signal the offset moved outwards and the estimate leans the other way); set
-// xlate_cutoff_hz = 16e3 to steer by it.
+// xlate_cutoff_hz = 16e3 to steer by it -- or offset_unit = true: with channel_offset = true it selects the
+// unit-amplitude statistic (AMPS_RECC_FLAG_STREAM_OFFSET_UNIT), which reads the offset behind the default filter too (+1500 Hz reads
+// +1495 Hz where the other reads -475 Hz).  The port stays "offset".
+// retune(xlate_center_hz) moves the translate stage's centre in mid-stream (amps_recc_retune_xlate): from the next work() call on the
+// stage delivers what a block made with that centre would; nothing is reset.  Call it from the thread that runs work() (a message
+// handler) or between runs; it throws std::runtime_error where the library refuses (no translate stage, a centre beyond the rate).
 #pragma once
 #include <amps/api.h>
 
@@ -29,7 +34,9 @@ class AMPS_API recc_fused : virtual public gr::sync_block {
 public:
     typedef AMPS_SPTR<recc_fused> sptr;
     static sptr make(int samples_per_symbol = 10, double xlate_rate_hz = 0.0, double xlate_center_hz = 0.0, int xlate_decim = 2,
-                     double xlate_cutoff_hz = 0.0, double xlate_width_hz = 0.0, bool channel_power = false, bool channel_offset = false);
+                     double xlate_cutoff_hz = 0.0, double xlate_width_hz = 0.0, bool channel_power = false, bool channel_offset = false,
+                     bool offset_unit = false);
+    virtual void retune(double xlate_center_hz) = 0;
 };
 
 } // namespace amps

@@ -18,7 +18,9 @@
 //                           them -- how far the mobile's carrier stands from centers_hz[channel], positive above it, and the number of
 //                           256-sample blocks it was read from (0 with 0.0 Hz if the handle no longer holds them).  Behind the default
 //                           10 kHz cut-off the figure is not usable -- the filter cuts the side of the signal the offset moved outwards,
-//                           and the estimate leans the other way; with cutoff_hz = 16e3 it reads about 5 % low;
+//                           and the estimate leans the other way; with cutoff_hz = 16e3 it reads about 5 % low.  With
+//                           offset_unit = true the figure is the unit-amplitude statistic's (AMPS_RECC_FLAG_STREAM_OFFSET_UNIT), which
+//                           is usable behind the default filter: within 26 Hz out to +-2.5 kHz (same section);
 // as gr::amps::recc_wideband publishes them.  channel c = the channel at centers_hz[c] relative to the stream's centre.
 #pragma once
 #include <amps/api.h>
@@ -43,9 +45,14 @@ public:
     //         to the device, no float copy on the host); the records are those of the plainly converted stream.
     // channel_power: keep per-channel received power (AMPS_RECC_FLAG_STREAM_POWER) and publish every record's burst power on "power"
     // channel_offset: measure the carrier offset (AMPS_RECC_FLAG_STREAM_OFFSET) and publish every record's on "offset"
+    // offset_unit: with channel_offset, the unit-amplitude statistic (AMPS_RECC_FLAG_STREAM_OFFSET_UNIT) instead; the port stays "offset"
     static sptr make(double rate_hz, const std::vector<double> &centers_hz, int decim = 4, int samples_per_symbol = 10, int slicer = -1,
                      double cutoff_hz = 0.0, double width_hz = 0.0, int input_format = 0, int interp = 1, bool channel_power = false,
-                     bool channel_offset = false);
+                     bool channel_offset = false, bool offset_unit = false);
+    // new centres in mid-stream (amps_recc_retune_xlate): as many as the block was made with; from the next work() call on the stage
+    // delivers what a block made with these centres would, and nothing is reset.  Call it from the thread that runs work() (a message
+    // handler) or between runs; throws std::runtime_error where the library refuses (another number of centres, one beyond the rate)
+    virtual void retune(const std::vector<double> &centers_hz) = 0;
 };
 
 } // namespace amps

@@ -17,13 +17,14 @@ class recc_fused_impl : public recc_fused {
     amps_recc_t *d_handle;
     bool d_raw;
     bool d_power;                                  // AMPS_RECC_FLAG_STREAM_POWER: every record's burst power goes out on "power"
-    bool d_offset;                                 // AMPS_RECC_FLAG_STREAM_OFFSET: every record's carrier offset goes out on "offset"
+    bool d_offset;                                 // AMPS_RECC_FLAG_STREAM_OFFSET or _OFFSET_UNIT: every record's carrier offset goes out on "offset"
     std::vector<unsigned char> d_bursts;
     static const int kMaxPush = 1 << 20;
     static const int kMaxRecs = 64;
 
 public:
-    recc_fused_impl(int sps, double xlate_rate, double xlate_center, int xlate_decim, double xlate_cutoff, double xlate_width, bool channel_power, bool channel_offset)
+    recc_fused_impl(int sps, double xlate_rate, double xlate_center, int xlate_decim, double xlate_cutoff, double xlate_width, bool channel_power, bool channel_offset,
+                    bool offset_unit)
         : gr::sync_block("recc_fused", gr::io_signature::make(1, 1, 2 * sizeof(float)), gr::io_signature::make(0, 0, 0)), d_handle(nullptr),
           d_raw(xlate_rate > 0.0), d_power(channel_power), d_offset(channel_offset), d_bursts((size_t)kMaxRecs * AMPS_RECC_CAPTURE_SYMS)
     {
@@ -34,7 +35,7 @@ public:
         cfg.max_samples_per_push = kMaxPush;
         cfg.max_bursts = kMaxRecs;
         cfg.device = -1;
-        cfg.flags = AMPS_RECC_FLAG_KEEP_BURSTS | (channel_power ? AMPS_RECC_FLAG_STREAM_POWER : 0u) | (channel_offset ? AMPS_RECC_FLAG_STREAM_OFFSET : 0u);   // the captured symbols travel with the record
+        cfg.flags = AMPS_RECC_FLAG_KEEP_BURSTS | (channel_power ? AMPS_RECC_FLAG_STREAM_POWER : 0u) | (channel_offset ? (offset_unit ? AMPS_RECC_FLAG_STREAM_OFFSET_UNIT : AMPS_RECC_FLAG_STREAM_OFFSET) : 0u);   // the captured symbols travel with the record
         int rc = amps_recc_create(&d_handle, &cfg);
         if (rc != 0) throw std::runtime_error(std::string("amps::recc_fused: ") + amps_recc_strerror(rc));
         if (d_raw) {
@@ -57,6 +58,12 @@ public:
         if (d_offset) message_port_register_out(pmt::mp("offset"));
     }
     ~recc_fused_impl() { amps_recc_destroy(d_handle); }
+
+    void retune(double xlate_center_hz) override
+    {
+        const int rc = amps_recc_retune_xlate(d_handle, &xlate_center_hz, 1);
+        if (rc != 0) throw std::runtime_error(std::string("amps::recc_fused (retune): ") + amps_recc_strerror(rc));
+    }
 
     int work(int noutput_items, gr_vector_const_void_star &input_items, gr_vector_void_star &)
     {
@@ -84,10 +91,10 @@ public:
 };
 
 recc_fused::sptr recc_fused::make(int samples_per_symbol, double xlate_rate_hz, double xlate_center_hz, int xlate_decim, double xlate_cutoff_hz, double xlate_width_hz,
-                                  bool channel_power, bool channel_offset)
+                                  bool channel_power, bool channel_offset, bool offset_unit)
 {
     return gnuradio::get_initial_sptr(new recc_fused_impl(samples_per_symbol, xlate_rate_hz, xlate_center_hz, xlate_decim, xlate_cutoff_hz, xlate_width_hz,
-                                                          channel_power, channel_offset));
+                                                          channel_power, channel_offset, offset_unit));
 }
 
 } // namespace amps

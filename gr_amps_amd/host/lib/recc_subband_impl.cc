@@ -21,7 +21,7 @@ class recc_subband_impl : public recc_subband {
     bool d_power = false;                          // AMPS_RECC_FLAG_STREAM_POWER: every record's burst power goes out on "power"
     std::vector<float> d_pow;
     std::vector<uint32_t> d_nsnap;
-    bool d_offset = false;                         // AMPS_RECC_FLAG_STREAM_OFFSET: every record's carrier offset goes out on "offset"
+    bool d_offset = false;                         // AMPS_RECC_FLAG_STREAM_OFFSET or _OFFSET_UNIT: every record's carrier offset goes out on "offset"
     std::vector<float> d_off;
     std::vector<uint32_t> d_offn;
     static const int kMaxOut = 1 << 18;            // channel-rate samples per push: 1.3 s at 200 ksps
@@ -62,7 +62,7 @@ class recc_subband_impl : public recc_subband {
 
 public:
     recc_subband_impl(double rate_hz, const std::vector<double> &centers_hz, int decim, int sps, int slicer, double cutoff_hz, double width_hz, int input_format,
-                      int interp, bool channel_power, bool channel_offset)
+                      int interp, bool channel_power, bool channel_offset, bool offset_unit)
         : gr::sync_block("recc_subband", gr::io_signature::make(1, 1, (int)std::max<size_t>(item_size(input_format), 1)), gr::io_signature::make(0, 0, 0)),
           d_handle(nullptr), d_decim(decim), d_interp(interp), d_format(input_format), d_recs(kMaxRecs), d_bursts((size_t)kMaxRecs * AMPS_RECC_CAPTURE_SYMS),
           d_power(channel_power), d_pow(channel_power ? kMaxRecs : 0), d_nsnap(channel_power ? kMaxRecs : 0),
@@ -79,7 +79,7 @@ public:
         cfg.max_samples_per_push = kMaxOut;
         cfg.max_bursts = kMaxRecs;
         cfg.device = -1;
-        cfg.flags = AMPS_RECC_FLAG_KEEP_BURSTS | (channel_power ? AMPS_RECC_FLAG_STREAM_POWER : 0u) | (channel_offset ? AMPS_RECC_FLAG_STREAM_OFFSET : 0u)
+        cfg.flags = AMPS_RECC_FLAG_KEEP_BURSTS | (channel_power ? AMPS_RECC_FLAG_STREAM_POWER : 0u) | (channel_offset ? (offset_unit ? AMPS_RECC_FLAG_STREAM_OFFSET_UNIT : AMPS_RECC_FLAG_STREAM_OFFSET) : 0u)
                   | (slicer == 0 ? AMPS_RECC_FLAG_SLICER_ATAN : slicer == 1 ? AMPS_RECC_FLAG_SLICER_PRODUCT
                                                   : slicer == 2 ? AMPS_RECC_FLAG_SLICER_SINE : slicer == 3 ? AMPS_RECC_FLAG_SLICER_EXACT : 0u);
         int rc = amps_recc_create(&d_handle, &cfg);
@@ -117,6 +117,12 @@ public:
     }
     ~recc_subband_impl() { amps_recc_destroy(d_handle); }
 
+    void retune(const std::vector<double> &centers_hz) override
+    {
+        const int rc = amps_recc_retune_xlate(d_handle, centers_hz.data(), centers_hz.size());
+        if (rc != 0) throw std::runtime_error(std::string("amps::recc_subband (retune): ") + amps_recc_strerror(rc));
+    }
+
     int work(int noutput_items, gr_vector_const_void_star &input_items, gr_vector_void_star &)
     {
         const unsigned char *in = (const unsigned char *)input_items[0];
@@ -140,10 +146,11 @@ public:
 };
 
 recc_subband::sptr recc_subband::make(double rate_hz, const std::vector<double> &centers_hz, int decim, int samples_per_symbol, int slicer,
-                                      double cutoff_hz, double width_hz, int input_format, int interp, bool channel_power, bool channel_offset)
+                                      double cutoff_hz, double width_hz, int input_format, int interp, bool channel_power, bool channel_offset,
+                                      bool offset_unit)
 {
     return gnuradio::get_initial_sptr(new recc_subband_impl(rate_hz, centers_hz, decim, samples_per_symbol, slicer, cutoff_hz, width_hz, input_format, interp,
-                                                            channel_power, channel_offset));
+                                                            channel_power, channel_offset, offset_unit));
 }
 
 } // namespace amps

@@ -57,7 +57,9 @@ extern "C" {
                                      still 4, a flag added and nothing changed: AMPS_RECC_FLAG_STREAM_POWER, received power on the IQ and
                                      translate seams through amps_recc_channel_power / _burst_power / _power_ring_snaps;
                                      still 4, a flag and three entry points added and nothing changed: AMPS_RECC_FLAG_STREAM_OFFSET, carrier offset
-                                     on the IQ and translate seams through amps_recc_channel_autocorr / _burst_autocorr / _burst_offset) */
+                                     on the IQ and translate seams through amps_recc_channel_autocorr / _burst_autocorr / _burst_offset;
+                                     still 4, a flag and one entry point added and nothing changed: AMPS_RECC_FLAG_STREAM_OFFSET_UNIT, the
+                                     unit-amplitude statistic behind the same three entry points, and amps_recc_retune_xlate) */
 
 /* protocol constants of the reference */
 #define AMPS_RECC_TRIGGER_SYMS 74   /* lib/recc_impl.cc:76-77: 37 bits x 2 Manchester symbols   */
@@ -107,6 +109,13 @@ extern "C" {
                                                for it and no record changes.  Combines freely with AMPS_RECC_FLAG_STREAM_POWER.  On a handle
                                                with wideband_channels (fused or not), with max_samples_per_push == 0 (symbol seam only), or
                                                together with AMPS_RECC_FLAG_CHANNEL_POWER: -EINVAL */
+#define AMPS_RECC_FLAG_STREAM_OFFSET_UNIT 0x1000u /* the same ring, entry points, numbering, window and error rules as
+                                               AMPS_RECC_FLAG_STREAM_OFFSET, holding the UNIT-AMPLITUDE statistic U instead of A (defined
+                                               with the entry points below): the one to use behind a translate seam's channel filter, the
+                                               default 10 kHz one included.  Off by default; with it off nothing is allocated or launched
+                                               for it and no record changes.  A handle keeps one offset ring with one statistic: both
+                                               offset flags together are -EINVAL, as is every combination AMPS_RECC_FLAG_STREAM_OFFSET
+                                               refuses.  Combines freely with AMPS_RECC_FLAG_STREAM_POWER */
 #define AMPS_RECC_FLAG_MAJORITY    0x2u /* decode mode "majority" instead of "reference" (SURVEY.md 8f.2), see below */
 
 /* message classes, the branches of lib/recc_decode_impl.cc:108-168 */
@@ -444,6 +453,22 @@ int amps_recc_push_raw_as(amps_recc_t *h, const void *iq, size_t ld, size_t nsam
 int amps_recc_debug_xlate_shared_as(amps_recc_t *h, const void *iq, size_t nsamp, int format, int mem, float *out, size_t out_ld, size_t *nout);
 int amps_recc_debug_xlate_as(amps_recc_t *h, const void *iq, size_t ld, size_t nsamp, int format, int mem, float *out, size_t out_ld, size_t *nout);
 
+/* Retune: replace the centres of the translate form configured last (amps_recc_set_xlate, _set_xlate_shared or _set_xlate_resampled)
+ * in mid-stream.  Taps, carry, absolute positions, the decimation or L / M and everything behind the stage are kept; nothing is
+ * reset.  n must equal the configured number of centres -- n_channels for the shared and the resampled form, 1 for the per-row form --
+ * else -EINVAL; each centre is checked as the configuration checked it (|center_hz| <= rate_hz, a NaN refused: -EINVAL); -ENOSYS where
+ * no translate form is configured.  A refused call leaves the handle as it was.
+ * The new centres take effect with the NEXT push (or debug tap).  The update is ordered on the handle's stream behind the kernels
+ * already queued, the host does not wait for the device, and center_hz is not read after the call returns.  It may be issued between
+ * amps_recc_drain_begin and amps_recc_drain_end.
+ * CONTRACT.  A sample's phasor comes from its absolute index times its channel's step and the carry holds unmixed input, so from the
+ * first push after the call the stage's output -- what amps_recc_debug_xlate_shared[_as] / amps_recc_debug_xlate[_as] return -- is bit
+ * for bit that of a twin handle configured with the new centres from the start and fed the same pushes.
+ * Downstream ONE discriminator product spans the change: the first new output against the carried last old one.  The block of A / U
+ * and of block power that contains that sample, and any capture that spans it, are therefore not those of the twin.  Records of bursts
+ * whose dotting begins at least 2048 channel-rate samples after the retune point are byte-identical to the twin's. */
+int amps_recc_retune_xlate(amps_recc_t *h, const double *center_hz, size_t n);
+
 /* Reference-timing seam (checking mode): the flow graph's OWN sub-chain in front of amps_recc, computed on the device as GNU
  * Radio 3.7 defines it -- analog.quadrature_demod_cf(1) -> digital.clock_recovery_mm_ff(omega 10, gain_omega .25*.175^2*3,
  * mu 0, gain_mu .05, omega_relative_limit .005) -> digital.binary_slicer_fb (grc/recctest.grc:458, 846-874, 807) -- for
@@ -556,14 +581,15 @@ uint32_t amps_recc_power_ring_snaps(const amps_recc_t *h);
  *   channel >= n_channels: -EINVAL.
  * Cost: one short kernel behind the streaming kernel per push, one more read of the push's samples. */
 
-/* ---- carrier offset of the IQ and translate seams (handles created with AMPS_RECC_FLAG_STREAM_OFFSET; -ENOSYS without it) ----
+/* ---- carrier offset of the IQ and translate seams (handles created with AMPS_RECC_FLAG_STREAM_OFFSET or AMPS_RECC_FLAG_STREAM_OFFSET_UNIT; -ENOSYS without) ----
  * How far a mobile's carrier stands from the centre of its channel, from the lag-one autocorrelation (pulse-pair) sum of the stream:
  * Manchester FM is balanced over every bit, so over a burst at offset f the products y[s] conj(y[s - 1]) sum to
  * e^(j 2 pi f / fs) (N+ e^(jd) + N- e^(-jd)) with N+ = N-, whose argument is 2 pi f / fs.  The sum is amplitude-weighted: noise-only
  * blocks add little.  Behind a channel filter that cuts into the offset signal the estimate reads low, because the filter takes
  * amplitude from the side of the spectrum the offset moved outwards and the sum leans to the other: 4 - 5 % low behind a translate
  * seam's filter with cutoff_hz = 16e3, and behind the default 10 kHz cut-off so far that it comes out with the WRONG SIGN -- measure
- * behind 16 kHz, or on amps_recc_push_iq (DESIGN.md 4.7g has the measured table).
+ * behind 16 kHz, or on amps_recc_push_iq (DESIGN.md 4.7g has the measured table) -- or create the handle with
+ * AMPS_RECC_FLAG_STREAM_OFFSET_UNIT, whose statistic U (defined at the end of this comment) is right behind the default filter too.
  * Numbering, rows and blocks are those of AMPS_RECC_FLAG_STREAM_POWER above: y_c[s] the channel-rate sample the streaming kernel slices,
  *   s absolute (amps_recc_set_origin counted), row = channel, a block AMPS_RECC_POWER_STRIDE = 256 samples.
  * Block j of row c is  A[c][j] = 2^-8 * sum over s = 256 j ... 256 j + 255 of y_c[s] * conj(y_c[s - 1]) : complex, an fp32 pair
@@ -582,7 +608,34 @@ uint32_t amps_recc_power_ring_snaps(const amps_recc_t *h);
  *   push still has its whole capture inside the window when that push is drained; values depend on the stream only (not on the cut
  *   into pushes, ld, residence or integer format: bit-identical in each case); amps_recc_reset empties the window, the debug taps leave it
  *   alone.  With both flags on nothing of either changes: the power values are those of a handle with AMPS_RECC_FLAG_STREAM_POWER alone.
- * Cost: one short kernel behind the streaming kernel per push, one more read of the push's samples. */
+ * Cost: one short kernel behind the streaming kernel per push, one more read of the push's samples.
+ *
+ * THE UNIT-AMPLITUDE STATISTIC (handles created with AMPS_RECC_FLAG_STREAM_OFFSET_UNIT instead).  Every product is brought to unit
+ * amplitude before it is summed, so a sample counts by its phase step alone and a filter that takes amplitude from one side of the
+ * spectrum no longer pulls the sum to the other: behind the DEFAULT 10 kHz filter the burst estimate has the right sign and stays within
+ * 26 Hz of what was sent out to +-2.5 kHz (CPU measurement, DESIGN.md 4.7g: +1500 Hz reads +1495 where A reads -475), and on the IQ
+ * seam it is the better of the two at every level tried.  Use it wherever a channel filter stands in front; A remains for callers who
+ * want the amplitude weighting (noise-only blocks count little in A and fully in U).
+ * Block j of row c is  U[c][j] = 2^-8 * sum over s = 256 j ... 256 j + 255 of u(s),  u(s) = p(s) / |p(s)|,  p(s) = (re(s), im(s)) exactly
+ *   the two fp32 fma expressions above.  u(s) = (0, 0) where both components of p(s) are zero -- the product with y_c[origin - 1] = 0 is
+ *   one such term -- and where a component of p(s) is not finite (fc32 input only).  The divisor stays 2^8 whatever the number of
+ *   zero terms.  An unmodulated carrier reads e^(j 2 pi f / fs) whatever its amplitude.
+ * Normalisation, ONE sequence, fp32, independent of re^2 + im^2 fitting the format: with e the binary exponent of the larger of |re|,
+ *   |im| (that magnitude = f 2^e, 0.5 <= f < 1, subnormals included), re' = re 2^-e and im' = im 2^-e (exact scalings);
+ *   m = fma(im', im', re' * re'), which lies in [0.25, 2); r = the device's reciprocal square root of m (v_rsq_f32, within 1 ulp, NOT
+ *   correctly rounded); u = (re' * r, im' * r).
+ * Summation: lane grouping, ascending order, the xor butterfly 32 ... 1 and the exact times 2^-8 are those of A, on u(s) in place of the
+ *   product.  Values are bit-identical however the stream is cut into pushes, whatever ld, residence or integer format.
+ * Error, against u computed exactly from the fp32 samples, for products that are normal fp32 numbers (a product that underflows has
+ *   lost bits before it is normalised): p carries at most 2 u |p| (u = 2^-24) even where one component cancels, the
+ *   normalisation about 4 u more (m's two roundings halved by the root, 1 ulp of the root, one multiply), so a term is within about 6 u of
+ *   the exact unit vector; the 255 additions add at most 255 u times the sum of |terms| <= 256.  Each component of U lies within
+ *   261 * 2^-24 = 1.6e-5 of exact, ABSOLUTE (|U| <= 1).  Because the root is not correctly rounded this is a bound against the CPU model,
+ *   not bit equality with it.
+ * amps_recc_channel_autocorr, _burst_autocorr and _burst_offset return U, its sum over a capture's blocks and that sum's argument in
+ *   Hz, with every rule stated for A.  |sum of U| / n_blocks lies in [0, 1] and is a COHERENCE figure: near 1 for a clean carrier or
+ *   a strong burst, falling towards 0 as noise takes over; it is read from amps_recc_burst_autocorr and needs no entry point.
+ * Cost: as A plus the normalisation's arithmetic; the kernel reads the same bytes. */
 /* out[(row * out_ld + i) * 2 + {0, 1}] = {re, im} of A[row][first_block + i], i < n, into host memory out[rows][out_ld][2], once the
  * pushes enqueued so far have finished; *rows = n_channels, *produced_blocks = one past the newest block (either may be NULL).  n = 0
  * only reports.  -ERANGE outside the held window; -EINVAL for a null handle, or out == NULL / out_ld < n with n > 0; -ESTALE as the
