@@ -892,32 +892,40 @@ class Recc:
         256 (first + i + 1)), which exists once the whole block has been sliced.  Default: everything currently held -- on either seam
         [max(ceil(origin / 256), produced - ring), produced), `produced` as the library reports it; `first` alone: from there to the
         newest."""
-        L = load()
+        return self._ring_rows("amps_recc_channel_power", self.power_ring_snaps, np.float32, first, n)
+
+    def _ring_rows(self, name, ring_slots, dtype, first, n):
+        """channel_power / channel_autocorr: ask what is produced, default to the held window, allocate, fetch"""
+        fn = getattr(load(), name)
         rows, prod = C.c_uint32(0), C.c_uint64(0)
-        rc = L.amps_recc_channel_power(self._h, 0, 0, None, 0, C.byref(rows), C.byref(prod))
+        rc = fn(self._h, 0, 0, None, 0, C.byref(rows), C.byref(prod))
         if rc:
-            raise AmpsError(rc, "amps_recc_channel_power")
+            raise AmpsError(rc, name)
         if first is None:
-            first = max(-(-self._origin // POWER_STRIDE), prod.value - self.power_ring_snaps)      # the held window's first snapshot
+            first = max(-(-self._origin // POWER_STRIDE), prod.value - ring_slots)      # the held window's first entry
         if n is None:
             n = max(0, prod.value - first)
-        out = np.zeros((rows.value, n), np.float32)
+        out = np.zeros((rows.value, n), dtype)
         if n:
-            rc = L.amps_recc_channel_power(self._h, first, n, _hostptr(out), n, None, None)
+            rc = fn(self._h, first, n, _hostptr(out), n, None, None)
             if rc:
-                raise AmpsError(rc, "amps_recc_channel_power")
+                raise AmpsError(rc, name)
         return out, int(first)
+
+    def _ring_bursts(self, name, records, dtype):
+        """burst_power / burst_autocorr / burst_offset: records in, one value and one count per record out"""
+        recs = np.ascontiguousarray(records, BURST_DTYPE).reshape(-1)
+        val, cnt = np.zeros(recs.size, dtype), np.zeros(recs.size, np.uint32)
+        rc = getattr(load(), name)(self._h, _hostptr(recs), recs.size, _hostptr(val), _hostptr(cnt))
+        if rc:
+            raise AmpsError(rc, name)
+        return val, cnt
 
     def burst_power(self, records):
         """(mean float32 [n], count uint32 [n]) for records as drain() returns them: the mean power snapshot (wideband seam) or power
         block (IQ and translate seams) of each record's channel over its capture and the number averaged, (0.0, 0) where the ring no
         longer (or not yet) holds them (amps_recc_burst_power)"""
-        recs = np.ascontiguousarray(records, BURST_DTYPE).reshape(-1)
-        mean, cnt = np.zeros(recs.size, np.float32), np.zeros(recs.size, np.uint32)
-        rc = load().amps_recc_burst_power(self._h, _hostptr(recs), recs.size, _hostptr(mean), _hostptr(cnt))
-        if rc:
-            raise AmpsError(rc, "amps_recc_burst_power")
-        return mean, cnt
+        return self._ring_bursts("amps_recc_burst_power", records, np.float32)
 
     # ---- carrier offset of the IQ and translate seams (handles created with stream_offset=True, or "unit" for the unit-amplitude
     # statistic, which is the one to use behind a channel filter): the lag-one autocorrelation sum of
@@ -936,41 +944,17 @@ class Recc:
         brought to unit amplitude, U) over the channel-rate samples
         [256 (first + i), 256 (first + i + 1)), once the pushes so far have finished (amps_recc_channel_autocorr).  Default: everything
         currently held, as channel_power on a stream_power handle"""
-        L = load()
-        rows, prod = C.c_uint32(0), C.c_uint64(0)
-        rc = L.amps_recc_channel_autocorr(self._h, 0, 0, None, 0, C.byref(rows), C.byref(prod))
-        if rc:
-            raise AmpsError(rc, "amps_recc_channel_autocorr")
-        if first is None:
-            first = max(-(-self._origin // POWER_STRIDE), prod.value - self.autocorr_ring_blocks)   # the held window's first block
-        if n is None:
-            n = max(0, prod.value - first)
-        out = np.zeros((rows.value, n), np.complex64)
-        if n:
-            rc = L.amps_recc_channel_autocorr(self._h, first, n, _hostptr(out), n, None, None)
-            if rc:
-                raise AmpsError(rc, "amps_recc_channel_autocorr")
-        return out, int(first)
+        return self._ring_rows("amps_recc_channel_autocorr", self.autocorr_ring_blocks, np.complex64, first, n)
 
     def burst_autocorr(self, records):
         """(sum complex64 [n], count uint32 [n]) for records as drain() returns them: the sum of A over the blocks wholly inside each
         record's capture and their number, (0, 0) where the ring no longer (or not yet) holds them (amps_recc_burst_autocorr)"""
-        recs = np.ascontiguousarray(records, BURST_DTYPE).reshape(-1)
-        total, cnt = np.zeros(recs.size, np.complex64), np.zeros(recs.size, np.uint32)
-        rc = load().amps_recc_burst_autocorr(self._h, _hostptr(recs), recs.size, _hostptr(total), _hostptr(cnt))
-        if rc:
-            raise AmpsError(rc, "amps_recc_burst_autocorr")
-        return total, cnt
+        return self._ring_bursts("amps_recc_burst_autocorr", records, np.complex64)
 
     def burst_offset(self, records):
         """(offset in Hz float32 [n], count uint32 [n]): the argument of burst_autocorr's sums times fs / 2 pi, fs = 20000 * sps; 0.0
         where nothing is held (amps_recc_burst_offset).  Positive: the mobile is above the channel centre"""
-        recs = np.ascontiguousarray(records, BURST_DTYPE).reshape(-1)
-        hz, cnt = np.zeros(recs.size, np.float32), np.zeros(recs.size, np.uint32)
-        rc = load().amps_recc_burst_offset(self._h, _hostptr(recs), recs.size, _hostptr(hz), _hostptr(cnt))
-        if rc:
-            raise AmpsError(rc, "amps_recc_burst_offset")
-        return hz, cnt
+        return self._ring_bursts("amps_recc_burst_offset", records, np.float32)
 
     def set_timing(self, mode):
         """mode: "off" | "all" | "dominant" (only the streaming kernel of the seam in use is bracketed by HIP events) |

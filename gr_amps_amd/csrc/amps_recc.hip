@@ -82,8 +82,8 @@ int reset_state(amps_recc *h)
 {
     hipStream_t s = h->stream.get();
     if (int rc = capture_reset(h->cap, s)) return rc;
-    if (int rc = power_ring_reset(h->power, s)) return rc;
-    if (int rc = autocorr_ring_reset(h->offset, s)) return rc;
+    if (int rc = block_ring_reset(h->power, s)) return rc;
+    if (int rc = block_ring_reset(h->offset, s)) return rc;
     if (int rc = records_reset(h->lists, s)) return rc;
     if (int rc = symbols_reset(h->sym, s)) return rc;
     if (int rc = channelizer_reset(h->chz, s)) return rc;
@@ -91,6 +91,35 @@ int reset_state(amps_recc *h)
     if (int rc = ref_reset(h->ref, s)) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     return 0;
+}
+
+// The ring entry points (`ring`: h->power or h->offset, named by member so that a null handle is an argument error like any other).
+// Errors in the order include/amps_recc.h states: -EINVAL for the arguments (args_ok), -ENOSYS without the ring, -ESTALE; a query by
+// record then reports only for n = 0, is -E2BIG above 2^32 - 1 records, and finds a foreign channel (-EINVAL) before any wait.
+int idle_stream(amps_recc *h) { HIP_TRY(hipSetDevice(h->device)); return sync_stream(h, h->stream.get()); }
+
+template <class Ring> int ring_entry(amps_recc *h, Ring amps_recc::*ring, bool args_ok)
+{
+    if (!h || !args_ok) return -EINVAL;
+    if (!(h->*ring).ring) return -ENOSYS;
+    STALE_CHECK(h);
+    return 0;
+}
+
+template <class Ring> int ring_channels(amps_recc *h, Ring amps_recc::*ring, uint64_t first, size_t n, float *out, size_t out_ld, uint32_t *rows, uint64_t *produced)
+{
+    if (int rc = ring_entry(h, ring, !n || (out && out_ld >= n))) return rc;
+    if (int rc = idle_stream(h)) return rc;
+    return block_ring_channels(h->*ring, h->cap.n_done, h->cap.origin, h->stream.get(), first, n, out, out_ld, rows, produced);
+}
+
+// res: one answer per record, for the caller to unpack; empty where nothing was asked
+template <class Ring> int ring_bursts(amps_recc *h, Ring amps_recc::*ring, const amps_recc_burst_t *recs, size_t n, bool outs_ok, std::vector<typename Ring::result_t> &res)
+{
+    if (int rc = ring_entry(h, ring, !n || (recs && outs_ok))) return rc;
+    if (n == 0) return 0;
+    if (n > 0xffffffffull) return -E2BIG;
+    return block_ring_bursts(h->*ring, h->cap.n_done, h->cap.origin, (uint32_t)AMPS_RECC_CAPTURE_SYMS * h->sps, h->stream.get(), [h] { return idle_stream(h); }, recs, n, res);
 }
 
 } // namespace
@@ -150,14 +179,11 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
     if (cfg->n_channels >= (1u << (64 - CAPQ_POS_BITS))) return -EINVAL;
     // received power exists where the fused filter bank runs: the snapshot kernel re-reads that launch's block and carry
     if ((cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER) && (!cfg->wideband_channels || (cfg->flags & AMPS_RECC_FLAG_UNFUSED_WIDEBAND))) return -EINVAL;
-    // on the IQ and translate seams the channel-rate stream itself is read once more: a flag of its own, for handles with the IQ seam
-    // and no filter bank
-    if ((cfg->flags & AMPS_RECC_FLAG_STREAM_POWER) &&
-        (cfg->wideband_channels || cfg->max_samples_per_push == 0 || (cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER))) return -EINVAL;
-    // the carrier offset is measured on the same stream, under the same conditions; it combines with AMPS_RECC_FLAG_STREAM_POWER
-    // in either statistic, and a handle keeps one ring with one of them
+    // on the IQ and translate seams the channel-rate stream itself is read once more, for its power and for the carrier offset: flags
+    // of their own, for handles with the IQ seam and no filter bank.  Power combines with the offset in either statistic, and a handle
+    // keeps one offset ring with one of them
     constexpr uint32_t OFFSET_FLAGS = AMPS_RECC_FLAG_STREAM_OFFSET | AMPS_RECC_FLAG_STREAM_OFFSET_UNIT;
-    if ((cfg->flags & OFFSET_FLAGS) &&
+    if ((cfg->flags & (AMPS_RECC_FLAG_STREAM_POWER | OFFSET_FLAGS)) &&
         (cfg->wideband_channels || cfg->max_samples_per_push == 0 || (cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER))) return -EINVAL;
     if ((cfg->flags & OFFSET_FLAGS) == OFFSET_FLAGS) return -EINVAL;
     int ndev = 0;
@@ -198,11 +224,11 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
     step("pinned record lists mapped");
     if (!rc && cfg->max_samples_per_push) rc = capture_create(h->cap, *cfg, h->C, h->slicer, cfg->wideband_channels != 0, dev);
     step("IQ seam buffers allocated");
-    if (!rc && (cfg->flags & AMPS_RECC_FLAG_STREAM_POWER)) rc = power_ring_create(h->power, PowerRule::BLOCK, h->C, h->cap.ring_words);
-    if (!rc && (cfg->flags & OFFSET_FLAGS)) rc = autocorr_ring_create(h->offset, h->C, h->cap.ring_words, (cfg->flags & AMPS_RECC_FLAG_STREAM_OFFSET_UNIT) != 0);
+    if (!rc && (cfg->flags & AMPS_RECC_FLAG_STREAM_POWER)) rc = block_ring_create(h->power, PowerRule::BLOCK, h->C, h->cap.ring_words);
+    if (!rc && (cfg->flags & OFFSET_FLAGS)) rc = block_ring_create(h->offset, PowerRule::BLOCK, h->C, h->cap.ring_words, (cfg->flags & AMPS_RECC_FLAG_STREAM_OFFSET_UNIT) != 0);
     if (!rc && cfg->wideband_channels) rc = channelizer_create(h->chz, *cfg);
     step("channelizer created");
-    if (!rc && (cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER)) rc = power_ring_create(h->power, PowerRule::SNAPSHOT, h->chz.C, h->cap.ring_words, &h->chz.row2chan, cfg->n_channels);
+    if (!rc && (cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER)) rc = block_ring_create(h->power, PowerRule::SNAPSHOT, h->chz.C, h->cap.ring_words, false, &h->chz.row2chan, cfg->n_channels);
     if (!rc) rc = reset_state(h);
     step("state reset");
     if (rc) { amps_recc_destroy(h); return rc; }
@@ -857,46 +883,30 @@ int amps_recc_debug_slicer_bits(amps_recc_t *h, uint64_t first, size_t n, uint8_
 
 int amps_recc_channel_power(amps_recc_t *h, uint64_t first_snap, size_t n, float *out, size_t out_ld, uint32_t *rows, uint64_t *produced_snaps)
 {
-    if (!h || (n && (!out || out_ld < n))) return -EINVAL;
-    if (!h->power.ring) return -ENOSYS;
-    STALE_CHECK(h);
-    HIP_TRY(hipSetDevice(h->device));
-    if (int rc = sync_stream(h, h->stream.get())) return rc;
-    return power_ring_channels(h->power, h->cap.n_done, h->cap.origin, h->stream.get(), first_snap, n, out, out_ld, rows, produced_snaps);
+    return ring_channels(h, &amps_recc::power, first_snap, n, out, out_ld, rows, produced_snaps);
 }
 
 int amps_recc_burst_power(amps_recc_t *h, const amps_recc_burst_t *recs, size_t n, float *mean_power, uint32_t *n_snaps)
 {
-    if (!h || (n && (!recs || !mean_power || !n_snaps))) return -EINVAL;
-    if (!h->power.ring) return -ENOSYS;
-    STALE_CHECK(h);
-    if (n == 0) return 0;
-    if (n > 0xffffffffull) return -E2BIG;
-    auto idle = [h]() -> int { HIP_TRY(hipSetDevice(h->device)); return sync_stream(h, h->stream.get()); };
-    return power_ring_bursts(h->power, h->cap.n_done, h->cap.origin, (uint32_t)AMPS_RECC_CAPTURE_SYMS * h->sps, h->stream.get(), idle, recs, n, mean_power, n_snaps);
+    std::vector<uint2> res;                                       // {mean as float bits, count}
+    if (int rc = ring_bursts(h, &amps_recc::power, recs, n, mean_power && n_snaps, res)) return rc;
+    for (size_t i = 0; i < res.size(); i++) { std::memcpy(&mean_power[i], &res[i].x, sizeof(float)); n_snaps[i] = res[i].y; }
+    return 0;
 }
 
 uint32_t amps_recc_power_ring_snaps(const amps_recc_t *h) { return h && h->power.ring ? h->power.slots : 0u; }
 
 int amps_recc_channel_autocorr(amps_recc_t *h, uint64_t first_block, size_t n, float *out, size_t out_ld, uint32_t *rows, uint64_t *produced_blocks)
 {
-    if (!h || (n && (!out || out_ld < n))) return -EINVAL;
-    if (!h->offset.ring) return -ENOSYS;
-    STALE_CHECK(h);
-    HIP_TRY(hipSetDevice(h->device));
-    if (int rc = sync_stream(h, h->stream.get())) return rc;
-    return autocorr_ring_channels(h->offset, h->cap.n_done, h->cap.origin, h->stream.get(), first_block, n, out, out_ld, rows, produced_blocks);
+    return ring_channels(h, &amps_recc::offset, first_block, n, out, out_ld, rows, produced_blocks);
 }
 
 int amps_recc_burst_autocorr(amps_recc_t *h, const amps_recc_burst_t *recs, size_t n, float *sum, uint32_t *n_blocks)
 {
-    if (!h || (n && (!recs || !sum || !n_blocks))) return -EINVAL;
-    if (!h->offset.ring) return -ENOSYS;
-    STALE_CHECK(h);
-    if (n == 0) return 0;
-    if (n > 0xffffffffull) return -E2BIG;
-    auto idle = [h]() -> int { HIP_TRY(hipSetDevice(h->device)); return sync_stream(h, h->stream.get()); };
-    return autocorr_ring_bursts(h->offset, h->cap.n_done, h->cap.origin, (uint32_t)AMPS_RECC_CAPTURE_SYMS * h->sps, h->stream.get(), idle, recs, n, sum, n_blocks);
+    std::vector<AutocorrBurstSum> res;
+    if (int rc = ring_bursts(h, &amps_recc::offset, recs, n, sum && n_blocks, res)) return rc;
+    for (size_t i = 0; i < res.size(); i++) { sum[2 * i] = res[i].re; sum[2 * i + 1] = res[i].im; n_blocks[i] = res[i].count; }
+    return 0;
 }
 
 int amps_recc_burst_offset(amps_recc_t *h, const amps_recc_burst_t *recs, size_t n, float *offset_hz, uint32_t *n_blocks)

@@ -13,13 +13,13 @@
 //                              frame's 32 KB window in flight at once), the radix-4 pass, chz_p2 and chz_p3 in one LDS frame buffer,
 //                              then re^2 + im^2 of the handle's bins into the power ring, snapshot-major ([slot][row]: coalesced)
 //
-// The ring, its window and the queries are recc_power_ring.hip.h: this header is the ring's producer on the wideband seam.
+// The ring and the queries are recc_block_ring.hip.h, its window recc_ring_window.h: this header is the ring's producer on the wideband seam.
 #pragma once
 #include "amps_recc.h"
 #include "recc_chz_common.hip.h"
 #include "recc_chz_fft.hip.h"
 #include "recc_chz_fold.hip.h"
-#include "recc_power_ring.hip.h"
+#include "recc_block_ring.hip.h"
 
 namespace amps {
 

@@ -15,9 +15,11 @@
 //                                one ring with one of the two statistics
 //   autocorr_ring_gather_kernel  the complex twin of power_ring_gather_kernel: one wave per record, the sum over a capture's blocks
 //
-// Which blocks exist and which a capture takes is recc_power_ring.hip.h under PowerRule::BLOCK (power_ring_window, power_ring_range):
-// this header keeps the ring ([slots][C] float2, block j in slot j mod slots, slots = 64 * ring_words / 256: the slicer-bit ring's
-// window), its reset with the seam, the copy-out of whole rows and the queries by record.
+// The ring is AutocorrRing below: the BlockRing of recc_block_ring.hip.h with float2 entries ([slots][C], block j in slot j mod slots,
+// slots = 64 * ring_words / 256: the slicer-bit ring's window), PowerRule::BLOCK, channel = row and this header's gather kernel.  Create,
+// reset, the copy-out of whole rows and the queries by record are that header's, the window recc_ring_window.h's, the launch geometry
+// stream_block_launch's (recc_stream_power.hip.h): this header keeps the numeric statement, the kernels and which of the two producers
+// is launched.
 //
 // THE SUMMATION ORDER OF A BLOCK (include/amps_recc.h states it; values are bit-identical however the stream was cut into pushes).
 // With a = y[s] and b = y[s - 1], fp32, re and im summed separately and in the same order:
@@ -36,8 +38,7 @@
 // A record whose capture is not wholly inside the held window goes to the kernel with count = 0 and comes back {0, 0}, 0.
 #pragma once
 #include <cmath>
-#include "recc_front.hip.h"
-#include "recc_power_ring.hip.h"
+#include "recc_stream_power.hip.h"
 
 namespace amps {
 
@@ -170,88 +171,13 @@ __global__ __launch_bounds__(256) void autocorr_ring_gather_kernel(const float2 
 }
 
 // ---- host side ----
-struct AutocorrRing {
-    DevBuf<float2> ring;                      // [slots][rows] complex sums; null: the handle was created without the flag
-    uint32_t slots = 0, rows = 0;             // slots: a power of two; row = channel
-    bool unit = false;                        // the ring's one statistic: U (AMPS_RECC_FLAG_STREAM_OFFSET_UNIT) instead of A
-    DevBuf<PowerBurstQuery> q_dev;            // amps_recc_burst_autocorr / _burst_offset scratch (grow-only)
-    DevBuf<AutocorrBurstSum> q_out;
-};
+// the handle's carrier-offset ring: created under PowerRule::BLOCK with channel = row, `unit` says which statistic it keeps
+typedef BlockRing<float2, AutocorrBurstSum, autocorr_ring_gather_kernel> AutocorrRing;
 
-// ring_words: of the slicer-bit ring, whose window the ring shares (a power of two, >= 32)
-inline int autocorr_ring_create(AutocorrRing &p, uint32_t rows, uint32_t ring_words, bool unit)
-{
-    p.unit = unit;
-    p.slots = 64u * ring_words / AMPS_RECC_POWER_STRIDE;
-    p.rows = rows;
-    return p.ring.alloc((size_t)p.slots * rows);
-}
-
-// with the seam (capture_reset puts n_done back to 0, which empties the window; the ring's floats are cleared for tidiness)
-inline int autocorr_ring_reset(AutocorrRing &p, hipStream_t s)
-{
-    if (!p.ring) return 0;
-    HIP_TRY(hipMemsetAsync(p.ring.get(), 0, sizeof(float2) * (size_t)p.slots * p.rows, s));
-    return 0;
-}
-
-// behind the streaming-kernel launch `fa` of capture_run_iq (fa.P > 0): the blocks j with n_done < 256 (j + 1) <= n_done + P, if any
+// behind the streaming-kernel launch `fa` of capture_run_iq: the ring's one producer
 inline void stream_autocorr_launch(const AutocorrRing &p, const FrontArgs &fa, hipStream_t s)
 {
-    const uint64_t S = AMPS_RECC_POWER_STRIDE;
-    const uint64_t first = fa.n_done / S, nblk = (fa.n_done + fa.P) / S - first;
-    if (nblk == 0) return;                                        // e.g. a 64-sample launch that ends at s = 128 mod 256
-    const uint32_t groups = (fa.n_channels + 3) / 4;
-    const StreamAutocorrArgs a{ fa.block, fa.carry, fa.ld, fa.n_done, fa.r_prev, fa.n_channels, first, p.ring.get(), p.slots - 1, groups };
-    hipLaunchKernelGGL(p.unit ? stream_unit_autocorr_kernel : stream_autocorr_kernel, dim3((uint32_t)(nblk * groups)), dim3(256), 0, s, a);
-}
-
-// amps_recc_channel_autocorr on an idle stream at position n_done: out is [rows][out_ld][2]
-inline int autocorr_ring_channels(const AutocorrRing &p, uint64_t n_done, uint64_t origin, hipStream_t s, uint64_t first_block, size_t n, float *out,
-                                  size_t out_ld, uint32_t *rows, uint64_t *produced_blocks)
-{
-    const PowerWindow w = power_ring_window(PowerRule::BLOCK, p.slots, n_done, origin);
-    if (rows) *rows = p.rows;
-    if (produced_blocks) *produced_blocks = w.hi;
-    if (n == 0) return 0;
-    if (first_block < w.lo || first_block > w.hi || n > w.hi - first_block) return -ERANGE;
-    // the ring is entry-major: n slots (two runs where the range wraps) to the host, transposed there
-    const size_t C = p.rows, s0 = (size_t)(first_block & (p.slots - 1)), n1 = std::min<size_t>(n, p.slots - s0);
-    std::vector<float2> snap(n * C);
-    HIP_TRY(hipMemcpyAsync(snap.data(), p.ring.get() + s0 * C, sizeof(float2) * n1 * C, hipMemcpyDeviceToHost, s));
-    if (n > n1) HIP_TRY(hipMemcpyAsync(snap.data() + n1 * C, p.ring.get(), sizeof(float2) * (n - n1) * C, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (size_t c = 0; c < C; c++)
-        for (size_t i = 0; i < n; i++) { out[2 * (c * out_ld + i)] = snap[i * C + c].x; out[2 * (c * out_ld + i) + 1] = snap[i * C + c].y; }
-    return 0;
-}
-
-// amps_recc_burst_autocorr: -EINVAL for a foreign channel comes before any wait; idle() makes the device current and waits for the
-// stream (the window is that of an idle stream; the copies below are synchronous); span = samples of a capture; sum is [n][2]
-template <class Idle> int autocorr_ring_bursts(AutocorrRing &p, uint64_t n_done, uint64_t origin, uint32_t span, hipStream_t s, Idle &&idle,
-                                               const amps_recc_burst_t *recs, size_t n, float *sum, uint32_t *n_blocks)
-{
-    std::vector<PowerBurstQuery> q(n);
-    for (size_t i = 0; i < n; i++) {
-        if (recs[i].channel >= p.rows) return -EINVAL;
-        q[i].row = recs[i].channel;
-    }
-    if (int rc = idle()) return rc;
-    if (p.q_dev.reserve(n) || p.q_out.reserve(n)) return -ENOMEM;
-    const PowerWindow w = power_ring_window(PowerRule::BLOCK, p.slots, n_done, origin);
-    for (size_t i = 0; i < n; i++) {
-        const PowerRange r = power_ring_range(PowerRule::BLOCK, recs[i].position, span, w);
-        q[i].j0 = r.j0; q[i].count = r.count;
-    }
-    HIP_TRY(hipMemcpy(p.q_dev.get(), q.data(), sizeof(PowerBurstQuery) * n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(autocorr_ring_gather_kernel, dim3((uint32_t)((n + 3) / 4)), dim3(256), 0, s, p.ring.get(), p.rows, p.slots - 1, p.q_dev.get(),
-                       (uint32_t)n, p.q_out.get());
-    HIP_TRY(hipGetLastError());
-    std::vector<AutocorrBurstSum> res(n);
-    HIP_TRY(hipMemcpyAsync(res.data(), p.q_out.get(), sizeof(AutocorrBurstSum) * n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (size_t i = 0; i < n; i++) { sum[2 * i] = res[i].re; sum[2 * i + 1] = res[i].im; n_blocks[i] = res[i].count; }
-    return 0;
+    stream_block_launch(p.unit ? stream_unit_autocorr_kernel : stream_autocorr_kernel, p, fa, s);
 }
 
 // amps_recc_burst_offset: the argument of a burst sum as a frequency, fs = 20000 * samples per symbol; in double, rounded to float

@@ -11,7 +11,9 @@
 //
 //   stream_power_kernel          one wave per (block, channel), the four waves of a workgroup on neighbouring channels; no LDS
 //
-// The ring, its window and the queries are recc_power_ring.hip.h: this header is the ring's producer on the IQ and translate seams.
+// The ring and the queries are recc_block_ring.hip.h, its window recc_ring_window.h: this header is the power ring's producer on the IQ
+// and translate seams, and holds the one launch behind the streaming kernel (stream_block_launch) that the carrier-offset kernels of
+// recc_stream_offset.hip.h share.
 //
 // THE SUMMATION ORDER OF A BLOCK (include/amps_recc.h states it; values are bit-identical however the stream was cut into pushes):
 //   term(s)  = fma(im, im, re * re)                                                  fp32, one rounding in the product, one in the fma
@@ -21,7 +23,7 @@
 // The ring keeps R / 256 blocks per channel, R = 64 * ring_words the span of the slicer-bit ring: both rings hold the same window.
 #pragma once
 #include "recc_front.hip.h"
-#include "recc_power_ring.hip.h"
+#include "recc_block_ring.hip.h"
 
 namespace amps {
 
@@ -65,15 +67,18 @@ __global__ __launch_bounds__(256) void stream_power_kernel(StreamPowerArgs a)
     if (lane == 0) a.ring[(size_t)((uint32_t)j & a.slot_mask) * a.n_channels + c] = acc * (1.0f / AMPS_RECC_POWER_STRIDE);
 }
 
-// behind the streaming-kernel launch `fa` of capture_run_iq (fa.P > 0): the blocks j with n_done < 256 (j + 1) <= n_done + P, if any
-inline void stream_power_launch(const PowerRing &p, const FrontArgs &fa, hipStream_t s)
+// The one launch of the block kernels (this header's and the two of recc_stream_offset.hip.h), each with its own argument struct of
+// the members above: behind the streaming-kernel launch `fa` of capture_run_iq (fa.P > 0), the blocks j with
+// n_done < 256 (j + 1) <= n_done + P, if any, into ring p
+template <class Args, class Ring> void stream_block_launch(void (*kernel)(Args), const Ring &p, const FrontArgs &fa, hipStream_t s)
 {
     const uint64_t S = AMPS_RECC_POWER_STRIDE;
     const uint64_t first = fa.n_done / S, nblk = (fa.n_done + fa.P) / S - first;
     if (nblk == 0) return;                                        // e.g. a 64-sample launch that ends at s = 128 mod 256
     const uint32_t groups = (fa.n_channels + 3) / 4;
-    const StreamPowerArgs a{ fa.block, fa.carry, fa.ld, fa.n_done, fa.r_prev, fa.n_channels, first, p.ring.get(), p.slots - 1, groups };
-    hipLaunchKernelGGL(stream_power_kernel, dim3((uint32_t)(nblk * groups)), dim3(256), 0, s, a);
+    const Args a{ fa.block, fa.carry, fa.ld, fa.n_done, fa.r_prev, fa.n_channels, first, p.ring.get(), p.slots - 1, groups };
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)(nblk * groups)), dim3(256), 0, s, a);
 }
+inline void stream_power_launch(const PowerRing &p, const FrontArgs &fa, hipStream_t s) { stream_block_launch(stream_power_kernel, p, fa, s); }
 
 } // namespace amps

@@ -1,5 +1,5 @@
 """The burst mean of amps_recc_burst_power, restated in numpy float32: the reduction of one ring row in the order the gather kernel
-states (gr_amps_amd/csrc/recc_power_ring.hip.h), which both received-power flags share.
+states (gr_amps_amd/csrc/recc_block_ring.hip.h), which both received-power flags share.
 
   lane l   : a_l = 0 + e[l] + e[l + 64] + ...                       ascending, float32
   wave     : for o = 32, 16, 8, 4, 2, 1:  a = a + a[idx ^ o]         float32
