@@ -4,6 +4,9 @@ AMPS band out (BASELINE configs[3]; replaces 832 x [freq_xlating_fir_filter_ccc 
 
     python examples/decode_wideband.py            # 12 mobiles on random channels, the stream pushed in ragged blocks
     python examples/decode_wideband.py --sc16     # the same stream as a 16-bit converter delivers it: interleaved int16 I/Q, pushed as it is
+    python examples/decode_wideband.py --channels 128   # one SDR's worth: a 3.84 Msps stream (or 256: 7.68, 512: 15.36) through the bank of
+                                                        # that many branches, every bin a channel.  Bin channels / 2 sits on +- fs / 2, where a
+                                                        # real radio's anti-alias filter rolls off: expect less of a mobile there than here
 """
 import os
 import sys
@@ -13,11 +16,12 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gr_amps_amd import capi, synth_wideband as sw
 
-FIRST_BIN, CHANNELS = 96, 832                     # the band selection: FFT bins 96 .. 927 of the 1024-branch filter bank
-NSAMP = 12 * (1 << 20)                            # 0.41 s of signal
+BANK = int(sys.argv[sys.argv.index("--channels") + 1]) if "--channels" in sys.argv[1:] else 1024   # branches of the filter bank: fs = BANK x 30 kHz
+FIRST_BIN, CHANNELS = (96, 832) if BANK == 1024 else (0, BANK)   # the band selection: FFT bins 96 .. 927 of the 1024-branch filter bank, or every bin of a narrow one
+NSAMP = 12 * (1 << 20) * BANK // 1024             # 0.41 s of signal
 rng = np.random.default_rng(7)
-plan = [(FIRST_BIN + int(c), int(rng.integers(4000, NSAMP - 3456 * 1536 - 4000))) for c in rng.choice(CHANNELS, 12, replace=False)]
-x, truth = sw.make_wideband(NSAMP, plan, seed=7, snr_db=20.0, sym_ppm=50.0)   # every mobile 50 ppm off the nominal bit clock
+plan = [(FIRST_BIN + int(c), int(rng.integers(4000, NSAMP - 3456 * 3 * BANK // 2 - 4000))) for c in rng.choice(CHANNELS, 12, replace=False)]
+x, truth = sw.make_wideband(NSAMP, plan, seed=7, snr_db=20.0, sym_ppm=50.0, fs=BANK * 30e3, bins=BANK)   # every mobile 50 ppm off the nominal bit clock
 
 SC16 = "--sc16" in sys.argv[1:]
 if SC16:                                          # full scale for the loudest sample, a power of two; no slicer decision depends on the scale
@@ -25,14 +29,14 @@ if SC16:                                          # full scale for the loudest s
     x = np.rint(np.stack([x.real, x.imag], axis=1) * scale).astype(np.int16)   # [n, 2]: 4 bytes per sample instead of 8
 
 try:
-    rx = capi.Recc(n_channels=CHANNELS, max_samples=NSAMP // 512 + 72, max_bursts=256,
-                   wideband={"channels": 1024, "first_channel": FIRST_BIN})     # decimation: the library default (768: 40 ksps per channel)
+    rx = capi.Recc(n_channels=CHANNELS, max_samples=NSAMP // (BANK // 2) + 72, max_bursts=256,
+                   wideband={"channels": BANK, "first_channel": FIRST_BIN})     # decimation: the library default (3/4 of the branches: 40 ksps per channel)
 except capi.AmpsError as e:
     sys.exit("no MI355X here (%s): the library has no CPU fallback" % e)
 with rx:
     pos = 0
     while pos < NSAMP:                            # blocks of any size: what is left of a frame waits in the handle for the next push
-        n = min(int(rng.integers(100_000, 3_000_000)), NSAMP - pos)
+        n = min(int(rng.integers(100_000, 3_000_000)) * BANK // 1024, NSAMP - pos)
         (rx.push_wideband_short if SC16 else rx.push_wideband)(x[pos:pos + n])
         pos += n
     recs = rx.drain()

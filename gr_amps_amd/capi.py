@@ -94,6 +94,10 @@ class XlatePlan(C.Structure):
     _fields_ = [("decim", C.c_uint32), ("samples_per_symbol", C.c_uint32), ("ntaps", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class WidebandPlan(C.Structure):
+    _fields_ = [("channels", C.c_uint32), ("decim", C.c_uint32), ("samples_per_symbol", C.c_uint32), ("taps", C.c_uint32)]
+
+
 class XlateResampleCfg(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("interp", C.c_uint32), ("decim", C.c_uint32), ("n_centers", C.c_uint32), ("_pad", C.c_uint32),
@@ -148,6 +152,7 @@ EXPORTS = (
     "amps_recc_set_xlate_resampled", "amps_recc_xlate_resample_plan",
     "amps_recc_channel_autocorr", "amps_recc_burst_autocorr", "amps_recc_burst_offset",
     "amps_recc_retune_xlate",
+    "amps_recc_wideband_plan",
 )
 _XLATE_RESAMPLED = ("amps_recc_set_xlate_resampled", "amps_recc_xlate_resample_plan")
 _XLATE_AS = ("amps_recc_push_raw_shared_as", "amps_recc_push_raw_as", "amps_recc_debug_xlate_shared_as", "amps_recc_debug_xlate_as")
@@ -254,12 +259,14 @@ def load():
     if hasattr(L, "amps_recc_set_xlate_resampled"):   # absent only from A/B builds of earlier revisions (AMPS_RECC_LIB)
         L.amps_recc_set_xlate_resampled.argtypes = [vp, C.POINTER(XlateResampleCfg)]
         L.amps_recc_xlate_resample_plan.argtypes = [C.c_double, C.c_double, C.POINTER(ResamplePlan), C.c_size_t]
+    if hasattr(L, "amps_recc_wideband_plan"):         # absent only from A/B builds of earlier revisions (AMPS_RECC_LIB)
+        L.amps_recc_wideband_plan.argtypes = [C.c_double, C.POINTER(WidebandPlan), C.c_size_t]
     L.amps_bch_encode_words.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp]
     L.amps_bch_decode_words.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, vp, vp]
     for name in EXPORTS:
         if name in ("amps_recc_default_slicer", "amps_recc_default_wideband_decim", "amps_recc_debug_exact_slice", "amps_recc_rccl_unique_id", "amps_recc_rccl_init",
                     "amps_recc_push_wideband_bcast", "amps_recc_drain_gather", "amps_recc_debug_slicer_bits",
-                    "amps_recc_push_wideband_short", "amps_recc_xlate_shared_plan") + _NEW_IN_ABI4 + _POWER + _OFFSET + _RETUNE + _XLATE_SHARED + _XLATE_AS + _XLATE_RESAMPLED and not hasattr(L, name):
+                    "amps_recc_push_wideband_short", "amps_recc_xlate_shared_plan", "amps_recc_wideband_plan") + _NEW_IN_ABI4 + _POWER + _OFFSET + _RETUNE + _XLATE_SHARED + _XLATE_AS + _XLATE_RESAMPLED and not hasattr(L, name):
             continue
         if name not in ("amps_recc_strerror", "amps_recc_burst_size", "amps_recc_destroy"):   # every other entry point returns int
             getattr(L, name).restype = C.c_uint32 if name == "amps_recc_power_ring_snaps" else C.c_int
@@ -362,12 +369,16 @@ class Recc:
             {FLAG_SLICER_ATAN: "atan", FLAG_SLICER_PRODUCT: "product", FLAG_SLICER_SINE: "sine", FLAG_SLICER_EXACT: "exact"}[_SLICER_FLAGS[slicer]]
         self.sync_torch = sync_torch
         if wideband:
-            # "decim" absent / 0 = the library default; the samples per symbol follow the decimation unless they are given
+            # "decim" absent / 0 = the library default (3/4 of the channels at the narrow banks: the same ratio); the samples per symbol
+            # follow the decimation unless they are given
             wideband = dict(wideband)
             if not wideband.get("decim"):
-                wideband["decim"] = int(L.amps_recc_default_wideband_decim()) if hasattr(L, "amps_recc_default_wideband_decim") else 512
+                if int(wideband["channels"]) < 1024:
+                    wideband["decim"] = 3 * int(wideband["channels"]) // 4
+                else:
+                    wideband["decim"] = int(L.amps_recc_default_wideband_decim()) if hasattr(L, "amps_recc_default_wideband_decim") else 512
             if sps is None:
-                sps = 1536 // int(wideband["decim"])
+                sps = 3 * int(wideband["channels"]) // (2 * int(wideband["decim"]))
         elif sps is None:
             sps = 10
         cfg = Cfg()
@@ -796,7 +807,7 @@ class Recc:
             iq = np.ascontiguousarray(iq, np.complex64).reshape(-1)
         n = iq.shape[0]
         ptr, mem, keep = _as_ptr(iq)
-        cap = n // 512 + 2
+        cap = n // min(512, self.decim or 512) + 6          # the frames of the block, and up to four whose samples waited in the carry
         out = np.zeros((self.n_channels, cap), np.complex64)
         nf = C.c_size_t(0)
         rc = load().amps_recc_debug_channelize(self._h, ptr, n, mem, _hostptr(out), cap, C.byref(nf))
@@ -1006,6 +1017,19 @@ def subband_plan(rate_hz, width_hz=0.0):
     out = (XlatePlan * max(n, 1))()
     n = L.amps_recc_xlate_shared_plan(rate_hz, width_hz, out, n)
     return [(int(p.decim), int(p.samples_per_symbol), int(p.ntaps)) for p in out[:n]]
+
+
+def wideband_plan(rate_hz):
+    """Which filter bank for a wideband stream at rate_hz?  The (channels, decim, sps, taps) Recc(wideband={"channels": .., "decim": ..})
+    accepts for that rate, the default decimation first: two for 30.72, 15.36, 7.68 and 3.84 Msps, none for any other rate.  Needs no
+    GPU (amps_recc_wideband_plan)."""
+    L = load()
+    n = L.amps_recc_wideband_plan(rate_hz, None, 0)
+    if n < 0:
+        raise AmpsError(n, "amps_recc_wideband_plan")
+    out = (WidebandPlan * max(n, 1))()
+    n = L.amps_recc_wideband_plan(rate_hz, out, n)
+    return [(int(p.channels), int(p.decim), int(p.samples_per_symbol), int(p.taps)) for p in out[:n]]
 
 
 def resample_plan(rate_hz, width_hz=0.0):

@@ -160,17 +160,18 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
     *out = nullptr;
     if (cfg_in->struct_size != sizeof(amps_recc_cfg_t)) return -EINVAL;
     amps_recc_cfg_t cfg_v = *cfg_in;                                  // wideband handles: decimation 0 = the library default, samples per symbol 0 = what goes with it
+    const bool narrow = chz_is_narrow(cfg_v.wideband_channels);       // the banks of 512, 256 and 128 branches: the library's default ratio D = 3 M / 4
     if (cfg_v.wideband_channels) {
-        if (cfg_v.wideband_decim == 0) cfg_v.wideband_decim = amps_recc_default_wideband_decim();
-        if (cfg_v.samples_per_symbol == 0 && (cfg_v.wideband_decim == (uint32_t)CHZ_D || cfg_v.wideband_decim == (uint32_t)CHZ_D768))
-            cfg_v.samples_per_symbol = 1536u / cfg_v.wideband_decim;
+        if (cfg_v.wideband_decim == 0) cfg_v.wideband_decim = narrow ? 3u * cfg_v.wideband_channels / 4u : amps_recc_default_wideband_decim();
+        if (!chz_geometry_ok(cfg_v.wideband_channels, cfg_v.wideband_decim)) return -EINVAL;
+        if (cfg_v.samples_per_symbol == 0) cfg_v.samples_per_symbol = 3u * cfg_v.wideband_channels / (2u * cfg_v.wideband_decim);
     }
     const amps_recc_cfg_t *cfg = &cfg_v;
     if (cfg->n_channels < 1 || cfg->max_bursts < 1) return -EINVAL;
-    // the channelizer's geometry (M = 1024 at 30.72 Msps) delivers 60 ksps = 3 samples per Manchester symbol at D = 512 and 40 ksps =
-    // 2 at D = 768; the bit-domain kernels behind it are built for exactly those.  Two samples per symbol exist on the wideband seam only
-    // (the streaming kernel of the IQ seam has no such instantiation).
-    const bool wide768 = cfg->wideband_channels && cfg->wideband_decim == (uint32_t)CHZ_D768;
+    // the channelizer's geometry (M channels of 30 kHz at M x 30 ksps) delivers 60 ksps = 3 samples per Manchester symbol at D = M / 2 and
+    // 40 ksps = 2 at D = 3 M / 4; the bit-domain kernels behind it are built for exactly those.  Two samples per symbol exist on the wideband
+    // seam only (the streaming kernel of the IQ seam has no such instantiation).
+    const bool wide768 = cfg->wideband_channels && 4u * cfg->wideband_decim == 3u * cfg->wideband_channels;
     if (cfg->max_samples_per_push && !(wide768 ? cfg->samples_per_symbol == 2 : sps_supported(cfg->samples_per_symbol))) return -EINVAL;
     if (cfg->wideband_channels && (cfg->samples_per_symbol != (wide768 ? 2u : 3u) || cfg->max_samples_per_push == 0)) return -EINVAL;
     if (cfg->sync_tolerance > AMPS_RECC_MAX_SYNC_TOLERANCE) return -EINVAL;
@@ -178,13 +179,16 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
     if (sl & (sl - 1)) return -EINVAL;                             // at most one slicer spec
     if (cfg->n_channels >= (1u << (64 - CAPQ_POS_BITS))) return -EINVAL;
     // received power exists where the fused filter bank runs: the snapshot kernel re-reads that launch's block and carry
-    if ((cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER) && (!cfg->wideband_channels || (cfg->flags & AMPS_RECC_FLAG_UNFUSED_WIDEBAND))) return -EINVAL;
+    if ((cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER) && (!cfg->wideband_channels || narrow || (cfg->flags & AMPS_RECC_FLAG_UNFUSED_WIDEBAND))) return -EINVAL;
+    // the narrow banks are the two-kernel form: no channel groups, and what the other wideband_* fields may hold
+    if (narrow && (cfg->wideband_groups > 1 || cfg->n_channels > cfg->wideband_channels || cfg->wideband_first_channel >= cfg->wideband_channels ||
+                   (cfg->wideband_taps_per_branch != 0 && cfg->wideband_taps_per_branch != 8))) return -EINVAL;
     // on the IQ and translate seams the channel-rate stream itself is read once more, for its power and for the carrier offset: flags
-    // of their own, for handles with the IQ seam and no filter bank.  Power combines with the offset in either statistic, and a handle
-    // keeps one offset ring with one of them
+    // of their own, for handles with the IQ seam and no 1024 bank (a narrow bank's block goes through the IQ seam's streaming kernel,
+    // which fills the rings there too).  Power combines with the offset in either statistic, and a handle keeps one offset ring with one of them
     constexpr uint32_t OFFSET_FLAGS = AMPS_RECC_FLAG_STREAM_OFFSET | AMPS_RECC_FLAG_STREAM_OFFSET_UNIT;
     if ((cfg->flags & (AMPS_RECC_FLAG_STREAM_POWER | OFFSET_FLAGS)) &&
-        (cfg->wideband_channels || cfg->max_samples_per_push == 0 || (cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER))) return -EINVAL;
+        ((cfg->wideband_channels && !narrow) || cfg->max_samples_per_push == 0 || (cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER))) return -EINVAL;
     if ((cfg->flags & OFFSET_FLAGS) == OFFSET_FLAGS) return -EINVAL;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return -ENODEV;
@@ -333,8 +337,9 @@ static int push_wideband_block(amps_recc_t *h, const void *iq, size_t nsamp, int
     h->cap.origin_locked = true;
     HIP_TRY(hipSetDevice(h->device));
     // Fused form (default): filter bank + discriminator + boxcar + slicer in one kernel, then the bit-domain
-    // correlator.  AMPS_RECC_FLAG_UNFUSED_WIDEBAND keeps the two-kernel form (channel-major intermediate in HBM).
-    const bool fused = !(h->cfg.flags & AMPS_RECC_FLAG_UNFUSED_WIDEBAND);
+    // correlator.  AMPS_RECC_FLAG_UNFUSED_WIDEBAND keeps the two-kernel form (channel-major intermediate in HBM), which is the only
+    // form of the narrow banks.
+    const bool fused = !(h->cfg.flags & AMPS_RECC_FLAG_UNFUSED_WIDEBAND) && h->chz.M == CHZ_M;
     const float2 *chan_iq = nullptr;
     uint64_t ld = 0;
     uint32_t nout = 0;
@@ -351,7 +356,7 @@ static int push_wideband_block(amps_recc_t *h, const void *iq, size_t nsamp, int
     if (rc) return rc;
     if (nout > h->cfg.max_samples_per_push) return -E2BIG;
     if (fused) return capture_run_bits(h->cap, h->lists, h->tm, h->stream.get(), nout);
-    return capture_run_iq(h->cap, h->lists, h->tm, h->stream.get(), chan_iq, ld, nout);
+    return capture_run_iq(h->cap, h->lists, h->tm, h->stream.get(), chan_iq, ld, nout, power_of(h), offset_of(h));   // (rings: narrow banks only)
 }
 
 int amps_recc_push_wideband(amps_recc_t *h, const float *iq, size_t nsamp, int mem) { return push_wideband_block(h, iq, nsamp, mem, false); }
@@ -371,7 +376,7 @@ int amps_recc_rccl_unique_id(uint8_t *id)
 int amps_recc_rccl_init(amps_recc_t *h, const uint8_t *id, int nranks, int rank)
 {
     if (!h) return -EINVAL;
-    if (!h->chz.enabled) return -ENOSYS;
+    if (!h->chz.enabled || h->chz.M != CHZ_M) return -ENOSYS;    // one band over several GPUs is the 1024 bank's
     HIP_TRY(hipSetDevice(h->device));
     RcclLocal loc;
     loc.groups = h->cfg.wideband_groups >= 2 ? h->cfg.wideband_groups : 0;
@@ -608,6 +613,20 @@ int amps_recc_xlate_shared_plan(double rate_hz, double width_hz, amps_recc_xlate
         if (xlate_admit(true, decim, (uint32_t)sps, rate_hz, 10e3, width_hz, &ntaps)) continue;   // the default cut-off of xlate_configure
         if ((size_t)n < cap) out[n] = amps_recc_xlate_plan_t{ decim, (uint32_t)sps, ntaps, 0 };
         n++;
+    }
+    return n;
+}
+
+int amps_recc_wideband_plan(double rate_hz, amps_recc_wideband_plan_t *out, size_t cap)
+{
+    if (!(rate_hz > 0.0) || std::isinf(rate_hz) || (cap && !out)) return -EINVAL;
+    int n = 0;
+    for (uint32_t M = (uint32_t)CHZ_M; M >= 128u; M >>= 1) {
+        if (std::fabs(rate_hz - 30e3 * M) > 0.5) continue;
+        for (uint32_t D : { 3u * M / 4u, M / 2u }) {               // the default ratio first
+            if ((size_t)n < cap) out[n] = amps_recc_wideband_plan_t{ M, D, 3u * M / (2u * D), 8u * M };
+            n++;
+        }
     }
     return n;
 }

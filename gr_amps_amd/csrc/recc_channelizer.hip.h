@@ -40,6 +40,7 @@
 #include "recc_chz_fold.hip.h"
 #include "recc_chz_slicer.hip.h"
 #include "recc_power.hip.h"       // chz_power_launch: the power snapshots behind a fused launch
+#include "recc_chz_narrow.hip.h"  // the banks of 512, 256 and 128 branches: a kernel of their own behind the same state, carry and host code
 
 namespace amps {
 
@@ -141,7 +142,8 @@ __global__ __launch_bounds__(768, 3) void chz12_short_kernel(ChzArgs a)
 struct ChannelizerState {
     bool enabled = false;
     int P = 8;
-    int D = CHZ_D;                  // input samples per frame: 512 (3 samples per symbol) or 768 (2)
+    int M = CHZ_M;                  // branches: 1024 (chz12_kernel), or 512, 256, 128 (chz_narrow_kernel: the two-kernel form only)
+    int D = CHZ_D;                  // input samples per frame: M / 2 (3 samples per symbol) or 3 M / 4 (2)
     uint32_t C = 0;                 // rows this handle decodes (= the band's channels, or one group of them)
     uint32_t groups = 1, group = 0; // cfg.wideband_groups / wideband_group
     DevBuf<uint16_t> bin2row;       // device [M]
@@ -149,6 +151,7 @@ struct ChannelizerState {
     uint32_t max_frames = 0;        // per push
     uint32_t target_wgs = 256;      // resident workgroups of the filter-bank kernel (one 768-thread workgroup per CU)
     DevBuf<float> taps;             // [L]
+    DevBuf<float2> twiddle;         // M < 1024: [M], e^{-2 pi i k / M}
     DevBuf<float2> carry[2];
     int carry_cur = 0;
     uint32_t carry_len = 0;         // L - D + leftover
@@ -167,14 +170,14 @@ inline double bessel_i0(double x)
     return s;
 }
 
-// Kaiser(beta = 8) windowed sinc at fs = M * 30 kHz, unit DC gain; -6 dB at 13 kHz behind the D = 512 bank, at 15 kHz behind the D = 768 one
+// Kaiser(beta = 8) windowed sinc at fs = M * 30 kHz, unit DC gain; -6 dB at 13 kHz behind the D = M / 2 bank, at 15 kHz behind the D = 3 M / 4 one
 // (40 ksps per channel leave the slicer two sampling phases per symbol instead of three: the wider pass band gives back, under a
 // carrier offset, what the coarser timing costs -- profiles/r06/decim768_cpu_gonogo.txt; oracle/channelizer.py: cutoff_for_decim)
-inline double chz_cutoff_hz(int D) { return D == CHZ_D768 ? 15.0e3 : 13.0e3; }
-inline std::vector<float> chz_design_taps(int P, int D = CHZ_D)
+inline double chz_cutoff_hz(int D, int M = CHZ_M) { return 4 * D == 3 * M ? 15.0e3 : 13.0e3; }
+inline std::vector<float> chz_design_taps(int P, int D = CHZ_D, int M = CHZ_M)
 {
-    const int L = P * CHZ_M;
-    const double fc = chz_cutoff_hz(D) / (CHZ_M * 30.0e3);      // cycles per sample
+    const int L = P * M;
+    const double fc = chz_cutoff_hz(D, M) / (M * 30.0e3);       // cycles per sample
     const double beta = 8.0, i0b = bessel_i0(beta);
     std::vector<double> h(L);
     double sum = 0.0;
@@ -192,36 +195,44 @@ inline std::vector<float> chz_design_taps(int P, int D = CHZ_D)
     return out;
 }
 
-inline uint32_t chz_hist(int P, int D) { return (uint32_t)(P * CHZ_M - D + CHZ_PRE * D); }
-inline size_t chz_carry_cap(int P, int D) { return (size_t)chz_hist(P, D) + 64 * D; }   // + leftover (< 64 frames)
+// samples of history the carry holds in front of a launch's frame 0: the filter's own L - D, and at M = 1024 the pre-roll's CHZ_PRE
+// frames (the narrow banks have no pre-roll: a workgroup stages its frames' whole history)
+inline uint32_t chz_hist(int P, int D, int M = CHZ_M) { return (uint32_t)(P * M - D + (M == CHZ_M ? CHZ_PRE * D : 0)); }
+inline size_t chz_carry_cap(int P, int D, int M = CHZ_M) { return (size_t)chz_hist(P, D, M) + 64 * D; }   // + leftover (< 64 frames)
 
 inline int channelizer_reset(ChannelizerState &z, hipStream_t s)
 {
     if (!z.enabled) return 0;
-    const size_t cap = chz_carry_cap(z.P, z.D);
+    const size_t cap = chz_carry_cap(z.P, z.D, z.M);
     if (hipMemsetAsync(z.carry[0].get(), 0, sizeof(float2) * cap, s) != hipSuccess) return -EIO;
     if (hipMemsetAsync(z.carry[1].get(), 0, sizeof(float2) * cap, s) != hipSuccess) return -EIO;
     z.carry_cur = 0;
-    z.carry_len = chz_hist(z.P, z.D);                // all-zero history, no leftover
+    z.carry_len = chz_hist(z.P, z.D, z.M);           // all-zero history, no leftover
     z.frames_done = 0;
     return 0;
 }
 
 inline void channelizer_destroy(ChannelizerState &z) { z = ChannelizerState(); }
 
+// the bank sizes of chz_narrow_kernel
+inline bool chz_is_narrow(uint32_t M) { return M == 512 || M == 256 || M == 128; }
+// The geometries the seam serves: M = 1024, 512, 256 or 128 branches at D = M / 2 or 3 M / 4 input samples per frame
+inline bool chz_geometry_ok(uint32_t M, uint32_t D) { return (M == (uint32_t)CHZ_M || chz_is_narrow(M)) && (2 * D == M || 4 * D == 3 * M); }
+
 // bins and rows of a handle: row i = the i-th channel (in band order) of the band selection [first, first + n) that belongs to the
 // handle's group -- all of them without groups.  Returns the row count, or a negative errno for an invalid split.
 inline int chz_rows(const amps_recc_cfg_t &cfg, std::vector<uint16_t> *bin2row, std::vector<uint32_t> *row2chan)
 {
     const uint32_t G = cfg.wideband_groups > 1 ? cfg.wideband_groups : 1u;
+    const uint32_t M = chz_is_narrow(cfg.wideband_channels) ? cfg.wideband_channels : (uint32_t)CHZ_M;
     if ((G != 1 && G != 2 && G != 4 && G != 8) || cfg.wideband_group >= G) return -EINVAL;
-    if (cfg.n_channels > (uint32_t)CHZ_M || cfg.wideband_first_channel >= (uint32_t)CHZ_M) return -EINVAL;
+    if (cfg.n_channels > M || cfg.wideband_first_channel >= M) return -EINVAL;
     const uint32_t W = 64u / G;
-    if (bin2row) bin2row->assign(CHZ_M, (uint16_t)0xffffu);
+    if (bin2row) bin2row->assign(M, (uint16_t)0xffffu);
     if (row2chan) row2chan->clear();
     uint32_t rows = 0;
     for (uint32_t c = 0; c < cfg.n_channels; c++) {
-        const uint32_t k = (cfg.wideband_first_channel + c) & (CHZ_M - 1);
+        const uint32_t k = (cfg.wideband_first_channel + c) & (M - 1);
         if ((k & 63u) / W != cfg.wideband_group) continue;
         if (bin2row) (*bin2row)[k] = (uint16_t)rows;
         if (row2chan) row2chan->push_back(c);
@@ -232,24 +243,32 @@ inline int chz_rows(const amps_recc_cfg_t &cfg, std::vector<uint16_t> *bin2row, 
 
 inline int channelizer_create(ChannelizerState &z, const amps_recc_cfg_t &cfg)
 {
-    if (cfg.wideband_channels != CHZ_M || (cfg.wideband_decim != CHZ_D && cfg.wideband_decim != CHZ_D768)) return -EINVAL;   // M = 1024, D = 512 or 768
+    if (!chz_geometry_ok(cfg.wideband_channels, cfg.wideband_decim)) return -EINVAL;
+    const int M = (int)cfg.wideband_channels;
+    const bool narrow = M != CHZ_M;
+    if (narrow && cfg.wideband_groups > 1) return -EINVAL;         // channel groups exist in the fused form, which the narrow banks do not have
     const int P = cfg.wideband_taps_per_branch ? (int)cfg.wideband_taps_per_branch : 8;
-    if (P != 8) return -EINVAL;                                   // the register ring of chz12_kernel is laid out for eight taps per branch
-    if (cfg.n_channels > CHZ_M || cfg.wideband_first_channel >= CHZ_M || cfg.max_samples_per_push == 0) return -EINVAL;
+    if (P != 8) return -EINVAL;                                   // the register ring of chz12_kernel is laid out for eight taps per branch, and so is chz_narrow_kernel's fold
+    if (cfg.n_channels > (uint32_t)M || cfg.wideband_first_channel >= (uint32_t)M || cfg.max_samples_per_push == 0) return -EINVAL;
     std::vector<uint16_t> b2r;
     const int rows = chz_rows(cfg, &b2r, &z.row2chan);
     if (rows < 1) return rows < 0 ? rows : -EINVAL;
-    z.P = P; z.D = (int)cfg.wideband_decim; z.C = (uint32_t)rows;
+    z.P = P; z.M = M; z.D = (int)cfg.wideband_decim; z.C = (uint32_t)rows;
     z.groups = cfg.wideband_groups > 1 ? cfg.wideband_groups : 1u; z.group = cfg.wideband_group;
-    if (z.bin2row.alloc(CHZ_M)) return -ENOMEM;
-    if (hipMemcpy(z.bin2row.get(), b2r.data(), sizeof(uint16_t) * CHZ_M, hipMemcpyHostToDevice) != hipSuccess) return -EIO;
+    if (z.bin2row.alloc(M)) return -ENOMEM;
+    if (hipMemcpy(z.bin2row.get(), b2r.data(), sizeof(uint16_t) * M, hipMemcpyHostToDevice) != hipSuccess) return -EIO;
     z.max_frames = cfg.max_samples_per_push;
     z.ld = ((uint64_t)z.max_frames + 7) & ~7ull;
-    const size_t L = (size_t)P * CHZ_M;
-    std::vector<float> h = chz_design_taps(P, z.D);
+    const size_t L = (size_t)P * M;
+    std::vector<float> h = chz_design_taps(P, z.D, M);
     if (z.taps.alloc(L)) return -ENOMEM;
     if (hipMemcpy(z.taps.get(), h.data(), sizeof(float) * L, hipMemcpyHostToDevice) != hipSuccess) return -EIO;
-    if (z.carry[0].alloc(chz_carry_cap(P, z.D)) || z.carry[1].alloc(chz_carry_cap(P, z.D))) return -ENOMEM;
+    if (z.carry[0].alloc(chz_carry_cap(P, z.D, M)) || z.carry[1].alloc(chz_carry_cap(P, z.D, M))) return -ENOMEM;
+    if (narrow) {
+        const std::vector<float2> w = chz_narrow_twiddles(M);
+        if (z.twiddle.alloc(M)) return -ENOMEM;
+        if (hipMemcpy(z.twiddle.get(), w.data(), sizeof(float2) * M, hipMemcpyHostToDevice) != hipSuccess) return -EIO;
+    }
     // z.out (the channel-major block, C x ld x 8 B: 1.7 GB for a full band at 2^18 frames per push) is allocated by the first
     // unfused / debug run: the fused form never touches it
     {
@@ -309,7 +328,8 @@ struct ChzRunIn {
 // Channelise in.nsamp new wideband samples.
 inline int channelizer_run(ChannelizerState &z, const ChzRunIn &in, hipStream_t s, const float2 **chan_iq, uint64_t *ld, uint32_t *nframes_out)
 {
-    const bool fused = in.fused;
+    const bool narrow = z.M != CHZ_M;                             // chz_narrow_kernel: the two-kernel form whatever was asked, either sample type read in place
+    const bool fused = in.fused && !narrow;
     const size_t nsamp = in.nsamp;
     bool sc16 = in.sc16;
     if (!z.enabled) return -ENOSYS;
@@ -323,14 +343,14 @@ inline int channelizer_run(ChannelizerState &z, const ChzRunIn &in, hipStream_t 
         d = staged;
     }
     if (!fused && !z.out && z.out.alloc((size_t)z.C * z.ld)) return -ENOMEM;
-    const uint32_t hist = chz_hist(z.P, z.D);
+    const uint32_t hist = chz_hist(z.P, z.D, z.M);
     const uint32_t leftover = z.carry_len - hist;
     const uint64_t avail = (uint64_t)leftover + nsamp;
-    // frames consumed: a multiple of four (a launch starts where the stream position is a multiple of M: frame parity 0 at D = 512,
-    // frame phase 0 of 4 at D = 768), and in the fused form a multiple of 64 (whole words of the RECC bit ring); the rest waits in the carry
-    const uint32_t nframes = (uint32_t)(avail / (uint32_t)z.D) & (fused ? ~63u : z.D == CHZ_D ? ~1u : ~3u);
+    // frames consumed: a multiple of two or four (a launch starts where the stream position is a multiple of M: frame parity 0 at
+    // D = M / 2, frame phase 0 of 4 at D = 3 M / 4), and in the fused form a multiple of 64 (whole words of the RECC bit ring); the rest waits in the carry
+    const uint32_t nframes = (uint32_t)(avail / (uint32_t)z.D) & (fused ? ~63u : 2 * z.D == z.M ? ~1u : ~3u);
     if (nframes > z.max_frames) return -E2BIG;
-    if (sc16 && (!fused || z.short_prepass)) {
+    if (sc16 && !narrow && (!fused || z.short_prepass)) {
         // the block as fc32 in a buffer of its own, then everything as for an fc32 block.  Stream order keeps the buffer safe: the
         // kernels of the previous push that read it run before this conversion
         if (z.cvt.capacity() < nsamp) {
@@ -346,7 +366,13 @@ inline int channelizer_run(ChannelizerState &z, const ChzRunIn &in, hipStream_t 
     const uint32_t new_left = (uint32_t)(avail - consumed);
     bool carry_in_kernel = false;
     ChzArgs a{};
-    if (nframes) {
+    if (nframes && narrow) {
+        ChzNarrowArgs na{};
+        na.block = d; na.carry = z.carry[z.carry_cur].get(); na.taps = z.taps.get(); na.twiddle = z.twiddle.get(); na.out = z.out.get(); na.ld = z.ld;
+        na.bin2row = z.bin2row.get(); na.carry_len = z.carry_len; na.nsamp = (uint32_t)nsamp; na.nframes = nframes; na.n_channels = z.C;
+        const uint32_t fr = (uint32_t)chz_narrow_fr(z.M, z.D);
+        hipLaunchKernelGGL(chz_narrow_kernel_for(z.M, z.D, sc16), dim3((nframes + fr - 1) / fr), dim3(256), 0, s, na);
+    } else if (nframes) {
         a.block = (const float2 *)d; a.carry = z.carry[z.carry_cur].get(); a.taps = z.taps.get(); a.out = z.out.get(); a.ld = z.ld;
         a.carry_len = z.carry_len; a.nsamp = (uint32_t)nsamp; a.nframes = nframes; a.hist = hist;
         // one resident round of 768-thread workgroups, one per CU; each refills its delay lines and re-runs eight pre-roll

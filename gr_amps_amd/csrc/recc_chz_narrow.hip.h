@@ -1,0 +1,252 @@
+// recc_chz_narrow.hip.h -- the filter bank of the wideband seam at M = 512, 256 and 128 branches (15.36, 7.68 and 3.84 Msps: the rates
+// one SDR delivers), D = M / 2 or 3 M / 4.  The same weighted-overlap-add bank as recc_channelizer.hip.h defines at its top and
+// oracle/channelizer.py models -- P = 8 taps per branch, frame m over samples [(m+1) D - 8 M, (m+1) D), the fold modulo M with the
+// absolute phase reference n0 mod M, an M-point DFT -- in the two-kernel form only: the active bins leave as rows of the channel-major
+// fc32 block, which the streaming kernel of the IQ seam takes from there (capture_run_iq), as in the unfused form of the 1024 bank.
+//
+// Mapping: a 256-thread workgroup owns FR consecutive frames for all M bins.
+//   stage : the (FR - 1) D + 8 M input samples of its frames, carry first and block behind it, expanded to fc32 (chz_cvt), once in LDS
+//   fold  : a thread keeps the eight taps h[p M + j] of its branch j in registers (two branches at M = 512) and folds a frame with
+//           eight FMAs per branch out of LDS; the roll n0 mod M is an index offset of the store (FR is a multiple of the roll's
+//           period -- 2 frames at D = M / 2, 4 at D = 3 M / 4 -- and so is every launch: a workgroup's frame f has roll ((f+1) D) mod M)
+//   FFT   : all FR frames at once, Stockham passes in place over LDS: every thread reads its butterflies, the workgroup meets, every
+//           thread writes.  512 = 8 x 8 x 8, 256 = 16 x 16, 128 = 16 x 8; twiddles from a table the host computed in double precision
+//   store : thread -> (bin, frame) with the frame running fastest: a row leaves as one run of FR x 8 bytes
+// A frame's arithmetic is a fixed sequence of operations on its own 8 M samples: it depends neither on how the stream was cut into
+// pushes nor on which workgroup computes it.  No atomics, nothing handed from one workgroup to another.
+//
+// FR per geometry (LDS <= 80 KiB, so that two workgroups fit a CU) and the share of the input a launch reads a second time,
+// 8 M / (FR D) -- the 8 M - D samples of history in front of a workgroup's first frame, which its neighbour stages too (from L2):
+//   M = 512: D = 256: FR =  8, 2.00     D = 384: FR =  4, 2.67
+//   M = 256: D = 128: FR = 16, 1.00     D = 192: FR = 16, 0.67
+//   M = 128: D =  64: FR = 32, 0.50     D =  96: FR = 32, 0.33
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <vector>
+#include "recc_chz_common.hip.h"
+#include "recc_chz_fft.hip.h"
+
+namespace amps {
+
+struct ChzNarrowArgs {
+    const void *block;       // new wideband samples of this push: float2, or chz_sc16 (chz_narrow_kernel<.., chz_sc16>)
+    const float2 *carry;     // [carry_len]: the hist = 8 M - D samples in front of frame 0, then what earlier pushes left over
+    const float *taps;       // [8 M] prototype
+    const float2 *twiddle;   // [M]: e^{-2 pi i k / M}
+    float2 *out;             // [n_channels][ld] channel-major output of this push
+    uint64_t ld;
+    const uint16_t *bin2row; // [M]: row of FFT bin k in `out`, >= n_channels for a bin this handle does not decode
+    uint32_t carry_len;
+    uint32_t nsamp;          // new samples
+    uint32_t nframes;        // frames this launch produces: a multiple of the roll's period
+    uint32_t n_channels;
+};
+
+__host__ __device__ constexpr bool chz_narrow_geometry(int M, int D) { return (M == 512 || M == 256 || M == 128) && (2 * D == M || 4 * D == 3 * M); }
+// frames per workgroup
+__host__ __device__ constexpr int chz_narrow_fr(int M, int D) { return M == 512 ? (2 * D == M ? 8 : 4) : M == 256 ? 16 : 32; }
+// LDS layout of a frame: element n at n + n / 32 (a store of stride 8 or 16 elements across lanes then walks the banks), frames S
+// elements apart, S odd (the store phase reads one bin of consecutive frames across lanes)
+__host__ __device__ constexpr int chz_narrow_pos(int n) { return n + (n >> 5); }
+__host__ __device__ constexpr int chz_narrow_stride(int M) { return M + M / 32 + 1; }
+__host__ __device__ constexpr int chz_narrow_stage(int M, int D) { return (chz_narrow_fr(M, D) - 1) * D + 8 * M; }
+__host__ __device__ constexpr size_t chz_narrow_lds_bytes(int M, int D) { return sizeof(float2) * ((size_t)chz_narrow_stage(M, D) + (size_t)chz_narrow_fr(M, D) * chz_narrow_stride(M)); }
+
+// DFT-R in place, natural order
+__device__ __forceinline__ void chz_dft(cf2 (&v)[2]) { const cf2 a = v[0], b = v[1]; v[0] = a + b; v[1] = a - b; }
+__device__ __forceinline__ void chz_dft(cf2 (&v)[4]) { dft4(v[0], v[1], v[2], v[3], v); }
+__device__ __forceinline__ void chz_dft(cf2 (&v)[8])
+{
+    constexpr float R2 = 0.70710678118654752f;
+    cf2 e[4], o[4];
+    dft4(v[0], v[2], v[4], v[6], e);
+    dft4(v[1], v[3], v[5], v[7], o);
+    o[1] = cmul_s(o[1], (cf2){ R2, -R2 });                      // W8^1
+    o[2] = mul_mi(o[2]);                                        // W8^2 = -i
+    o[3] = cmul_s(o[3], (cf2){ -R2, -R2 });                     // W8^3
+#pragma unroll
+    for (int k = 0; k < 4; k++) { v[k] = e[k] + o[k]; v[k + 4] = e[k] - o[k]; }
+}
+// 4 x DFT4 over a (s = 4a + b), twiddle W16^{bc}, 4 x DFT4 over b -> X[c + 4d]: the butterfly of chz_p2
+__device__ __forceinline__ void chz_dft(cf2 (&u)[16])
+{
+    cf2 v[4][4];
+#pragma unroll
+    for (int b = 0; b < 4; b++) dft4(u[b], u[4 + b], u[8 + b], u[12 + b], v[b]);
+    constexpr float C1 = 0.92387953251128674f, S1 = 0.38268343236508977f, R2 = 0.70710678118654752f;
+    v[1][1] = cmul_s(v[1][1], (cf2){ C1, -S1 });
+    v[1][2] = cmul_s(v[1][2], (cf2){ R2, -R2 });
+    v[1][3] = cmul_s(v[1][3], (cf2){ S1, -C1 });
+    v[2][1] = cmul_s(v[2][1], (cf2){ R2, -R2 });
+    v[2][2] = mul_mi(v[2][2]);
+    v[2][3] = cmul_s(v[2][3], (cf2){ -R2, -R2 });
+    v[3][1] = cmul_s(v[3][1], (cf2){ S1, -C1 });
+    v[3][2] = cmul_s(v[3][2], (cf2){ -R2, -R2 });
+    v[3][3] = cmul_s(v[3][3], (cf2){ -C1, S1 });
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        cf2 X[4];
+        dft4(v[0][c], v[1][c], v[2][c], v[3][c], X);
+#pragma unroll
+        for (int d = 0; d < 4; d++) u[c + 4 * d] = X[d];
+    }
+}
+
+// One Stockham pass of radix R over FR frames of M points, NS = the product of the radices before it: butterfly j of a frame reads
+// elements j + r M / R, turns element r by W_{NS R}^{r (j mod NS)}, and writes DFT_R of them to (j / NS) NS R + (j mod NS) + r NS.
+// In place: every element is read once and written once, and the workgroup meets between the two.
+template <int M, int R, int NS, int FR>
+__device__ __forceinline__ void chz_narrow_pass(cf2 *u, const float2 *tw, int t)
+{
+    constexpr int S = chz_narrow_stride(M), BPF = M / R, NB = FR * BPF / 256;
+    static_assert(NB >= 1 && NB * 256 == FR * BPF, "whole butterflies per thread");
+    cf2 v[NB][R];
+#pragma unroll
+    for (int q = 0; q < NB; q++) {
+        const int g = t + 256 * q, f = g / BPF, j = g % BPF;
+        const cf2 *A = u + f * S;
+#pragma unroll
+        for (int r = 0; r < R; r++) v[q][r] = A[chz_narrow_pos(j + r * BPF)];
+        if constexpr (NS > 1) {
+            const int k = j % NS;
+#pragma unroll
+            for (int r = 1; r < R; r++) { const float2 w = tw[r * k * (M / (NS * R))]; v[q][r] = cmul(v[q][r], (cf2){ w.x, w.y }); }
+        }
+        chz_dft(v[q]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NB; q++) {
+        const int g = t + 256 * q, f = g / BPF, j = g % BPF;
+        cf2 *A = u + f * S;
+        const int j0 = (j / NS) * NS * R + j % NS;
+#pragma unroll
+        for (int r = 0; r < R; r++) A[chz_narrow_pos(j0 + r * NS)] = v[q][r];
+    }
+    __syncthreads();
+}
+
+template <int M, int DEC, typename T>
+__global__ __launch_bounds__(256) void chz_narrow_kernel(ChzNarrowArgs a)
+{
+    static_assert(chz_narrow_geometry(M, DEC), "M = 512, 256 or 128 at D = M / 2 or 3 M / 4");
+    constexpr int FR = chz_narrow_fr(M, DEC), S = chz_narrow_stride(M), NST = chz_narrow_stage(M, DEC);
+    constexpr int E = FR * M / 256;                              // (frame, branch) pairs, and later (bin, frame) pairs, per thread
+    constexpr int BR = M > 256 ? M / 256 : 1;                    // branches whose taps a thread keeps
+    static_assert(chz_narrow_lds_bytes(M, DEC) <= 80 * 1024, "two workgroups per CU");
+    __shared__ cf2 xin[NST];
+    __shared__ cf2 u[FR * S];
+    const int t = threadIdx.x;
+    const uint32_t frame0 = blockIdx.x * (uint32_t)FR;
+
+    float h[BR][8];
+#pragma unroll
+    for (int b = 0; b < BR; b++)
+#pragma unroll
+        for (int p = 0; p < 8; p++) h[b][p] = a.taps[p * M + (t + 256 * b) % M];
+
+    // stage: sample i of the workgroup is carry-relative sample frame0 D + i; behind the stream's end (frames this launch does not
+    // produce) zeros
+    // -- eight loads in flight per thread: every load is unconditional, from an address that is valid whatever the sample is (element 0
+    // of the carry, which is never empty, or of the block, which has a sample whenever a launch produces a frame), and what it returned
+    // is kept or replaced by zero afterwards, so that a batch costs one memory latency and not eight
+    {
+        constexpr int NLD = (NST + 255) / 256, BATCH = 8;
+        const uint64_t c0 = (uint64_t)frame0 * DEC;
+        const T *blk = (const T *)a.block;
+#pragma unroll 1
+        for (int i0 = 0; i0 < NLD; i0 += BATCH) {
+            cf2 v[BATCH];
+#pragma unroll
+            for (int b = 0; b < BATCH; b++) {
+                const uint64_t ci = c0 + (uint64_t)(t + 256 * (i0 + b));
+                const bool in_carry = ci < a.carry_len;
+                const uint64_t bi = ci - a.carry_len;
+                const bool in_block = !in_carry && bi < a.nsamp;
+                if constexpr (chz_is_short<T>::value) {
+                    const float2 c = a.carry[in_carry ? ci : 0];
+                    const cf2 s = chz_cvt(blk[in_block ? bi : 0]);
+                    v[b] = in_carry ? (cf2){ c.x, c.y } : in_block ? s : (cf2){ 0.f, 0.f };
+                } else {
+                    const float2 c = *(in_carry ? a.carry + ci : in_block ? blk + bi : a.carry);
+                    v[b] = (in_carry || in_block) ? (cf2){ c.x, c.y } : (cf2){ 0.f, 0.f };
+                }
+            }
+#pragma unroll
+            for (int b = 0; b < BATCH; b++) {
+                const int i = t + 256 * (i0 + b);
+                if (i < NST) xin[i] = v[b];
+            }
+        }
+    }
+    __syncthreads();
+
+    // fold
+#pragma unroll
+    for (int q = 0; q < E; q++) {
+        const int idx = t + 256 * q, f = idx / M, j = idx % M;
+        const float (&hb)[8] = h[M > 256 ? q % BR : 0];
+        const cf2 *x = xin + f * DEC + j;
+        cf2 acc = x[0] * hb[0];
+#pragma unroll
+        for (int p = 1; p < 8; p++) { const cf2 s = x[p * M]; acc = (cf2){ fmaf(hb[p], s.x, acc.x), fmaf(hb[p], s.y, acc.y) }; }
+        // q and M fix f up to the thread's half at M = 128; the roll ((f + 1) D) mod M takes 2 or 4 values
+        u[f * S + chz_narrow_pos((j + ((f + 1) * DEC) % M) & (M - 1))] = acc;
+    }
+    __syncthreads();
+
+    if constexpr (M == 512) {
+        chz_narrow_pass<M, 8, 1, FR>(u, a.twiddle, t);
+        chz_narrow_pass<M, 8, 8, FR>(u, a.twiddle, t);
+        chz_narrow_pass<M, 8, 64, FR>(u, a.twiddle, t);
+    } else if constexpr (M == 256) {
+        chz_narrow_pass<M, 16, 1, FR>(u, a.twiddle, t);
+        chz_narrow_pass<M, 16, 16, FR>(u, a.twiddle, t);
+    } else {
+        chz_narrow_pass<M, 16, 1, FR>(u, a.twiddle, t);
+        chz_narrow_pass<M, 8, 16, FR>(u, a.twiddle, t);
+    }
+
+    // store: the frame runs fastest across lanes
+#pragma unroll
+    for (int q = 0; q < E; q++) {
+        const int idx = t + 256 * q, f = idx % FR, bin = idx / FR;
+        const uint32_t row = a.bin2row[bin], frame = frame0 + (uint32_t)f;
+        if (row < a.n_channels && frame < a.nframes) {
+            const cf2 y = u[f * S + chz_narrow_pos(bin)];
+            a.out[(uint64_t)row * a.ld + frame] = make_float2(y.x, y.y);
+        }
+    }
+}
+
+typedef void (*chz_narrow_kernel_t)(ChzNarrowArgs);
+template <int M, typename T> chz_narrow_kernel_t chz_narrow_kernel_of(int D)
+{
+    return 2 * D == M ? chz_narrow_kernel<M, M / 2, T> : chz_narrow_kernel<M, 3 * M / 4, T>;
+}
+// the instantiation for (branches, input samples per frame, sample type of the block); nullptr for a geometry there is none for
+inline chz_narrow_kernel_t chz_narrow_kernel_for(int M, int D, bool sc16)
+{
+    if (!chz_narrow_geometry(M, D)) return nullptr;
+    switch (M) {
+    case 512: return sc16 ? chz_narrow_kernel_of<512, chz_sc16>(D) : chz_narrow_kernel_of<512, float2>(D);
+    case 256: return sc16 ? chz_narrow_kernel_of<256, chz_sc16>(D) : chz_narrow_kernel_of<256, float2>(D);
+    default: return sc16 ? chz_narrow_kernel_of<128, chz_sc16>(D) : chz_narrow_kernel_of<128, float2>(D);
+    }
+}
+
+// e^{-2 pi i k / M}, k < M, rounded once from double precision
+inline std::vector<float2> chz_narrow_twiddles(int M)
+{
+    std::vector<float2> w(M);
+    for (int k = 0; k < M; k++) {
+        const double ph = -2.0 * M_PI * (double)k / (double)M;
+        w[k] = make_float2((float)std::cos(ph), (float)std::sin(ph));
+    }
+    // the four axis points exactly
+    w[0] = make_float2(1.f, 0.f); w[M / 4] = make_float2(0.f, -1.f); w[M / 2] = make_float2(-1.f, 0.f); w[3 * M / 4] = make_float2(0.f, 1.f);
+    return w;
+}
+
+} // namespace amps

@@ -10,7 +10,9 @@
 //                                      in .sc16 (or a sixth argument `sc16`) is read as interleaved 16-bit I/Q and goes through the block's
 //                                      16-bit input.  An argument `power` behind those (the seventh, or the eighth behind `sc16`) makes the block
 //                                      keep received power: every burst's lines are followed by `MSG power channel <c> <10 log10(mean power)> dB
-//                                      n=<snapshots>`; without it the output is what it always was
+//                                      n=<snapshots>`; without it the output is what it always was.  An argument `channels=<M>` anywhere behind
+//                                      the file (M = 512, 256 or 128) reads the capture as a stream at M x 30 ksps -- 15.36, 7.68 or 3.84 Msps --
+//                                      through the M-branch bank: all M bins from bin 0 (recc_wideband::make(M, 0, ..., channels = M))
 //   recctest widerank <file.fc32> <chunk> <idfile> <nranks> <rank> [mode]   ONE rank of the same band over `nranks` processes (2, 4 or 8; one per GPU of a
 //                                      node): gr::amps::recc_wideband::make(832, 96, -1, nranks, rank) + set_rccl -- rank 0 owns the capture and the
 //                                      library distributes it (mode 0 = ncclBroadcast, 1 = scatter + all-gather); the other ranks' items only pace
@@ -151,6 +153,14 @@ int main(int argc, char **argv)
         else break;
         argc--;
     }
+    // wide: `channels=<M>` anywhere behind the file selects a narrow bank; the positional arguments are what is left
+    int wide_channels = 1024;
+    for (int i = 3; mode == "wide" && i < argc;) {
+        if (std::strncmp(argv[i], "channels=", 9) != 0) { i++; continue; }
+        wide_channels = std::atoi(argv[i] + 9);
+        for (int j = i; j + 1 < argc; j++) argv[j] = argv[j + 1];
+        argc--;
+    }
     const int chunk = argc > 3 ? std::atoi(argv[3]) : 4096;
     std::ifstream f(argv[2], std::ios::binary);
     if (!f) { std::perror(argv[2]); return 2; }
@@ -202,6 +212,7 @@ int main(int argc, char **argv)
             bool power = false;
             for (int i = 6; !ranks && i < argc && i < 9; i++) power = power || std::string(argv[i]) == "power";
             auto src = ranks ? gr::amps::recc_wideband::make(832, 96, -1, nranks, rank)
+                             : wide_channels != 1024 ? gr::amps::recc_wideband::make(wide_channels, 0, argc > 4 ? std::atoi(argv[4]) : -1, 0, 0, argc > 5 ? std::atoi(argv[5]) : 0, sc16, power, wide_channels)
                              : gr::amps::recc_wideband::make(832, 96, argc > 4 ? std::atoi(argv[4]) : -1, 0, 0, argc > 5 ? std::atoi(argv[5]) : 0, sc16, power);
             if (ranks) {
                 // the control plane is the application's: here, a file

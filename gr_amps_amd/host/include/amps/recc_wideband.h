@@ -11,6 +11,10 @@
 //                           (linear, unscaled: 1.0 for a mobile at full scale of an fc32 stream, int16 units squared behind short_input) and
 //                           the number of power snapshots averaged (26 / 27 at decim 768, 39 / 40 at 512; 0 with power 0.0 if the handle no
 //                           longer held them).  The block drains after every push, so every record is covered.
+// With channels = 512, 256 or 128 the input is a stream at channels x 30 kHz = 15.36, 7.68 or 3.84 Msps -- what one SDR delivers -- through
+// the bank of that many branches, in the two-kernel form (cfg.wideband_channels of include/amps_recc.h); "power" then carries the stream
+// power of the IQ seam (AMPS_RECC_FLAG_STREAM_POWER: the mean of |y|^2 over the blocks of 256 channel-rate samples inside the capture).
+// Bin channels / 2 is centred on +- fs / 2, where the radio's own anti-alias filter rolls off: a channel there is as good as the radio.
 // channel 0 = FFT bin `first_bin` (centre first_bin x 30 kHz above the stream's centre, modulo the sample rate).
 #pragma once
 #include <amps/api.h>
@@ -33,8 +37,10 @@ public:
     //         sample to the device, no float copy on the host).  Scale does not matter to any slicer spec.  set_rccl is refused on such
     //         a block: the distributed seam carries fc32.
     // channel_power: keep per-channel received power (AMPS_RECC_FLAG_CHANNEL_POWER) and publish every record's burst power on "power"
+    // channels: branches of the filter bank = 30 kHz channels across the stream: 1024, or 512, 256, 128 (n_channels <= channels, first_bin <
+    //         channels; decim = channels / 2 or 3 channels / 4, 0 = the latter; groups and set_rccl belong to 1024)
     static sptr make(int n_channels = 832, int first_bin = 96, int slicer = -1, int groups = 0, int group = 0, int decim = 0, bool short_input = false,
-                     bool channel_power = false);
+                     bool channel_power = false, int channels = 1024);
     // Let ONE rank own the stream: after this call (a collective over all `nranks` blocks; `id` = the 128 bytes one of them got from
     // rccl_unique_id(), carried between the processes by the application) work() distributes rank `root`'s input over xGMI with RCCL
     // inside amps_recc_push_wideband_dist (mode 0 = flat broadcast, 1 = scatter + all-gather: AMPS_RECC_DIST_*).  The other ranks'

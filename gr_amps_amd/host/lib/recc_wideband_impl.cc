@@ -1,4 +1,4 @@
-// recc_wideband_impl.cc -- gr::amps::recc_wideband: one 30.72 Msps complex stream in, (channel, burst) and (channel, record) pairs out.
+// recc_wideband_impl.cc -- gr::amps::recc_wideband: one 30.72 Msps complex stream (or 15.36, 7.68, 3.84 Msps: channels < 1024) in, (channel, burst) and (channel, record) pairs out.
 #include <amps/recc_wideband.h>
 #include <cerrno>
 #include <cstdio>
@@ -27,7 +27,7 @@ class recc_wideband_impl : public recc_wideband {
     std::vector<uint32_t> d_nsnap;
 
 public:
-    recc_wideband_impl(int C, int first_bin, int slicer, int groups, int group, int decim, bool short_input, bool channel_power)
+    recc_wideband_impl(int C, int first_bin, int slicer, int groups, int group, int decim, bool short_input, bool channel_power, int channels)
         : gr::sync_block("recc_wideband", gr::io_signature::make(1, 1, short_input ? 2 * sizeof(short) : 2 * sizeof(float)), gr::io_signature::make(0, 0, 0)),
           d_handle(nullptr), d_recs(kMaxRecs), d_bursts((size_t)kMaxRecs * AMPS_RECC_CAPTURE_SYMS), d_short(short_input), d_power(channel_power),
           d_pow(channel_power ? kMaxRecs : 0), d_nsnap(channel_power ? kMaxRecs : 0)
@@ -36,15 +36,17 @@ public:
         cfg.struct_size = sizeof(cfg);
         cfg.n_channels = (uint32_t)C;
         cfg.samples_per_symbol = 0;                // what goes with the decimation: 3 (60 ksps per channel, D = 512) or 2 (40 ksps, D = 768)
-        cfg.max_samples_per_push = kMaxPush / 512 + 72;
+        const bool narrow = channels > 0 && channels < 1024;       // the two-kernel form: received power is the IQ seam's
+        const int dmin = narrow ? (decim > 0 ? decim : 3 * channels / 4) : 512;   // fewest input samples a frame takes
+        cfg.max_samples_per_push = (uint32_t)(kMaxPush / dmin + 72);
         cfg.max_bursts = kMaxRecs;
         cfg.device = -1;
         cfg.flags = AMPS_RECC_FLAG_KEEP_BURSTS | (slicer == 0 ? AMPS_RECC_FLAG_SLICER_ATAN : slicer == 1 ? AMPS_RECC_FLAG_SLICER_PRODUCT
                                                   : slicer == 2 ? AMPS_RECC_FLAG_SLICER_SINE : slicer == 3 ? AMPS_RECC_FLAG_SLICER_EXACT : 0u)
-                    | (channel_power ? AMPS_RECC_FLAG_CHANNEL_POWER : 0u);
+                    | (channel_power ? (narrow ? AMPS_RECC_FLAG_STREAM_POWER : AMPS_RECC_FLAG_CHANNEL_POWER) : 0u);
         cfg.wideband_groups = (uint32_t)groups;
         cfg.wideband_group = (uint32_t)group;
-        cfg.wideband_channels = 1024;
+        cfg.wideband_channels = (uint32_t)channels;
         cfg.wideband_decim = (uint32_t)decim;     // 0 = amps_recc_default_wideband_decim()
         cfg.wideband_taps_per_branch = 8;
         cfg.wideband_first_channel = (uint32_t)first_bin;
@@ -132,9 +134,9 @@ public:
     }
 };
 
-recc_wideband::sptr recc_wideband::make(int n_channels, int first_bin, int slicer, int groups, int group, int decim, bool short_input, bool channel_power)
+recc_wideband::sptr recc_wideband::make(int n_channels, int first_bin, int slicer, int groups, int group, int decim, bool short_input, bool channel_power, int channels)
 {
-    return gnuradio::get_initial_sptr(new recc_wideband_impl(n_channels, first_bin, slicer, groups, group, decim, short_input, channel_power));
+    return gnuradio::get_initial_sptr(new recc_wideband_impl(n_channels, first_bin, slicer, groups, group, decim, short_input, channel_power, channels));
 }
 
 std::string recc_wideband::rccl_unique_id()

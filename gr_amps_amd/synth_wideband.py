@@ -13,8 +13,8 @@ def bin_freq(k, fs=FS_WIDE, m=M):
     return k * fs / m if k < m // 2 else (k - m) * fs / m
 
 
-def make_wideband(nsamp, bursts, seed, snr_db=30.0, fs=FS_WIDE, noise_bw=60e3, sym_ppm=0.0, cfo_hz=0.0):
-    """bursts: list of (fft_bin, sample_offset).  Every burst is a random message.  AWGN is scaled so the
+def make_wideband(nsamp, bursts, seed, snr_db=30.0, fs=FS_WIDE, noise_bw=60e3, sym_ppm=0.0, cfo_hz=0.0, bins=M):
+    """bursts: list of (fft_bin, sample_offset); the band has `bins` bins of fs / bins each (a narrow bank: fs = bins * 30 kHz).  Every burst is a random message.  AWGN is scaled so the
     SNR is `snr_db` inside one channel's 60 kHz output bandwidth.  Returns (complex64 [nsamp], truth dict
     keyed by (bin, offset)).  sym_ppm / cfo_hz: symbol-clock and carrier offset of every mobile (synth.fsk_modulate)."""
     rng = np.random.default_rng(seed)
@@ -32,6 +32,6 @@ def make_wideband(nsamp, bursts, seed, snr_db=30.0, fs=FS_WIDE, noise_bw=60e3, s
         if m <= 0:
             continue
         ph = 2.0 * np.pi * np.cumsum(f[:m]) / fs + rng.uniform(0, 2 * np.pi)
-        x[off:off + m] += np.exp(1j * (ph + 2.0 * np.pi * bin_freq(k, fs) * n[off:off + m] / fs))
+        x[off:off + m] += np.exp(1j * (ph + 2.0 * np.pi * bin_freq(k, fs, bins) * n[off:off + m] / fs))
         truth[(k, off)] = (kind, min10, esn, dialed, words)
     return x.astype(np.complex64), truth

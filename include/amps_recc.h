@@ -59,7 +59,9 @@ extern "C" {
                                      still 4, a flag and three entry points added and nothing changed: AMPS_RECC_FLAG_STREAM_OFFSET, carrier offset
                                      on the IQ and translate seams through amps_recc_channel_autocorr / _burst_autocorr / _burst_offset;
                                      still 4, a flag and one entry point added and nothing changed: AMPS_RECC_FLAG_STREAM_OFFSET_UNIT, the
-                                     unit-amplitude statistic behind the same three entry points, and amps_recc_retune_xlate) */
+                                     unit-amplitude statistic behind the same three entry points, and amps_recc_retune_xlate;
+                                     still 4, one entry point added and nothing changed: amps_recc_wideband_plan, with cfg.wideband_channels = 512,
+                                     256 and 128, the wideband seam at 15.36, 7.68 and 3.84 Msps) */
 
 /* protocol constants of the reference */
 #define AMPS_RECC_TRIGGER_SYMS 74   /* lib/recc_impl.cc:76-77: 37 bits x 2 Manchester symbols   */
@@ -97,18 +99,21 @@ extern "C" {
                                                stand-in for clock_recovery_mm_ff's loop (grc/recctest.grc:846-874) */
 #define AMPS_RECC_FLAG_CHANNEL_POWER 0x200u /* wideband seam, fused form: keep per-channel received power (amps_recc_channel_power,
                                                amps_recc_burst_power below).  Off by default; with it off nothing is allocated or launched for it.
-                                               With AMPS_RECC_FLAG_UNFUSED_WIDEBAND, or on a handle without wideband_channels: -EINVAL */
+                                               With AMPS_RECC_FLAG_UNFUSED_WIDEBAND, on a handle without wideband_channels, or with
+                                               wideband_channels < 1024 (its snapshot kernel is the 1024 bank's): -EINVAL */
 #define AMPS_RECC_FLAG_STREAM_POWER 0x400u /* IQ and translate seams: keep per-channel received power (the same three entry points; the
                                                definition for these seams stands below theirs).  Off by default; with it off nothing is
-                                               allocated or launched for it and no record changes.  On a handle with wideband_channels
-                                               (fused or not), with max_samples_per_push == 0 (symbol seam only), or together with
-                                               AMPS_RECC_FLAG_CHANNEL_POWER: -EINVAL */
+                                               allocated or launched for it and no record changes.  Also taken by a wideband handle with
+                                               wideband_channels < 1024, whose block goes through the IQ seam.  On a handle with
+                                               wideband_channels = 1024 (fused or not), with max_samples_per_push == 0 (symbol seam only), or
+                                               together with AMPS_RECC_FLAG_CHANNEL_POWER: -EINVAL */
 #define AMPS_RECC_FLAG_STREAM_OFFSET 0x800u /* IQ and translate seams: keep the per-channel lag-one autocorrelation sums from which a burst's
                                                carrier offset is read (amps_recc_channel_autocorr, amps_recc_burst_autocorr,
                                                amps_recc_burst_offset below).  Off by default; with it off nothing is allocated or launched
-                                               for it and no record changes.  Combines freely with AMPS_RECC_FLAG_STREAM_POWER.  On a handle
-                                               with wideband_channels (fused or not), with max_samples_per_push == 0 (symbol seam only), or
-                                               together with AMPS_RECC_FLAG_CHANNEL_POWER: -EINVAL */
+                                               for it and no record changes.  Combines freely with AMPS_RECC_FLAG_STREAM_POWER.  Also taken
+                                               with wideband_channels < 1024 (fs = 30 kHz M / D there).  On a handle with wideband_channels
+                                               = 1024 (fused or not), with max_samples_per_push == 0 (symbol seam only), or together with
+                                               AMPS_RECC_FLAG_CHANNEL_POWER: -EINVAL */
 #define AMPS_RECC_FLAG_STREAM_OFFSET_UNIT 0x1000u /* the same ring, entry points, numbering, window and error rules as
                                                AMPS_RECC_FLAG_STREAM_OFFSET, holding the UNIT-AMPLITUDE statistic U instead of A (defined
                                                with the entry points below): the one to use behind a translate seam's channel filter, the
@@ -203,8 +208,16 @@ typedef struct amps_recc_cfg {
     uint32_t max_bursts;           /* capacity of the device-side result list per push/drain (>=1)        */
     int32_t  device;               /* HIP device ordinal, -1 = current device                             */
     uint32_t flags;                /* AMPS_RECC_FLAG_*                                                    */
-    uint32_t wideband_channels;    /* channelizer seam: M branches: 1024 (0 = seam unused); other values: -EINVAL */
-    uint32_t wideband_decim;       /* channelizer seam: D input samples per output frame; 0 = amps_recc_default_wideband_decim().
+    uint32_t wideband_channels;    /* channelizer seam: M branches of 30 kHz, for a stream at M * 30 ksps: 1024 (30.72 Msps), or 512, 256, 128
+                                    * (15.36, 7.68, 3.84 Msps: the narrow banks, see amps_recc_wideband_plan); 0 = seam unused; other values:
+                                    * -EINVAL.  At M < 1024 the seam is the two-kernel form (AMPS_RECC_FLAG_UNFUSED_WIDEBAND is accepted and
+                                    * changes nothing), wideband_groups > 1 and AMPS_RECC_FLAG_CHANNEL_POWER are -EINVAL, amps_recc_rccl_init
+                                    * answers -ENOSYS, and AMPS_RECC_FLAG_STREAM_POWER / _STREAM_OFFSET / _STREAM_OFFSET_UNIT are accepted:
+                                    * blocks of 256 channel-rate samples, as on the IQ seam.  Bin M / 2 is centred on +- fs / 2, where the
+                                    * radio's own anti-alias filter rolls off: a channel there is received as the radio delivers it */
+    uint32_t wideband_decim;       /* channelizer seam: D input samples per output frame: M / 2 or 3 M / 4, anything else -EINVAL.
+                                    * M = 1024: 0 = amps_recc_default_wideband_decim().  M < 1024: 0 = 3 M / 4, the same ratio.
+                                    * samples_per_symbol = 0 is filled in as 3 M / (2 D).  At M = 1024:
                                     * 768 (4/3 x oversampled: 40 ksps per channel, samples_per_symbol = 2; the default since round 6)
                                     * or 512 (2x oversampled: 60 ksps, samples_per_symbol = 3; 1.5 x the frames per input byte,
                                     * 0.2 - 0.7 dB more sensitive)                                                     */
@@ -379,6 +392,14 @@ int amps_recc_set_xlate_shared(amps_recc_t *h, const amps_recc_xlate_shared_cfg_
  * no handle and no device needed, and it asks the same function the configuration asks, so the two cannot disagree. */
 typedef struct amps_recc_xlate_plan { uint32_t decim, samples_per_symbol, ntaps, _pad; } amps_recc_xlate_plan_t;
 int amps_recc_xlate_shared_plan(double rate_hz, double width_hz, amps_recc_xlate_plan_t *out, size_t cap);
+
+/* Which filter bank for a wideband stream at rate_hz?  No device needed.  Writes up to `cap` entries of what amps_recc_create accepts as
+ * (wideband_channels, wideband_decim, samples_per_symbol) for that rate, the default decimation first, `taps` the prototype's length, and
+ * returns how many the rate admits (call with cap = 0 to size): two for a rate within 0.5 Hz of M * 30 kHz, M = 1024, 512, 256 or 128 --
+ * 3.84e6: (128, 96, 2, 1024), (128, 64, 3, 1024) -- and 0 for any other rate (10e6, 20e6, 1.92e6: resample in front, or use the
+ * translate seam below 3.2 Msps).  -EINVAL: rate_hz not positive and finite, out == NULL with cap > 0. */
+typedef struct amps_recc_wideband_plan { uint32_t channels, decim, samples_per_symbol, taps; } amps_recc_wideband_plan_t;
+int amps_recc_wideband_plan(double rate_hz, amps_recc_wideband_plan_t *out, size_t cap);
 /* For the rates it answers with nothing, ask amps_recc_xlate_resample_plan below. */
 /* iq is ONE row of nsamp samples at rate_hz.  Any nsamp <= decim * max_samples_per_push (-E2BIG beyond); leftover samples (fewer than
  * decim) wait for the next push.  Host and device blocks follow the ownership rules of amps_recc_push_raw; amps_recc_reset restarts
