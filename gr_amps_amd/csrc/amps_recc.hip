@@ -170,7 +170,8 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
     if (cfg->n_channels < 1 || cfg->max_bursts < 1) return -EINVAL;
     // the channelizer's geometry (M channels of 30 kHz at M x 30 ksps) delivers 60 ksps = 3 samples per Manchester symbol at D = M / 2 and
     // 40 ksps = 2 at D = 3 M / 4; the bit-domain kernels behind it are built for exactly those.  Two samples per symbol exist on the wideband
-    // seam only (the streaming kernel of the IQ seam has no such instantiation).
+    // seam only: the streaming kernel has the instantiation (recc_front_kernel<2, ...>), reached by the two-kernel form -- the unfused 1024
+    // bank at D = 768 and every narrow bank at D = 3 M / 4, its default ratio -- and sps_supported refuses it to a handle of the IQ seam.
     const bool wide768 = cfg->wideband_channels && 4u * cfg->wideband_decim == 3u * cfg->wideband_channels;
     if (cfg->max_samples_per_push && !(wide768 ? cfg->samples_per_symbol == 2 : sps_supported(cfg->samples_per_symbol))) return -EINVAL;
     if (cfg->wideband_channels && (cfg->samples_per_symbol != (wide768 ? 2u : 3u) || cfg->max_samples_per_push == 0)) return -EINVAL;

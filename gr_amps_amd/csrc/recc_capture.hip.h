@@ -76,7 +76,8 @@ template <int SPS> front_kernel_t front_kernel_of(int slicer, bool tol)
 }
 // The streaming kernel for (samples per symbol, slicer spec, tolerant sync); nullptr for a rate it is not built for.  This switch
 // is the one table of the rates the streaming kernel supports.  sps = 2 is launchable but not supported (sps_supported): only the
-// unfused (two-kernel) form of the wideband seam at D = 768 reaches it, never a handle of the IQ seam.
+// two-kernel form of the wideband seam at D = 3 M / 4 reaches it -- the unfused 1024 bank at D = 768 and every narrow bank (512, 256,
+// 128 branches) at its default ratio, which has no other form -- never a handle of the IQ seam.
 inline front_kernel_t front_kernel_for(uint32_t sps, int slicer, bool tol)
 {
     static const struct { uint32_t sps; front_kernel_t (*of)(int, bool); } rates[] = {
