@@ -20,7 +20,7 @@ HOSTSRC  = $(HOST)/lib/recc_impl.cc $(HOST)/lib/recc_decode_impl.cc $(HOST)/lib/
 
 all: $(PKG)/libamps_recc.so $(PKG)/libgnuradio-amps-mi355x.so $(PKG)/recctest oracle/libamps_oracle.so
 
-$(PKG)/libamps_recc.so: $(CSRC)/amps_recc.hip $(wildcard $(CSRC)/*.h) $(wildcard include/*.h)
+$(PKG)/libamps_recc.so: $(CSRC)/amps_recc.hip $(wildcard $(CSRC)/*.h) $(wildcard $(CSRC)/*.inc) $(wildcard include/*.h)
 	$(HIPCC) $(HIPFLAGS) -Iinclude -I$(CSRC) $(CSRC)/amps_recc.hip -o $@
 
 $(PKG)/libgnuradio-amps-mi355x.so: $(HOSTSRC) $(wildcard $(HOST)/lib/*.h) $(HOST)/gr_min/gnuradio_min.h include/amps_recc.h $(PKG)/libamps_recc.so

@@ -7,6 +7,8 @@ AMPS band out (BASELINE configs[3]; replaces 832 x [freq_xlating_fir_filter_ccc 
     python examples/decode_wideband.py --channels 128   # one SDR's worth: a 3.84 Msps stream (or 256: 7.68, 512: 15.36) through the bank of
                                                         # that many branches, every bin a channel.  Bin channels / 2 sits on +- fs / 2, where a
                                                         # real radio's anti-alias filter rolls off: expect less of a mobile there than here
+    python examples/decode_wideband.py --channels 128 --sc8   # ... as a HackRF delivers it: interleaved int8 I/Q at a full scale of 100, pushed
+                                                              # as it is (2 bytes per sample); meaningful with --channels 512, 256 or 128
 """
 import os
 import sys
@@ -27,6 +29,9 @@ SC16 = "--sc16" in sys.argv[1:]
 if SC16:                                          # full scale for the loudest sample, a power of two; no slicer decision depends on the scale
     scale = 2.0 ** np.floor(np.log2(30000.0 / max(np.abs(x.real).max(), np.abs(x.imag).max())))
     x = np.rint(np.stack([x.real, x.imag], axis=1) * scale).astype(np.int16)   # [n, 2]: 4 bytes per sample instead of 8
+SC8 = "--sc8" in sys.argv[1:] and not SC16
+if SC8:                                           # the loudest sample at 100 of 127
+    x = np.rint(np.stack([x.real, x.imag], axis=1) * (100.0 / max(np.abs(x.real).max(), np.abs(x.imag).max()))).astype(np.int8)   # [n, 2]: 2 bytes per sample
 
 try:
     rx = capi.Recc(n_channels=CHANNELS, max_samples=NSAMP // (BANK // 2) + 72, max_bursts=256,
@@ -37,7 +42,10 @@ with rx:
     pos = 0
     while pos < NSAMP:                            # blocks of any size: what is left of a frame waits in the handle for the next push
         n = min(int(rng.integers(100_000, 3_000_000)) * BANK // 1024, NSAMP - pos)
-        (rx.push_wideband_short if SC16 else rx.push_wideband)(x[pos:pos + n])
+        if SC8:
+            rx.push_wideband_as(x[pos:pos + n], capi.SAMPLES_SC8)
+        else:
+            (rx.push_wideband_short if SC16 else rx.push_wideband)(x[pos:pos + n])
         pos += n
     recs = rx.drain()
 sent = {k - FIRST_BIN: v[1] for (k, _), v in truth.items()}

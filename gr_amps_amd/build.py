@@ -17,7 +17,7 @@ def _sources():
     out = []
     for d in (CSRC, os.path.join(_ROOT, "include")):
         for f in sorted(os.listdir(d)):
-            if f.endswith((".hip", ".h", ".hpp")):
+            if f.endswith((".hip", ".h", ".hpp", ".inc")):        # .inc: text a header includes (recc_chz_narrow_body.inc)
                 out.append(os.path.join(d, f))
     return out
 

@@ -153,7 +153,9 @@ EXPORTS = (
     "amps_recc_channel_autocorr", "amps_recc_burst_autocorr", "amps_recc_burst_offset",
     "amps_recc_retune_xlate",
     "amps_recc_wideband_plan",
+    "amps_recc_push_wideband_as", "amps_recc_debug_channelize_as",
 )
+_WIDEBAND_AS = ("amps_recc_push_wideband_as", "amps_recc_debug_channelize_as")
 _XLATE_RESAMPLED = ("amps_recc_set_xlate_resampled", "amps_recc_xlate_resample_plan")
 _XLATE_AS = ("amps_recc_push_raw_shared_as", "amps_recc_push_raw_as", "amps_recc_debug_xlate_shared_as", "amps_recc_debug_xlate_as")
 _XLATE_SHARED = ("amps_recc_set_xlate_shared", "amps_recc_push_raw_shared", "amps_recc_debug_xlate_shared")
@@ -261,12 +263,15 @@ def load():
         L.amps_recc_xlate_resample_plan.argtypes = [C.c_double, C.c_double, C.POINTER(ResamplePlan), C.c_size_t]
     if hasattr(L, "amps_recc_wideband_plan"):         # absent only from A/B builds of earlier revisions (AMPS_RECC_LIB)
         L.amps_recc_wideband_plan.argtypes = [C.c_double, C.POINTER(WidebandPlan), C.c_size_t]
+    if hasattr(L, "amps_recc_push_wideband_as"):      # absent only from A/B builds of earlier revisions (AMPS_RECC_LIB)
+        L.amps_recc_push_wideband_as.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int]
+        L.amps_recc_debug_channelize_as.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.amps_bch_encode_words.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp]
     L.amps_bch_decode_words.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, vp, vp]
     for name in EXPORTS:
         if name in ("amps_recc_default_slicer", "amps_recc_default_wideband_decim", "amps_recc_debug_exact_slice", "amps_recc_rccl_unique_id", "amps_recc_rccl_init",
                     "amps_recc_push_wideband_bcast", "amps_recc_drain_gather", "amps_recc_debug_slicer_bits",
-                    "amps_recc_push_wideband_short", "amps_recc_xlate_shared_plan", "amps_recc_wideband_plan") + _NEW_IN_ABI4 + _POWER + _OFFSET + _RETUNE + _XLATE_SHARED + _XLATE_AS + _XLATE_RESAMPLED and not hasattr(L, name):
+                    "amps_recc_push_wideband_short", "amps_recc_xlate_shared_plan", "amps_recc_wideband_plan") + _NEW_IN_ABI4 + _POWER + _OFFSET + _RETUNE + _XLATE_SHARED + _XLATE_AS + _XLATE_RESAMPLED + _WIDEBAND_AS and not hasattr(L, name):
             continue
         if name not in ("amps_recc_strerror", "amps_recc_burst_size", "amps_recc_destroy"):   # every other entry point returns int
             getattr(L, name).restype = C.c_uint32 if name == "amps_recc_power_ring_snaps" else C.c_int
@@ -303,7 +308,9 @@ def convert_samples(a, format):
     `format`'s dtype, shaped [..., n, 2] or [..., 2n], to complex64 [..., n] by the plain conversion, no scaling -- int16 / int8:
     ((float)i, (float)q); uint8 (offset binary): ((float)i - 127.5, (float)q - 127.5); fc32: the float32 pairs (or complex64) as they
     are.  Every value is exact in binary32.  Recc.push_raw_shared_as(a, format) IS Recc.push_raw_shared(convert_samples(a, format)),
-    and so for the other three _as calls.  A dtype that does not match the format is a TypeError, never a cast."""
+    and so for the other three _as calls.  It is the definition for the wideband seam too: Recc.push_wideband_as(a, format) IS
+    Recc.push_wideband(convert_samples(a, format)), and Recc.debug_channelize_as likewise.  A dtype that does not match the format
+    is a TypeError, never a cast."""
     if format not in SAMPLE_DTYPES:
         raise ValueError("unknown sample format %r" % (format,))
     if not isinstance(a, np.ndarray):
@@ -659,6 +666,30 @@ class Recc:
         rc = load().amps_recc_push_wideband_short(self._h, ptr, n, mem)
         if rc:
             raise AmpsError(rc, "amps_recc_push_wideband_short")
+
+    # ---- wideband seam on an SDR's integer samples (sc16, sc8, cu8), read in place: include/amps_recc.h, amps_recc_push_wideband_as
+    def push_wideband_as(self, iq, format):
+        """push_wideband on a block in `format` (SAMPLES_*): a numpy array of the format's dtype shaped [n, 2] or [2n] (staged as it
+        is, 2 bytes per sample for sc8 and cu8) or a torch device tensor of that dtype (read in place).  By definition
+        push_wideband(convert_samples(iq, format)); a dtype that does not match the format is a TypeError, never a cast."""
+        iq, n = _typed_block(iq, format, None, "push_wideband_as")
+        ptr, mem, keep = _as_ptr(iq, self.sync_torch)
+        rc = load().amps_recc_push_wideband_as(self._h, ptr, n or 0, format, mem)
+        if rc:
+            raise AmpsError(rc, "amps_recc_push_wideband_as")
+
+    def debug_channelize_as(self, iq, format):
+        """Channelizer only (test tap) on a block in `format`: [n, 2] or [2n] -> complex64 [C][nframes]."""
+        iq, n = _typed_block(iq, format, None, "debug_channelize_as")
+        n = n or 0
+        ptr, mem, keep = _as_ptr(iq)
+        cap = n // min(512, self.decim or 512) + 6          # as debug_channelize
+        out = np.zeros((self.n_channels, cap), np.complex64)
+        nf = C.c_size_t(0)
+        rc = load().amps_recc_debug_channelize_as(self._h, ptr, n, format, mem, _hostptr(out), cap, C.byref(nf))
+        if rc:
+            raise AmpsError(rc, "amps_recc_debug_channelize_as")
+        return out[:, :nf.value].copy()
 
     # ---- one band over the GPUs of a node: RCCL inside the C ABI (include/amps_recc.h, amps_recc_push_wideband_bcast)
     @staticmethod

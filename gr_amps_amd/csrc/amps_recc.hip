@@ -327,10 +327,11 @@ int amps_recc_push_iq(amps_recc_t *h, const float *iq, size_t ld, size_t nsamp, 
     return rc;
 }
 
-// the wideband seam for either sample type of the block: fc32, or interleaved 16-bit I/Q (amps_recc_push_wideband_short)
-static int push_wideband_block(amps_recc_t *h, const void *iq, size_t nsamp, int mem, bool sc16)
+// the wideband seam for every sample format of the block (AMPS_RECC_SAMPLES_*): fc32, interleaved 16-bit I/Q
+// (amps_recc_push_wideband_short) or 8-bit I/Q (amps_recc_push_wideband_as)
+static int push_wideband_block(amps_recc_t *h, const void *iq, size_t nsamp, int mem, int format)
 {
-    if (!h) return -EINVAL;
+    if (!h || !chz_sample_bytes(format)) return -EINVAL;
     STALE_CHECK(h);
     if (!h->chz.enabled) return -ENOSYS;
     if (nsamp == 0) return 0;
@@ -348,7 +349,7 @@ static int push_wideband_block(amps_recc_t *h, const void *iq, size_t nsamp, int
     {
         SpanGuard g(h->tm, h->stream.get(), true, T_CHANNELIZER, nsamp);
         ChzRunIn in;
-        in.iq = iq; in.nsamp = nsamp; in.mem = mem; in.sc16 = sc16; in.fused = fused;
+        in.iq = iq; in.nsamp = nsamp; in.mem = mem; in.format = format; in.fused = fused;
         in.gring = h->cap.gring.get(); in.ring_words = h->cap.ring_words; in.n_done = h->cap.n_done; in.slicer = h->slicer;
         in.power = power_of(h);
         in.after_main = SpanGuard::end_cb; in.after_ctx = &g;
@@ -360,8 +361,9 @@ static int push_wideband_block(amps_recc_t *h, const void *iq, size_t nsamp, int
     return capture_run_iq(h->cap, h->lists, h->tm, h->stream.get(), chan_iq, ld, nout, power_of(h), offset_of(h));   // (rings: narrow banks only)
 }
 
-int amps_recc_push_wideband(amps_recc_t *h, const float *iq, size_t nsamp, int mem) { return push_wideband_block(h, iq, nsamp, mem, false); }
-int amps_recc_push_wideband_short(amps_recc_t *h, const int16_t *iq, size_t nsamp, int mem) { return push_wideband_block(h, iq, nsamp, mem, true); }
+int amps_recc_push_wideband(amps_recc_t *h, const float *iq, size_t nsamp, int mem) { return push_wideband_block(h, iq, nsamp, mem, AMPS_RECC_SAMPLES_FC32); }
+int amps_recc_push_wideband_short(amps_recc_t *h, const int16_t *iq, size_t nsamp, int mem) { return push_wideband_block(h, iq, nsamp, mem, AMPS_RECC_SAMPLES_SC16); }
+int amps_recc_push_wideband_as(amps_recc_t *h, const void *iq, size_t nsamp, int format, int mem) { return push_wideband_block(h, iq, nsamp, mem, format); }
 
 int amps_recc_rccl_unique_id(uint8_t *id)
 {
@@ -854,14 +856,19 @@ done:
 
 int amps_recc_debug_channelize(amps_recc_t *h, const float *iq, size_t nsamp, int mem, float *out, size_t out_ld, size_t *nframes)
 {
-    if (!h || !iq || !out || !nframes) return -EINVAL;
+    return amps_recc_debug_channelize_as(h, iq, nsamp, AMPS_RECC_SAMPLES_FC32, mem, out, out_ld, nframes);
+}
+
+int amps_recc_debug_channelize_as(amps_recc_t *h, const void *iq, size_t nsamp, int format, int mem, float *out, size_t out_ld, size_t *nframes)
+{
+    if (!h || !iq || !out || !nframes || !chz_sample_bytes(format)) return -EINVAL;
     if (!h->chz.enabled) return -ENOSYS;
     HIP_TRY(hipSetDevice(h->device));
     const float2 *chan_iq = nullptr;
     uint64_t ld = 0;
     uint32_t nout = 0;
-    ChzRunIn in;                                             // the unfused form on fc32: the channel-major block is the output
-    in.iq = iq; in.nsamp = nsamp; in.mem = mem;
+    ChzRunIn in;                                             // the unfused form: the channel-major block is the output
+    in.iq = iq; in.nsamp = nsamp; in.mem = mem; in.format = format;
     int rc = channelizer_run(h->chz, in, h->stream.get(), &chan_iq, &ld, &nout);
     if (rc) return rc;
     *nframes = nout;

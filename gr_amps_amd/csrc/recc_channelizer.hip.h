@@ -113,9 +113,25 @@ __global__ __launch_bounds__(256) void chz_carry_short_kernel(const chz_sc16 *bl
     for (uint32_t k = blockIdx.x * 256 + threadIdx.x; k < out_len; k += gridDim.x * 256)
         carry_out[k] = chz_carry_sample(block, carry_in, carry_len, nsamp, hist, consumed, k);
 }
+// ... and behind a push of 8-bit I/Q (T = xl_sc8 or xl_cu8: amps_recc_push_wideband_as)
+template <typename T>
+__global__ __launch_bounds__(256) void chz_carry_b8_kernel(const T *block, const float2 *carry_in, float2 *carry_out,
+                                                            uint32_t carry_len, uint32_t nsamp, uint32_t hist, uint32_t consumed,
+                                                            uint32_t out_len)
+{
+    for (uint32_t k = blockIdx.x * 256 + threadIdx.x; k < out_len; k += gridDim.x * 256)
+        carry_out[k] = chz_carry_sample(block, carry_in, carry_len, nsamp, hist, consumed, k);
+}
 // sc16 -> fc32, a sample per thread: in front of the fc32 filter bank where the checking modes (unfused form, amps_recc_debug_channelize)
 // and the AMPS_RECC_SHORT_PREPASS experiment take a 16-bit block
 __global__ __launch_bounds__(256) void chz_short_to_float_kernel(const chz_sc16 *in, float2 *out, uint32_t n)
+{
+    for (uint32_t k = blockIdx.x * 256 + threadIdx.x; k < n; k += gridDim.x * 256) { const cf2 c = chz_cvt(in[k]); out[k] = make_float2(c.x, c.y); }
+}
+// sc8 / cu8 -> fc32 likewise: in front of the 1024 bank always (no radio delivers 8 bits at 30.72 Msps; converted capture files do),
+// so that every form of that bank -- fused or not, channel groups, the power ring -- runs as on an fc32 block
+template <typename T>
+__global__ __launch_bounds__(256) void chz_b8_to_float_kernel(const T *in, float2 *out, uint32_t n)
 {
     for (uint32_t k = blockIdx.x * 256 + threadIdx.x; k < n; k += gridDim.x * 256) { const cf2 c = chz_cvt(in[k]); out[k] = make_float2(c.x, c.y); }
 }
@@ -158,8 +174,8 @@ struct ChannelizerState {
     uint64_t frames_done = 0;
     DevBuf<float2> out;             // [C][ld]
     uint64_t ld = 0;
-    HostStage stage;                // host-resident wideband input as the caller's samples (fc32 or sc16), sized in bytes: the largest block so far
-    DevBuf<float2> cvt;             // an sc16 block expanded to fc32: the checking modes and the pre-pass experiment only
+    HostStage stage;                // host-resident wideband input as the caller's samples (fc32, sc16, sc8 or cu8), sized in bytes: the largest block so far
+    DevBuf<float2> cvt;             // an integer block expanded to fc32, M = 1024 only: sc16 in the checking modes and the pre-pass experiment, sc8 / cu8 always
     bool short_prepass = false;     // AMPS_RECC_SHORT_PREPASS=1 at create: sc16 blocks go through chz_short_to_float_kernel + the fc32 kernel
 };
 
@@ -314,7 +330,8 @@ struct ChzRunIn {
     const void *iq = nullptr;                // `nsamp` new wideband samples, host or device (`mem`: AMPS_MEM_*)
     size_t nsamp = 0;
     int mem = AMPS_MEM_DEVICE;
-    bool sc16 = false;                       // interleaved 16-bit I/Q (4 bytes per sample), else fc32: read in place by the fused form, expanded to fc32 first otherwise
+    int format = AMPS_RECC_SAMPLES_FC32;     // AMPS_RECC_SAMPLES_*.  sc16: read in place by the fused form and the narrow banks, expanded to fc32 first otherwise;
+                                             // sc8 / cu8: read in place by the narrow banks, expanded to fc32 first at M = 1024
     bool fused = false;                      // false: the channel-major block (*chan_iq / *ld / *nframes; even number of frames); true: slicer bits only, 64 frames at a time
     uint64_t *gring = nullptr;               // fused: the slicer-bit ring, written at absolute sample index n_done..
     uint32_t ring_words = 0;
@@ -328,15 +345,16 @@ struct ChzRunIn {
 // Channelise in.nsamp new wideband samples.
 inline int channelizer_run(ChannelizerState &z, const ChzRunIn &in, hipStream_t s, const float2 **chan_iq, uint64_t *ld, uint32_t *nframes_out)
 {
-    const bool narrow = z.M != CHZ_M;                             // chz_narrow_kernel: the two-kernel form whatever was asked, either sample type read in place
+    const bool narrow = z.M != CHZ_M;                             // chz_narrow_kernel: the two-kernel form whatever was asked, every sample format read in place
     const bool fused = in.fused && !narrow;
     const size_t nsamp = in.nsamp;
-    bool sc16 = in.sc16;
+    int format = in.format;
     if (!z.enabled) return -ENOSYS;
+    if (!chz_sample_bytes(format)) return -EINVAL;
     if (!fused && z.groups > 1) return -ENOSYS;                   // channel groups exist in the fused form only
     const void *d = in.iq;
     if (in.mem == AMPS_MEM_HOST) {                                // one row of bytes, as the caller's samples
-        const size_t bytes = (sc16 ? sizeof(chz_sc16) : sizeof(float2)) * nsamp;
+        const size_t bytes = chz_sample_bytes(format) * nsamp;
         const uint8_t *staged = nullptr;
         uint64_t pitch = 0;
         if (int rc = z.stage.stage((const uint8_t *)in.iq, bytes, bytes, 1, bytes, &staged, &pitch)) return rc;
@@ -350,7 +368,8 @@ inline int channelizer_run(ChannelizerState &z, const ChzRunIn &in, hipStream_t 
     // D = M / 2, frame phase 0 of 4 at D = 3 M / 4), and in the fused form a multiple of 64 (whole words of the RECC bit ring); the rest waits in the carry
     const uint32_t nframes = (uint32_t)(avail / (uint32_t)z.D) & (fused ? ~63u : 2 * z.D == z.M ? ~1u : ~3u);
     if (nframes > z.max_frames) return -E2BIG;
-    if (sc16 && !narrow && (!fused || z.short_prepass)) {
+    const bool b8 = format == AMPS_RECC_SAMPLES_SC8 || format == AMPS_RECC_SAMPLES_CU8;
+    if (!narrow && (b8 || (format == AMPS_RECC_SAMPLES_SC16 && (!fused || z.short_prepass)))) {
         // the block as fc32 in a buffer of its own, then everything as for an fc32 block.  Stream order keeps the buffer safe: the
         // kernels of the previous push that read it run before this conversion
         if (z.cvt.capacity() < nsamp) {
@@ -358,10 +377,13 @@ inline int channelizer_run(ChannelizerState &z, const ChzRunIn &in, hipStream_t 
             if (z.cvt.reserve(nsamp)) return -ENOMEM;
         }
         const uint32_t blocks = (uint32_t)std::min<size_t>((nsamp + 255) / 256, 65536);
-        hipLaunchKernelGGL(chz_short_to_float_kernel, dim3(blocks), dim3(256), 0, s, (const chz_sc16 *)d, z.cvt.get(), (uint32_t)nsamp);
+        if (format == AMPS_RECC_SAMPLES_SC8) hipLaunchKernelGGL(chz_b8_to_float_kernel<xl_sc8>, dim3(blocks), dim3(256), 0, s, (const xl_sc8 *)d, z.cvt.get(), (uint32_t)nsamp);
+        else if (format == AMPS_RECC_SAMPLES_CU8) hipLaunchKernelGGL(chz_b8_to_float_kernel<xl_cu8>, dim3(blocks), dim3(256), 0, s, (const xl_cu8 *)d, z.cvt.get(), (uint32_t)nsamp);
+        else hipLaunchKernelGGL(chz_short_to_float_kernel, dim3(blocks), dim3(256), 0, s, (const chz_sc16 *)d, z.cvt.get(), (uint32_t)nsamp);
         d = z.cvt.get();
-        sc16 = false;
+        format = AMPS_RECC_SAMPLES_FC32;
     }
+    const bool sc16 = format == AMPS_RECC_SAMPLES_SC16;          // what is left of the formats at M = 1024
     const uint32_t consumed = nframes * (uint32_t)z.D;                // virtual samples consumed (incl. leftover)
     const uint32_t new_left = (uint32_t)(avail - consumed);
     bool carry_in_kernel = false;
@@ -371,7 +393,7 @@ inline int channelizer_run(ChannelizerState &z, const ChzRunIn &in, hipStream_t 
         na.block = d; na.carry = z.carry[z.carry_cur].get(); na.taps = z.taps.get(); na.twiddle = z.twiddle.get(); na.out = z.out.get(); na.ld = z.ld;
         na.bin2row = z.bin2row.get(); na.carry_len = z.carry_len; na.nsamp = (uint32_t)nsamp; na.nframes = nframes; na.n_channels = z.C;
         const uint32_t fr = (uint32_t)chz_narrow_fr(z.M, z.D);
-        hipLaunchKernelGGL(chz_narrow_kernel_for(z.M, z.D, sc16), dim3((nframes + fr - 1) / fr), dim3(256), 0, s, na);
+        hipLaunchKernelGGL(chz_narrow_kernel_for(z.M, z.D, format), dim3((nframes + fr - 1) / fr), dim3(256), 0, s, na);
     } else if (nframes) {
         a.block = (const float2 *)d; a.carry = z.carry[z.carry_cur].get(); a.taps = z.taps.get(); a.out = z.out.get(); a.ld = z.ld;
         a.carry_len = z.carry_len; a.nsamp = (uint32_t)nsamp; a.nframes = nframes; a.hist = hist;
@@ -399,6 +421,10 @@ inline int channelizer_run(ChannelizerState &z, const ChzRunIn &in, hipStream_t 
 #endif
     if (!carry_in_kernel) {
         if (sc16) hipLaunchKernelGGL(chz_carry_short_kernel, dim3((hist + new_left + 255) / 256), dim3(256), 0, s, (const chz_sc16 *)d, z.carry[z.carry_cur].get(),
+                                     z.carry[z.carry_cur ^ 1].get(), z.carry_len, (uint32_t)nsamp, hist, consumed, hist + new_left);
+        else if (format == AMPS_RECC_SAMPLES_SC8) hipLaunchKernelGGL(chz_carry_b8_kernel<xl_sc8>, dim3((hist + new_left + 255) / 256), dim3(256), 0, s, (const xl_sc8 *)d, z.carry[z.carry_cur].get(),
+                                     z.carry[z.carry_cur ^ 1].get(), z.carry_len, (uint32_t)nsamp, hist, consumed, hist + new_left);
+        else if (format == AMPS_RECC_SAMPLES_CU8) hipLaunchKernelGGL(chz_carry_b8_kernel<xl_cu8>, dim3((hist + new_left + 255) / 256), dim3(256), 0, s, (const xl_cu8 *)d, z.carry[z.carry_cur].get(),
                                      z.carry[z.carry_cur ^ 1].get(), z.carry_len, (uint32_t)nsamp, hist, consumed, hist + new_left);
         else hipLaunchKernelGGL(chz_carry_kernel, dim3((hist + new_left + 255) / 256), dim3(256), 0, s, (const float2 *)d, z.carry[z.carry_cur].get(),
                                 z.carry[z.carry_cur ^ 1].get(), z.carry_len, (uint32_t)nsamp, hist, consumed, hist + new_left);

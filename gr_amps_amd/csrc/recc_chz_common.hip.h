@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "amps_recc.h"              // AMPS_RECC_SAMPLES_*
 
 namespace amps {
 
@@ -49,6 +50,28 @@ template <typename T> struct chz_is_short { static constexpr bool value = false;
 template <> struct chz_is_short<chz_sc16> { static constexpr bool value = true; };
 __device__ __forceinline__ cf2 chz_cvt(float2 s) { return (cf2){ s.x, s.y }; }
 __device__ __forceinline__ cf2 chz_cvt(chz_sc16 s) { return (cf2){ (float)s.x, (float)s.y }; }
+// The 8-bit wire formats of the translate seams and of the wideband seam's _as entry points (include/amps_recc.h,
+// AMPS_RECC_SAMPLES_SC8 / _CU8), in the same style: two bytes per sample, I first.  xl_cvt is their one definition -- cu8 is offset
+// binary, (float)i - 127.5f, 9 significant bits -- and chz_cvt hands its result to the filter bank.
+struct alignas(2) xl_sc8 { int8_t x, y; };
+struct alignas(2) xl_cu8 { uint8_t x, y; };
+__device__ __forceinline__ float2 xl_cvt(xl_sc8 s) { return make_float2((float)s.x, (float)s.y); }
+__device__ __forceinline__ float2 xl_cvt(xl_cu8 s) { return make_float2((float)s.x - 127.5f, (float)s.y - 127.5f); }
+template <> struct chz_is_short<xl_sc8> { static constexpr bool value = true; };
+template <> struct chz_is_short<xl_cu8> { static constexpr bool value = true; };
+__device__ __forceinline__ cf2 chz_cvt(xl_sc8 s) { const float2 f = xl_cvt(s); return (cf2){ f.x, f.y }; }
+__device__ __forceinline__ cf2 chz_cvt(xl_cu8 s) { const float2 f = xl_cvt(s); return (cf2){ f.x, f.y }; }
+// bytes of one sample of a format (AMPS_RECC_SAMPLES_*); 0: no such format
+inline size_t chz_sample_bytes(int format)
+{
+    switch (format) {
+    case AMPS_RECC_SAMPLES_FC32: return sizeof(float2);
+    case AMPS_RECC_SAMPLES_SC16: return sizeof(chz_sc16);
+    case AMPS_RECC_SAMPLES_SC8: return sizeof(xl_sc8);
+    case AMPS_RECC_SAMPLES_CU8: return sizeof(xl_cu8);
+    default: return 0;
+    }
+}
 // Buffer resource (V#) of the fast loader (round 6).  The fold role's prefetch used `global_load_dwordx2 v, v_off, s[base:base+1]` with
 // a 64-bit scalar base per frame: clamp the frame index to the block, multiply, subtract, shift, add with carry -- nine scalar
 // instructions per frame and two more per chunk, ~65 per half-step in the wave whose instruction count IS the kernel's critical path

@@ -30,7 +30,7 @@
 namespace amps {
 
 struct ChzNarrowArgs {
-    const void *block;       // new wideband samples of this push: float2, or chz_sc16 (chz_narrow_kernel<.., chz_sc16>)
+    const void *block;       // new wideband samples of this push: float2 or chz_sc16 (chz_narrow_kernel), xl_sc8 or xl_cu8 (chz_narrow_b8_kernel)
     const float2 *carry;     // [carry_len]: the hist = 8 M - D samples in front of frame 0, then what earlier pushes left over
     const float *taps;       // [8 M] prototype
     const float2 *twiddle;   // [M]: e^{-2 pi i k / M}
@@ -127,112 +127,46 @@ __device__ __forceinline__ void chz_narrow_pass(cf2 *u, const float2 *tw, int t)
     __syncthreads();
 }
 
+// The kernel's body is recc_chz_narrow_body.inc, once per entry point (see there for why it is text, not a function).
 template <int M, int DEC, typename T>
 __global__ __launch_bounds__(256) void chz_narrow_kernel(ChzNarrowArgs a)
 {
-    static_assert(chz_narrow_geometry(M, DEC), "M = 512, 256 or 128 at D = M / 2 or 3 M / 4");
-    constexpr int FR = chz_narrow_fr(M, DEC), S = chz_narrow_stride(M), NST = chz_narrow_stage(M, DEC);
-    constexpr int E = FR * M / 256;                              // (frame, branch) pairs, and later (bin, frame) pairs, per thread
-    constexpr int BR = M > 256 ? M / 256 : 1;                    // branches whose taps a thread keeps
-    static_assert(chz_narrow_lds_bytes(M, DEC) <= 80 * 1024, "two workgroups per CU");
-    __shared__ cf2 xin[NST];
-    __shared__ cf2 u[FR * S];
-    const int t = threadIdx.x;
-    const uint32_t frame0 = blockIdx.x * (uint32_t)FR;
-
-    float h[BR][8];
-#pragma unroll
-    for (int b = 0; b < BR; b++)
-#pragma unroll
-        for (int p = 0; p < 8; p++) h[b][p] = a.taps[p * M + (t + 256 * b) % M];
-
-    // stage: sample i of the workgroup is carry-relative sample frame0 D + i; behind the stream's end (frames this launch does not
-    // produce) zeros
-    // -- eight loads in flight per thread: every load is unconditional, from an address that is valid whatever the sample is (element 0
-    // of the carry, which is never empty, or of the block, which has a sample whenever a launch produces a frame), and what it returned
-    // is kept or replaced by zero afterwards, so that a batch costs one memory latency and not eight
-    {
-        constexpr int NLD = (NST + 255) / 256, BATCH = 8;
-        const uint64_t c0 = (uint64_t)frame0 * DEC;
-        const T *blk = (const T *)a.block;
-#pragma unroll 1
-        for (int i0 = 0; i0 < NLD; i0 += BATCH) {
-            cf2 v[BATCH];
-#pragma unroll
-            for (int b = 0; b < BATCH; b++) {
-                const uint64_t ci = c0 + (uint64_t)(t + 256 * (i0 + b));
-                const bool in_carry = ci < a.carry_len;
-                const uint64_t bi = ci - a.carry_len;
-                const bool in_block = !in_carry && bi < a.nsamp;
-                if constexpr (chz_is_short<T>::value) {
-                    const float2 c = a.carry[in_carry ? ci : 0];
-                    const cf2 s = chz_cvt(blk[in_block ? bi : 0]);
-                    v[b] = in_carry ? (cf2){ c.x, c.y } : in_block ? s : (cf2){ 0.f, 0.f };
-                } else {
-                    const float2 c = *(in_carry ? a.carry + ci : in_block ? blk + bi : a.carry);
-                    v[b] = (in_carry || in_block) ? (cf2){ c.x, c.y } : (cf2){ 0.f, 0.f };
-                }
-            }
-#pragma unroll
-            for (int b = 0; b < BATCH; b++) {
-                const int i = t + 256 * (i0 + b);
-                if (i < NST) xin[i] = v[b];
-            }
-        }
-    }
-    __syncthreads();
-
-    // fold
-#pragma unroll
-    for (int q = 0; q < E; q++) {
-        const int idx = t + 256 * q, f = idx / M, j = idx % M;
-        const float (&hb)[8] = h[M > 256 ? q % BR : 0];
-        const cf2 *x = xin + f * DEC + j;
-        cf2 acc = x[0] * hb[0];
-#pragma unroll
-        for (int p = 1; p < 8; p++) { const cf2 s = x[p * M]; acc = (cf2){ fmaf(hb[p], s.x, acc.x), fmaf(hb[p], s.y, acc.y) }; }
-        // q and M fix f up to the thread's half at M = 128; the roll ((f + 1) D) mod M takes 2 or 4 values
-        u[f * S + chz_narrow_pos((j + ((f + 1) * DEC) % M) & (M - 1))] = acc;
-    }
-    __syncthreads();
-
-    if constexpr (M == 512) {
-        chz_narrow_pass<M, 8, 1, FR>(u, a.twiddle, t);
-        chz_narrow_pass<M, 8, 8, FR>(u, a.twiddle, t);
-        chz_narrow_pass<M, 8, 64, FR>(u, a.twiddle, t);
-    } else if constexpr (M == 256) {
-        chz_narrow_pass<M, 16, 1, FR>(u, a.twiddle, t);
-        chz_narrow_pass<M, 16, 16, FR>(u, a.twiddle, t);
-    } else {
-        chz_narrow_pass<M, 16, 1, FR>(u, a.twiddle, t);
-        chz_narrow_pass<M, 8, 16, FR>(u, a.twiddle, t);
-    }
-
-    // store: the frame runs fastest across lanes
-#pragma unroll
-    for (int q = 0; q < E; q++) {
-        const int idx = t + 256 * q, f = idx % FR, bin = idx / FR;
-        const uint32_t row = a.bin2row[bin], frame = frame0 + (uint32_t)f;
-        if (row < a.n_channels && frame < a.nframes) {
-            const cf2 y = u[f * S + chz_narrow_pos(bin)];
-            a.out[(uint64_t)row * a.ld + frame] = make_float2(y.x, y.y);
-        }
-    }
+#include "recc_chz_narrow_body.inc"
+}
+// the same on a block of 8-bit I/Q read in place (T = xl_sc8 or xl_cu8), 2 bytes per sample from HBM: a name of their own for
+// these instantiations, nothing else
+template <int M, int DEC, typename T>
+__global__ __launch_bounds__(256) void chz_narrow_b8_kernel(ChzNarrowArgs a)
+{
+    static_assert(sizeof(T) == 2, "an 8-bit pair");
+#include "recc_chz_narrow_body.inc"
 }
 
 typedef void (*chz_narrow_kernel_t)(ChzNarrowArgs);
 template <int M, typename T> chz_narrow_kernel_t chz_narrow_kernel_of(int D)
 {
-    return 2 * D == M ? chz_narrow_kernel<M, M / 2, T> : chz_narrow_kernel<M, 3 * M / 4, T>;
+    if constexpr (sizeof(T) == 2) return 2 * D == M ? chz_narrow_b8_kernel<M, M / 2, T> : chz_narrow_b8_kernel<M, 3 * M / 4, T>;
+    else return 2 * D == M ? chz_narrow_kernel<M, M / 2, T> : chz_narrow_kernel<M, 3 * M / 4, T>;
 }
-// the instantiation for (branches, input samples per frame, sample type of the block); nullptr for a geometry there is none for
-inline chz_narrow_kernel_t chz_narrow_kernel_for(int M, int D, bool sc16)
+template <int M> chz_narrow_kernel_t chz_narrow_kernel_of(int D, int format)
+{
+    switch (format) {
+    case AMPS_RECC_SAMPLES_FC32: return chz_narrow_kernel_of<M, float2>(D);
+    case AMPS_RECC_SAMPLES_SC16: return chz_narrow_kernel_of<M, chz_sc16>(D);
+    case AMPS_RECC_SAMPLES_SC8: return chz_narrow_kernel_of<M, xl_sc8>(D);
+    case AMPS_RECC_SAMPLES_CU8: return chz_narrow_kernel_of<M, xl_cu8>(D);
+    default: return nullptr;
+    }
+}
+// the instantiation for (branches, input samples per frame, sample format of the block: AMPS_RECC_SAMPLES_*); nullptr for a geometry
+// or a format there is none for
+inline chz_narrow_kernel_t chz_narrow_kernel_for(int M, int D, int format)
 {
     if (!chz_narrow_geometry(M, D)) return nullptr;
     switch (M) {
-    case 512: return sc16 ? chz_narrow_kernel_of<512, chz_sc16>(D) : chz_narrow_kernel_of<512, float2>(D);
-    case 256: return sc16 ? chz_narrow_kernel_of<256, chz_sc16>(D) : chz_narrow_kernel_of<256, float2>(D);
-    default: return sc16 ? chz_narrow_kernel_of<128, chz_sc16>(D) : chz_narrow_kernel_of<128, float2>(D);
+    case 512: return chz_narrow_kernel_of<512>(D, format);
+    case 256: return chz_narrow_kernel_of<256>(D, format);
+    default: return chz_narrow_kernel_of<128>(D, format);
     }
 }
 

@@ -72,14 +72,11 @@ __host__ __device__ constexpr bool xlate_is_wide(uint32_t D) { return D == 5 || 
 // the integer wire formats, read IN PLACE: one dword (sc16) or one 16-bit load (sc8, cu8) per lane and sample, consecutive lanes on
 // consecutive samples.  An integer form is DEFINED as the fc32 form on the plainly converted block, and every conversion below is
 // exact in binary32 (cu8: (float)i is exact and i - 127.5 has 9 significant bits), so converting where the sample is fetched --
-// xl_window, the one fetch of each kernel -- leaves every later operation on the bits it has in the fc32 form.
+// xl_window, the one fetch of each kernel -- leaves every later operation on the bits it has in the fc32 form.  xl_sc8, xl_cu8 and
+// their xl_cvt live in recc_chz_common.hip.h, which the wideband seam's narrow banks share.
 using xl_sc16 = chz_sc16;
-struct alignas(2) xl_sc8 { int8_t x, y; };
-struct alignas(2) xl_cu8 { uint8_t x, y; };
 __device__ __forceinline__ float2 xl_cvt(float2 s) { return s; }
 __device__ __forceinline__ float2 xl_cvt(xl_sc16 s) { return make_float2((float)s.x, (float)s.y); }
-__device__ __forceinline__ float2 xl_cvt(xl_sc8 s) { return make_float2((float)s.x, (float)s.y); }
-__device__ __forceinline__ float2 xl_cvt(xl_cu8 s) { return make_float2((float)s.x - 127.5f, (float)s.y - 127.5f); }
 
 struct XlateArgs {
     const void *block;       // [rows][ld_in] new samples of the kernel's sample type; rows = C (per-row form) or 1 (shared form)
@@ -419,13 +416,7 @@ inline xlate_carry_kernel_t xlate_carry_kernel_for(int format)
 // bytes of one sample of a format; 0: no such format
 inline size_t xlate_sample_bytes(int format)
 {
-    switch (format) {
-    case AMPS_RECC_SAMPLES_FC32: return sizeof(float2);
-    case AMPS_RECC_SAMPLES_SC16: return sizeof(xl_sc16);
-    case AMPS_RECC_SAMPLES_SC8: return sizeof(xl_sc8);
-    case AMPS_RECC_SAMPLES_CU8: return sizeof(xl_cu8);
-    default: return 0;
-    }
+    return chz_sample_bytes(format);
 }
 inline uint32_t xlate_max_taps(bool shared, uint32_t D) { return !shared ? XL_MAX_TAPS : xlate_is_wide(D) ? XLW_MAX_TAPS : XLS_MAX_TAPS; }
 typedef void (*xlate_rational_kernel_t)(XlateRationalArgs);

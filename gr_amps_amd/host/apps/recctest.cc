@@ -8,7 +8,9 @@
 //   recctest wide <file.fc32> [chunk] [slicer] [decim]  one 30.72 Msps wideband capture -> gr::amps::recc_wideband (832 channels from bin 96); every
 //                                      burst's lines are prefixed with its channel; decoded through the "bursts" port.  A file whose name ends
 //                                      in .sc16 (or a sixth argument `sc16`) is read as interleaved 16-bit I/Q and goes through the block's
-//                                      16-bit input.  An argument `power` behind those (the seventh, or the eighth behind `sc16`) makes the block
+//                                      16-bit input; .sc8 / .cs8 (or `sc8`) is read as int8 pairs and .cu8 (or `cu8`) as offset-binary uint8
+//                                      pairs, through the block's input format (what HackRF and RTL-SDR tools write; the silence behind a
+//                                      .cu8 file is the codes 127 / 128 alternating).  An argument `power` behind those (the seventh, or the eighth behind `sc16`) makes the block
 //                                      keep received power: every burst's lines are followed by `MSG power channel <c> <10 log10(mean power)> dB
 //                                      n=<snapshots>`; without it the output is what it always was.  An argument `channels=<M>` anywhere behind
 //                                      the file (M = 512, 256 or 128) reads the capture as a stream at M x 30 ksps -- 15.36, 7.68 or 3.84 Msps --
@@ -207,13 +209,15 @@ int main(int argc, char **argv)
             if (ranks && argc < 7) { std::fprintf(stderr, "usage: %s widerank <file> <chunk> <idfile> <nranks> <rank> [mode]\n", argv[0]); return 2; }
             const int nranks = ranks ? std::atoi(argv[5]) : 0, rank = ranks ? std::atoi(argv[6]) : 0;
             const std::string path = argv[2];
-            const bool sc16 = !ranks && ((path.size() > 5 && path.compare(path.size() - 5, 5, ".sc16") == 0) || (argc > 6 && std::string(argv[6]) == "sc16"));
-            const size_t item = sc16 ? 4 : 8;                         // bytes per wideband sample
+            const size_t dot = path.rfind('.');
+            const std::string ext = dot == std::string::npos ? "" : path.substr(dot), arg6 = argc > 6 ? argv[6] : "";
+            const int format = ranks ? 0 : ext == ".sc16" || arg6 == "sc16" ? 1 : ext == ".sc8" || ext == ".cs8" || arg6 == "sc8" ? 2 : ext == ".cu8" || arg6 == "cu8" ? 3 : 0;   // AMPS_RECC_SAMPLES_*
+            const size_t item = format == 0 ? 8 : format == 1 ? 4 : 2;   // bytes per wideband sample
             bool power = false;
             for (int i = 6; !ranks && i < argc && i < 9; i++) power = power || std::string(argv[i]) == "power";
             auto src = ranks ? gr::amps::recc_wideband::make(832, 96, -1, nranks, rank)
-                             : wide_channels != 1024 ? gr::amps::recc_wideband::make(wide_channels, 0, argc > 4 ? std::atoi(argv[4]) : -1, 0, 0, argc > 5 ? std::atoi(argv[5]) : 0, sc16, power, wide_channels)
-                             : gr::amps::recc_wideband::make(832, 96, argc > 4 ? std::atoi(argv[4]) : -1, 0, 0, argc > 5 ? std::atoi(argv[5]) : 0, sc16, power);
+                             : wide_channels != 1024 ? gr::amps::recc_wideband::make(wide_channels, 0, argc > 4 ? std::atoi(argv[4]) : -1, 0, 0, argc > 5 ? std::atoi(argv[5]) : 0, false, power, wide_channels, format)
+                             : gr::amps::recc_wideband::make(832, 96, argc > 4 ? std::atoi(argv[4]) : -1, 0, 0, argc > 5 ? std::atoi(argv[5]) : 0, false, power, 1024, format);
             if (ranks) {
                 // the control plane is the application's: here, a file
                 std::string id;
@@ -252,6 +256,8 @@ int main(int argc, char **argv)
             gr::msg_connect(src, "bursts", dm, "bursts");
             if (power) gr::msg_connect(src, "power", dm, "power");
             std::vector<char> tail((size_t)64 * 768 * item, 0);       // silence: flushes the frames the fused form holds back (64 frames of at most 768 samples)
+            if (format == 3)                                          // cu8 has no zero: (127, 128), (128, 127), ... = -+0.5, half a step either side of it
+                for (size_t i = 0; i < tail.size(); i++) tail[i] = (char)(127 + (((i >> 1) ^ i) & 1));
             data.resize(data.size() / item * item);
             data.insert(data.end(), tail.begin(), tail.end());
             const size_t ns = data.size() / item;

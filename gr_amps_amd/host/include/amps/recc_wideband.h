@@ -8,7 +8,7 @@
 //                 "power"   (blocks made with channel_power = true only) pmt::cons(from_long(channel), blob(8)) for every record, behind its
 //                           "records" message: the 8 bytes are { float mean_power; uint32_t n_snaps; } in host byte order, as
 //                           amps_recc_burst_power returns them -- the mean |filter-bank output|^2 of the record's channel over its capture
-//                           (linear, unscaled: 1.0 for a mobile at full scale of an fc32 stream, int16 units squared behind short_input) and
+//                           (linear, unscaled: 1.0 for a mobile at full scale of an fc32 stream, the input's own units squared behind an integer format) and
 //                           the number of power snapshots averaged (26 / 27 at decim 768, 39 / 40 at 512; 0 with power 0.0 if the handle no
 //                           longer held them).  The block drains after every push, so every record is covered.
 // With channels = 512, 256 or 128 the input is a stream at channels x 30 kHz = 15.36, 7.68 or 3.84 Msps -- what one SDR delivers -- through
@@ -39,8 +39,13 @@ public:
     // channel_power: keep per-channel received power (AMPS_RECC_FLAG_CHANNEL_POWER) and publish every record's burst power on "power"
     // channels: branches of the filter bank = 30 kHz channels across the stream: 1024, or 512, 256, 128 (n_channels <= channels, first_bin <
     //         channels; decim = channels / 2 or 3 channels / 4, 0 = the latter; groups and set_rccl belong to 1024)
+    // input_format: AMPS_RECC_SAMPLES_* of include/amps_recc.h.  0 = one gr_complex per item (or two shorts behind short_input = true,
+    //         which keeps meaning format 1); 1 (sc16) = two shorts; 2 (sc8) = two signed bytes, what a HackRF streams at 3.84 to
+    //         15.36 Msps; 3 (cu8) = two offset-binary bytes.  Items of 8, 4, 2 and 2 bytes, pushed as they are
+    //         (amps_recc_push_wideband_as: no float copy on the host).  A non-zero input_format other than 1 together with
+    //         short_input = true throws, as does an unknown format; set_rccl is refused on every integer format.
     static sptr make(int n_channels = 832, int first_bin = 96, int slicer = -1, int groups = 0, int group = 0, int decim = 0, bool short_input = false,
-                     bool channel_power = false, int channels = 1024);
+                     bool channel_power = false, int channels = 1024, int input_format = 0);
     // Let ONE rank own the stream: after this call (a collective over all `nranks` blocks; `id` = the 128 bytes one of them got from
     // rccl_unique_id(), carried between the processes by the application) work() distributes rank `root`'s input over xGMI with RCCL
     // inside amps_recc_push_wideband_dist (mode 0 = flat broadcast, 1 = scatter + all-gather: AMPS_RECC_DIST_*).  The other ranks'

@@ -21,15 +21,30 @@ class recc_wideband_impl : public recc_wideband {
     int d_root = 0, d_rank = 0, d_mode = AMPS_RECC_DIST_BROADCAST;
     unsigned long long d_stream_samples = 0, d_paced_items = 0;   // non-root ranks: samples the root has distributed / items this rank's pacing input has offered
     bool d_ended = false;                          // the root's end of stream has been sent (root) / seen (the others)
-    bool d_short = false;                          // items are two shorts (interleaved 16-bit I/Q, "sc16"): amps_recc_push_wideband_short
+    int d_format = AMPS_RECC_SAMPLES_FC32;         // AMPS_RECC_SAMPLES_* of the items: one gr_complex, two shorts ("sc16") or two bytes ("sc8", "cu8")
     bool d_power = false;                          // AMPS_RECC_FLAG_CHANNEL_POWER: every record's burst power goes out on "power"
     std::vector<float> d_pow;
     std::vector<uint32_t> d_nsnap;
 
 public:
-    recc_wideband_impl(int C, int first_bin, int slicer, int groups, int group, int decim, bool short_input, bool channel_power, int channels)
-        : gr::sync_block("recc_wideband", gr::io_signature::make(1, 1, short_input ? 2 * sizeof(short) : 2 * sizeof(float)), gr::io_signature::make(0, 0, 0)),
-          d_handle(nullptr), d_recs(kMaxRecs), d_bursts((size_t)kMaxRecs * AMPS_RECC_CAPTURE_SYMS), d_short(short_input), d_power(channel_power),
+    // bytes of one item of a format; 0: no such format
+    static size_t item_size(int format)
+    {
+        return format == AMPS_RECC_SAMPLES_FC32 ? 2 * sizeof(float) : format == AMPS_RECC_SAMPLES_SC16 ? 2 * sizeof(short)
+             : format == AMPS_RECC_SAMPLES_SC8 || format == AMPS_RECC_SAMPLES_CU8 ? 2 : 0;
+    }
+    // short_input = true keeps meaning format 1; it contradicts every other non-zero format
+    static int checked_format(bool short_input, int input_format)
+    {
+        if (!item_size(input_format)) throw std::runtime_error("amps::recc_wideband: input_format must be 0 (fc32), 1 (sc16), 2 (sc8) or 3 (cu8)");
+        if (short_input && input_format != AMPS_RECC_SAMPLES_FC32 && input_format != AMPS_RECC_SAMPLES_SC16)
+            throw std::runtime_error("amps::recc_wideband: short_input means input_format 1 (sc16)");
+        return short_input ? AMPS_RECC_SAMPLES_SC16 : input_format;
+    }
+
+    recc_wideband_impl(int C, int first_bin, int slicer, int groups, int group, int decim, bool short_input, bool channel_power, int channels, int input_format)
+        : gr::sync_block("recc_wideband", gr::io_signature::make(1, 1, (int)item_size(checked_format(short_input, input_format))), gr::io_signature::make(0, 0, 0)),
+          d_handle(nullptr), d_recs(kMaxRecs), d_bursts((size_t)kMaxRecs * AMPS_RECC_CAPTURE_SYMS), d_format(checked_format(short_input, input_format)), d_power(channel_power),
           d_pow(channel_power ? kMaxRecs : 0), d_nsnap(channel_power ? kMaxRecs : 0)
     {
         amps_recc_cfg_t cfg = {};
@@ -60,8 +75,8 @@ public:
 
     void set_rccl(const std::string &id, int nranks, int rank, int root, int mode)
     {
-        // (the blocks RCCL carries are fc32: amps_recc_push_wideband_dist has no 16-bit form)
-        if (d_short) throw std::runtime_error("amps::recc_wideband: set_rccl is not available on a block with 16-bit input; distribute an fc32 stream");
+        // (the blocks RCCL carries are fc32: amps_recc_push_wideband_dist has no integer form)
+        if (d_format != AMPS_RECC_SAMPLES_FC32) throw std::runtime_error("amps::recc_wideband: set_rccl is not available on a block with 16-bit or 8-bit input; distribute an fc32 stream");
         if (id.size() != AMPS_RECC_RCCL_ID_BYTES) throw std::runtime_error("amps::recc_wideband: the RCCL id is 128 bytes");
         if (mode != AMPS_RECC_DIST_BROADCAST && mode != AMPS_RECC_DIST_SCATTER_ALLGATHER) throw std::runtime_error("amps::recc_wideband: unknown distribution mode");
         int rc = amps_recc_rccl_init(d_handle, (const uint8_t *)id.data(), nranks, rank);
@@ -81,8 +96,7 @@ public:
             const bool root = d_rank == d_root;
             rc = amps_recc_push_wideband_dist(d_handle, root ? (const float *)in : nullptr, root ? n : 0, AMPS_MEM_HOST, d_root, d_mode, &pushed);
             d_stream_samples += pushed;
-        } else if (d_short) rc = amps_recc_push_wideband_short(d_handle, (const int16_t *)in, n, AMPS_MEM_HOST);
-        else rc = amps_recc_push_wideband(d_handle, (const float *)in, n, AMPS_MEM_HOST);
+        } else rc = amps_recc_push_wideband_as(d_handle, in, n, d_format, AMPS_MEM_HOST);
         if (rc == -ENODATA) { d_ended = true; return false; }   // the root's stream has ended: a clean WORK_DONE, the communicator is left alone
         if (rc != 0) { std::fprintf(stderr, "amps::recc_wideband: %s\n", amps_recc_strerror(rc)); return leave(); }
         if (!recc_drain_and_publish(*this, "recc_wideband", true, d_handle, d_recs.data(), d_bursts.data(), kMaxRecs, d_power ? d_pow.data() : nullptr,
@@ -111,7 +125,7 @@ public:
     int work(int noutput_items, gr_vector_const_void_star &input_items, gr_vector_void_star &)
     {
         const char *in = (const char *)input_items[0];
-        const size_t item = d_short ? 2 * sizeof(short) : 2 * sizeof(float);
+        const size_t item = item_size(d_format);
         if (d_bcast && d_rank != d_root) {
             // A non-root rank: its items are pacing only.  The ranks stay in step by STREAM POSITION, not by call or item counts (which
             // the schedulers of different processes do not share): this rank joins collectives -- each of whatever size the root
@@ -134,9 +148,9 @@ public:
     }
 };
 
-recc_wideband::sptr recc_wideband::make(int n_channels, int first_bin, int slicer, int groups, int group, int decim, bool short_input, bool channel_power, int channels)
+recc_wideband::sptr recc_wideband::make(int n_channels, int first_bin, int slicer, int groups, int group, int decim, bool short_input, bool channel_power, int channels, int input_format)
 {
-    return gnuradio::get_initial_sptr(new recc_wideband_impl(n_channels, first_bin, slicer, groups, group, decim, short_input, channel_power, channels));
+    return gnuradio::get_initial_sptr(new recc_wideband_impl(n_channels, first_bin, slicer, groups, group, decim, short_input, channel_power, channels, input_format));
 }
 
 std::string recc_wideband::rccl_unique_id()

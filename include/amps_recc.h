@@ -61,7 +61,9 @@ extern "C" {
                                      still 4, a flag and one entry point added and nothing changed: AMPS_RECC_FLAG_STREAM_OFFSET_UNIT, the
                                      unit-amplitude statistic behind the same three entry points, and amps_recc_retune_xlate;
                                      still 4, one entry point added and nothing changed: amps_recc_wideband_plan, with cfg.wideband_channels = 512,
-                                     256 and 128, the wideband seam at 15.36, 7.68 and 3.84 Msps) */
+                                     256 and 128, the wideband seam at 15.36, 7.68 and 3.84 Msps;
+                                     still 4, two entry points added and nothing changed: amps_recc_push_wideband_as / _debug_channelize_as, the
+                                     wideband seam on 8-bit I/Q (sc8, cu8), read in place on every bank) */
 
 /* protocol constants of the reference */
 #define AMPS_RECC_TRIGGER_SYMS 74   /* lib/recc_impl.cc:76-77: 37 bits x 2 Manchester symbols   */
@@ -319,7 +321,8 @@ int amps_recc_push_wideband(amps_recc_t *h, const float *iq, size_t nsamp, int m
  * 4-byte aligned (a slice that starts at an odd sample is legal).  The fused filter bank reads the 16-bit block in place, 4 bytes
  * per sample from the host and from HBM; no fc32 copy of it exists (the checking form AMPS_RECC_FLAG_UNFUSED_WIDEBAND expands it first).
  * Not offered in 16 bits: amps_recc_push_wideband_dist / _bcast (the blocks RCCL carries stay fc32) and the IQ seam, whose callers have
- * already filtered in float.  The translate seams take 16-bit and 8-bit samples through their _as entry points (AMPS_RECC_SAMPLES_*). */
+ * already filtered in float.  The translate seams take 16-bit and 8-bit samples through their _as entry points (AMPS_RECC_SAMPLES_*),
+ * and so does this seam: amps_recc_push_wideband_as below. */
 int amps_recc_push_wideband_short(amps_recc_t *h, const int16_t *iq, size_t nsamp, int mem);
 
 /* translate seam: the channel filter the reference's test flow graph wires in front of the
@@ -468,11 +471,31 @@ int amps_recc_xlate_resample_plan(double rate_hz, double width_hz, amps_recc_res
  * copy of it exists on the host or on the device.
  * No scaling and no DC removal are offered: the stage is linear, so the filter's `gain` is the place for a scale, and a tuner's DC
  * lands on centre 0, where no control channel sits.
- * Not offered in integer formats: amps_recc_push_iq, 8-bit input on the wideband seam, the distributed pushes. */
+ * Not offered in integer formats: amps_recc_push_iq (its callers have already filtered in float) and the distributed pushes
+ * amps_recc_push_wideband_dist / _bcast (the blocks RCCL carries stay fc32). */
 int amps_recc_push_raw_shared_as(amps_recc_t *h, const void *iq, size_t nsamp, int format, int mem);
 int amps_recc_push_raw_as(amps_recc_t *h, const void *iq, size_t ld, size_t nsamp, int format, int mem);
 int amps_recc_debug_xlate_shared_as(amps_recc_t *h, const void *iq, size_t nsamp, int format, int mem, float *out, size_t out_ld, size_t *nout);
 int amps_recc_debug_xlate_as(amps_recc_t *h, const void *iq, size_t ld, size_t nsamp, int format, int mem, float *out, size_t out_ld, size_t *nout);
+
+/* wideband seam on an SDR's integer samples, read IN PLACE on every bank: a HackRF streams 3.84 to 15.36 Msps as sc8 and nothing else.
+ * DEFINITION.  Each _as call is the fc32 call of the same name (amps_recc_push_wideband, amps_recc_debug_channelize) on the block
+ * converted by the plain AMPS_RECC_SAMPLES_* conversion above, no scaling (cu8: minus 127.5).  Every conversion is exact in binary32,
+ * so the result is the same stream, the same fc32 carry, the same output bits from the filter bank, the same records, the same power
+ * and autocorrelation rings and the same error codes: -EINVAL, -ENOSYS on a handle without the wideband seam, -E2BIG with nothing
+ * consumed, -ESTALE; nsamp == 0 returns 0 from the push.  format == AMPS_RECC_SAMPLES_FC32 IS amps_recc_push_wideband,
+ * AMPS_RECC_SAMPLES_SC16 IS amps_recc_push_wideband_short; an unknown format is -EINVAL.  Formats may alternate push by push on one
+ * handle, with each other and with the two existing entry points.  nsamp counts SAMPLES, whatever their size.  A device block need
+ * only be aligned to one sample: 2 bytes for sc8 and cu8 (a slice that starts at an odd sample is legal), and the kernels touch no
+ * aligned dword that holds no byte of it.  A host block is staged as it is, at 2 bytes per sample; ownership is as for the fc32 call.
+ * The banks of 512, 256 and 128 branches read the 8-bit block in place, 2 bytes per sample over the host link and from HBM; no fc32
+ * copy of it exists.  The 1024 bank (30.72 Msps: no radio delivers 8 bits there, converted capture files do) expands an 8-bit block
+ * to fc32 on the device first and then runs as on any fc32 block, in every form it has.
+ * Received power (amps_recc_channel_power / _burst_power) reads in the input's own units squared.  No scaling is offered: the bank
+ * is linear and no slicer's decision depends on scale. */
+int amps_recc_push_wideband_as(amps_recc_t *h, const void *iq, size_t nsamp, int format, int mem);
+int amps_recc_debug_channelize_as(amps_recc_t *h, const void *iq, size_t nsamp, int format, int mem,
+                                  float *out, size_t out_ld, size_t *nframes);
 
 /* Retune: replace the centres of the translate form configured last (amps_recc_set_xlate, _set_xlate_shared or _set_xlate_resampled)
  * in mid-stream.  Taps, carry, absolute positions, the decimation or L / M and everything behind the stage are kept; nothing is

@@ -1,11 +1,13 @@
 """What the narrow filter banks cost: the wideband seam at M = 512, 256, 128 branches (15.36, 7.68, 3.84 Msps), D = M / 2 and 3 M / 4,
-on fc32 and on sc16 blocks, beside the two-kernel form of the 1024 bank (AMPS_RECC_FLAG_UNFUSED_WIDEBAND, all 1024 bins) as the
+on fc32, sc16 and sc8 blocks (the same noise in each format), beside the two-kernel form of the 1024 bank (AMPS_RECC_FLAG_UNFUSED_WIDEBAND, all 1024 bins) as the
 yardstick per input sample -- all in ONE process, because boxes differ by up to 12 %.
 
 Per geometry one second of stream (M x 30 000 samples, rounded up to whole pushes) is pushed from a device-resident block of 2^22
 samples of noise, every bin a channel, spec D.  Times come from amps_recc_get_timing in timing mode "all": ms_channelizer is the
 filter-bank kernel, the step is the sum of every kernel the push launches (filter bank, streaming kernel, resolve, carry, decode).
-The legs alternate: yardstick, the twelve narrow legs, yardstick again, `rounds` times; the table holds each leg's median over the rounds.
+The legs alternate: yardstick, then per geometry fc32, sc16, sc8 and the same three again (legs A and B: what two legs of one format
+differ by is the noise a difference between formats has to exceed), yardstick again, `rounds` times; the table holds each leg's median
+over the rounds.
 
 usage (GPU box):  python scripts/bench_narrow_bank.py [rounds = 3]
 prints a table; numbers from different jobs do not compare."""
@@ -27,7 +29,9 @@ g = torch.Generator(device=dev)
 g.manual_seed(5)
 block_f = torch.view_as_complex(torch.randn((PUSH, 2), generator=g, device=dev, dtype=torch.float32).contiguous())
 block_s = torch.round(torch.view_as_real(block_f) * 4000.0).clamp(-32000, 32000).to(torch.int16).contiguous()
+block_b = torch.round(torch.view_as_real(block_f) * 30.0).clamp(-127, 127).to(torch.int8).contiguous()
 torch.cuda.synchronize()
+FORMATS = {"fc32": (capi.SAMPLES_FC32, block_f), "sc16": (capi.SAMPLES_SC16, block_s), "sc8": (capi.SAMPLES_SC8, block_b)}
 
 
 def handle(M, D, unfused=False):
@@ -37,9 +41,10 @@ def handle(M, D, unfused=False):
     return r
 
 
-def leg(r, short, npush):
+def leg(r, fmt, npush):
     """(ms_channelizer per push, step ms per push) over npush pushes behind two of warm-up"""
-    push, block = (r.push_wideband_short, block_s) if short else (r.push_wideband, block_f)
+    format, block = FORMATS[fmt]
+    push = lambda b: r.push_wideband_as(b, format)
     for _ in range(2):
         push(block)
     r.drain(copy=False)
@@ -51,16 +56,15 @@ def leg(r, short, npush):
     return t["ms_channelizer"] / npush, sum(t[k] for k in STEP_KEYS) / npush
 
 
-legs = [(1024, 768, False, True), (1024, 512, False, True)]
-legs += [(M, D, short, False) for M in (512, 256, 128) for D in (3 * M // 4, M // 2) for short in (False, True)]
-handles = {(M, D): handle(M, D, unfused) for M, D, short, unfused in legs if not short}
+yardstick = [(1024, 768, "fc32", "A"), (1024, 512, "fc32", "A")]
+legs = yardstick + [(M, D, fmt, ab) for M in (512, 256, 128) for D in (3 * M // 4, M // 2) for ab in "AB" for fmt in ("fc32", "sc16", "sc8")]
+legs += [(M, D, fmt, "B") for M, D, fmt, _ in yardstick]     # the yardstick first and last
+handles = {(M, D): handle(M, D, M == 1024) for M, D, fmt, ab in legs}
 results = {}
 for rnd in range(rounds):
-    order = legs + legs[:2]                                   # the yardstick first and last
-    for i, (M, D, short, unfused) in enumerate(order):
+    for M, D, fmt, ab in legs:
         npush = -(-M * 30000 // PUSH)
-        key = (M, D, short, "B" if i >= len(legs) else "A")
-        results.setdefault(key, []).append(leg(handles[(M, D)], short, npush))
+        results.setdefault((M, D, fmt, ab), []).append(leg(handles[(M, D)], fmt, npush))
 for h in handles.values():
     h.close()
 
@@ -68,9 +72,9 @@ print("rounds %d, pushes of 2^22 samples, every bin a channel, spec D; medians" 
 print("%-28s %7s %10s %10s %9s %9s %11s %11s" % ("leg", "pushes", "chz ms", "step ms", "chz Msps", "step Msps", "x real time", "ns/sample"))
 yard = {}
 for key in sorted(results, key=lambda k: (-k[0], -k[1], k[2], k[3])):
-    M, D, short, ab = key
+    M, D, fmt, ab = key
     chz, step = (float(np.median([v[i] for v in results[key]])) for i in (0, 1))
-    name = "M=%d D=%d %s%s" % (M, D, "sc16" if short else "fc32", (" unfused (%s)" % ab) if M == 1024 else "")
+    name = "M=%d D=%d %s %s" % (M, D, fmt, ("unfused (%s)" % ab) if M == 1024 else "(%s)" % ab)
     fs = M * 30e3
     print("%-28s %7d %10.4f %10.4f %9.0f %9.0f %11.0f %11.4f" % (name, -(-M * 30000 // PUSH), chz, step, PUSH / chz / 1e3, PUSH / step / 1e3,
                                                                  PUSH / step * 1e3 / fs, chz * 1e6 / PUSH))
