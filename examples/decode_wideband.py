@@ -8,7 +8,9 @@ AMPS band out (BASELINE configs[3]; replaces 832 x [freq_xlating_fir_filter_ccc 
                                                         # that many branches, every bin a channel.  Bin channels / 2 sits on +- fs / 2, where a
                                                         # real radio's anti-alias filter rolls off: expect less of a mobile there than here
     python examples/decode_wideband.py --channels 128 --sc8   # ... as a HackRF delivers it: interleaved int8 I/Q at a full scale of 100, pushed
-                                                              # as it is (2 bytes per sample); meaningful with --channels 512, 256 or 128
+                                                              # as it is (2 bytes per sample); meaningful with --channels below 1024
+    python examples/decode_wideband.py --channels 500 [--sc8] # a radio on a 100 MHz clock: a 5 Msps stream (or 1000: 10, 2000: 20, 2500: 25 Msps)
+                                                              # through the bank of that many branches of 10 kHz, a channel on every third bin
 """
 import os
 import sys
@@ -19,11 +21,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gr_amps_amd import capi, synth_wideband as sw
 
 BANK = int(sys.argv[sys.argv.index("--channels") + 1]) if "--channels" in sys.argv[1:] else 1024   # branches of the filter bank: fs = BANK x 30 kHz
-FIRST_BIN, CHANNELS = (96, 832) if BANK == 1024 else (0, BANK)   # the band selection: FFT bins 96 .. 927 of the 1024-branch filter bank, or every bin of a narrow one
-NSAMP = 12 * (1 << 20) * BANK // 1024             # 0.41 s of signal
+GRID10 = BANK in capi.GRID10_CHANNELS             # ... or BANK x 10 kHz: bins of 10 kHz, a channel on every third one, 40 ksps per channel
+BIN_HZ, STRIDE = (10e3, 3) if GRID10 else (30e3, 1)
+FIRST_BIN, CHANNELS = (96, 832) if BANK == 1024 else (0, BANK // STRIDE)   # the band selection: FFT bins 96 .. 927 of the 1024-branch filter bank, or every channel of a smaller one
+FS = BANK * BIN_HZ
+NSAMP = 12 * (1 << 20) * BANK // (1024 * STRIDE)  # 0.41 s of signal
 rng = np.random.default_rng(7)
-plan = [(FIRST_BIN + int(c), int(rng.integers(4000, NSAMP - 3456 * 3 * BANK // 2 - 4000))) for c in rng.choice(CHANNELS, 12, replace=False)]
-x, truth = sw.make_wideband(NSAMP, plan, seed=7, snr_db=20.0, sym_ppm=50.0, fs=BANK * 30e3, bins=BANK)   # every mobile 50 ppm off the nominal bit clock
+plan = [((FIRST_BIN + STRIDE * int(c)) % BANK, int(rng.integers(4000, NSAMP - 3456 * int(FS) // 20000 - 4000))) for c in rng.choice(CHANNELS, 12, replace=False)]
+x, truth = sw.make_wideband(NSAMP, plan, seed=7, snr_db=20.0, sym_ppm=50.0, fs=FS, bins=BANK)   # every mobile 50 ppm off the nominal bit clock
 
 SC16 = "--sc16" in sys.argv[1:]
 if SC16:                                          # full scale for the loudest sample, a power of two; no slicer decision depends on the scale
@@ -34,8 +39,10 @@ if SC8:                                           # the loudest sample at 100 of
     x = np.rint(np.stack([x.real, x.imag], axis=1) * (100.0 / max(np.abs(x.real).max(), np.abs(x.imag).max()))).astype(np.int8)   # [n, 2]: 2 bytes per sample
 
 try:
-    rx = capi.Recc(n_channels=CHANNELS, max_samples=NSAMP // (BANK // 2) + 72, max_bursts=256,
-                   wideband={"channels": BANK, "first_channel": FIRST_BIN})     # decimation: the library default (3/4 of the branches: 40 ksps per channel)
+    wideband = {"channels": BANK, "first_channel": FIRST_BIN}                   # decimation: the library default (3/4 of the branches: 40 ksps per channel)
+    if GRID10:
+        wideband["decim"] = BANK // 4                                            # ... which the banks of 10 kHz bins want stated: 40 ksps per channel too
+    rx = capi.Recc(n_channels=CHANNELS, max_samples=NSAMP // (BANK // 4 if GRID10 else BANK // 2) + 72, max_bursts=256, wideband=wideband)
 except capi.AmpsError as e:
     sys.exit("no MI355X here (%s): the library has no CPU fallback" % e)
 with rx:
@@ -48,7 +55,7 @@ with rx:
             (rx.push_wideband_short if SC16 else rx.push_wideband)(x[pos:pos + n])
         pos += n
     recs = rx.drain()
-sent = {k - FIRST_BIN: v[1] for (k, _), v in truth.items()}
+sent = {(k - FIRST_BIN) % BANK // STRIDE: v[1] for (k, _), v in truth.items()}
 print("%d bursts sent, %d decoded" % (len(sent), len(recs)))
 for r in recs:
     ch, got = int(r["channel"]), r["min"].decode()

@@ -98,6 +98,11 @@ class WidebandPlan(C.Structure):
     _fields_ = [("channels", C.c_uint32), ("decim", C.c_uint32), ("samples_per_symbol", C.c_uint32), ("taps", C.c_uint32)]
 
 
+class WidebandGridPlan(C.Structure):
+    _fields_ = [("channels", C.c_uint32), ("decim", C.c_uint32), ("samples_per_symbol", C.c_uint32), ("taps", C.c_uint32),
+                ("bin_hz", C.c_uint32), ("channel_stride", C.c_uint32), ("max_channels", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class XlateResampleCfg(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("interp", C.c_uint32), ("decim", C.c_uint32), ("n_centers", C.c_uint32), ("_pad", C.c_uint32),
@@ -152,9 +157,10 @@ EXPORTS = (
     "amps_recc_set_xlate_resampled", "amps_recc_xlate_resample_plan",
     "amps_recc_channel_autocorr", "amps_recc_burst_autocorr", "amps_recc_burst_offset",
     "amps_recc_retune_xlate",
-    "amps_recc_wideband_plan",
+    "amps_recc_wideband_plan", "amps_recc_wideband_grid_plan",
     "amps_recc_push_wideband_as", "amps_recc_debug_channelize_as",
 )
+GRID10_CHANNELS = (2500, 2000, 1000, 500)   # branches of the wideband seam's banks of 10 kHz bins: 25, 20, 10 and 5 Msps
 _WIDEBAND_AS = ("amps_recc_push_wideband_as", "amps_recc_debug_channelize_as")
 _XLATE_RESAMPLED = ("amps_recc_set_xlate_resampled", "amps_recc_xlate_resample_plan")
 _XLATE_AS = ("amps_recc_push_raw_shared_as", "amps_recc_push_raw_as", "amps_recc_debug_xlate_shared_as", "amps_recc_debug_xlate_as")
@@ -263,6 +269,8 @@ def load():
         L.amps_recc_xlate_resample_plan.argtypes = [C.c_double, C.c_double, C.POINTER(ResamplePlan), C.c_size_t]
     if hasattr(L, "amps_recc_wideband_plan"):         # absent only from A/B builds of earlier revisions (AMPS_RECC_LIB)
         L.amps_recc_wideband_plan.argtypes = [C.c_double, C.POINTER(WidebandPlan), C.c_size_t]
+    if hasattr(L, "amps_recc_wideband_grid_plan"):    # likewise
+        L.amps_recc_wideband_grid_plan.argtypes = [C.c_double, C.POINTER(WidebandGridPlan), C.c_size_t]
     if hasattr(L, "amps_recc_push_wideband_as"):      # absent only from A/B builds of earlier revisions (AMPS_RECC_LIB)
         L.amps_recc_push_wideband_as.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int]
         L.amps_recc_debug_channelize_as.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
@@ -271,7 +279,7 @@ def load():
     for name in EXPORTS:
         if name in ("amps_recc_default_slicer", "amps_recc_default_wideband_decim", "amps_recc_debug_exact_slice", "amps_recc_rccl_unique_id", "amps_recc_rccl_init",
                     "amps_recc_push_wideband_bcast", "amps_recc_drain_gather", "amps_recc_debug_slicer_bits",
-                    "amps_recc_push_wideband_short", "amps_recc_xlate_shared_plan", "amps_recc_wideband_plan") + _NEW_IN_ABI4 + _POWER + _OFFSET + _RETUNE + _XLATE_SHARED + _XLATE_AS + _XLATE_RESAMPLED + _WIDEBAND_AS and not hasattr(L, name):
+                    "amps_recc_push_wideband_short", "amps_recc_xlate_shared_plan", "amps_recc_wideband_plan", "amps_recc_wideband_grid_plan") + _NEW_IN_ABI4 + _POWER + _OFFSET + _RETUNE + _XLATE_SHARED + _XLATE_AS + _XLATE_RESAMPLED + _WIDEBAND_AS and not hasattr(L, name):
             continue
         if name not in ("amps_recc_strerror", "amps_recc_burst_size", "amps_recc_destroy"):   # every other entry point returns int
             getattr(L, name).restype = C.c_uint32 if name == "amps_recc_power_ring_snaps" else C.c_int
@@ -379,6 +387,12 @@ class Recc:
             # "decim" absent / 0 = the library default (3/4 of the channels at the narrow banks: the same ratio); the samples per symbol
             # follow the decimation unless they are given
             wideband = dict(wideband)
+            # the banks of 10 kHz bins (GRID10_CHANNELS at decim = channels / 4, which has to be stated): two samples per symbol, three
+            # taps per branch.  Without a decim they are filled in like any other size below 1024, and the library refuses the result
+            if int(wideband["channels"]) in GRID10_CHANNELS and 4 * int(wideband.get("decim") or 0) == int(wideband["channels"]):
+                wideband.setdefault("taps_per_branch", 3)
+                if sps is None:
+                    sps = 2
             if not wideband.get("decim"):
                 if int(wideband["channels"]) < 1024:
                     wideband["decim"] = 3 * int(wideband["channels"]) // 4
@@ -1061,6 +1075,20 @@ def wideband_plan(rate_hz):
     out = (WidebandPlan * max(n, 1))()
     n = L.amps_recc_wideband_plan(rate_hz, out, n)
     return [(int(p.channels), int(p.decim), int(p.samples_per_symbol), int(p.taps)) for p in out[:n]]
+
+
+def wideband_grid_plan(rate_hz):
+    """wideband_plan for every bank the seam has: (channels, decim, sps, taps, bin_hz, channel_stride, max_channels) per entry.  The
+    entries of wideband_plan with (30000, 1, channels) behind them, and for 25, 20, 10 and 5 Msps the bank of rate / 10 kHz branches:
+    10e6 -> [(1000, 250, 2, 3000, 10000, 3, 333)], for Recc(wideband={"channels": 1000, "decim": 250}), a channel on every third
+    bin.  Needs no GPU (amps_recc_wideband_grid_plan)."""
+    L = load()
+    n = L.amps_recc_wideband_grid_plan(rate_hz, None, 0)
+    if n < 0:
+        raise AmpsError(n, "amps_recc_wideband_grid_plan")
+    out = (WidebandGridPlan * max(n, 1))()
+    n = L.amps_recc_wideband_grid_plan(rate_hz, out, n)
+    return [(int(p.channels), int(p.decim), int(p.samples_per_symbol), int(p.taps), int(p.bin_hz), int(p.channel_stride), int(p.max_channels)) for p in out[:n]]
 
 
 def resample_plan(rate_hz, width_hz=0.0):

@@ -161,10 +161,11 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
     if (cfg_in->struct_size != sizeof(amps_recc_cfg_t)) return -EINVAL;
     amps_recc_cfg_t cfg_v = *cfg_in;                                  // wideband handles: decimation 0 = the library default, samples per symbol 0 = what goes with it
     const bool narrow = chz_is_narrow(cfg_v.wideband_channels);       // the banks of 512, 256 and 128 branches: the library's default ratio D = 3 M / 4
+    const bool grid10 = chz_is_grid10(cfg_v.wideband_channels);       // the banks of 2500, 2000, 1000 and 500 branches of 10 kHz: D = M / 4, stated by the caller
     if (cfg_v.wideband_channels) {
-        if (cfg_v.wideband_decim == 0) cfg_v.wideband_decim = narrow ? 3u * cfg_v.wideband_channels / 4u : amps_recc_default_wideband_decim();
+        if (cfg_v.wideband_decim == 0 && !grid10) cfg_v.wideband_decim = narrow ? 3u * cfg_v.wideband_channels / 4u : amps_recc_default_wideband_decim();
         if (!chz_geometry_ok(cfg_v.wideband_channels, cfg_v.wideband_decim)) return -EINVAL;
-        if (cfg_v.samples_per_symbol == 0) cfg_v.samples_per_symbol = 3u * cfg_v.wideband_channels / (2u * cfg_v.wideband_decim);
+        if (cfg_v.samples_per_symbol == 0) cfg_v.samples_per_symbol = grid10 ? 2u : 3u * cfg_v.wideband_channels / (2u * cfg_v.wideband_decim);
     }
     const amps_recc_cfg_t *cfg = &cfg_v;
     if (cfg->n_channels < 1 || cfg->max_bursts < 1) return -EINVAL;
@@ -172,7 +173,8 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
     // 40 ksps = 2 at D = 3 M / 4; the bit-domain kernels behind it are built for exactly those.  Two samples per symbol exist on the wideband
     // seam only: the streaming kernel has the instantiation (recc_front_kernel<2, ...>), reached by the two-kernel form -- the unfused 1024
     // bank at D = 768 and every narrow bank at D = 3 M / 4, its default ratio -- and sps_supported refuses it to a handle of the IQ seam.
-    const bool wide768 = cfg->wideband_channels && 4u * cfg->wideband_decim == 3u * cfg->wideband_channels;
+    // The banks of 10 kHz bins (M x 10 ksps, D = M / 4) deliver the same 40 ksps.
+    const bool wide768 = cfg->wideband_channels && (grid10 || 4u * cfg->wideband_decim == 3u * cfg->wideband_channels);
     if (cfg->max_samples_per_push && !(wide768 ? cfg->samples_per_symbol == 2 : sps_supported(cfg->samples_per_symbol))) return -EINVAL;
     if (cfg->wideband_channels && (cfg->samples_per_symbol != (wide768 ? 2u : 3u) || cfg->max_samples_per_push == 0)) return -EINVAL;
     if (cfg->sync_tolerance > AMPS_RECC_MAX_SYNC_TOLERANCE) return -EINVAL;
@@ -180,16 +182,19 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
     if (sl & (sl - 1)) return -EINVAL;                             // at most one slicer spec
     if (cfg->n_channels >= (1u << (64 - CAPQ_POS_BITS))) return -EINVAL;
     // received power exists where the fused filter bank runs: the snapshot kernel re-reads that launch's block and carry
-    if ((cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER) && (!cfg->wideband_channels || narrow || (cfg->flags & AMPS_RECC_FLAG_UNFUSED_WIDEBAND))) return -EINVAL;
+    if ((cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER) && (!cfg->wideband_channels || narrow || grid10 || (cfg->flags & AMPS_RECC_FLAG_UNFUSED_WIDEBAND))) return -EINVAL;
     // the narrow banks are the two-kernel form: no channel groups, and what the other wideband_* fields may hold
     if (narrow && (cfg->wideband_groups > 1 || cfg->n_channels > cfg->wideband_channels || cfg->wideband_first_channel >= cfg->wideband_channels ||
                    (cfg->wideband_taps_per_branch != 0 && cfg->wideband_taps_per_branch != 8))) return -EINVAL;
+    // ... and so are the banks of 10 kHz bins: a channel on every third bin, three taps per branch
+    if (grid10 && (cfg->wideband_groups > 1 || 3ull * cfg->n_channels > cfg->wideband_channels || cfg->wideband_first_channel >= cfg->wideband_channels ||
+                   (cfg->wideband_taps_per_branch != 0 && cfg->wideband_taps_per_branch != (uint32_t)CHZ_GRID10_P))) return -EINVAL;
     // on the IQ and translate seams the channel-rate stream itself is read once more, for its power and for the carrier offset: flags
     // of their own, for handles with the IQ seam and no 1024 bank (a narrow bank's block goes through the IQ seam's streaming kernel,
     // which fills the rings there too).  Power combines with the offset in either statistic, and a handle keeps one offset ring with one of them
     constexpr uint32_t OFFSET_FLAGS = AMPS_RECC_FLAG_STREAM_OFFSET | AMPS_RECC_FLAG_STREAM_OFFSET_UNIT;
     if ((cfg->flags & (AMPS_RECC_FLAG_STREAM_POWER | OFFSET_FLAGS)) &&
-        ((cfg->wideband_channels && !narrow) || cfg->max_samples_per_push == 0 || (cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER))) return -EINVAL;
+        ((cfg->wideband_channels && !narrow && !grid10) || cfg->max_samples_per_push == 0 || (cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER))) return -EINVAL;
     if ((cfg->flags & OFFSET_FLAGS) == OFFSET_FLAGS) return -EINVAL;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return -ENODEV;
@@ -630,6 +635,24 @@ int amps_recc_wideband_plan(double rate_hz, amps_recc_wideband_plan_t *out, size
             if ((size_t)n < cap) out[n] = amps_recc_wideband_plan_t{ M, D, 3u * M / (2u * D), 8u * M };
             n++;
         }
+    }
+    return n;
+}
+
+int amps_recc_wideband_grid_plan(double rate_hz, amps_recc_wideband_grid_plan_t *out, size_t cap)
+{
+    if (!(rate_hz > 0.0) || std::isinf(rate_hz) || (cap && !out)) return -EINVAL;
+    // the banks of 30 kHz bins: what amps_recc_wideband_plan answers, a channel on every bin
+    amps_recc_wideband_plan_t old[4];
+    int n = amps_recc_wideband_plan(rate_hz, old, 4);
+    if (n < 0) return n;
+    for (int i = 0; i < n && i < 4; i++)
+        if ((size_t)i < cap) out[i] = amps_recc_wideband_grid_plan_t{ old[i].channels, old[i].decim, old[i].samples_per_symbol, old[i].taps, 30000u, 1u, old[i].channels, 0u };
+    // the banks of 10 kHz bins: M = rate / 10 kHz branches, D = M / 4, a channel on every third bin
+    for (uint32_t M : { 2500u, 2000u, 1000u, 500u }) {
+        if (std::fabs(rate_hz - CHZ_GRID10_BIN_HZ * M) > 0.5) continue;
+        if ((size_t)n < cap) out[n] = amps_recc_wideband_grid_plan_t{ M, M / 4u, 2u, (uint32_t)CHZ_GRID10_P * M, (uint32_t)CHZ_GRID10_BIN_HZ, (uint32_t)CHZ_GRID10_STRIDE, M / (uint32_t)CHZ_GRID10_STRIDE, 0u };
+        n++;
     }
     return n;
 }

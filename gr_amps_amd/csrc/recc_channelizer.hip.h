@@ -41,6 +41,7 @@
 #include "recc_chz_slicer.hip.h"
 #include "recc_power.hip.h"       // chz_power_launch: the power snapshots behind a fused launch
 #include "recc_chz_narrow.hip.h"  // the banks of 512, 256 and 128 branches: a kernel of their own behind the same state, carry and host code
+#include "recc_chz_grid10.hip.h"  // the banks of 2500, 2000, 1000 and 500 branches of 10 kHz (25, 20, 10 and 5 Msps): likewise
 
 namespace amps {
 
@@ -158,8 +159,8 @@ __global__ __launch_bounds__(768, 3) void chz12_short_kernel(ChzArgs a)
 struct ChannelizerState {
     bool enabled = false;
     int P = 8;
-    int M = CHZ_M;                  // branches: 1024 (chz12_kernel), or 512, 256, 128 (chz_narrow_kernel: the two-kernel form only)
-    int D = CHZ_D;                  // input samples per frame: M / 2 (3 samples per symbol) or 3 M / 4 (2)
+    int M = CHZ_M;                  // branches: 1024 (chz12_kernel), or 512, 256, 128 (chz_narrow_kernel) or 2500, 2000, 1000, 500 (chz_grid10_kernel): the two-kernel form only
+    int D = CHZ_D;                  // input samples per frame: M / 2 (3 samples per symbol) or 3 M / 4 (2); M / 4 (2) at the banks of 10 kHz bins
     uint32_t C = 0;                 // rows this handle decodes (= the band's channels, or one group of them)
     uint32_t groups = 1, group = 0; // cfg.wideband_groups / wideband_group
     DevBuf<uint16_t> bin2row;       // device [M]
@@ -186,14 +187,15 @@ inline double bessel_i0(double x)
     return s;
 }
 
-// Kaiser(beta = 8) windowed sinc at fs = M * 30 kHz, unit DC gain; -6 dB at 13 kHz behind the D = M / 2 bank, at 15 kHz behind the D = 3 M / 4 one
+// Kaiser(beta = 8) windowed sinc at fs = M * bin_hz (30 kHz; 10 kHz at the banks of recc_chz_grid10.hip.h), unit DC gain; -6 dB at 13 kHz behind the D = M / 2 bank, at 15 kHz behind the D = 3 M / 4 one
 // (40 ksps per channel leave the slicer two sampling phases per symbol instead of three: the wider pass band gives back, under a
 // carrier offset, what the coarser timing costs -- profiles/r06/decim768_cpu_gonogo.txt; oracle/channelizer.py: cutoff_for_decim)
-inline double chz_cutoff_hz(int D, int M = CHZ_M) { return 4 * D == 3 * M ? 15.0e3 : 13.0e3; }
-inline std::vector<float> chz_design_taps(int P, int D = CHZ_D, int M = CHZ_M)
+// The banks of 10 kHz bins (D = M / 4) deliver 40 ksps per channel too and take the same 15 kHz.
+inline double chz_cutoff_hz(int D, int M = CHZ_M) { return (4 * D == 3 * M || chz_grid10_geometry(M, D)) ? 15.0e3 : 13.0e3; }
+inline std::vector<float> chz_design_taps(int P, int D = CHZ_D, int M = CHZ_M, double bin_hz = 30.0e3)
 {
     const int L = P * M;
-    const double fc = chz_cutoff_hz(D, M) / (M * 30.0e3);       // cycles per sample
+    const double fc = chz_cutoff_hz(D, M) / (M * bin_hz);        // cycles per sample
     const double beta = 8.0, i0b = bessel_i0(beta);
     std::vector<double> h(L);
     double sum = 0.0;
@@ -232,23 +234,35 @@ inline void channelizer_destroy(ChannelizerState &z) { z = ChannelizerState(); }
 
 // the bank sizes of chz_narrow_kernel
 inline bool chz_is_narrow(uint32_t M) { return M == 512 || M == 256 || M == 128; }
-// The geometries the seam serves: M = 1024, 512, 256 or 128 branches at D = M / 2 or 3 M / 4 input samples per frame
-inline bool chz_geometry_ok(uint32_t M, uint32_t D) { return (M == (uint32_t)CHZ_M || chz_is_narrow(M)) && (2 * D == M || 4 * D == 3 * M); }
+// the bank sizes of chz_grid10_kernel: bins of 10 kHz, an AMPS channel on every third
+inline bool chz_is_grid10(uint32_t M) { return chz_grid10_size((int)M); }
+// what a bank of M branches is laid out for: the width of a bin, the bins from one channel to the next, the taps per branch
+inline double chz_bin_hz(uint32_t M) { return chz_is_grid10(M) ? CHZ_GRID10_BIN_HZ : 30.0e3; }
+inline uint32_t chz_channel_stride(uint32_t M) { return chz_is_grid10(M) ? (uint32_t)CHZ_GRID10_STRIDE : 1u; }
+inline uint32_t chz_taps_per_branch(uint32_t M) { return chz_is_grid10(M) ? (uint32_t)CHZ_GRID10_P : 8u; }
+// The geometries the seam serves: M = 1024, 512, 256 or 128 branches of 30 kHz at D = M / 2 or 3 M / 4 input samples per frame, and
+// M = 2500, 2000, 1000 or 500 branches of 10 kHz at D = M / 4
+inline bool chz_geometry_ok(uint32_t M, uint32_t D)
+{
+    if (chz_is_grid10(M)) return 4 * D == M;
+    return (M == (uint32_t)CHZ_M || chz_is_narrow(M)) && (2 * D == M || 4 * D == 3 * M);
+}
 
-// bins and rows of a handle: row i = the i-th channel (in band order) of the band selection [first, first + n) that belongs to the
-// handle's group -- all of them without groups.  Returns the row count, or a negative errno for an invalid split.
+// bins and rows of a handle: row i = the i-th channel (in band order) of the band selection -- n channels from bin `first` on, a bin
+// apart, or three on the banks of 10 kHz bins -- that belongs to the handle's group -- all of them without groups.  Returns the row count, or a negative errno for an invalid split.
 inline int chz_rows(const amps_recc_cfg_t &cfg, std::vector<uint16_t> *bin2row, std::vector<uint32_t> *row2chan)
 {
     const uint32_t G = cfg.wideband_groups > 1 ? cfg.wideband_groups : 1u;
-    const uint32_t M = chz_is_narrow(cfg.wideband_channels) ? cfg.wideband_channels : (uint32_t)CHZ_M;
+    const uint32_t M = chz_is_narrow(cfg.wideband_channels) || chz_is_grid10(cfg.wideband_channels) ? cfg.wideband_channels : (uint32_t)CHZ_M;
+    const uint32_t stride = chz_channel_stride(M);
     if ((G != 1 && G != 2 && G != 4 && G != 8) || cfg.wideband_group >= G) return -EINVAL;
-    if (cfg.n_channels > M || cfg.wideband_first_channel >= M) return -EINVAL;
+    if ((uint64_t)stride * cfg.n_channels > M || cfg.wideband_first_channel >= M) return -EINVAL;
     const uint32_t W = 64u / G;
     if (bin2row) bin2row->assign(M, (uint16_t)0xffffu);
     if (row2chan) row2chan->clear();
     uint32_t rows = 0;
     for (uint32_t c = 0; c < cfg.n_channels; c++) {
-        const uint32_t k = (cfg.wideband_first_channel + c) & (M - 1);
+        const uint32_t k = (cfg.wideband_first_channel + stride * c) % M;
         if ((k & 63u) / W != cfg.wideband_group) continue;
         if (bin2row) (*bin2row)[k] = (uint16_t)rows;
         if (row2chan) row2chan->push_back(c);
@@ -263,9 +277,9 @@ inline int channelizer_create(ChannelizerState &z, const amps_recc_cfg_t &cfg)
     const int M = (int)cfg.wideband_channels;
     const bool narrow = M != CHZ_M;
     if (narrow && cfg.wideband_groups > 1) return -EINVAL;         // channel groups exist in the fused form, which the narrow banks do not have
-    const int P = cfg.wideband_taps_per_branch ? (int)cfg.wideband_taps_per_branch : 8;
-    if (P != 8) return -EINVAL;                                   // the register ring of chz12_kernel is laid out for eight taps per branch, and so is chz_narrow_kernel's fold
-    if (cfg.n_channels > (uint32_t)M || cfg.wideband_first_channel >= (uint32_t)M || cfg.max_samples_per_push == 0) return -EINVAL;
+    const int P = cfg.wideband_taps_per_branch ? (int)cfg.wideband_taps_per_branch : (int)chz_taps_per_branch((uint32_t)M);
+    if (P != (int)chz_taps_per_branch((uint32_t)M)) return -EINVAL;   // the register ring of chz12_kernel is laid out for eight taps per branch, and so is chz_narrow_kernel's fold; chz_grid10_kernel's for three
+    if ((uint64_t)chz_channel_stride((uint32_t)M) * cfg.n_channels > (uint32_t)M || cfg.wideband_first_channel >= (uint32_t)M || cfg.max_samples_per_push == 0) return -EINVAL;
     std::vector<uint16_t> b2r;
     const int rows = chz_rows(cfg, &b2r, &z.row2chan);
     if (rows < 1) return rows < 0 ? rows : -EINVAL;
@@ -276,7 +290,7 @@ inline int channelizer_create(ChannelizerState &z, const amps_recc_cfg_t &cfg)
     z.max_frames = cfg.max_samples_per_push;
     z.ld = ((uint64_t)z.max_frames + 7) & ~7ull;
     const size_t L = (size_t)P * M;
-    std::vector<float> h = chz_design_taps(P, z.D, M);
+    std::vector<float> h = chz_design_taps(P, z.D, M, chz_bin_hz((uint32_t)M));
     if (z.taps.alloc(L)) return -ENOMEM;
     if (hipMemcpy(z.taps.get(), h.data(), sizeof(float) * L, hipMemcpyHostToDevice) != hipSuccess) return -EIO;
     if (z.carry[0].alloc(chz_carry_cap(P, z.D, M)) || z.carry[1].alloc(chz_carry_cap(P, z.D, M))) return -ENOMEM;
@@ -365,7 +379,7 @@ inline int channelizer_run(ChannelizerState &z, const ChzRunIn &in, hipStream_t 
     const uint32_t leftover = z.carry_len - hist;
     const uint64_t avail = (uint64_t)leftover + nsamp;
     // frames consumed: a multiple of two or four (a launch starts where the stream position is a multiple of M: frame parity 0 at
-    // D = M / 2, frame phase 0 of 4 at D = 3 M / 4), and in the fused form a multiple of 64 (whole words of the RECC bit ring); the rest waits in the carry
+    // D = M / 2, frame phase 0 of 4 at D = 3 M / 4 and at D = M / 4), and in the fused form a multiple of 64 (whole words of the RECC bit ring); the rest waits in the carry
     const uint32_t nframes = (uint32_t)(avail / (uint32_t)z.D) & (fused ? ~63u : 2 * z.D == z.M ? ~1u : ~3u);
     if (nframes > z.max_frames) return -E2BIG;
     const bool b8 = format == AMPS_RECC_SAMPLES_SC8 || format == AMPS_RECC_SAMPLES_CU8;
@@ -392,8 +406,11 @@ inline int channelizer_run(ChannelizerState &z, const ChzRunIn &in, hipStream_t 
         ChzNarrowArgs na{};
         na.block = d; na.carry = z.carry[z.carry_cur].get(); na.taps = z.taps.get(); na.twiddle = z.twiddle.get(); na.out = z.out.get(); na.ld = z.ld;
         na.bin2row = z.bin2row.get(); na.carry_len = z.carry_len; na.nsamp = (uint32_t)nsamp; na.nframes = nframes; na.n_channels = z.C;
-        const uint32_t fr = (uint32_t)chz_narrow_fr(z.M, z.D);
-        hipLaunchKernelGGL(chz_narrow_kernel_for(z.M, z.D, format), dim3((nframes + fr - 1) / fr), dim3(256), 0, s, na);
+        const bool grid10 = chz_is_grid10((uint32_t)z.M);
+        const uint32_t fr = (uint32_t)(grid10 ? chz_grid10_fr(z.M) : chz_narrow_fr(z.M, z.D));
+        const chz_narrow_kernel_t kern = grid10 ? chz_grid10_kernel_for(z.M, format) : chz_narrow_kernel_for(z.M, z.D, format);
+        if (!kern) return -EINVAL;
+        hipLaunchKernelGGL(kern, dim3((nframes + fr - 1) / fr), dim3(256), 0, s, na);
     } else if (nframes) {
         a.block = (const float2 *)d; a.carry = z.carry[z.carry_cur].get(); a.taps = z.taps.get(); a.out = z.out.get(); a.ld = z.ld;
         a.carry_len = z.carry_len; a.nsamp = (uint32_t)nsamp; a.nframes = nframes; a.hist = hist;

@@ -1,0 +1,228 @@
+// recc_chz_grid10.hip.h -- the filter bank of the wideband seam at rates that are multiples of 10 kHz but not of 30 kHz: M = fs / 10 kHz
+// = 2500, 2000, 1000 or 500 branches (25, 20, 10 and 5 Msps: what radios on a 100 or 200 MHz clock, and the 10 Msps dongles, deliver),
+// D = M / 4 input samples per frame: 40 ksps per channel, two samples per Manchester symbol.  Bins are 10 kHz apart, so a 30 kHz
+// channel sits on every third one (the host's bin2row says which).  The same weighted-overlap-add bank as recc_channelizer.hip.h
+// defines at its top and oracle/channelizer.py models -- here P = 3 taps per branch (300 us of prototype), frame m over samples
+// [(m+1) D - 3 M, (m+1) D), the fold modulo M with the absolute phase reference n0 mod M, an M-point DFT -- in the two-kernel form
+// only, like the narrow banks (recc_chz_narrow.hip.h), whose argument block (ChzNarrowArgs: taps [3 M], hist = 3 M - D here), carry
+// and host code it shares.
+//
+// Mapping: a 256-thread workgroup owns FR consecutive frames for all M bins.
+//   stage : the (FR - 1) D + 3 M input samples of its frames, carry first and block behind it, expanded to fc32 (chz_cvt), once in LDS
+//   fold  : a thread owns branches t + 256 b, keeps their three taps in registers and folds every frame of the workgroup with one
+//           multiply and two FMAs per branch, in that order, out of LDS; the roll n0 mod M is an index offset of the store (FR and
+//           every launch are multiples of the roll's period, four frames: a workgroup's frame f has roll ((f + 1) D) mod M).  The
+//           folded frames take the staged input's place in LDS: a thread keeps its results in registers until the workgroup has
+//           read all of the input, which halves the LDS of a workgroup and lets a second one share the CU at every size
+//   FFT   : all FR frames at once, Stockham passes in place over LDS, the radix-5 passes first and the power of two last:
+//           2500 = 5 x 5 x 5 x 5 x 4, 2000 = 5 x 5 x 5 x 16, 1000 = 5 x 5 x 5 x 8, 500 = 5 x 5 x 5 x 4.  FR M / R butterflies of a pass
+//           are no multiple of 256: the loops over a thread's butterflies are guarded.  Twiddles from the host's table (double precision)
+//   store : thread -> (bin, frame) with the frame running fastest: a row leaves in runs of FR x 8 bytes
+// A frame's arithmetic is a fixed sequence of operations on its own 3 M samples: it depends neither on how the stream was cut into
+// pushes nor on which workgroup computes it.  No atomics, nothing handed from one workgroup to another.
+//
+// LDS layout of a frame: element n at n, NO padding inside a frame.  The narrow banks pad n + n / 32 because their passes write with
+// strides of 8, 16, 64 ... elements across lanes, which fold onto a few banks.  Here every access is either stride 1 across lanes
+// (all reads of a pass: lane j reads j + r M / R, whatever M / 5 is; the fold; the write of the LAST pass, NS = M / R, which is why the
+// power-of-two radix runs last) or a write of the radix-5 passes at runs of NS consecutive elements 5 NS apart, NS = 1, 5, 25, 125:
+// odd strides, coprime with the 32 banks a write goes by.  Frames lie S elements apart with S = M rounded up to S mod 32 = 32 / FR:
+// the store phase reads (frame f, bin b) at f S + b with f running fastest across lanes, and FR frames x 32 / FR bins then cover the
+// 32 pairs of banks of a ds_read_b64 half-wave exactly once.
+//
+// FR, LDS (the larger of staged input and frame buffers) and the workgroups per CU it admits (the 3 M - D samples of history in front
+// of a workgroup's first frame are staged by its neighbour too, from L2: 12 / FR of the input is read a second time):
+//   M = 2500: FR = 4, 80 128 B, 2       M = 2000: FR = 4, 64 768 B, 2       M = 1000: FR = 4, 32 000 B, 5       M = 500: FR = 8, 33 024 B, 4
+#pragma once
+#include <hip/hip_runtime.h>
+#include "recc_chz_common.hip.h"
+#include "recc_chz_fft.hip.h"
+#include "recc_chz_narrow.hip.h"   // ChzNarrowArgs, chz_dft, chz_narrow_twiddles
+
+namespace amps {
+
+constexpr int CHZ_GRID10_P = 3;                                  // taps per branch
+constexpr double CHZ_GRID10_BIN_HZ = 10.0e3;
+constexpr int CHZ_GRID10_STRIDE = 3;                             // bins from one 30 kHz channel to the next
+
+__host__ __device__ constexpr bool chz_grid10_size(int M) { return M == 2500 || M == 2000 || M == 1000 || M == 500; }
+__host__ __device__ constexpr bool chz_grid10_geometry(int M, int D) { return chz_grid10_size(M) && 4 * D == M; }
+// frames per workgroup
+__host__ __device__ constexpr int chz_grid10_fr(int M) { return M == 500 ? 8 : 4; }
+// elements from one frame to the next in LDS: the smallest S >= M with S mod 32 = 32 / FR
+__host__ __device__ constexpr int chz_grid10_stride(int M) { return M + ((32 / chz_grid10_fr(M) - M % 32) % 32 + 32) % 32; }
+__host__ __device__ constexpr int chz_grid10_stage(int M) { return (chz_grid10_fr(M) - 1) * (M / 4) + CHZ_GRID10_P * M; }
+// cf2 elements of a workgroup's LDS: the staged input first, the FR frame buffers in its place afterwards
+__host__ __device__ constexpr int chz_grid10_lds_elems(int M) { return chz_grid10_stage(M) > chz_grid10_fr(M) * chz_grid10_stride(M) ? chz_grid10_stage(M) : chz_grid10_fr(M) * chz_grid10_stride(M); }
+__host__ __device__ constexpr size_t chz_grid10_lds_bytes(int M) { return sizeof(float2) * (size_t)chz_grid10_lds_elems(M); }
+
+// One Stockham pass as chz_narrow_pass defines it -- butterfly j of a frame reads elements j + r M / R, turns element r by
+// W_{NS R}^{r (j mod NS)}, and writes DFT_R of them to (j / NS) NS R + (j mod NS) + r NS -- over frames S elements apart without padding,
+// for any count of butterflies: a thread's last ones may not exist.  A sibling of chz_narrow_pass and not a generalisation of it: the
+// narrow banks' instantiations stay instruction for instruction what they were (profiles/grid10_bank/isa_identity.txt).
+template <int M, int R, int NS, int FR>
+__device__ __forceinline__ void chz_grid10_pass(cf2 *u, const float2 *tw, int t)
+{
+    constexpr int S = chz_grid10_stride(M), BPF = M / R, NBF = FR * BPF, NB = (NBF + 255) / 256;
+    static_assert(BPF * R == M && M % (NS * R) == 0, "NS R divides M");
+    cf2 v[NB][R];
+#pragma unroll
+    for (int q = 0; q < NB; q++) {
+        const int g = t + 256 * q, f = g / BPF, j = g % BPF;
+        if (g < NBF) {
+            const cf2 *A = u + f * S;
+#pragma unroll
+            for (int r = 0; r < R; r++) v[q][r] = A[j + r * BPF];
+            if constexpr (NS > 1) {
+                const int k = j % NS;
+#pragma unroll
+                for (int r = 1; r < R; r++) { const float2 w = tw[r * k * (M / (NS * R))]; v[q][r] = cmul(v[q][r], (cf2){ w.x, w.y }); }
+            }
+            chz_dft(v[q]);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NB; q++) {
+        const int g = t + 256 * q, f = g / BPF, j = g % BPF;
+        if (g < NBF) {
+            cf2 *A = u + f * S;
+            const int j0 = (j / NS) * NS * R + j % NS;
+#pragma unroll
+            for (int r = 0; r < R; r++) A[j0 + r * NS] = v[q][r];
+        }
+    }
+    __syncthreads();
+}
+
+// T: the sample type of a.block -- float2, chz_sc16, xl_sc8 or xl_cu8, every one read in place.  Only the staging loop knows it.
+template <int M, typename T>
+__global__ __launch_bounds__(256) void chz_grid10_kernel(ChzNarrowArgs a)
+{
+    static_assert(chz_grid10_size(M), "M = 2500, 2000, 1000 or 500");
+    constexpr int P = CHZ_GRID10_P, DEC = M / 4, FR = chz_grid10_fr(M), S = chz_grid10_stride(M), NST = chz_grid10_stage(M);
+    constexpr int NBR = (M + 255) / 256;                         // branches a thread folds
+    constexpr int E = (FR * M + 255) / 256;                      // (bin, frame) pairs a thread stores
+    static_assert(FR % 4 == 0 && S >= M && chz_grid10_lds_bytes(M) <= 80 * 1024, "whole periods of the roll; two workgroups per CU");
+    __shared__ cf2 lds[chz_grid10_lds_elems(M)];
+    cf2 *const xin = lds, *const u = lds;                        // [NST] staged input until the fold has read it, [FR * S] frames from then on
+    const int t = threadIdx.x;
+    const uint32_t frame0 = blockIdx.x * (uint32_t)FR;
+
+    float h[NBR][P];
+#pragma unroll
+    for (int b = 0; b < NBR; b++)
+#pragma unroll
+        for (int p = 0; p < P; p++) h[b][p] = a.taps[p * M + (t + 256 * b) % M];
+
+    // stage: sample i of the workgroup is carry-relative sample frame0 D + i; behind the stream's end (frames this launch does not
+    // produce) zeros.  As in the narrow banks' body: every load is unconditional, from an address that is valid whatever the sample is
+    // (element 0 of the carry, which is never empty, or of the block, which has a sample whenever a launch produces a frame), and what
+    // it returned is kept or replaced by zero afterwards, eight loads in flight per thread.  An integer block is read a sample per
+    // load, at the sample's own alignment
+    {
+        constexpr int NLD = (NST + 255) / 256, BATCH = 8;
+        const uint64_t c0 = (uint64_t)frame0 * DEC;
+        const T *blk = (const T *)a.block;
+#pragma unroll 1
+        for (int i0 = 0; i0 < NLD; i0 += BATCH) {
+            cf2 v[BATCH];
+#pragma unroll
+            for (int b = 0; b < BATCH; b++) {
+                const uint64_t ci = c0 + (uint64_t)(t + 256 * (i0 + b));
+                const bool in_carry = ci < a.carry_len;
+                const uint64_t bi = ci - a.carry_len;
+                const bool in_block = !in_carry && bi < a.nsamp;
+                if constexpr (chz_is_short<T>::value) {
+                    const float2 c = a.carry[in_carry ? ci : 0];
+                    const cf2 s = chz_cvt(blk[in_block ? bi : 0]);
+                    v[b] = in_carry ? (cf2){ c.x, c.y } : in_block ? s : (cf2){ 0.f, 0.f };
+                } else {
+                    const float2 c = *(in_carry ? a.carry + ci : in_block ? blk + bi : a.carry);
+                    v[b] = (in_carry || in_block) ? (cf2){ c.x, c.y } : (cf2){ 0.f, 0.f };
+                }
+            }
+#pragma unroll
+            for (int b = 0; b < BATCH; b++) {
+                const int i = t + 256 * (i0 + b);
+                if (i < NST) xin[i] = v[b];
+            }
+        }
+    }
+    __syncthreads();
+
+    // fold: into registers, and into the input's place once every thread has read what it needs of it
+    cf2 acc[NBR][FR];
+#pragma unroll
+    for (int b = 0; b < NBR; b++) {
+        const int j = t + 256 * b;
+        if (j < M) {
+#pragma unroll
+            for (int f = 0; f < FR; f++) {
+                const cf2 *x = xin + f * DEC + j;
+                acc[b][f] = x[0] * h[b][0];
+#pragma unroll
+                for (int p = 1; p < P; p++) { const cf2 s = x[p * M]; acc[b][f] = (cf2){ fmaf(h[b][p], s.x, acc[b][f].x), fmaf(h[b][p], s.y, acc[b][f].y) }; }
+            }
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int b = 0; b < NBR; b++) {
+        const int j = t + 256 * b;
+        if (j < M) {
+#pragma unroll
+            for (int f = 0; f < FR; f++) {
+                const int k = j + ((f + 1) & 3) * DEC;           // + ((f + 1) D) mod M
+                u[f * S + (k >= M ? k - M : k)] = acc[b][f];
+            }
+        }
+    }
+    __syncthreads();
+
+    chz_grid10_pass<M, 5, 1, FR>(u, a.twiddle, t);
+    chz_grid10_pass<M, 5, 5, FR>(u, a.twiddle, t);
+    chz_grid10_pass<M, 5, 25, FR>(u, a.twiddle, t);
+    if constexpr (M == 2500) {
+        chz_grid10_pass<M, 5, 125, FR>(u, a.twiddle, t);
+        chz_grid10_pass<M, 4, 625, FR>(u, a.twiddle, t);
+    } else {
+        chz_grid10_pass<M, M / 125, 125, FR>(u, a.twiddle, t);
+    }
+
+    // store: the frame runs fastest across lanes
+#pragma unroll
+    for (int q = 0; q < E; q++) {
+        const int idx = t + 256 * q, f = idx % FR, bin = idx / FR;
+        if (bin < M) {
+            const uint32_t row = a.bin2row[bin], frame = frame0 + (uint32_t)f;
+            if (row < a.n_channels && frame < a.nframes) {
+                const cf2 y = u[f * S + bin];
+                a.out[(uint64_t)row * a.ld + frame] = make_float2(y.x, y.y);
+            }
+        }
+    }
+}
+
+template <int M> chz_narrow_kernel_t chz_grid10_kernel_of(int format)
+{
+    switch (format) {
+    case AMPS_RECC_SAMPLES_FC32: return chz_grid10_kernel<M, float2>;
+    case AMPS_RECC_SAMPLES_SC16: return chz_grid10_kernel<M, chz_sc16>;
+    case AMPS_RECC_SAMPLES_SC8: return chz_grid10_kernel<M, xl_sc8>;
+    case AMPS_RECC_SAMPLES_CU8: return chz_grid10_kernel<M, xl_cu8>;
+    default: return nullptr;
+    }
+}
+// the instantiation for (branches, sample format of the block: AMPS_RECC_SAMPLES_*); nullptr for a size or a format there is none for
+inline chz_narrow_kernel_t chz_grid10_kernel_for(int M, int format)
+{
+    switch (M) {
+    case 2500: return chz_grid10_kernel_of<2500>(format);
+    case 2000: return chz_grid10_kernel_of<2000>(format);
+    case 1000: return chz_grid10_kernel_of<1000>(format);
+    case 500: return chz_grid10_kernel_of<500>(format);
+    default: return nullptr;
+    }
+}
+
+} // namespace amps

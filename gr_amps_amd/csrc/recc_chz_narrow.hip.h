@@ -56,6 +56,18 @@ __host__ __device__ constexpr size_t chz_narrow_lds_bytes(int M, int D) { return
 // DFT-R in place, natural order
 __device__ __forceinline__ void chz_dft(cf2 (&v)[2]) { const cf2 a = v[0], b = v[1]; v[0] = a + b; v[1] = a - b; }
 __device__ __forceinline__ void chz_dft(cf2 (&v)[4]) { dft4(v[0], v[1], v[2], v[3], v); }
+// radix 5 (the banks of recc_chz_grid10.hip.h): sums and differences of the pairs (1, 4) and (2, 3), then X[k] and X[5 - k] share
+// their real-coefficient half (cos 2 pi / 5, cos 4 pi / 5) and differ in the sign of -i times the other (sin 2 pi / 5, sin 4 pi / 5)
+__device__ __forceinline__ void chz_dft(cf2 (&v)[5])
+{
+    constexpr float C1 = 0.30901699437494742f, C2 = -0.80901699437494742f, S1 = 0.95105651629515357f, S2 = 0.58778525229247313f;
+    const cf2 t1 = v[1] + v[4], t2 = v[2] + v[3], t3 = v[1] - v[4], t4 = v[2] - v[3];
+    const cf2 m1 = v[0] + C1 * t1 + C2 * t2, m2 = v[0] + C2 * t1 + C1 * t2;
+    const cf2 n1 = S1 * t3 + S2 * t4, n2 = S2 * t3 - S1 * t4;
+    v[0] = v[0] + t1 + t2;
+    v[1] = add_mi(m1, n1); v[4] = sub_mi(m1, n1);
+    v[2] = add_mi(m2, n2); v[3] = sub_mi(m2, n2);
+}
 __device__ __forceinline__ void chz_dft(cf2 (&v)[8])
 {
     constexpr float R2 = 0.70710678118654752f;

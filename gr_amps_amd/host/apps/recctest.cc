@@ -14,7 +14,9 @@
 //                                      keep received power: every burst's lines are followed by `MSG power channel <c> <10 log10(mean power)> dB
 //                                      n=<snapshots>`; without it the output is what it always was.  An argument `channels=<M>` anywhere behind
 //                                      the file (M = 512, 256 or 128) reads the capture as a stream at M x 30 ksps -- 15.36, 7.68 or 3.84 Msps --
-//                                      through the M-branch bank: all M bins from bin 0 (recc_wideband::make(M, 0, ..., channels = M))
+//                                      through the M-branch bank: all M bins from bin 0 (recc_wideband::make(M, 0, ..., channels = M)); M = 2500,
+//                                      2000, 1000 or 500: a capture at M x 10 kHz (25, 20, 10, 5 Msps) through the bank of M branches of
+//                                      10 kHz, the M / 3 channels on bins 0, 3, 6 ... at decim = M / 4, which recctest sets itself
 //   recctest widerank <file.fc32> <chunk> <idfile> <nranks> <rank> [mode]   ONE rank of the same band over `nranks` processes (2, 4 or 8; one per GPU of a
 //                                      node): gr::amps::recc_wideband::make(832, 96, -1, nranks, rank) + set_rccl -- rank 0 owns the capture and the
 //                                      library distributes it (mode 0 = ncclBroadcast, 1 = scatter + all-gather); the other ranks' items only pace
@@ -215,7 +217,9 @@ int main(int argc, char **argv)
             const size_t item = format == 0 ? 8 : format == 1 ? 4 : 2;   // bytes per wideband sample
             bool power = false;
             for (int i = 6; !ranks && i < argc && i < 9; i++) power = power || std::string(argv[i]) == "power";
+            const bool grid10 = wide_channels == 2500 || wide_channels == 2000 || wide_channels == 1000 || wide_channels == 500;   // bins of 10 kHz
             auto src = ranks ? gr::amps::recc_wideband::make(832, 96, -1, nranks, rank)
+                             : grid10 ? gr::amps::recc_wideband::make(wide_channels / 3, 0, argc > 4 ? std::atoi(argv[4]) : -1, 0, 0, wide_channels / 4, false, power, wide_channels, format)
                              : wide_channels != 1024 ? gr::amps::recc_wideband::make(wide_channels, 0, argc > 4 ? std::atoi(argv[4]) : -1, 0, 0, argc > 5 ? std::atoi(argv[5]) : 0, false, power, wide_channels, format)
                              : gr::amps::recc_wideband::make(832, 96, argc > 4 ? std::atoi(argv[4]) : -1, 0, 0, argc > 5 ? std::atoi(argv[5]) : 0, false, power, 1024, format);
             if (ranks) {

@@ -15,6 +15,10 @@
 // the bank of that many branches, in the two-kernel form (cfg.wideband_channels of include/amps_recc.h); "power" then carries the stream
 // power of the IQ seam (AMPS_RECC_FLAG_STREAM_POWER: the mean of |y|^2 over the blocks of 256 channel-rate samples inside the capture).
 // Bin channels / 2 is centred on +- fs / 2, where the radio's own anti-alias filter rolls off: a channel there is as good as the radio.
+// With channels = 2500, 2000, 1000 or 500 and decim = channels / 4 the input is a stream at channels x 10 kHz = 25, 20, 10 or 5 Msps --
+// a radio on a 100 or 200 MHz clock, a 10 Msps dongle -- through the bank of that many branches of 10 kHz, likewise in the two-kernel
+// form: a 30 kHz channel on every third bin, channel c = bin (first_bin + 3 c) mod channels, n_channels <= channels / 3, 40 ksps per
+// channel.  first_bin then counts 10 kHz bins: a tuner on any multiple of 10 kHz puts every channel centre on a bin.
 // channel 0 = FFT bin `first_bin` (centre first_bin x 30 kHz above the stream's centre, modulo the sample rate).
 #pragma once
 #include <amps/api.h>
@@ -38,7 +42,9 @@ public:
     //         a block: the distributed seam carries fc32.
     // channel_power: keep per-channel received power (AMPS_RECC_FLAG_CHANNEL_POWER) and publish every record's burst power on "power"
     // channels: branches of the filter bank = 30 kHz channels across the stream: 1024, or 512, 256, 128 (n_channels <= channels, first_bin <
-    //         channels; decim = channels / 2 or 3 channels / 4, 0 = the latter; groups and set_rccl belong to 1024)
+    //         channels; decim = channels / 2 or 3 channels / 4, 0 = the latter; groups and set_rccl belong to 1024); or 2500, 2000, 1000,
+    //         500 branches of 10 kHz: make(n_channels <= channels / 3, first_bin, ..., decim = channels / 4, ..., channels, input_format),
+    //         e.g. decim = 500, channels = 2000 for 20 Msps -- the decimation has to be stated there, 0 is refused
     // input_format: AMPS_RECC_SAMPLES_* of include/amps_recc.h.  0 = one gr_complex per item (or two shorts behind short_input = true,
     //         which keeps meaning format 1); 1 (sc16) = two shorts; 2 (sc8) = two signed bytes, what a HackRF streams at 3.84 to
     //         15.36 Msps; 3 (cu8) = two offset-binary bytes.  Items of 8, 4, 2 and 2 bytes, pushed as they are

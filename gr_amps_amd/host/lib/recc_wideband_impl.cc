@@ -1,4 +1,4 @@
-// recc_wideband_impl.cc -- gr::amps::recc_wideband: one 30.72 Msps complex stream (or 15.36, 7.68, 3.84 Msps: channels < 1024) in, (channel, burst) and (channel, record) pairs out.
+// recc_wideband_impl.cc -- gr::amps::recc_wideband: one 30.72 Msps complex stream (or 15.36, 7.68, 3.84 Msps: channels < 1024; or 25, 20, 10, 5 Msps: channels = 2500 ... 500 of 10 kHz) in, (channel, burst) and (channel, record) pairs out.
 #include <amps/recc_wideband.h>
 #include <cerrno>
 #include <cstdio>
@@ -51,7 +51,7 @@ public:
         cfg.struct_size = sizeof(cfg);
         cfg.n_channels = (uint32_t)C;
         cfg.samples_per_symbol = 0;                // what goes with the decimation: 3 (60 ksps per channel, D = 512) or 2 (40 ksps, D = 768)
-        const bool narrow = channels > 0 && channels < 1024;       // the two-kernel form: received power is the IQ seam's
+        const bool narrow = channels > 0 && channels != 1024;      // every bank but the 1024 one is the two-kernel form: received power is the IQ seam's
         const int dmin = narrow ? (decim > 0 ? decim : 3 * channels / 4) : 512;   // fewest input samples a frame takes
         cfg.max_samples_per_push = (uint32_t)(kMaxPush / dmin + 72);
         cfg.max_bursts = kMaxRecs;
@@ -63,7 +63,7 @@ public:
         cfg.wideband_group = (uint32_t)group;
         cfg.wideband_channels = (uint32_t)channels;
         cfg.wideband_decim = (uint32_t)decim;     // 0 = amps_recc_default_wideband_decim()
-        cfg.wideband_taps_per_branch = 8;
+        cfg.wideband_taps_per_branch = 0;         // the bank's own: 8, or 3 at the banks of 10 kHz bins
         cfg.wideband_first_channel = (uint32_t)first_bin;
         int rc = amps_recc_create(&d_handle, &cfg);
         if (rc != 0) throw std::runtime_error(std::string("amps::recc_wideband: ") + amps_recc_strerror(rc));

@@ -63,7 +63,9 @@ extern "C" {
                                      still 4, one entry point added and nothing changed: amps_recc_wideband_plan, with cfg.wideband_channels = 512,
                                      256 and 128, the wideband seam at 15.36, 7.68 and 3.84 Msps;
                                      still 4, two entry points added and nothing changed: amps_recc_push_wideband_as / _debug_channelize_as, the
-                                     wideband seam on 8-bit I/Q (sc8, cu8), read in place on every bank) */
+                                     wideband seam on 8-bit I/Q (sc8, cu8), read in place on every bank;
+                                     still 4, one entry point added and nothing changed: amps_recc_wideband_grid_plan, with cfg.wideband_channels =
+                                     2500, 2000, 1000 and 500 at wideband_decim = M / 4, the wideband seam at 25, 20, 10 and 5 Msps) */
 
 /* protocol constants of the reference */
 #define AMPS_RECC_TRIGGER_SYMS 74   /* lib/recc_impl.cc:76-77: 37 bits x 2 Manchester symbols   */
@@ -113,7 +115,7 @@ extern "C" {
                                                carrier offset is read (amps_recc_channel_autocorr, amps_recc_burst_autocorr,
                                                amps_recc_burst_offset below).  Off by default; with it off nothing is allocated or launched
                                                for it and no record changes.  Combines freely with AMPS_RECC_FLAG_STREAM_POWER.  Also taken
-                                               with wideband_channels < 1024 (fs = 30 kHz M / D there).  On a handle with wideband_channels
+                                               with wideband_channels < 1024 (fs = 30 kHz M / D there) and with the banks of 10 kHz bins (fs = 40 kHz).  On a handle with wideband_channels
                                                = 1024 (fused or not), with max_samples_per_push == 0 (symbol seam only), or together with
                                                AMPS_RECC_FLAG_CHANNEL_POWER: -EINVAL */
 #define AMPS_RECC_FLAG_STREAM_OFFSET_UNIT 0x1000u /* the same ring, entry points, numbering, window and error rules as
@@ -216,15 +218,23 @@ typedef struct amps_recc_cfg {
                                     * changes nothing), wideband_groups > 1 and AMPS_RECC_FLAG_CHANNEL_POWER are -EINVAL, amps_recc_rccl_init
                                     * answers -ENOSYS, and AMPS_RECC_FLAG_STREAM_POWER / _STREAM_OFFSET / _STREAM_OFFSET_UNIT are accepted:
                                     * blocks of 256 channel-rate samples, as on the IQ seam.  Bin M / 2 is centred on +- fs / 2, where the
-                                    * radio's own anti-alias filter rolls off: a channel there is received as the radio delivers it */
+                                    * radio's own anti-alias filter rolls off: a channel there is received as the radio delivers it.
+                                    * Or M branches of 10 kHz, for a stream at M * 10 ksps: 2500, 2000, 1000, 500 (25, 20, 10, 5 Msps: the
+                                    * rates of radios on a 100 or 200 MHz clock, see amps_recc_wideband_grid_plan), ONLY together with
+                                    * wideband_decim = M / 4 stated explicitly.  Everything said of M < 1024 holds for these banks too.  A
+                                    * 30 kHz channel sits on every third bin: channel c of the handle is bin (wideband_first_channel + 3 c)
+                                    * mod M, and 3 n_channels <= M (833, 666, 333, 166 channels at most), -EINVAL beyond.  A tuner set to any
+                                    * multiple of 10 kHz puts every channel centre on a bin */
     uint32_t wideband_decim;       /* channelizer seam: D input samples per output frame: M / 2 or 3 M / 4, anything else -EINVAL.
                                     * M = 1024: 0 = amps_recc_default_wideband_decim().  M < 1024: 0 = 3 M / 4, the same ratio.
+                                    * M = 2500, 2000, 1000, 500: M / 4 (40 ksps per channel, samples_per_symbol = 2, 0 is filled in as 2);
+                                    * 0 and every other value are -EINVAL there.
                                     * samples_per_symbol = 0 is filled in as 3 M / (2 D).  At M = 1024:
                                     * 768 (4/3 x oversampled: 40 ksps per channel, samples_per_symbol = 2; the default since round 6)
                                     * or 512 (2x oversampled: 60 ksps, samples_per_symbol = 3; 1.5 x the frames per input byte,
                                     * 0.2 - 0.7 dB more sensitive)                                                     */
-    uint32_t wideband_taps_per_branch; /* prototype length = taps_per_branch * M: 8 (0 selects 8)              */
-    uint32_t wideband_first_channel;   /* first FFT bin that is an active RECC channel                    */
+    uint32_t wideband_taps_per_branch; /* prototype length = taps_per_branch * M: 8 (0 selects 8); at the banks of 10 kHz bins 3 (0 selects 3) */
+    uint32_t wideband_first_channel;   /* first FFT bin that is an active RECC channel, < M (it counts 10 kHz bins at M = 2500 ... 500) */
     uint32_t sync_tolerance;       /* IQ / wideband seams: accept a trigger with up to this many of its 74
                                     * symbols wrong.  0 = exact match, the reference's memmem
                                     * (lib/recc_impl.cc:118) -- keep 0 for parity runs.  <= AMPS_RECC_MAX_SYNC_TOLERANCE */
@@ -403,7 +413,15 @@ int amps_recc_xlate_shared_plan(double rate_hz, double width_hz, amps_recc_xlate
  * translate seam below 3.2 Msps).  -EINVAL: rate_hz not positive and finite, out == NULL with cap > 0. */
 typedef struct amps_recc_wideband_plan { uint32_t channels, decim, samples_per_symbol, taps; } amps_recc_wideband_plan_t;
 int amps_recc_wideband_plan(double rate_hz, amps_recc_wideband_plan_t *out, size_t cap);
-/* For the rates it answers with nothing, ask amps_recc_xlate_resample_plan below. */
+/* The same question for every bank the seam has, the ones whose bins are not 30 kHz wide included.  Same count, cap and error rules.
+ * An entry adds the width of a bin, the bins from one channel to the next (channel c = bin (wideband_first_channel + channel_stride c)
+ * mod channels) and the most n_channels a handle takes.  For 30.72, 15.36, 7.68 and 3.84 Msps: the entries of amps_recc_wideband_plan
+ * with bin_hz = 30000, channel_stride = 1, max_channels = channels.  For a rate within 0.5 Hz of M * 10 kHz, M = 2500, 2000, 1000 or 500,
+ * one entry (M, M / 4, 2, 3 M, 10000, 3, M / 3) -- 10e6: (1000, 250, 2, 3000, 10000, 3, 333) -- with wideband_decim to be stated as given.
+ * Nothing for 12.5, 6.25, 2.5 or 1.92 Msps, where rate / 40 kHz is no integer. */
+typedef struct amps_recc_wideband_grid_plan { uint32_t channels, decim, samples_per_symbol, taps, bin_hz, channel_stride, max_channels, _pad; } amps_recc_wideband_grid_plan_t;
+int amps_recc_wideband_grid_plan(double rate_hz, amps_recc_wideband_grid_plan_t *out, size_t cap);
+/* For the rates both answer with nothing, ask amps_recc_xlate_resample_plan below. */
 /* iq is ONE row of nsamp samples at rate_hz.  Any nsamp <= decim * max_samples_per_push (-E2BIG beyond); leftover samples (fewer than
  * decim) wait for the next push.  Host and device blocks follow the ownership rules of amps_recc_push_raw; amps_recc_reset restarts
  * the stream; ms_xlate of amps_recc_get_timing counts the kernel.  -ESTALE as the data seams. */
@@ -489,7 +507,8 @@ int amps_recc_debug_xlate_as(amps_recc_t *h, const void *iq, size_t ld, size_t n
  * only be aligned to one sample: 2 bytes for sc8 and cu8 (a slice that starts at an odd sample is legal), and the kernels touch no
  * aligned dword that holds no byte of it.  A host block is staged as it is, at 2 bytes per sample; ownership is as for the fc32 call.
  * The banks of 512, 256 and 128 branches read the 8-bit block in place, 2 bytes per sample over the host link and from HBM; no fc32
- * copy of it exists.  The 1024 bank (30.72 Msps: no radio delivers 8 bits there, converted capture files do) expands an 8-bit block
+ * copy of it exists, and so do the banks of 2500, 2000, 1000 and 500 branches (25 to 5 Msps: an N2xx's sc16 or sc8 over the wire, an
+ * Airspy's or SDRplay's sc16, a HackRF's sc8 at 20 and 10 Msps), for every format.  The 1024 bank (30.72 Msps: no radio delivers 8 bits there, converted capture files do) expands an 8-bit block
  * to fc32 on the device first and then runs as on any fc32 block, in every form it has.
  * Received power (amps_recc_channel_power / _burst_power) reads in the input's own units squared.  No scaling is offered: the bank
  * is linear and no slicer's decision depends on scale. */
