@@ -11,6 +11,17 @@ AMPS band out (BASELINE configs[3]; replaces 832 x [freq_xlating_fir_filter_ccc 
                                                               # as it is (2 bytes per sample); meaningful with --channels below 1024
     python examples/decode_wideband.py --channels 500 [--sc8] # a radio on a 100 MHz clock: a 5 Msps stream (or 1000: 10, 2000: 20, 2500: 25 Msps)
                                                               # through the bank of that many branches of 10 kHz, a channel on every third bin
+    python examples/decode_wideband.py --channels 128 --tuner-error 9000              # a radio whose crystal is 11 ppm off at 835 MHz: every
+                                                                                      # mobile 9 kHz above its bin's centre; nothing decodes
+    python examples/decode_wideband.py --channels 128 --tuner-error 9000 --shift 9000 # ... corrected inside the filter bank (--channels below
+                                                                                      # 1024): amps_recc_set_wideband_shift, all twelve again
+    python examples/decode_wideband.py --channels 500 --tuner-error 2000 --afc        # the handle measures what is left: the first half of the
+                                                                                      # stream runs uncorrected with the unit-amplitude carrier
+                                                                                      # offset on, the median burst_offset of what it decoded
+                                                                                      # becomes the shift, the stream goes on; nothing is reset.
+                                                                                      # --afc refines: it needs bursts that still decode, about
+                                                                                      # +-3 kHz of error.  A coarse search beyond that (try
+                                                                                      # shifts 5 kHz apart until bursts appear) is the caller's
 """
 import os
 import sys
@@ -26,9 +37,22 @@ BIN_HZ, STRIDE = (10e3, 3) if GRID10 else (30e3, 1)
 FIRST_BIN, CHANNELS = (96, 832) if BANK == 1024 else (0, BANK // STRIDE)   # the band selection: FFT bins 96 .. 927 of the 1024-branch filter bank, or every channel of a smaller one
 FS = BANK * BIN_HZ
 NSAMP = 12 * (1 << 20) * BANK // (1024 * STRIDE)  # 0.41 s of signal
+
+def _option(name, default):
+    return float(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv[1:] else default
+
+
+TUNER_ERROR = _option("--tuner-error", 0.0)       # the radio delivers everything this many hertz too high
+SHIFT = _option("--shift", 0.0)                   # ... and the filter bank takes this many back out
+AFC = "--afc" in sys.argv[1:]
+if (SHIFT or AFC) and BANK == 1024:
+    sys.exit("--shift and --afc need --channels below 1024: the 1024 bank has no mixer (radios that reach 30.72 Msps have a TCXO)")
+BURST = 3456 * int(FS) // 20000                   # wideband samples of one burst
 rng = np.random.default_rng(7)
-plan = [((FIRST_BIN + STRIDE * int(c)) % BANK, int(rng.integers(4000, NSAMP - 3456 * int(FS) // 20000 - 4000))) for c in rng.choice(CHANNELS, 12, replace=False)]
-x, truth = sw.make_wideband(NSAMP, plan, seed=7, snr_db=20.0, sym_ppm=50.0, fs=FS, bins=BANK)   # every mobile 50 ppm off the nominal bit clock
+plan = [((FIRST_BIN + STRIDE * int(c)) % BANK, int(rng.integers(4000, NSAMP - BURST - 4000))) for c in rng.choice(CHANNELS, 12, replace=False)]
+if AFC:                                           # the shift changes at NSAMP / 2: no burst is on the air there (a burst that spans the change is not the twin's)
+    plan = [(k, int(rng.integers(4000, NSAMP // 2 - BURST - 4000) if i % 2 else rng.integers(NSAMP // 2 + 4000, NSAMP - BURST - 4000))) for i, (k, _) in enumerate(plan)]
+x, truth = sw.make_wideband(NSAMP, plan, seed=7, snr_db=20.0, sym_ppm=50.0, fs=FS, bins=BANK, cfo_hz=TUNER_ERROR)   # every mobile 50 ppm off the nominal bit clock
 
 SC16 = "--sc16" in sys.argv[1:]
 if SC16:                                          # full scale for the loudest sample, a power of two; no slicer decision depends on the scale
@@ -42,19 +66,33 @@ try:
     wideband = {"channels": BANK, "first_channel": FIRST_BIN}                   # decimation: the library default (3/4 of the branches: 40 ksps per channel)
     if GRID10:
         wideband["decim"] = BANK // 4                                            # ... which the banks of 10 kHz bins want stated: 40 ksps per channel too
-    rx = capi.Recc(n_channels=CHANNELS, max_samples=NSAMP // (BANK // 4 if GRID10 else BANK // 2) + 72, max_bursts=256, wideband=wideband)
+    rx = capi.Recc(n_channels=CHANNELS, max_samples=NSAMP // (BANK // 4 if GRID10 else BANK // 2) + 72, max_bursts=256, wideband=wideband,
+                   stream_offset="unit" if AFC else False)
 except capi.AmpsError as e:
     sys.exit("no MI355X here (%s): the library has no CPU fallback" % e)
 with rx:
-    pos = 0
+    if SHIFT:
+        rx.set_wideband_shift(SHIFT)
+    pos, early = 0, None
     while pos < NSAMP:                            # blocks of any size: what is left of a frame waits in the handle for the next push
         n = min(int(rng.integers(100_000, 3_000_000)) * BANK // 1024, NSAMP - pos)
+        if AFC and early is None:
+            n = min(n, NSAMP // 2 - pos)
+            if n == 0:                            # half way: steer by what has been decoded so far, then go on with the stream
+                early = rx.drain()
+                hz = rx.burst_offset(early)[0] if len(early) else np.zeros(0)
+                if len(hz):
+                    rx.set_wideband_shift(SHIFT + float(np.median(hz)))
+                print("afc: %d bursts read %+.0f Hz (median); shift now %+.1f Hz" % (len(hz), float(np.median(hz)) if len(hz) else 0.0, rx.wideband_shift))
+                continue
         if SC8:
             rx.push_wideband_as(x[pos:pos + n], capi.SAMPLES_SC8)
         else:
             (rx.push_wideband_short if SC16 else rx.push_wideband)(x[pos:pos + n])
         pos += n
     recs = rx.drain()
+    if early is not None:
+        recs = np.concatenate([early, recs])
 sent = {(k - FIRST_BIN) % BANK // STRIDE: v[1] for (k, _), v in truth.items()}
 print("%d bursts sent, %d decoded" % (len(sent), len(recs)))
 for r in recs:

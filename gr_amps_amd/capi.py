@@ -159,9 +159,11 @@ EXPORTS = (
     "amps_recc_retune_xlate",
     "amps_recc_wideband_plan", "amps_recc_wideband_grid_plan",
     "amps_recc_push_wideband_as", "amps_recc_debug_channelize_as",
+    "amps_recc_set_wideband_shift", "amps_recc_wideband_shift",
 )
 GRID10_CHANNELS = (2500, 2000, 1000, 500)   # branches of the wideband seam's banks of 10 kHz bins: 25, 20, 10 and 5 Msps
 _WIDEBAND_AS = ("amps_recc_push_wideband_as", "amps_recc_debug_channelize_as")
+_WIDEBAND_SHIFT = ("amps_recc_set_wideband_shift", "amps_recc_wideband_shift")
 _XLATE_RESAMPLED = ("amps_recc_set_xlate_resampled", "amps_recc_xlate_resample_plan")
 _XLATE_AS = ("amps_recc_push_raw_shared_as", "amps_recc_push_raw_as", "amps_recc_debug_xlate_shared_as", "amps_recc_debug_xlate_as")
 _XLATE_SHARED = ("amps_recc_set_xlate_shared", "amps_recc_push_raw_shared", "amps_recc_debug_xlate_shared")
@@ -274,12 +276,15 @@ def load():
     if hasattr(L, "amps_recc_push_wideband_as"):      # absent only from A/B builds of earlier revisions (AMPS_RECC_LIB)
         L.amps_recc_push_wideband_as.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int]
         L.amps_recc_debug_channelize_as.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    if hasattr(L, "amps_recc_set_wideband_shift"):    # likewise
+        L.amps_recc_set_wideband_shift.argtypes = [vp, C.c_double]
+        L.amps_recc_wideband_shift.argtypes = [vp, C.POINTER(C.c_double)]
     L.amps_bch_encode_words.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp]
     L.amps_bch_decode_words.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, vp, vp]
     for name in EXPORTS:
         if name in ("amps_recc_default_slicer", "amps_recc_default_wideband_decim", "amps_recc_debug_exact_slice", "amps_recc_rccl_unique_id", "amps_recc_rccl_init",
                     "amps_recc_push_wideband_bcast", "amps_recc_drain_gather", "amps_recc_debug_slicer_bits",
-                    "amps_recc_push_wideband_short", "amps_recc_xlate_shared_plan", "amps_recc_wideband_plan", "amps_recc_wideband_grid_plan") + _NEW_IN_ABI4 + _POWER + _OFFSET + _RETUNE + _XLATE_SHARED + _XLATE_AS + _XLATE_RESAMPLED + _WIDEBAND_AS and not hasattr(L, name):
+                    "amps_recc_push_wideband_short", "amps_recc_xlate_shared_plan", "amps_recc_wideband_plan", "amps_recc_wideband_grid_plan") + _NEW_IN_ABI4 + _POWER + _OFFSET + _RETUNE + _XLATE_SHARED + _XLATE_AS + _XLATE_RESAMPLED + _WIDEBAND_AS + _WIDEBAND_SHIFT and not hasattr(L, name):
             continue
         if name not in ("amps_recc_strerror", "amps_recc_burst_size", "amps_recc_destroy"):   # every other entry point returns int
             getattr(L, name).restype = C.c_uint32 if name == "amps_recc_power_ring_snaps" else C.c_int
@@ -556,6 +561,24 @@ class Recc:
         rc = load().amps_recc_retune_xlate(self._h, cen.ctypes.data_as(C.POINTER(C.c_double)), cen.size)
         if rc:
             raise AmpsError(rc, "amps_recc_retune_xlate")
+
+    def set_wideband_shift(self, shift_hz):
+        """Correct a tuner's frequency error inside the filter bank (amps_recc_set_wideband_shift; the banks below 1024 branches):
+        shift_hz is the frequency in the delivered stream of what shall land on bin 0's centre, so a radio that delivers everything
+        e hertz too high gets +e.  Takes effect with the next push; from then on the bank delivers, bit for bit, what a handle with
+        this shift from the start would.  Nothing is reset and the host does not wait; 0 runs the unmixed kernels again."""
+        rc = load().amps_recc_set_wideband_shift(self._h, float(shift_hz))
+        if rc:
+            raise AmpsError(rc, "amps_recc_set_wideband_shift")
+
+    @property
+    def wideband_shift(self):
+        """The shift in force in hertz, as quantised to the mixer's step (amps_recc_wideband_shift)."""
+        hz = C.c_double(0.0)
+        rc = load().amps_recc_wideband_shift(self._h, C.byref(hz))
+        if rc:
+            raise AmpsError(rc, "amps_recc_wideband_shift")
+        return hz.value
 
     def set_xlate_resampled(self, rate_hz, centers_hz, interp, decim, gain=0.0, cutoff_hz=0.0, width_hz=0.0):
         """set_xlate_shared for the rates no integer decimation serves: the shared stream is resampled by interp / decim (2.048 Msps

@@ -685,6 +685,22 @@ int amps_recc_retune_xlate(amps_recc_t *h, const double *center_hz, size_t n)
     return xlate_retune(h->xl, center_hz, n, h->stream.get());
 }
 
+// The tuner correction of the wideband seam: host state only.  The next launch of the bank carries the step by value, so nothing is
+// written to the device, nothing is waited for, and the call may come between drain_begin and drain_end.
+int amps_recc_set_wideband_shift(amps_recc_t *h, double shift_hz)
+{
+    if (!h) return -EINVAL;
+    return wideband_shift_from(h->chz.enabled, (uint32_t)h->chz.M, chz_bin_hz((uint32_t)h->chz.M), shift_hz, &h->chz.shift);
+}
+
+int amps_recc_wideband_shift(const amps_recc_t *h, double *shift_hz)
+{
+    if (!h || !shift_hz) return -EINVAL;
+    if (!h->chz.enabled || h->chz.M == CHZ_M) return -ENOSYS;
+    *shift_hz = h->chz.shift.hz;
+    return 0;
+}
+
 int amps_recc_xlate_resample_plan(double rate_hz, double width_hz, amps_recc_resample_plan_t *out, size_t cap)
 {
     if (width_hz == 0.0) width_hz = 4.5e3;                     // the default of amps_recc_set_xlate_resampled

@@ -41,6 +41,7 @@
 #include "recc_chz_slicer.hip.h"
 #include "recc_power.hip.h"       // chz_power_launch: the power snapshots behind a fused launch
 #include "recc_chz_narrow.hip.h"  // the banks of 512, 256 and 128 branches: a kernel of their own behind the same state, carry and host code
+#include "recc_wideband_shift.h"  // WidebandShift: the tuner correction of the banks below 1024 branches
 #include "recc_chz_grid10.hip.h"  // the banks of 2500, 2000, 1000 and 500 branches of 10 kHz (25, 20, 10 and 5 Msps): likewise
 
 namespace amps {
@@ -173,6 +174,7 @@ struct ChannelizerState {
     int carry_cur = 0;
     uint32_t carry_len = 0;         // L - D + leftover
     uint64_t frames_done = 0;
+    WidebandShift shift;            // amps_recc_set_wideband_shift (M < 1024): a non-zero step launches the mixing twins.  Kept over a reset
     DevBuf<float2> out;             // [C][ld]
     uint64_t ld = 0;
     HostStage stage;                // host-resident wideband input as the caller's samples (fc32, sc16, sc8 or cu8), sized in bytes: the largest block so far
@@ -408,9 +410,17 @@ inline int channelizer_run(ChannelizerState &z, const ChzRunIn &in, hipStream_t 
         na.bin2row = z.bin2row.get(); na.carry_len = z.carry_len; na.nsamp = (uint32_t)nsamp; na.nframes = nframes; na.n_channels = z.C;
         const bool grid10 = chz_is_grid10((uint32_t)z.M);
         const uint32_t fr = (uint32_t)(grid10 ? chz_grid10_fr(z.M) : chz_narrow_fr(z.M, z.D));
-        const chz_narrow_kernel_t kern = grid10 ? chz_grid10_kernel_for(z.M, format) : chz_narrow_kernel_for(z.M, z.D, format);
-        if (!kern) return -EINVAL;
-        hipLaunchKernelGGL(kern, dim3((nframes + fr - 1) / fr), dim3(256), 0, s, na);
+        if (z.shift.step) {
+            // every launch mixes all it stages, carry included (the carry keeps unmixed input), by the sample's absolute index
+            const ChzMixArgs ma{ na, (int64_t)(z.frames_done * (uint64_t)z.D) - (int64_t)hist, z.shift.step };
+            const chz_mix_kernel_t kern = grid10 ? chz_grid10_mix_kernel_for(z.M, format) : chz_narrow_mix_kernel_for(z.M, z.D, format);
+            if (!kern) return -EINVAL;
+            hipLaunchKernelGGL(kern, dim3((nframes + fr - 1) / fr), dim3(256), 0, s, ma);
+        } else {
+            const chz_narrow_kernel_t kern = grid10 ? chz_grid10_kernel_for(z.M, format) : chz_narrow_kernel_for(z.M, z.D, format);
+            if (!kern) return -EINVAL;
+            hipLaunchKernelGGL(kern, dim3((nframes + fr - 1) / fr), dim3(256), 0, s, na);
+        }
     } else if (nframes) {
         a.block = (const float2 *)d; a.carry = z.carry[z.carry_cur].get(); a.taps = z.taps.get(); a.out = z.out.get(); a.ld = z.ld;
         a.carry_len = z.carry_len; a.nsamp = (uint32_t)nsamp; a.nframes = nframes; a.hist = hist;

@@ -26,6 +26,7 @@
 #include <vector>
 #include "recc_chz_common.hip.h"
 #include "recc_chz_fft.hip.h"
+#include "recc_xlate.hip.h"         // xl_mix: the mixing twins (amps_recc_set_wideband_shift)
 
 namespace amps {
 
@@ -42,6 +43,17 @@ struct ChzNarrowArgs {
     uint32_t nframes;        // frames this launch produces: a multiple of the roll's period
     uint32_t n_channels;
 };
+
+// The mixing twins' arguments (chz_narrow_mix_kernel, chz_grid10_mix_kernel): the bank's, untouched, and the mixer's behind them, by
+// value with every launch -- a new shift needs no device write.
+struct ChzMixArgs {
+    ChzNarrowArgs bank;
+    int64_t abs0;            // absolute wideband index of carry element 0: frames_done D - hist, negative in front of the stream
+    uint64_t step;           // shift_hz / fs as a 0.64 fixed-point fraction of a turn per sample (xlate_steps_from)
+};
+// what a thread staged for carry-relative sample ci, mixed: x e^{-j 2 pi frac(n step)} with n the sample's absolute index, by xl_mix
+// as the translate seams define it -- per sample, no running rotation, so the bits depend on nothing but the sample and n
+__device__ __forceinline__ cf2 chz_mix_staged(cf2 v, const ChzMixArgs &m, uint64_t ci) { return xl_mix(make_float2(v.x, v.y), (uint64_t)m.abs0 + ci, m.step); }
 
 __host__ __device__ constexpr bool chz_narrow_geometry(int M, int D) { return (M == 512 || M == 256 || M == 128) && (2 * D == M || 4 * D == 3 * M); }
 // frames per workgroup
@@ -154,7 +166,18 @@ __global__ __launch_bounds__(256) void chz_narrow_b8_kernel(ChzNarrowArgs a)
 #include "recc_chz_narrow_body.inc"
 }
 
+// the mixing twin, every sample type behind one name: the staging loop mixes, the rest is the body as it stands
+template <int M, int DEC, typename T>
+__global__ __launch_bounds__(256) void chz_narrow_mix_kernel(ChzMixArgs m)
+{
+    const ChzNarrowArgs &a = m.bank;
+#define CHZ_BODY_MIX m
+#include "recc_chz_narrow_body.inc"
+#undef CHZ_BODY_MIX
+}
+
 typedef void (*chz_narrow_kernel_t)(ChzNarrowArgs);
+typedef void (*chz_mix_kernel_t)(ChzMixArgs);
 template <int M, typename T> chz_narrow_kernel_t chz_narrow_kernel_of(int D)
 {
     if constexpr (sizeof(T) == 2) return 2 * D == M ? chz_narrow_b8_kernel<M, M / 2, T> : chz_narrow_b8_kernel<M, 3 * M / 4, T>;
@@ -179,6 +202,28 @@ inline chz_narrow_kernel_t chz_narrow_kernel_for(int M, int D, int format)
     case 512: return chz_narrow_kernel_of<512>(D, format);
     case 256: return chz_narrow_kernel_of<256>(D, format);
     default: return chz_narrow_kernel_of<128>(D, format);
+    }
+}
+
+template <int M, typename T> chz_mix_kernel_t chz_narrow_mix_kernel_of(int D) { return 2 * D == M ? chz_narrow_mix_kernel<M, M / 2, T> : chz_narrow_mix_kernel<M, 3 * M / 4, T>; }
+template <int M> chz_mix_kernel_t chz_narrow_mix_kernel_of(int D, int format)
+{
+    switch (format) {
+    case AMPS_RECC_SAMPLES_FC32: return chz_narrow_mix_kernel_of<M, float2>(D);
+    case AMPS_RECC_SAMPLES_SC16: return chz_narrow_mix_kernel_of<M, chz_sc16>(D);
+    case AMPS_RECC_SAMPLES_SC8: return chz_narrow_mix_kernel_of<M, xl_sc8>(D);
+    case AMPS_RECC_SAMPLES_CU8: return chz_narrow_mix_kernel_of<M, xl_cu8>(D);
+    default: return nullptr;
+    }
+}
+// the mixing twin of chz_narrow_kernel_for's instantiation
+inline chz_mix_kernel_t chz_narrow_mix_kernel_for(int M, int D, int format)
+{
+    if (!chz_narrow_geometry(M, D)) return nullptr;
+    switch (M) {
+    case 512: return chz_narrow_mix_kernel_of<512>(D, format);
+    case 256: return chz_narrow_mix_kernel_of<256>(D, format);
+    default: return chz_narrow_mix_kernel_of<128>(D, format);
     }
 }
 

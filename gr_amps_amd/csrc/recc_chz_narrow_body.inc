@@ -8,6 +8,9 @@
 // changed -- all twelve chz_narrow_kernel instantiations came out as different code with the argument by reference (4 to 82 lines
 // longer), and six of them with the argument by value.  As text they compile to the instruction stream they had before the 8-bit
 // entry point existed.
+// A third entry point, chz_narrow_mix_kernel (amps_recc_set_wideband_shift), defines CHZ_BODY_MIX as its ChzMixArgs around the include:
+// what a thread loaded is then mixed by the sample's absolute index (chz_mix_staged) on its way into LDS, and nothing else differs.
+// The other two do not define it and see the text they saw before.
     static_assert(chz_narrow_geometry(M, DEC), "M = 512, 256 or 128 at D = M / 2 or 3 M / 4");
     constexpr int FR = chz_narrow_fr(M, DEC), S = chz_narrow_stride(M), NST = chz_narrow_stage(M, DEC);
     constexpr int E = FR * M / 256;                              // (frame, branch) pairs, and later (bin, frame) pairs, per thread
@@ -52,6 +55,9 @@
                     const float2 c = *(in_carry ? a.carry + ci : in_block ? blk + bi : a.carry);
                     v[b] = (in_carry || in_block) ? (cf2){ c.x, c.y } : (cf2){ 0.f, 0.f };
                 }
+#ifdef CHZ_BODY_MIX                                              // the mixing twin: see the top of this file
+                v[b] = chz_mix_staged(v[b], CHZ_BODY_MIX, ci);
+#endif
             }
 #pragma unroll
             for (int b = 0; b < BATCH; b++) {

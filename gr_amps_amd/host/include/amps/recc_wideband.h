@@ -50,8 +50,14 @@ public:
     //         15.36 Msps; 3 (cu8) = two offset-binary bytes.  Items of 8, 4, 2 and 2 bytes, pushed as they are
     //         (amps_recc_push_wideband_as: no float copy on the host).  A non-zero input_format other than 1 together with
     //         short_input = true throws, as does an unknown format; set_rccl is refused on every integer format.
+    // shift_hz: the tuner's frequency error, corrected inside the filter bank (amps_recc_set_wideband_shift: every bank but the 1024
+    //         one): the frequency in the delivered stream of what shall land on bin 0's centre, +e for a radio that delivers
+    //         everything e hertz too high.  0 = none.  A non-zero shift on a 1024 bank, or beyond +- fs / 2, throws.
     static sptr make(int n_channels = 832, int first_bin = 96, int slicer = -1, int groups = 0, int group = 0, int decim = 0, bool short_input = false,
-                     bool channel_power = false, int channels = 1024, int input_format = 0);
+                     bool channel_power = false, int channels = 1024, int input_format = 0, double shift_hz = 0.0);
+    // Replace the shift in mid-stream: in force from the next work() call on, nothing reset, and from then on the bank delivers what a
+    // block made with this shift would.  Throws where the library refuses (NaN, beyond +- fs / 2, a 1024 bank).
+    virtual void set_shift(double shift_hz) = 0;
     // Let ONE rank own the stream: after this call (a collective over all `nranks` blocks; `id` = the 128 bytes one of them got from
     // rccl_unique_id(), carried between the processes by the application) work() distributes rank `root`'s input over xGMI with RCCL
     // inside amps_recc_push_wideband_dist (mode 0 = flat broadcast, 1 = scatter + all-gather: AMPS_RECC_DIST_*).  The other ranks'

@@ -42,7 +42,7 @@ public:
         return short_input ? AMPS_RECC_SAMPLES_SC16 : input_format;
     }
 
-    recc_wideband_impl(int C, int first_bin, int slicer, int groups, int group, int decim, bool short_input, bool channel_power, int channels, int input_format)
+    recc_wideband_impl(int C, int first_bin, int slicer, int groups, int group, int decim, bool short_input, bool channel_power, int channels, int input_format, double shift_hz)
         : gr::sync_block("recc_wideband", gr::io_signature::make(1, 1, (int)item_size(checked_format(short_input, input_format))), gr::io_signature::make(0, 0, 0)),
           d_handle(nullptr), d_recs(kMaxRecs), d_bursts((size_t)kMaxRecs * AMPS_RECC_CAPTURE_SYMS), d_format(checked_format(short_input, input_format)), d_power(channel_power),
           d_pow(channel_power ? kMaxRecs : 0), d_nsnap(channel_power ? kMaxRecs : 0)
@@ -67,11 +67,20 @@ public:
         cfg.wideband_first_channel = (uint32_t)first_bin;
         int rc = amps_recc_create(&d_handle, &cfg);
         if (rc != 0) throw std::runtime_error(std::string("amps::recc_wideband: ") + amps_recc_strerror(rc));
+        if (shift_hz != 0.0) {
+            try { set_shift(shift_hz); } catch (...) { amps_recc_destroy(d_handle); throw; }
+        }
         message_port_register_out(pmt::mp("bursts"));
         message_port_register_out(pmt::mp("records"));
         if (d_power) message_port_register_out(pmt::mp("power"));
     }
     ~recc_wideband_impl() { amps_recc_destroy(d_handle); }
+
+    void set_shift(double shift_hz)
+    {
+        int rc = amps_recc_set_wideband_shift(d_handle, shift_hz);
+        if (rc != 0) throw std::runtime_error(std::string("amps::recc_wideband: shift: ") + amps_recc_strerror(rc));
+    }
 
     void set_rccl(const std::string &id, int nranks, int rank, int root, int mode)
     {
@@ -148,9 +157,9 @@ public:
     }
 };
 
-recc_wideband::sptr recc_wideband::make(int n_channels, int first_bin, int slicer, int groups, int group, int decim, bool short_input, bool channel_power, int channels, int input_format)
+recc_wideband::sptr recc_wideband::make(int n_channels, int first_bin, int slicer, int groups, int group, int decim, bool short_input, bool channel_power, int channels, int input_format, double shift_hz)
 {
-    return gnuradio::get_initial_sptr(new recc_wideband_impl(n_channels, first_bin, slicer, groups, group, decim, short_input, channel_power, channels, input_format));
+    return gnuradio::get_initial_sptr(new recc_wideband_impl(n_channels, first_bin, slicer, groups, group, decim, short_input, channel_power, channels, input_format, shift_hz));
 }
 
 std::string recc_wideband::rccl_unique_id()

@@ -65,7 +65,9 @@ extern "C" {
                                      still 4, two entry points added and nothing changed: amps_recc_push_wideband_as / _debug_channelize_as, the
                                      wideband seam on 8-bit I/Q (sc8, cu8), read in place on every bank;
                                      still 4, one entry point added and nothing changed: amps_recc_wideband_grid_plan, with cfg.wideband_channels =
-                                     2500, 2000, 1000 and 500 at wideband_decim = M / 4, the wideband seam at 25, 20, 10 and 5 Msps) */
+                                     2500, 2000, 1000 and 500 at wideband_decim = M / 4, the wideband seam at 25, 20, 10 and 5 Msps;
+                                     still 4, two entry points added and nothing changed: amps_recc_set_wideband_shift / amps_recc_wideband_shift,
+                                     a tuner's frequency error corrected inside the banks below 1024 branches) */
 
 /* protocol constants of the reference */
 #define AMPS_RECC_TRIGGER_SYMS 74   /* lib/recc_impl.cc:76-77: 37 bits x 2 Manchester symbols   */
@@ -515,6 +517,32 @@ int amps_recc_debug_xlate_as(amps_recc_t *h, const void *iq, size_t ld, size_t n
 int amps_recc_push_wideband_as(amps_recc_t *h, const void *iq, size_t nsamp, int format, int mem);
 int amps_recc_debug_channelize_as(amps_recc_t *h, const void *iq, size_t nsamp, int format, int mem,
                                   float *out, size_t out_ld, size_t *nframes);
+
+/* The tuner's frequency error, corrected inside the filter bank: a bank has fixed bins, and a radio whose crystal is a few ppm off (1 ppm
+ * is 835 Hz at 835 MHz) delivers every channel that far from its bin's centre.  With a shift set, the bank runs on
+ *     z[n] = x[n] e^(-j 2 pi frac(n step))
+ * in place of x[n].  n is the wideband sample's absolute index, counted from the handle's creation or last amps_recc_reset
+ * (amps_recc_set_origin numbers channel-rate samples and does not move it).  step is shift_hz / fs as a 0.64 fixed-point fraction of a
+ * turn, fs = wideband_channels x 30 kHz, or x 10 kHz at the banks of 10 kHz bins.  The product is the translate seams' mixer: the phasor
+ * from the top 24 bits of the wrapped 64-bit product n step through sincospif, one fp32 complex multiply, evaluated per sample from
+ * the absolute index and never as a running rotation.  A sample gets the same bits whichever workgroup stages it, whichever push it
+ * arrived in and whatever format it had.
+ * Sign: shift_hz is the frequency in the delivered stream of what shall land on bin 0's centre.  A radio that delivers everything e
+ * hertz too high gets shift_hz = +e.
+ * The shift takes effect with the next push or debug tap.  Nothing is reset: taps, carry (which keeps UNMIXED input: every launch
+ * mixes all it stages with the step in force), positions and everything behind the bank are kept; no device write, no host wait, so
+ * the call may be made between drain_begin and drain_end.  shift_hz == 0, the state after create, runs the unmixed kernels: the
+ * behaviour without this call, bit for bit.  amps_recc_reset keeps the shift and restarts n at 0.
+ * Contract, as for amps_recc_retune_xlate: from the first push after the call the bank's output is bit for bit that of a twin handle
+ * that had the new shift from the start and was fed the same pushes.  Records of bursts whose dotting begins at least 2048
+ * channel-rate samples after that push's first frame are byte-identical to the twin's; the one discriminator product and the ring
+ * blocks that span the change are not.
+ * -EINVAL: h == NULL, a NaN, |shift_hz| > fs / 2.  -ENOSYS: a handle without the wideband seam, or with wideband_channels = 1024 (the
+ * fused bank has no mixing form; radios that reach 30.72 Msps have a TCXO).  A refused call leaves the handle as it was.
+ * amps_recc_wideband_shift reads the shift in force back as quantised to the step, within fs 2^-64 of what was set (-EINVAL for a
+ * NULL argument, -ENOSYS as above). */
+int amps_recc_set_wideband_shift(amps_recc_t *h, double shift_hz);
+int amps_recc_wideband_shift(const amps_recc_t *h, double *shift_hz);
 
 /* Retune: replace the centres of the translate form configured last (amps_recc_set_xlate, _set_xlate_shared or _set_xlate_resampled)
  * in mid-stream.  Taps, carry, absolute positions, the decimation or L / M and everything behind the stage are kept; nothing is
