@@ -128,7 +128,7 @@ extern "C" {
 
 int amps_recc_abi_version(void) { return AMPS_RECC_ABI_VERSION; }
 int amps_recc_default_slicer(void) { return AMPS_SLICER_DEFAULT; }
-uint32_t amps_recc_default_wideband_decim(void) { return (uint32_t)CHZ_D768; }
+uint32_t amps_recc_default_wideband_decim(void) { return chz_bank_of(CHZ_M)->default_decim; }
 size_t amps_recc_burst_size(void) { return sizeof(amps_recc_burst_t); }
 
 const char *amps_recc_strerror(int code)
@@ -159,42 +159,22 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
     if (!out || !cfg_in) return -EINVAL;
     *out = nullptr;
     if (cfg_in->struct_size != sizeof(amps_recc_cfg_t)) return -EINVAL;
-    amps_recc_cfg_t cfg_v = *cfg_in;                                  // wideband handles: decimation 0 = the library default, samples per symbol 0 = what goes with it
-    const bool narrow = chz_is_narrow(cfg_v.wideband_channels);       // the banks of 512, 256 and 128 branches: the library's default ratio D = 3 M / 4
-    const bool grid10 = chz_is_grid10(cfg_v.wideband_channels);       // the banks of 2500, 2000, 1000 and 500 branches of 10 kHz: D = M / 4, stated by the caller
-    if (cfg_v.wideband_channels) {
-        if (cfg_v.wideband_decim == 0 && !grid10) cfg_v.wideband_decim = narrow ? 3u * cfg_v.wideband_channels / 4u : amps_recc_default_wideband_decim();
-        if (!chz_geometry_ok(cfg_v.wideband_channels, cfg_v.wideband_decim)) return -EINVAL;
-        if (cfg_v.samples_per_symbol == 0) cfg_v.samples_per_symbol = grid10 ? 2u : 3u * cfg_v.wideband_channels / (2u * cfg_v.wideband_decim);
-    }
+    // everything that depends on the filter bank -- the wideband_* fields, a wideband handle's samples per symbol (decimation 0 = the
+    // bank's default, samples per symbol 0 = what goes with it), the flags a bank has or lacks -- is admitted and filled in in one place
+    amps_recc_cfg_t cfg_v;
+    uint32_t rows = 0;                                                // the handle's: its channels, or its channel group's share of them
+    if (int rc = chz_resolve_cfg(*cfg_in, &cfg_v, &rows)) return rc;
     const amps_recc_cfg_t *cfg = &cfg_v;
     if (cfg->n_channels < 1 || cfg->max_bursts < 1) return -EINVAL;
-    // the channelizer's geometry (M channels of 30 kHz at M x 30 ksps) delivers 60 ksps = 3 samples per Manchester symbol at D = M / 2 and
-    // 40 ksps = 2 at D = 3 M / 4; the bit-domain kernels behind it are built for exactly those.  Two samples per symbol exist on the wideband
-    // seam only: the streaming kernel has the instantiation (recc_front_kernel<2, ...>), reached by the two-kernel form -- the unfused 1024
-    // bank at D = 768 and every narrow bank at D = 3 M / 4, its default ratio -- and sps_supported refuses it to a handle of the IQ seam.
-    // The banks of 10 kHz bins (M x 10 ksps, D = M / 4) deliver the same 40 ksps.
-    const bool wide768 = cfg->wideband_channels && (grid10 || 4u * cfg->wideband_decim == 3u * cfg->wideband_channels);
-    if (cfg->max_samples_per_push && !(wide768 ? cfg->samples_per_symbol == 2 : sps_supported(cfg->samples_per_symbol))) return -EINVAL;
-    if (cfg->wideband_channels && (cfg->samples_per_symbol != (wide768 ? 2u : 3u) || cfg->max_samples_per_push == 0)) return -EINVAL;
+    // Two samples per symbol exist on the wideband seam only: the streaming kernel has the instantiation (recc_front_kernel<2, ...>),
+    // reached by the two-kernel form of a bank that delivers 40 ksps per channel, and sps_supported refuses it to a handle of the IQ seam
+    if (!cfg->wideband_channels && cfg->max_samples_per_push && !sps_supported(cfg->samples_per_symbol)) return -EINVAL;
     if (cfg->sync_tolerance > AMPS_RECC_MAX_SYNC_TOLERANCE) return -EINVAL;
     const uint32_t sl = cfg->flags & (AMPS_RECC_FLAG_SLICER_PRODUCT | AMPS_RECC_FLAG_SLICER_SINE | AMPS_RECC_FLAG_SLICER_ATAN | AMPS_RECC_FLAG_SLICER_EXACT);
     if (sl & (sl - 1)) return -EINVAL;                             // at most one slicer spec
     if (cfg->n_channels >= (1u << (64 - CAPQ_POS_BITS))) return -EINVAL;
-    // received power exists where the fused filter bank runs: the snapshot kernel re-reads that launch's block and carry
-    if ((cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER) && (!cfg->wideband_channels || narrow || grid10 || (cfg->flags & AMPS_RECC_FLAG_UNFUSED_WIDEBAND))) return -EINVAL;
-    // the narrow banks are the two-kernel form: no channel groups, and what the other wideband_* fields may hold
-    if (narrow && (cfg->wideband_groups > 1 || cfg->n_channels > cfg->wideband_channels || cfg->wideband_first_channel >= cfg->wideband_channels ||
-                   (cfg->wideband_taps_per_branch != 0 && cfg->wideband_taps_per_branch != 8))) return -EINVAL;
-    // ... and so are the banks of 10 kHz bins: a channel on every third bin, three taps per branch
-    if (grid10 && (cfg->wideband_groups > 1 || 3ull * cfg->n_channels > cfg->wideband_channels || cfg->wideband_first_channel >= cfg->wideband_channels ||
-                   (cfg->wideband_taps_per_branch != 0 && cfg->wideband_taps_per_branch != (uint32_t)CHZ_GRID10_P))) return -EINVAL;
-    // on the IQ and translate seams the channel-rate stream itself is read once more, for its power and for the carrier offset: flags
-    // of their own, for handles with the IQ seam and no 1024 bank (a narrow bank's block goes through the IQ seam's streaming kernel,
-    // which fills the rings there too).  Power combines with the offset in either statistic, and a handle keeps one offset ring with one of them
+    // power combines with the offset in either statistic, and a handle keeps one offset ring with one of them
     constexpr uint32_t OFFSET_FLAGS = AMPS_RECC_FLAG_STREAM_OFFSET | AMPS_RECC_FLAG_STREAM_OFFSET_UNIT;
-    if ((cfg->flags & (AMPS_RECC_FLAG_STREAM_POWER | OFFSET_FLAGS)) &&
-        ((cfg->wideband_channels && !narrow && !grid10) || cfg->max_samples_per_push == 0 || (cfg->flags & AMPS_RECC_FLAG_CHANNEL_POWER))) return -EINVAL;
     if ((cfg->flags & OFFSET_FLAGS) == OFFSET_FLAGS) return -EINVAL;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return -ENODEV;
@@ -212,13 +192,7 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
     if (!h) return -ENOMEM;
     h->cfg = *cfg;
     h->device = dev;
-    h->C = cfg->n_channels;
-    if (cfg->wideband_channels && cfg->wideband_groups > 1) {      // a channel-group handle owns only its group's rows
-        if (cfg->flags & AMPS_RECC_FLAG_UNFUSED_WIDEBAND) { delete h; return -EINVAL; }
-        const int rows = chz_rows(*cfg, nullptr, nullptr);
-        if (rows < 1) { delete h; return -EINVAL; }
-        h->C = (uint32_t)rows;
-    }
+    h->C = rows;
     h->sps = cfg->samples_per_symbol;
     h->slicer = (cfg->flags & AMPS_RECC_FLAG_SLICER_PRODUCT) ? AMPS_SLICER_PRODUCT
               : (cfg->flags & AMPS_RECC_FLAG_SLICER_SINE) ? AMPS_SLICER_SINE
@@ -345,8 +319,8 @@ static int push_wideband_block(amps_recc_t *h, const void *iq, size_t nsamp, int
     HIP_TRY(hipSetDevice(h->device));
     // Fused form (default): filter bank + discriminator + boxcar + slicer in one kernel, then the bit-domain
     // correlator.  AMPS_RECC_FLAG_UNFUSED_WIDEBAND keeps the two-kernel form (channel-major intermediate in HBM), which is the only
-    // form of the narrow banks.
-    const bool fused = !(h->cfg.flags & AMPS_RECC_FLAG_UNFUSED_WIDEBAND) && h->chz.M == CHZ_M;
+    // form of the banks without a fused one.
+    const bool fused = !(h->cfg.flags & AMPS_RECC_FLAG_UNFUSED_WIDEBAND) && h->chz.has(CHZ_HAS_FUSED);
     const float2 *chan_iq = nullptr;
     uint64_t ld = 0;
     uint32_t nout = 0;
@@ -363,7 +337,7 @@ static int push_wideband_block(amps_recc_t *h, const void *iq, size_t nsamp, int
     if (rc) return rc;
     if (nout > h->cfg.max_samples_per_push) return -E2BIG;
     if (fused) return capture_run_bits(h->cap, h->lists, h->tm, h->stream.get(), nout);
-    return capture_run_iq(h->cap, h->lists, h->tm, h->stream.get(), chan_iq, ld, nout, power_of(h), offset_of(h));   // (rings: narrow banks only)
+    return capture_run_iq(h->cap, h->lists, h->tm, h->stream.get(), chan_iq, ld, nout, power_of(h), offset_of(h));   // (rings: CHZ_HAS_STREAM_RINGS only)
 }
 
 int amps_recc_push_wideband(amps_recc_t *h, const float *iq, size_t nsamp, int mem) { return push_wideband_block(h, iq, nsamp, mem, AMPS_RECC_SAMPLES_FC32); }
@@ -384,7 +358,7 @@ int amps_recc_rccl_unique_id(uint8_t *id)
 int amps_recc_rccl_init(amps_recc_t *h, const uint8_t *id, int nranks, int rank)
 {
     if (!h) return -EINVAL;
-    if (!h->chz.enabled || h->chz.M != CHZ_M) return -ENOSYS;    // one band over several GPUs is the 1024 bank's
+    if (!h->chz.has(CHZ_HAS_RCCL)) return -ENOSYS;              // one band over several GPUs is the 1024 bank's
     HIP_TRY(hipSetDevice(h->device));
     RcclLocal loc;
     loc.groups = h->cfg.wideband_groups >= 2 ? h->cfg.wideband_groups : 0;
@@ -625,35 +599,31 @@ int amps_recc_xlate_shared_plan(double rate_hz, double width_hz, amps_recc_xlate
     return n;
 }
 
-int amps_recc_wideband_plan(double rate_hz, amps_recc_wideband_plan_t *out, size_t cap)
+// both plan calls walk the bank table: the banks of 30 kHz bins in front of the banks of 10 kHz bins, a bank's default ratio first
+int amps_recc_wideband_grid_plan(double rate_hz, amps_recc_wideband_grid_plan_t *out, size_t cap)
 {
     if (!(rate_hz > 0.0) || std::isinf(rate_hz) || (cap && !out)) return -EINVAL;
     int n = 0;
-    for (uint32_t M = (uint32_t)CHZ_M; M >= 128u; M >>= 1) {
-        if (std::fabs(rate_hz - 30e3 * M) > 0.5) continue;
-        for (uint32_t D : { 3u * M / 4u, M / 2u }) {               // the default ratio first
-            if ((size_t)n < cap) out[n] = amps_recc_wideband_plan_t{ M, D, 3u * M / (2u * D), 8u * M };
+    for (const ChzBank &b : CHZ_BANKS) {
+        if (std::fabs(rate_hz - (double)b.sample_rate_hz()) > 0.5) continue;
+        for (uint32_t D : b.decim) {
+            if (!D) continue;
+            if ((size_t)n < cap) out[n] = amps_recc_wideband_grid_plan_t{ b.M, D, b.samples_per_symbol(D), b.taps * b.M, b.bin_hz, b.stride, b.max_channels(), 0u };
             n++;
         }
     }
     return n;
 }
 
-int amps_recc_wideband_grid_plan(double rate_hz, amps_recc_wideband_grid_plan_t *out, size_t cap)
+// the banks of 30 kHz bins, a channel on every bin: what the call above answers for their rates (at most two ratios of one bank)
+int amps_recc_wideband_plan(double rate_hz, amps_recc_wideband_plan_t *out, size_t cap)
 {
-    if (!(rate_hz > 0.0) || std::isinf(rate_hz) || (cap && !out)) return -EINVAL;
-    // the banks of 30 kHz bins: what amps_recc_wideband_plan answers, a channel on every bin
-    amps_recc_wideband_plan_t old[4];
-    int n = amps_recc_wideband_plan(rate_hz, old, 4);
-    if (n < 0) return n;
-    for (int i = 0; i < n && i < 4; i++)
-        if ((size_t)i < cap) out[i] = amps_recc_wideband_grid_plan_t{ old[i].channels, old[i].decim, old[i].samples_per_symbol, old[i].taps, 30000u, 1u, old[i].channels, 0u };
-    // the banks of 10 kHz bins: M = rate / 10 kHz branches, D = M / 4, a channel on every third bin
-    for (uint32_t M : { 2500u, 2000u, 1000u, 500u }) {
-        if (std::fabs(rate_hz - CHZ_GRID10_BIN_HZ * M) > 0.5) continue;
-        if ((size_t)n < cap) out[n] = amps_recc_wideband_grid_plan_t{ M, M / 4u, 2u, (uint32_t)CHZ_GRID10_P * M, (uint32_t)CHZ_GRID10_BIN_HZ, (uint32_t)CHZ_GRID10_STRIDE, M / (uint32_t)CHZ_GRID10_STRIDE, 0u };
-        n++;
-    }
+    if (cap && !out) return -EINVAL;
+    amps_recc_wideband_grid_plan_t g[2];
+    int n = amps_recc_wideband_grid_plan(rate_hz, g, 2);
+    if (n > 0 && g[0].channel_stride != 1u) n = 0;
+    for (int i = 0; i < n; i++)
+        if ((size_t)i < cap) out[i] = amps_recc_wideband_plan_t{ g[i].channels, g[i].decim, g[i].samples_per_symbol, g[i].taps };
     return n;
 }
 
@@ -690,13 +660,14 @@ int amps_recc_retune_xlate(amps_recc_t *h, const double *center_hz, size_t n)
 int amps_recc_set_wideband_shift(amps_recc_t *h, double shift_hz)
 {
     if (!h) return -EINVAL;
-    return wideband_shift_from(h->chz.enabled, (uint32_t)h->chz.M, chz_bin_hz((uint32_t)h->chz.M), shift_hz, &h->chz.shift);
+    const ChzBank *b = h->chz.bank;                            // null without the wideband seam
+    return wideband_shift_from(h->chz.has(CHZ_HAS_SHIFT), b ? b->M : 0u, b ? (double)b->bin_hz : 0.0, shift_hz, &h->chz.shift);
 }
 
 int amps_recc_wideband_shift(const amps_recc_t *h, double *shift_hz)
 {
     if (!h || !shift_hz) return -EINVAL;
-    if (!h->chz.enabled || h->chz.M == CHZ_M) return -ENOSYS;
+    if (!h->chz.has(CHZ_HAS_SHIFT)) return -ENOSYS;
     *shift_hz = h->chz.shift.hz;
     return 0;
 }

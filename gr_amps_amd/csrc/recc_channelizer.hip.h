@@ -21,7 +21,8 @@
 // frames.  Only slicer bits (1/64 of the input) reach HBM.  No MFMA: the contraction per channel is 8 taps deep and differs per
 // branch, and the FFT is a butterfly network (a DFT-16 as a matrix product costs 12x its flops at the f32 MFMA rate = the VALU rate).
 //
-// The parts, one concern per header: recc_chz_common.hip.h (constants, ChzArgs, sample types, packed fp32), recc_chz_fft.hip.h (the
+// The parts, one concern per header: recc_chz_banks.h (the table of bank sizes and the verdict on a cfg's wideband fields, free of HIP),
+// recc_chz_common.hip.h (constants, ChzArgs, sample types and their one list, packed fp32), recc_chz_fft.hip.h (the
 // passes and LDS layouts), recc_chz_fold.hip.h (register ring, loaders, fold; D = 512 and D = 768), recc_chz_slicer.hip.h (the fused
 // slicer), recc_chz12_body.hip.h (the kernel's body, as text).  This file: the kernels' entry points, the carry kernels and the host state.
 #pragma once
@@ -159,9 +160,9 @@ __global__ __launch_bounds__(768, 3) void chz12_short_kernel(ChzArgs a)
 
 struct ChannelizerState {
     bool enabled = false;
-    int P = 8;
-    int M = CHZ_M;                  // branches: 1024 (chz12_kernel), or 512, 256, 128 (chz_narrow_kernel) or 2500, 2000, 1000, 500 (chz_grid10_kernel): the two-kernel form only
-    int D = CHZ_D;                  // input samples per frame: M / 2 (3 samples per symbol) or 3 M / 4 (2); M / 4 (2) at the banks of 10 kHz bins
+    const ChzBank *bank = nullptr;  // the row of recc_chz_banks.h this handle runs: branches, family (which kernel), bin width, taps per branch, features
+    uint32_t D = CHZ_D;             // input samples per frame: one of the bank's decimations
+    bool has(uint32_t feature) const { return enabled && bank->has(feature); }   // CHZ_HAS_*: false without the seam
     uint32_t C = 0;                 // rows this handle decodes (= the band's channels, or one group of them)
     uint32_t groups = 1, group = 0; // cfg.wideband_groups / wideband_group
     DevBuf<uint16_t> bin2row;       // device [M]
@@ -169,16 +170,16 @@ struct ChannelizerState {
     uint32_t max_frames = 0;        // per push
     uint32_t target_wgs = 256;      // resident workgroups of the filter-bank kernel (one 768-thread workgroup per CU)
     DevBuf<float> taps;             // [L]
-    DevBuf<float2> twiddle;         // M < 1024: [M], e^{-2 pi i k / M}
+    DevBuf<float2> twiddle;         // the two-kernel families: [M], e^{-2 pi i k / M}
     DevBuf<float2> carry[2];
     int carry_cur = 0;
     uint32_t carry_len = 0;         // L - D + leftover
     uint64_t frames_done = 0;
-    WidebandShift shift;            // amps_recc_set_wideband_shift (M < 1024): a non-zero step launches the mixing twins.  Kept over a reset
+    WidebandShift shift;            // amps_recc_set_wideband_shift (CHZ_HAS_SHIFT): a non-zero step launches the mixing twins.  Kept over a reset
     DevBuf<float2> out;             // [C][ld]
     uint64_t ld = 0;
     HostStage stage;                // host-resident wideband input as the caller's samples (fc32, sc16, sc8 or cu8), sized in bytes: the largest block so far
-    DevBuf<float2> cvt;             // an integer block expanded to fc32, M = 1024 only: sc16 in the checking modes and the pre-pass experiment, sc8 / cu8 always
+    DevBuf<float2> cvt;             // an integer block expanded to fc32, the fused family only: sc16 in the checking modes and the pre-pass experiment, sc8 / cu8 always
     bool short_prepass = false;     // AMPS_RECC_SHORT_PREPASS=1 at create: sc16 blocks go through chz_short_to_float_kernel + the fc32 kernel
 };
 
@@ -189,15 +190,12 @@ inline double bessel_i0(double x)
     return s;
 }
 
-// Kaiser(beta = 8) windowed sinc at fs = M * bin_hz (30 kHz; 10 kHz at the banks of recc_chz_grid10.hip.h), unit DC gain; -6 dB at 13 kHz behind the D = M / 2 bank, at 15 kHz behind the D = 3 M / 4 one
-// (40 ksps per channel leave the slicer two sampling phases per symbol instead of three: the wider pass band gives back, under a
-// carrier offset, what the coarser timing costs -- profiles/r06/decim768_cpu_gonogo.txt; oracle/channelizer.py: cutoff_for_decim)
-// The banks of 10 kHz bins (D = M / 4) deliver 40 ksps per channel too and take the same 15 kHz.
-inline double chz_cutoff_hz(int D, int M = CHZ_M) { return (4 * D == 3 * M || chz_grid10_geometry(M, D)) ? 15.0e3 : 13.0e3; }
-inline std::vector<float> chz_design_taps(int P, int D = CHZ_D, int M = CHZ_M, double bin_hz = 30.0e3)
+// Kaiser(beta = 8) windowed sinc at the bank's sample rate, unit DC gain; -6 dB at the bank's cut-off for D input samples per frame
+// (ChzBank::cutoff_hz: 13 kHz in front of three samples per symbol, 15 kHz in front of two)
+inline std::vector<float> chz_design_taps(const ChzBank &bank, uint32_t D)
 {
-    const int L = P * M;
-    const double fc = chz_cutoff_hz(D, M) / (M * bin_hz);        // cycles per sample
+    const int L = (int)(bank.taps * bank.M);
+    const double fc = bank.cutoff_hz(D) / bank.sample_rate_hz();   // cycles per sample
     const double beta = 8.0, i0b = bessel_i0(beta);
     std::vector<double> h(L);
     double sum = 0.0;
@@ -215,89 +213,39 @@ inline std::vector<float> chz_design_taps(int P, int D = CHZ_D, int M = CHZ_M, d
     return out;
 }
 
-// samples of history the carry holds in front of a launch's frame 0: the filter's own L - D, and at M = 1024 the pre-roll's CHZ_PRE
-// frames (the narrow banks have no pre-roll: a workgroup stages its frames' whole history)
-inline uint32_t chz_hist(int P, int D, int M = CHZ_M) { return (uint32_t)(P * M - D + (M == CHZ_M ? CHZ_PRE * D : 0)); }
-inline size_t chz_carry_cap(int P, int D, int M = CHZ_M) { return (size_t)chz_hist(P, D, M) + 64 * D; }   // + leftover (< 64 frames)
-
 inline int channelizer_reset(ChannelizerState &z, hipStream_t s)
 {
     if (!z.enabled) return 0;
-    const size_t cap = chz_carry_cap(z.P, z.D, z.M);
+    const size_t cap = z.bank->carry_cap(z.D);
     if (hipMemsetAsync(z.carry[0].get(), 0, sizeof(float2) * cap, s) != hipSuccess) return -EIO;
     if (hipMemsetAsync(z.carry[1].get(), 0, sizeof(float2) * cap, s) != hipSuccess) return -EIO;
     z.carry_cur = 0;
-    z.carry_len = chz_hist(z.P, z.D, z.M);           // all-zero history, no leftover
+    z.carry_len = z.bank->hist(z.D);                 // all-zero history, no leftover
     z.frames_done = 0;
     return 0;
 }
 
 inline void channelizer_destroy(ChannelizerState &z) { z = ChannelizerState(); }
 
-// the bank sizes of chz_narrow_kernel
-inline bool chz_is_narrow(uint32_t M) { return M == 512 || M == 256 || M == 128; }
-// the bank sizes of chz_grid10_kernel: bins of 10 kHz, an AMPS channel on every third
-inline bool chz_is_grid10(uint32_t M) { return chz_grid10_size((int)M); }
-// what a bank of M branches is laid out for: the width of a bin, the bins from one channel to the next, the taps per branch
-inline double chz_bin_hz(uint32_t M) { return chz_is_grid10(M) ? CHZ_GRID10_BIN_HZ : 30.0e3; }
-inline uint32_t chz_channel_stride(uint32_t M) { return chz_is_grid10(M) ? (uint32_t)CHZ_GRID10_STRIDE : 1u; }
-inline uint32_t chz_taps_per_branch(uint32_t M) { return chz_is_grid10(M) ? (uint32_t)CHZ_GRID10_P : 8u; }
-// The geometries the seam serves: M = 1024, 512, 256 or 128 branches of 30 kHz at D = M / 2 or 3 M / 4 input samples per frame, and
-// M = 2500, 2000, 1000 or 500 branches of 10 kHz at D = M / 4
-inline bool chz_geometry_ok(uint32_t M, uint32_t D)
-{
-    if (chz_is_grid10(M)) return 4 * D == M;
-    return (M == (uint32_t)CHZ_M || chz_is_narrow(M)) && (2 * D == M || 4 * D == 3 * M);
-}
-
-// bins and rows of a handle: row i = the i-th channel (in band order) of the band selection -- n channels from bin `first` on, a bin
-// apart, or three on the banks of 10 kHz bins -- that belongs to the handle's group -- all of them without groups.  Returns the row count, or a negative errno for an invalid split.
-inline int chz_rows(const amps_recc_cfg_t &cfg, std::vector<uint16_t> *bin2row, std::vector<uint32_t> *row2chan)
-{
-    const uint32_t G = cfg.wideband_groups > 1 ? cfg.wideband_groups : 1u;
-    const uint32_t M = chz_is_narrow(cfg.wideband_channels) || chz_is_grid10(cfg.wideband_channels) ? cfg.wideband_channels : (uint32_t)CHZ_M;
-    const uint32_t stride = chz_channel_stride(M);
-    if ((G != 1 && G != 2 && G != 4 && G != 8) || cfg.wideband_group >= G) return -EINVAL;
-    if ((uint64_t)stride * cfg.n_channels > M || cfg.wideband_first_channel >= M) return -EINVAL;
-    const uint32_t W = 64u / G;
-    if (bin2row) bin2row->assign(M, (uint16_t)0xffffu);
-    if (row2chan) row2chan->clear();
-    uint32_t rows = 0;
-    for (uint32_t c = 0; c < cfg.n_channels; c++) {
-        const uint32_t k = (cfg.wideband_first_channel + stride * c) % M;
-        if ((k & 63u) / W != cfg.wideband_group) continue;
-        if (bin2row) (*bin2row)[k] = (uint16_t)rows;
-        if (row2chan) row2chan->push_back(c);
-        rows++;
-    }
-    return (int)rows;
-}
-
+// The filter bank of a cfg that chz_resolve_cfg has admitted and filled in: what can still fail here is allocation and copies.
 inline int channelizer_create(ChannelizerState &z, const amps_recc_cfg_t &cfg)
 {
-    if (!chz_geometry_ok(cfg.wideband_channels, cfg.wideband_decim)) return -EINVAL;
-    const int M = (int)cfg.wideband_channels;
-    const bool narrow = M != CHZ_M;
-    if (narrow && cfg.wideband_groups > 1) return -EINVAL;         // channel groups exist in the fused form, which the narrow banks do not have
-    const int P = cfg.wideband_taps_per_branch ? (int)cfg.wideband_taps_per_branch : (int)chz_taps_per_branch((uint32_t)M);
-    if (P != (int)chz_taps_per_branch((uint32_t)M)) return -EINVAL;   // the register ring of chz12_kernel is laid out for eight taps per branch, and so is chz_narrow_kernel's fold; chz_grid10_kernel's for three
-    if ((uint64_t)chz_channel_stride((uint32_t)M) * cfg.n_channels > (uint32_t)M || cfg.wideband_first_channel >= (uint32_t)M || cfg.max_samples_per_push == 0) return -EINVAL;
+    const ChzBank &bank = *chz_bank_of(cfg.wideband_channels);
+    const uint32_t M = bank.M, D = cfg.wideband_decim;
     std::vector<uint16_t> b2r;
-    const int rows = chz_rows(cfg, &b2r, &z.row2chan);
-    if (rows < 1) return rows < 0 ? rows : -EINVAL;
-    z.P = P; z.M = M; z.D = (int)cfg.wideband_decim; z.C = (uint32_t)rows;
+    z.C = chz_rows(bank, cfg, &b2r, &z.row2chan);
+    z.bank = &bank; z.D = D;
     z.groups = cfg.wideband_groups > 1 ? cfg.wideband_groups : 1u; z.group = cfg.wideband_group;
     if (z.bin2row.alloc(M)) return -ENOMEM;
     if (hipMemcpy(z.bin2row.get(), b2r.data(), sizeof(uint16_t) * M, hipMemcpyHostToDevice) != hipSuccess) return -EIO;
     z.max_frames = cfg.max_samples_per_push;
     z.ld = ((uint64_t)z.max_frames + 7) & ~7ull;
-    const size_t L = (size_t)P * M;
-    std::vector<float> h = chz_design_taps(P, z.D, M, chz_bin_hz((uint32_t)M));
-    if (z.taps.alloc(L)) return -ENOMEM;
-    if (hipMemcpy(z.taps.get(), h.data(), sizeof(float) * L, hipMemcpyHostToDevice) != hipSuccess) return -EIO;
-    if (z.carry[0].alloc(chz_carry_cap(P, z.D, M)) || z.carry[1].alloc(chz_carry_cap(P, z.D, M))) return -ENOMEM;
-    if (narrow) {
-        const std::vector<float2> w = chz_narrow_twiddles(M);
+    const std::vector<float> h = chz_design_taps(bank, D);
+    if (z.taps.alloc(h.size())) return -ENOMEM;
+    if (hipMemcpy(z.taps.get(), h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice) != hipSuccess) return -EIO;
+    if (z.carry[0].alloc(bank.carry_cap(D)) || z.carry[1].alloc(bank.carry_cap(D))) return -ENOMEM;
+    if (bank.family != ChzFamily::FUSED1024) {
+        const std::vector<float2> w = chz_narrow_twiddles((int)M);
         if (z.twiddle.alloc(M)) return -ENOMEM;
         if (hipMemcpy(z.twiddle.get(), w.data(), sizeof(float2) * M, hipMemcpyHostToDevice) != hipSuccess) return -EIO;
     }
@@ -314,6 +262,8 @@ inline int channelizer_create(ChannelizerState &z, const amps_recc_cfg_t &cfg)
     return 0;
 }
 
+static_assert(CHZ_BANKS[0].M == (uint32_t)CHZ_M && CHZ_BANKS[0].decim[0] == (uint32_t)CHZ_D768 && CHZ_BANKS[0].decim[1] == (uint32_t)CHZ_D && CHZ_BANKS[0].taps == 8u,
+              "recc_chz_banks.h states the 1024 bank as chz12_kernel is built");
 typedef void (*chz_kernel_t)(ChzArgs);
 // the filter-bank instantiation for (input samples per frame, fused slicer or channel-major IQ out, slicer spec, sample type of the
 // block: fc32, or sc16 read in place -- fused form only)
@@ -341,6 +291,48 @@ inline chz_kernel_t chz12_kernel_for(int D, bool fused, int slicer, bool sc16 = 
     return sc16 ? chz12_kernel_of<CHZ_D, true>(slicer) : chz12_kernel_of<CHZ_D, false>(slicer);
 }
 
+// The two-kernel families' instantiation for (branches, input samples per frame, sample type of the block, read in place), behind
+// Args = ChzNarrowArgs, or behind Args = ChzMixArgs its mixing twin.  The 8-bit types of the narrow banks go by a name of their own.
+template <class Args> using chz_bank_kernel_t = void (*)(Args);
+template <class Args, int M, int DEC, typename T> constexpr chz_bank_kernel_t<Args> chz_bank_kernel_of()
+{
+    constexpr bool mix = std::is_same<Args, ChzMixArgs>::value;
+    if constexpr (chz_grid10_size(M)) { if constexpr (mix) return chz_grid10_mix_kernel<M, T>; else return chz_grid10_kernel<M, T>; }
+    else if constexpr (mix) return chz_narrow_mix_kernel<M, DEC, T>;
+    else if constexpr (sizeof(T) == 2) return chz_narrow_b8_kernel<M, DEC, T>;
+    else return chz_narrow_kernel<M, DEC, T>;
+}
+// ... for (bank, one of its decimations, AMPS_RECC_SAMPLES_*); nullptr for a bank or a format there is none for
+template <class Args> inline chz_bank_kernel_t<Args> chz_bank_kernel_for(const ChzBank &bank, uint32_t D, int format)
+{
+    return chz_with_sample_type(format, [&](auto t) -> chz_bank_kernel_t<Args> {
+        using T = decltype(t);
+        const bool first = D == bank.decim[0];                    // 3 M / 4 at the narrow banks
+        switch (bank.M) {
+        case 512: return first ? chz_bank_kernel_of<Args, 512, 384, T>() : chz_bank_kernel_of<Args, 512, 256, T>();
+        case 256: return first ? chz_bank_kernel_of<Args, 256, 192, T>() : chz_bank_kernel_of<Args, 256, 128, T>();
+        case 128: return first ? chz_bank_kernel_of<Args, 128, 96, T>() : chz_bank_kernel_of<Args, 128, 64, T>();
+        case 2500: return chz_bank_kernel_of<Args, 2500, 625, T>();
+        case 2000: return chz_bank_kernel_of<Args, 2000, 500, T>();
+        case 1000: return chz_bank_kernel_of<Args, 1000, 250, T>();
+        case 500: return chz_bank_kernel_of<Args, 500, 125, T>();
+        default: return nullptr;
+        }
+    });
+}
+// the carry kernel behind a push of T, and the conversion to fc32 in front of the fused family's kernels (none for fc32 itself)
+template <typename T> constexpr auto chz_carry_kernel_of()
+{
+    if constexpr (std::is_same<T, float2>::value) return chz_carry_kernel;
+    else if constexpr (std::is_same<T, chz_sc16>::value) return chz_carry_short_kernel;
+    else return chz_carry_b8_kernel<T>;
+}
+template <typename T> constexpr auto chz_to_float_kernel_of()
+{
+    if constexpr (std::is_same<T, chz_sc16>::value) return chz_short_to_float_kernel;
+    else return chz_b8_to_float_kernel<T>;
+}
+
 // What channelizer_run is given: the block, the form, and what the fused form writes into.
 struct ChzRunIn {
     const void *iq = nullptr;                // `nsamp` new wideband samples, host or device (`mem`: AMPS_MEM_*)
@@ -361,11 +353,12 @@ struct ChzRunIn {
 // Channelise in.nsamp new wideband samples.
 inline int channelizer_run(ChannelizerState &z, const ChzRunIn &in, hipStream_t s, const float2 **chan_iq, uint64_t *ld, uint32_t *nframes_out)
 {
-    const bool narrow = z.M != CHZ_M;                             // chz_narrow_kernel: the two-kernel form whatever was asked, every sample format read in place
-    const bool fused = in.fused && !narrow;
+    if (!z.enabled) return -ENOSYS;
+    const ChzBank &bank = *z.bank;
+    const bool chz12 = bank.family == ChzFamily::FUSED1024;       // chz12_kernel; the other families: the two-kernel form whatever was asked, every sample format read in place
+    const bool fused = in.fused && bank.has(CHZ_HAS_FUSED);
     const size_t nsamp = in.nsamp;
     int format = in.format;
-    if (!z.enabled) return -ENOSYS;
     if (!chz_sample_bytes(format)) return -EINVAL;
     if (!fused && z.groups > 1) return -ENOSYS;                   // channel groups exist in the fused form only
     const void *d = in.iq;
@@ -377,15 +370,14 @@ inline int channelizer_run(ChannelizerState &z, const ChzRunIn &in, hipStream_t 
         d = staged;
     }
     if (!fused && !z.out && z.out.alloc((size_t)z.C * z.ld)) return -ENOMEM;
-    const uint32_t hist = chz_hist(z.P, z.D, z.M);
+    const uint32_t hist = bank.hist(z.D);
     const uint32_t leftover = z.carry_len - hist;
     const uint64_t avail = (uint64_t)leftover + nsamp;
-    // frames consumed: a multiple of two or four (a launch starts where the stream position is a multiple of M: frame parity 0 at
+    // frames consumed: whole periods of the roll (a launch starts where the stream position is a multiple of M: frame parity 0 at
     // D = M / 2, frame phase 0 of 4 at D = 3 M / 4 and at D = M / 4), and in the fused form a multiple of 64 (whole words of the RECC bit ring); the rest waits in the carry
-    const uint32_t nframes = (uint32_t)(avail / (uint32_t)z.D) & (fused ? ~63u : 2 * z.D == z.M ? ~1u : ~3u);
+    const uint32_t nframes = (uint32_t)(avail / z.D) & bank.frame_mask(z.D, fused);
     if (nframes > z.max_frames) return -E2BIG;
-    const bool b8 = format == AMPS_RECC_SAMPLES_SC8 || format == AMPS_RECC_SAMPLES_CU8;
-    if (!narrow && (b8 || (format == AMPS_RECC_SAMPLES_SC16 && (!fused || z.short_prepass)))) {
+    if (chz12 && format != AMPS_RECC_SAMPLES_FC32 && (format != AMPS_RECC_SAMPLES_SC16 || !fused || z.short_prepass)) {
         // the block as fc32 in a buffer of its own, then everything as for an fc32 block.  Stream order keeps the buffer safe: the
         // kernels of the previous push that read it run before this conversion
         if (z.cvt.capacity() < nsamp) {
@@ -393,33 +385,35 @@ inline int channelizer_run(ChannelizerState &z, const ChzRunIn &in, hipStream_t 
             if (z.cvt.reserve(nsamp)) return -ENOMEM;
         }
         const uint32_t blocks = (uint32_t)std::min<size_t>((nsamp + 255) / 256, 65536);
-        if (format == AMPS_RECC_SAMPLES_SC8) hipLaunchKernelGGL(chz_b8_to_float_kernel<xl_sc8>, dim3(blocks), dim3(256), 0, s, (const xl_sc8 *)d, z.cvt.get(), (uint32_t)nsamp);
-        else if (format == AMPS_RECC_SAMPLES_CU8) hipLaunchKernelGGL(chz_b8_to_float_kernel<xl_cu8>, dim3(blocks), dim3(256), 0, s, (const xl_cu8 *)d, z.cvt.get(), (uint32_t)nsamp);
-        else hipLaunchKernelGGL(chz_short_to_float_kernel, dim3(blocks), dim3(256), 0, s, (const chz_sc16 *)d, z.cvt.get(), (uint32_t)nsamp);
+        chz_with_sample_type(format, [&](auto t) {
+            using T = decltype(t);
+            if constexpr (!std::is_same<T, float2>::value) hipLaunchKernelGGL(chz_to_float_kernel_of<T>(), dim3(blocks), dim3(256), 0, s, (const T *)d, z.cvt.get(), (uint32_t)nsamp);
+            return 0;
+        });
         d = z.cvt.get();
         format = AMPS_RECC_SAMPLES_FC32;
     }
-    const bool sc16 = format == AMPS_RECC_SAMPLES_SC16;          // what is left of the formats at M = 1024
-    const uint32_t consumed = nframes * (uint32_t)z.D;                // virtual samples consumed (incl. leftover)
+    const bool sc16 = format == AMPS_RECC_SAMPLES_SC16;          // what is left of the formats in front of chz12_kernel
+    const uint32_t consumed = nframes * z.D;                          // virtual samples consumed (incl. leftover)
     const uint32_t new_left = (uint32_t)(avail - consumed);
     bool carry_in_kernel = false;
     ChzArgs a{};
-    if (nframes && narrow) {
+    if (nframes && !chz12) {
         ChzNarrowArgs na{};
         na.block = d; na.carry = z.carry[z.carry_cur].get(); na.taps = z.taps.get(); na.twiddle = z.twiddle.get(); na.out = z.out.get(); na.ld = z.ld;
         na.bin2row = z.bin2row.get(); na.carry_len = z.carry_len; na.nsamp = (uint32_t)nsamp; na.nframes = nframes; na.n_channels = z.C;
-        const bool grid10 = chz_is_grid10((uint32_t)z.M);
-        const uint32_t fr = (uint32_t)(grid10 ? chz_grid10_fr(z.M) : chz_narrow_fr(z.M, z.D));
+        const uint32_t fr = bank.fr[bank.decim_index(z.D)];
+        const dim3 grid((nframes + fr - 1) / fr);
         if (z.shift.step) {
             // every launch mixes all it stages, carry included (the carry keeps unmixed input), by the sample's absolute index
             const ChzMixArgs ma{ na, (int64_t)(z.frames_done * (uint64_t)z.D) - (int64_t)hist, z.shift.step };
-            const chz_mix_kernel_t kern = grid10 ? chz_grid10_mix_kernel_for(z.M, format) : chz_narrow_mix_kernel_for(z.M, z.D, format);
+            const auto kern = chz_bank_kernel_for<ChzMixArgs>(bank, z.D, format);
             if (!kern) return -EINVAL;
-            hipLaunchKernelGGL(kern, dim3((nframes + fr - 1) / fr), dim3(256), 0, s, ma);
+            hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, ma);
         } else {
-            const chz_narrow_kernel_t kern = grid10 ? chz_grid10_kernel_for(z.M, format) : chz_narrow_kernel_for(z.M, z.D, format);
+            const auto kern = chz_bank_kernel_for<ChzNarrowArgs>(bank, z.D, format);
             if (!kern) return -EINVAL;
-            hipLaunchKernelGGL(kern, dim3((nframes + fr - 1) / fr), dim3(256), 0, s, na);
+            hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, na);
         }
     } else if (nframes) {
         a.block = (const float2 *)d; a.carry = z.carry[z.carry_cur].get(); a.taps = z.taps.get(); a.out = z.out.get(); a.ld = z.ld;
@@ -447,14 +441,12 @@ inline int channelizer_run(ChannelizerState &z, const ChzRunIn &in, hipStream_t 
     if (a.tl) chz_timeline().dump("AMPS_RECC_CHZ_TIMELINE", CHZ_TL_STAMPS, s);   // the last launch's stamps
 #endif
     if (!carry_in_kernel) {
-        if (sc16) hipLaunchKernelGGL(chz_carry_short_kernel, dim3((hist + new_left + 255) / 256), dim3(256), 0, s, (const chz_sc16 *)d, z.carry[z.carry_cur].get(),
-                                     z.carry[z.carry_cur ^ 1].get(), z.carry_len, (uint32_t)nsamp, hist, consumed, hist + new_left);
-        else if (format == AMPS_RECC_SAMPLES_SC8) hipLaunchKernelGGL(chz_carry_b8_kernel<xl_sc8>, dim3((hist + new_left + 255) / 256), dim3(256), 0, s, (const xl_sc8 *)d, z.carry[z.carry_cur].get(),
-                                     z.carry[z.carry_cur ^ 1].get(), z.carry_len, (uint32_t)nsamp, hist, consumed, hist + new_left);
-        else if (format == AMPS_RECC_SAMPLES_CU8) hipLaunchKernelGGL(chz_carry_b8_kernel<xl_cu8>, dim3((hist + new_left + 255) / 256), dim3(256), 0, s, (const xl_cu8 *)d, z.carry[z.carry_cur].get(),
-                                     z.carry[z.carry_cur ^ 1].get(), z.carry_len, (uint32_t)nsamp, hist, consumed, hist + new_left);
-        else hipLaunchKernelGGL(chz_carry_kernel, dim3((hist + new_left + 255) / 256), dim3(256), 0, s, (const float2 *)d, z.carry[z.carry_cur].get(),
-                                z.carry[z.carry_cur ^ 1].get(), z.carry_len, (uint32_t)nsamp, hist, consumed, hist + new_left);
+        chz_with_sample_type(format, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(chz_carry_kernel_of<T>(), dim3((hist + new_left + 255) / 256), dim3(256), 0, s, (const T *)d, z.carry[z.carry_cur].get(),
+                               z.carry[z.carry_cur ^ 1].get(), z.carry_len, (uint32_t)nsamp, hist, consumed, hist + new_left);
+            return 0;
+        });
     }
     if (hipGetLastError() != hipSuccess) return -EIO;
     if (in.mem == AMPS_MEM_HOST) { if (int rc = z.stage.arm(s)) return rc; }

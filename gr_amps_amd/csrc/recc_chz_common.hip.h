@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "amps_recc.h"              // AMPS_RECC_SAMPLES_*
+#include "recc_chz_banks.h"         // the table of bank sizes; CHZ_PRE
 
 namespace amps {
 
@@ -39,7 +40,6 @@ struct ChzArgs {
     uint32_t consumed, carry_out_len;
     unsigned long long *tl;  // CHZ_TIMELINE builds: s_memtime stamps of workgroup 0 ([wave][step][8]), else unused
 };
-constexpr int CHZ_PRE = 4;   // frames of history the carry keeps beyond the filter's own L - D samples: what the exact half of a workgroup's pre-roll reaches back to
 
 typedef float cf2 __attribute__((ext_vector_type(2)));
 // A sample of the wideband block as the caller hands it over: fc32 (float2) or interleaved 16-bit I/Q ("sc16": I in the low half of
@@ -61,17 +61,21 @@ template <> struct chz_is_short<xl_sc8> { static constexpr bool value = true; };
 template <> struct chz_is_short<xl_cu8> { static constexpr bool value = true; };
 __device__ __forceinline__ cf2 chz_cvt(xl_sc8 s) { const float2 f = xl_cvt(s); return (cf2){ f.x, f.y }; }
 __device__ __forceinline__ cf2 chz_cvt(xl_cu8 s) { const float2 f = xl_cvt(s); return (cf2){ f.x, f.y }; }
-// bytes of one sample of a format (AMPS_RECC_SAMPLES_*); 0: no such format
-inline size_t chz_sample_bytes(int format)
+// The one list of sample formats (AMPS_RECC_SAMPLES_*): calls f with a value of the format's sample type -- a tag, only its type
+// matters -- and returns what f returns; a value-initialised result (0, nullptr) for a format there is none for.  A new format is a
+// `case` here and a chz_cvt above.
+template <class F> inline auto chz_with_sample_type(int format, F &&f) -> decltype(f(float2{}))
 {
     switch (format) {
-    case AMPS_RECC_SAMPLES_FC32: return sizeof(float2);
-    case AMPS_RECC_SAMPLES_SC16: return sizeof(chz_sc16);
-    case AMPS_RECC_SAMPLES_SC8: return sizeof(xl_sc8);
-    case AMPS_RECC_SAMPLES_CU8: return sizeof(xl_cu8);
-    default: return 0;
+    case AMPS_RECC_SAMPLES_FC32: return f(float2{});
+    case AMPS_RECC_SAMPLES_SC16: return f(chz_sc16{});
+    case AMPS_RECC_SAMPLES_SC8: return f(xl_sc8{});
+    case AMPS_RECC_SAMPLES_CU8: return f(xl_cu8{});
+    default: return {};
     }
 }
+// bytes of one sample of a format; 0: no such format
+inline size_t chz_sample_bytes(int format) { return chz_with_sample_type(format, [](auto t) { return sizeof(t); }); }
 // Buffer resource (V#) of the fast loader (round 6).  The fold role's prefetch used `global_load_dwordx2 v, v_off, s[base:base+1]` with
 // a 64-bit scalar base per frame: clamp the frame index to the block, multiply, subtract, shift, add with carry -- nine scalar
 // instructions per frame and two more per chunk, ~65 per half-step in the wave whose instruction count IS the kernel's critical path

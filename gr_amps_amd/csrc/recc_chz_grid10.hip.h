@@ -41,13 +41,22 @@
 namespace amps {
 
 constexpr int CHZ_GRID10_P = 3;                                  // taps per branch
-constexpr double CHZ_GRID10_BIN_HZ = 10.0e3;
-constexpr int CHZ_GRID10_STRIDE = 3;                             // bins from one 30 kHz channel to the next
 
 __host__ __device__ constexpr bool chz_grid10_size(int M) { return M == 2500 || M == 2000 || M == 1000 || M == 500; }
-__host__ __device__ constexpr bool chz_grid10_geometry(int M, int D) { return chz_grid10_size(M) && 4 * D == M; }
 // frames per workgroup
 __host__ __device__ constexpr int chz_grid10_fr(int M) { return M == 500 ? 8 : 4; }
+// ... which the host reads from the bank table: its GRID10 rows are exactly this header's sizes, taps and frames per workgroup
+constexpr bool chz_grid10_table_agrees()
+{
+    int n = 0;
+    for (const ChzBank &b : CHZ_BANKS) {
+        if (b.family != ChzFamily::GRID10) continue;
+        if (!chz_grid10_size((int)b.M) || 4u * b.decim[0] != b.M || b.decim[1] || b.taps != (uint32_t)CHZ_GRID10_P || (int)b.fr[0] != chz_grid10_fr((int)b.M)) return false;
+        n++;
+    }
+    return n == 4;
+}
+static_assert(chz_grid10_table_agrees(), "recc_chz_banks.h states the banks of 10 kHz bins as the kernels are built");
 // elements from one frame to the next in LDS: the smallest S >= M with S mod 32 = 32 / FR
 __host__ __device__ constexpr int chz_grid10_stride(int M) { return M + ((32 / chz_grid10_fr(M) - M % 32) % 32 + 32) % 32; }
 __host__ __device__ constexpr int chz_grid10_stage(int M) { return (chz_grid10_fr(M) - 1) * (M / 4) + CHZ_GRID10_P * M; }
@@ -109,50 +118,6 @@ __global__ __launch_bounds__(256) void chz_grid10_mix_kernel(ChzMixArgs m)
 #define CHZ_BODY_MIX m
 #include "recc_chz_grid10_body.inc"
 #undef CHZ_BODY_MIX
-}
-
-template <int M> chz_narrow_kernel_t chz_grid10_kernel_of(int format)
-{
-    switch (format) {
-    case AMPS_RECC_SAMPLES_FC32: return chz_grid10_kernel<M, float2>;
-    case AMPS_RECC_SAMPLES_SC16: return chz_grid10_kernel<M, chz_sc16>;
-    case AMPS_RECC_SAMPLES_SC8: return chz_grid10_kernel<M, xl_sc8>;
-    case AMPS_RECC_SAMPLES_CU8: return chz_grid10_kernel<M, xl_cu8>;
-    default: return nullptr;
-    }
-}
-// the instantiation for (branches, sample format of the block: AMPS_RECC_SAMPLES_*); nullptr for a size or a format there is none for
-inline chz_narrow_kernel_t chz_grid10_kernel_for(int M, int format)
-{
-    switch (M) {
-    case 2500: return chz_grid10_kernel_of<2500>(format);
-    case 2000: return chz_grid10_kernel_of<2000>(format);
-    case 1000: return chz_grid10_kernel_of<1000>(format);
-    case 500: return chz_grid10_kernel_of<500>(format);
-    default: return nullptr;
-    }
-}
-
-template <int M> chz_mix_kernel_t chz_grid10_mix_kernel_of(int format)
-{
-    switch (format) {
-    case AMPS_RECC_SAMPLES_FC32: return chz_grid10_mix_kernel<M, float2>;
-    case AMPS_RECC_SAMPLES_SC16: return chz_grid10_mix_kernel<M, chz_sc16>;
-    case AMPS_RECC_SAMPLES_SC8: return chz_grid10_mix_kernel<M, xl_sc8>;
-    case AMPS_RECC_SAMPLES_CU8: return chz_grid10_mix_kernel<M, xl_cu8>;
-    default: return nullptr;
-    }
-}
-// the mixing twin of chz_grid10_kernel_for's instantiation
-inline chz_mix_kernel_t chz_grid10_mix_kernel_for(int M, int format)
-{
-    switch (M) {
-    case 2500: return chz_grid10_mix_kernel_of<2500>(format);
-    case 2000: return chz_grid10_mix_kernel_of<2000>(format);
-    case 1000: return chz_grid10_mix_kernel_of<1000>(format);
-    case 500: return chz_grid10_mix_kernel_of<500>(format);
-    default: return nullptr;
-    }
 }
 
 } // namespace amps

@@ -20,42 +20,9 @@
 #pragma unroll
         for (int p = 0; p < P; p++) h[b][p] = a.taps[p * M + (t + 256 * b) % M];
 
-    // stage: sample i of the workgroup is carry-relative sample frame0 D + i; behind the stream's end (frames this launch does not
-    // produce) zeros.  As in the narrow banks' body: every load is unconditional, from an address that is valid whatever the sample is
-    // (element 0 of the carry, which is never empty, or of the block, which has a sample whenever a launch produces a frame), and what
-    // it returned is kept or replaced by zero afterwards, eight loads in flight per thread.  An integer block is read a sample per
-    // load, at the sample's own alignment
+    // stage the workgroup's input in LDS, expanded to fc32: recc_chz_stage.inc, the one text of both families' bodies
     {
-        constexpr int NLD = (NST + 255) / 256, BATCH = 8;
-        const uint64_t c0 = (uint64_t)frame0 * DEC;
-        const T *blk = (const T *)a.block;
-#pragma unroll 1
-        for (int i0 = 0; i0 < NLD; i0 += BATCH) {
-            cf2 v[BATCH];
-#pragma unroll
-            for (int b = 0; b < BATCH; b++) {
-                const uint64_t ci = c0 + (uint64_t)(t + 256 * (i0 + b));
-                const bool in_carry = ci < a.carry_len;
-                const uint64_t bi = ci - a.carry_len;
-                const bool in_block = !in_carry && bi < a.nsamp;
-                if constexpr (chz_is_short<T>::value) {
-                    const float2 c = a.carry[in_carry ? ci : 0];
-                    const cf2 s = chz_cvt(blk[in_block ? bi : 0]);
-                    v[b] = in_carry ? (cf2){ c.x, c.y } : in_block ? s : (cf2){ 0.f, 0.f };
-                } else {
-                    const float2 c = *(in_carry ? a.carry + ci : in_block ? blk + bi : a.carry);
-                    v[b] = (in_carry || in_block) ? (cf2){ c.x, c.y } : (cf2){ 0.f, 0.f };
-                }
-#ifdef CHZ_BODY_MIX                                              // the mixing twin: see the top of this file
-                v[b] = chz_mix_staged(v[b], CHZ_BODY_MIX, ci);
-#endif
-            }
-#pragma unroll
-            for (int b = 0; b < BATCH; b++) {
-                const int i = t + 256 * (i0 + b);
-                if (i < NST) xin[i] = v[b];
-            }
-        }
+#include "recc_chz_stage.inc"
     }
     __syncthreads();
 

@@ -58,6 +58,18 @@ __device__ __forceinline__ cf2 chz_mix_staged(cf2 v, const ChzMixArgs &m, uint64
 __host__ __device__ constexpr bool chz_narrow_geometry(int M, int D) { return (M == 512 || M == 256 || M == 128) && (2 * D == M || 4 * D == 3 * M); }
 // frames per workgroup
 __host__ __device__ constexpr int chz_narrow_fr(int M, int D) { return M == 512 ? (2 * D == M ? 8 : 4) : M == 256 ? 16 : 32; }
+// ... which the host reads from the bank table: its NARROW rows are exactly this header's geometries and frames per workgroup
+constexpr bool chz_narrow_table_agrees()
+{
+    int n = 0;
+    for (const ChzBank &b : CHZ_BANKS) {
+        if (b.family != ChzFamily::NARROW) continue;
+        for (int i = 0; i < 2; i++, n++)
+            if (!chz_narrow_geometry((int)b.M, (int)b.decim[i]) || b.taps != 8u || (int)b.fr[i] != chz_narrow_fr((int)b.M, (int)b.decim[i])) return false;
+    }
+    return n == 6;
+}
+static_assert(chz_narrow_table_agrees(), "recc_chz_banks.h states the narrow banks as the kernels are built");
 // LDS layout of a frame: element n at n + n / 32 (a store of stride 8 or 16 elements across lanes then walks the banks), frames S
 // elements apart, S odd (the store phase reads one bin of consecutive frames across lanes)
 __host__ __device__ constexpr int chz_narrow_pos(int n) { return n + (n >> 5); }
@@ -174,57 +186,6 @@ __global__ __launch_bounds__(256) void chz_narrow_mix_kernel(ChzMixArgs m)
 #define CHZ_BODY_MIX m
 #include "recc_chz_narrow_body.inc"
 #undef CHZ_BODY_MIX
-}
-
-typedef void (*chz_narrow_kernel_t)(ChzNarrowArgs);
-typedef void (*chz_mix_kernel_t)(ChzMixArgs);
-template <int M, typename T> chz_narrow_kernel_t chz_narrow_kernel_of(int D)
-{
-    if constexpr (sizeof(T) == 2) return 2 * D == M ? chz_narrow_b8_kernel<M, M / 2, T> : chz_narrow_b8_kernel<M, 3 * M / 4, T>;
-    else return 2 * D == M ? chz_narrow_kernel<M, M / 2, T> : chz_narrow_kernel<M, 3 * M / 4, T>;
-}
-template <int M> chz_narrow_kernel_t chz_narrow_kernel_of(int D, int format)
-{
-    switch (format) {
-    case AMPS_RECC_SAMPLES_FC32: return chz_narrow_kernel_of<M, float2>(D);
-    case AMPS_RECC_SAMPLES_SC16: return chz_narrow_kernel_of<M, chz_sc16>(D);
-    case AMPS_RECC_SAMPLES_SC8: return chz_narrow_kernel_of<M, xl_sc8>(D);
-    case AMPS_RECC_SAMPLES_CU8: return chz_narrow_kernel_of<M, xl_cu8>(D);
-    default: return nullptr;
-    }
-}
-// the instantiation for (branches, input samples per frame, sample format of the block: AMPS_RECC_SAMPLES_*); nullptr for a geometry
-// or a format there is none for
-inline chz_narrow_kernel_t chz_narrow_kernel_for(int M, int D, int format)
-{
-    if (!chz_narrow_geometry(M, D)) return nullptr;
-    switch (M) {
-    case 512: return chz_narrow_kernel_of<512>(D, format);
-    case 256: return chz_narrow_kernel_of<256>(D, format);
-    default: return chz_narrow_kernel_of<128>(D, format);
-    }
-}
-
-template <int M, typename T> chz_mix_kernel_t chz_narrow_mix_kernel_of(int D) { return 2 * D == M ? chz_narrow_mix_kernel<M, M / 2, T> : chz_narrow_mix_kernel<M, 3 * M / 4, T>; }
-template <int M> chz_mix_kernel_t chz_narrow_mix_kernel_of(int D, int format)
-{
-    switch (format) {
-    case AMPS_RECC_SAMPLES_FC32: return chz_narrow_mix_kernel_of<M, float2>(D);
-    case AMPS_RECC_SAMPLES_SC16: return chz_narrow_mix_kernel_of<M, chz_sc16>(D);
-    case AMPS_RECC_SAMPLES_SC8: return chz_narrow_mix_kernel_of<M, xl_sc8>(D);
-    case AMPS_RECC_SAMPLES_CU8: return chz_narrow_mix_kernel_of<M, xl_cu8>(D);
-    default: return nullptr;
-    }
-}
-// the mixing twin of chz_narrow_kernel_for's instantiation
-inline chz_mix_kernel_t chz_narrow_mix_kernel_for(int M, int D, int format)
-{
-    if (!chz_narrow_geometry(M, D)) return nullptr;
-    switch (M) {
-    case 512: return chz_narrow_mix_kernel_of<512>(D, format);
-    case 256: return chz_narrow_mix_kernel_of<256>(D, format);
-    default: return chz_narrow_mix_kernel_of<128>(D, format);
-    }
 }
 
 // e^{-2 pi i k / M}, k < M, rounded once from double precision

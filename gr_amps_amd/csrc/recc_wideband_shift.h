@@ -14,13 +14,13 @@ struct WidebandShift {
     double hz = 0.0;         // the shift in force, as quantised: within fs 2^-64 of what was asked
 };
 
-// The shift of a bank of M branches, bin_hz apart (fs = M bin_hz), from what the caller asks.  seam: the handle has the wideband seam.
-// -EINVAL for a NaN, -ENOSYS without the seam or at M = 1024 (the fused bank has no mixing twin), -EINVAL beyond +-fs / 2.  *out is
-// written only where the call succeeds.
-inline int wideband_shift_from(bool seam, uint32_t M, double bin_hz, double shift_hz, WidebandShift *out)
+// The shift of a bank of M branches, bin_hz apart (fs = M bin_hz), from what the caller asks.  has_shift: the handle has the wideband
+// seam and its bank a mixing twin (CHZ_HAS_SHIFT of recc_chz_banks.h: the fused bank has none).  -EINVAL for a NaN, -ENOSYS without
+// has_shift, -EINVAL beyond +-fs / 2.  *out is written only where the call succeeds.
+inline int wideband_shift_from(bool has_shift, uint32_t M, double bin_hz, double shift_hz, WidebandShift *out)
 {
     if (!out || std::isnan(shift_hz)) return -EINVAL;
-    if (!seam || M == 1024u) return -ENOSYS;
+    if (!has_shift) return -ENOSYS;
     const double fs = (double)M * bin_hz;
     if (!(std::fabs(shift_hz) <= 0.5 * fs)) return -EINVAL;
     uint64_t step = 0;

@@ -41,12 +41,13 @@ def test_header_and_binding_name_both_calls():
 def test_argument_checks_stand_alone_under_sanitizers(tmp_path):
     """gr_amps_amd/csrc/recc_wideband_shift.h is free of HIP: tests/wideband_shift_host.cc has its own main, is compiled with
     -fsanitize=address,undefined and run as a program of its own -- every refusal, steps of 0, +- fs / 4 and fs / 2, a negative
-    shift's two's complement, and the value read back within fs 2^-64 of what was set"""
+    shift's two's complement, and the value read back within fs 2^-64 of what was set.  Which bank has a shift is the bank table's word
+    (recc_chz_banks.h, CHZ_HAS_SHIFT), handed over as the library hands it: every bank below 1024 branches, and not the 1024 bank"""
     cxx = shutil.which("g++") or shutil.which("clang++") or shutil.which("c++")
     if not cxx:
         pytest.skip("no host C++ compiler")
     exe = str(tmp_path / "wideband_shift_host")
-    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I" + CSRC,
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I" + CSRC, "-I" + os.path.join(ROOT, "include"),
                     os.path.join(ROOT, "tests", "wideband_shift_host.cc"), "-o", exe], check=True)
     out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
     assert "wideband shift ok" in out
@@ -87,9 +88,9 @@ def test_mixing_twins_fit_their_originals_budget():
 
 
 def test_twins_add_no_inline_assembly_and_leave_every_kernel_as_it_was():
-    """the twins are the bodies' text with one call in the staging loop; what that call adds is plain C++ (xl_mix as it stands).  The
+    """the twins are the bodies' text with one call in the staging loop (recc_chz_stage.inc, which both bodies include); what that call adds is plain C++ (xl_mix as it stands).  The
     committed ISA comparison with the parent: nothing changed, nothing removed, the forty new names added"""
-    for f in ("recc_chz_narrow_body.inc", "recc_chz_grid10_body.inc", "recc_wideband_shift.h"):
+    for f in ("recc_chz_narrow_body.inc", "recc_chz_grid10_body.inc", "recc_chz_stage.inc", "recc_wideband_shift.h"):
         assert not re.search(r"\basm\b", open(os.path.join(CSRC, f)).read()), f
     narrow = open(os.path.join(CSRC, "recc_chz_narrow.hip.h")).read()
     mix = narrow[narrow.index("struct ChzMixArgs"):narrow.index("__host__ __device__ constexpr bool chz_narrow_geometry")]

@@ -1,10 +1,11 @@
 // Stand-alone host program (no HIP, no Python): the argument checks and the step arithmetic behind amps_recc_set_wideband_shift and
-// amps_recc_wideband_shift (gr_amps_amd/csrc/recc_wideband_shift.h).  tests/test_cpu_wideband_shift.py compiles it with
+// amps_recc_wideband_shift (gr_amps_amd/csrc/recc_wideband_shift.h; which bank has the shift: recc_chz_banks.h).  tests/test_cpu_wideband_shift.py compiles it with
 // -fsanitize=address,undefined and runs it.
 #include <cmath>
 #include <cstdio>
 #include <initializer_list>
 #include <limits>
+#include "recc_chz_banks.h"
 #include "recc_wideband_shift.h"
 
 #define CHECK(x) do { if (!(x)) { std::fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #x); return 1; } } while (0)
@@ -15,11 +16,14 @@ int main()
     const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
     const WidebandShift MARK{ 0x1234567890abcdefull, 4321.0 };
     const auto untouched = [&](const WidebandShift &w) { return w.step == MARK.step && w.hz == MARK.hz; };
+    // what the library hands over in the first argument of a handle with the wideband seam: whether its bank's row has a mixing twin
+    const auto has_shift = [](uint32_t M) { const ChzBank *b = chz_bank_of(M); return b && b->has(CHZ_HAS_SHIFT); };
 
     // every bank the call serves: fs = M x 30 kHz or M x 10 kHz
     const struct { uint32_t M; double bin; } banks[] = { { 512, 30e3 }, { 256, 30e3 }, { 128, 30e3 }, { 2500, 10e3 }, { 2000, 10e3 }, { 1000, 10e3 }, { 500, 10e3 } };
     for (const auto &b : banks) {
         const double fs = b.M * b.bin;
+        CHECK(has_shift(b.M) && chz_bank_of(b.M)->bin_hz == b.bin);
         WidebandShift w = MARK;
         // refused: the handle's state is as it was
         CHECK(wideband_shift_from(true, b.M, b.bin, nan, &w) == -EINVAL && untouched(w));
@@ -48,12 +52,13 @@ int main()
             CHECK(std::fabs(p.hz - hz) <= tol && std::fabs(n.hz + hz) <= tol);
         }
     }
-    // the 1024 bank has no mixing form
+    // the 1024 bank has no mixing form: its row of the bank table lacks CHZ_HAS_SHIFT
     {
         WidebandShift w = MARK;
-        CHECK(wideband_shift_from(true, 1024, 30e3, 1e3, &w) == -ENOSYS && untouched(w));
-        CHECK(wideband_shift_from(true, 1024, 30e3, 0.0, &w) == -ENOSYS && untouched(w));
-        CHECK(wideband_shift_from(true, 1024, 30e3, nan, &w) == -EINVAL && untouched(w));
+        CHECK(chz_bank_of(1024) && !has_shift(1024));
+        CHECK(wideband_shift_from(has_shift(1024), 1024, 30e3, 1e3, &w) == -ENOSYS && untouched(w));
+        CHECK(wideband_shift_from(has_shift(1024), 1024, 30e3, 0.0, &w) == -ENOSYS && untouched(w));
+        CHECK(wideband_shift_from(has_shift(1024), 1024, 30e3, nan, &w) == -EINVAL && untouched(w));
     }
     std::puts("wideband shift ok");
     return 0;
