@@ -115,6 +115,17 @@ class ResamplePlan(C.Structure):
     _fields_ = [("interp", C.c_uint32), ("decim", C.c_uint32), ("samples_per_symbol", C.c_uint32), ("ntaps_per_phase", C.c_uint32)]
 
 
+class WidebandResampleCfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("interp", C.c_uint32), ("decim", C.c_uint32), ("_pad", C.c_uint32),
+                ("rate_hz", C.c_double), ("cutoff_hz", C.c_double), ("width_hz", C.c_double)]
+
+
+class WidebandResamplePlan(C.Structure):
+    _fields_ = [("interp", C.c_uint32), ("decim", C.c_uint32), ("channels", C.c_uint32), ("bank_decim", C.c_uint32),
+                ("samples_per_symbol", C.c_uint32), ("ntaps_per_phase", C.c_uint32), ("bin_hz", C.c_uint32), ("channel_stride", C.c_uint32),
+                ("usable_hz", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class RcclInfo(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("alive", C.c_int32), ("nranks", C.c_int32), ("rank", C.c_int32),
@@ -160,10 +171,12 @@ EXPORTS = (
     "amps_recc_wideband_plan", "amps_recc_wideband_grid_plan",
     "amps_recc_push_wideband_as", "amps_recc_debug_channelize_as",
     "amps_recc_set_wideband_shift", "amps_recc_wideband_shift",
+    "amps_recc_set_wideband_resample", "amps_recc_wideband_resample_plan", "amps_recc_debug_wideband_resample",
 )
 GRID10_CHANNELS = (2500, 2000, 1000, 500)   # branches of the wideband seam's banks of 10 kHz bins: 25, 20, 10 and 5 Msps
 _WIDEBAND_AS = ("amps_recc_push_wideband_as", "amps_recc_debug_channelize_as")
 _WIDEBAND_SHIFT = ("amps_recc_set_wideband_shift", "amps_recc_wideband_shift")
+_WIDEBAND_RESAMPLE = ("amps_recc_set_wideband_resample", "amps_recc_wideband_resample_plan", "amps_recc_debug_wideband_resample")
 _XLATE_RESAMPLED = ("amps_recc_set_xlate_resampled", "amps_recc_xlate_resample_plan")
 _XLATE_AS = ("amps_recc_push_raw_shared_as", "amps_recc_push_raw_as", "amps_recc_debug_xlate_shared_as", "amps_recc_debug_xlate_as")
 _XLATE_SHARED = ("amps_recc_set_xlate_shared", "amps_recc_push_raw_shared", "amps_recc_debug_xlate_shared")
@@ -279,12 +292,16 @@ def load():
     if hasattr(L, "amps_recc_set_wideband_shift"):    # likewise
         L.amps_recc_set_wideband_shift.argtypes = [vp, C.c_double]
         L.amps_recc_wideband_shift.argtypes = [vp, C.POINTER(C.c_double)]
+    if hasattr(L, "amps_recc_set_wideband_resample"):   # likewise
+        L.amps_recc_set_wideband_resample.argtypes = [vp, C.POINTER(WidebandResampleCfg)]
+        L.amps_recc_wideband_resample_plan.argtypes = [C.c_double, C.POINTER(WidebandResamplePlan), C.c_size_t]
+        L.amps_recc_debug_wideband_resample.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.amps_bch_encode_words.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp]
     L.amps_bch_decode_words.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, vp, vp]
     for name in EXPORTS:
         if name in ("amps_recc_default_slicer", "amps_recc_default_wideband_decim", "amps_recc_debug_exact_slice", "amps_recc_rccl_unique_id", "amps_recc_rccl_init",
                     "amps_recc_push_wideband_bcast", "amps_recc_drain_gather", "amps_recc_debug_slicer_bits",
-                    "amps_recc_push_wideband_short", "amps_recc_xlate_shared_plan", "amps_recc_wideband_plan", "amps_recc_wideband_grid_plan") + _NEW_IN_ABI4 + _POWER + _OFFSET + _RETUNE + _XLATE_SHARED + _XLATE_AS + _XLATE_RESAMPLED + _WIDEBAND_AS + _WIDEBAND_SHIFT and not hasattr(L, name):
+                    "amps_recc_push_wideband_short", "amps_recc_xlate_shared_plan", "amps_recc_wideband_plan", "amps_recc_wideband_grid_plan") + _NEW_IN_ABI4 + _POWER + _OFFSET + _RETUNE + _XLATE_SHARED + _XLATE_AS + _XLATE_RESAMPLED + _WIDEBAND_AS + _WIDEBAND_SHIFT + _WIDEBAND_RESAMPLE and not hasattr(L, name):
             continue
         if name not in ("amps_recc_strerror", "amps_recc_burst_size", "amps_recc_destroy"):   # every other entry point returns int
             getattr(L, name).restype = C.c_uint32 if name == "amps_recc_power_ring_snaps" else C.c_int
@@ -431,12 +448,19 @@ class Recc:
             cfg.wideband_group = wideband.get("group", 0)
         self.n_channels, self.sps, self.max_bursts, self.max_samples = n_channels, sps, max_bursts, max_samples
         self.decim = int(wideband["decim"]) if wideband else None
+        self.resample = None                                   # (interp, decim) of the wideband seam's resampler, where one is set
         self._origin = 0
         self._h = C.c_void_p()
         rc = L.amps_recc_create(C.byref(self._h), C.byref(cfg))
         if rc != 0:
             self._h = None
             raise AmpsError(rc, "amps_recc_create")
+        if wideband and wideband.get("resample"):              # (rate_hz, interp, decim): blocks arrive at rate_hz
+            try:
+                self.set_wideband_resample(*wideband["resample"])
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "_h", None) and _lib is not None:
@@ -580,6 +604,40 @@ class Recc:
             raise AmpsError(rc, "amps_recc_wideband_shift")
         return hz.value
 
+    def set_wideband_resample(self, rate_hz, interp, decim, cutoff_hz=0.0, width_hz=0.0):
+        """The wideband seam for a rate that is no bank's: blocks arrive at rate_hz and are resampled by interp / decim to the bank's
+        rate on their way into the filter bank (amps_recc_set_wideband_resample; 8 Msps x 5/4 into the 1000 bank, 12.5 Msps x 2/1
+        into the 2500 bank, ...).  interp and decim are 1 ... 8 and coprime, 1/2 <= interp / decim <= 4; wideband_resample_plan(rate_hz)
+        lists what a rate admits.  Every push_wideband* and debug_channelize* then takes blocks at rate_hz; decim 0 removes the stage.
+        Before the first push, or after reset()."""
+        x = WidebandResampleCfg(C.sizeof(WidebandResampleCfg), int(interp), int(decim), 0, float(rate_hz), float(cutoff_hz), float(width_hz))
+        rc = load().amps_recc_set_wideband_resample(self._h, C.byref(x))
+        if rc:
+            raise AmpsError(rc, "amps_recc_set_wideband_resample")
+        self.resample = (int(interp), int(decim)) if int(decim) else None
+
+    def debug_wideband_resample(self, iq, format=SAMPLES_FC32):
+        """The resampler only (test tap), continuing its stream: a block in `format` at the delivered rate -> complex64 [nout] at the
+        bank's rate."""
+        if format == SAMPLES_FC32 and isinstance(iq, np.ndarray) and iq.dtype == np.complex64:
+            iq, n = np.ascontiguousarray(iq).reshape(-1), iq.size
+        else:
+            iq, n = _typed_block(iq, format, None, "debug_wideband_resample")
+        n = n or 0
+        ptr, mem, keep = _as_ptr(iq)
+        interp, decim = self.resample or (1, 1)
+        cap = n * interp // decim + 2
+        out = np.zeros(cap, np.complex64)
+        no = C.c_size_t(0)
+        rc = load().amps_recc_debug_wideband_resample(self._h, ptr, n, format, mem, _hostptr(out), cap, C.byref(no))
+        if rc:
+            raise AmpsError(rc, "amps_recc_debug_wideband_resample")
+        return out[:no.value].copy()
+
+    def _bank_samples(self, n):
+        """samples at the bank's rate that n delivered samples come to at the most"""
+        return n if not self.resample else n * self.resample[0] // self.resample[1] + 1
+
     def set_xlate_resampled(self, rate_hz, centers_hz, interp, decim, gain=0.0, cutoff_hz=0.0, width_hz=0.0):
         """set_xlate_shared for the rates no integer decimation serves: the shared stream is resampled by interp / decim (2.048 Msps
         x 5/64, 2.5 Msps x 2/25, ...) to the handle's sps x 20 kHz by a polyphase resampler behind the per-channel mix
@@ -720,7 +778,7 @@ class Recc:
         iq, n = _typed_block(iq, format, None, "debug_channelize_as")
         n = n or 0
         ptr, mem, keep = _as_ptr(iq)
-        cap = n // min(512, self.decim or 512) + 6          # as debug_channelize
+        cap = self._bank_samples(n) // min(512, self.decim or 512) + 6          # as debug_channelize
         out = np.zeros((self.n_channels, cap), np.complex64)
         nf = C.c_size_t(0)
         rc = load().amps_recc_debug_channelize_as(self._h, ptr, n, format, mem, _hostptr(out), cap, C.byref(nf))
@@ -875,7 +933,7 @@ class Recc:
             iq = np.ascontiguousarray(iq, np.complex64).reshape(-1)
         n = iq.shape[0]
         ptr, mem, keep = _as_ptr(iq)
-        cap = n // min(512, self.decim or 512) + 6          # the frames of the block, and up to four whose samples waited in the carry
+        cap = self._bank_samples(n) // min(512, self.decim or 512) + 6          # the frames of the block, and up to four whose samples waited in the carry
         out = np.zeros((self.n_channels, cap), np.complex64)
         nf = C.c_size_t(0)
         rc = load().amps_recc_debug_channelize(self._h, ptr, n, mem, _hostptr(out), cap, C.byref(nf))
@@ -1112,6 +1170,21 @@ def wideband_grid_plan(rate_hz):
     out = (WidebandGridPlan * max(n, 1))()
     n = L.amps_recc_wideband_grid_plan(rate_hz, out, n)
     return [(int(p.channels), int(p.decim), int(p.samples_per_symbol), int(p.taps), int(p.bin_hz), int(p.channel_stride), int(p.max_channels)) for p in out[:n]]
+
+
+def wideband_resample_plan(rate_hz):
+    """Which ratio into which bank for a wideband stream at a rate wideband_grid_plan has nothing for?  The (interp, decim, channels,
+    bank_decim, sps, ntaps_per_phase, bin_hz, channel_stride, usable_hz) Recc(wideband={"channels": .., "decim": .., "resample":
+    (rate_hz, interp, decim)}) accepts: 8e6 -> (5, 2, 2000, 500, ...), (5, 4, 1000, 250, ...), (5, 8, 500, 125, ...).  Needs no GPU
+    (amps_recc_wideband_resample_plan)."""
+    L = load()
+    n = L.amps_recc_wideband_resample_plan(rate_hz, None, 0)
+    if n < 0:
+        raise AmpsError(n, "amps_recc_wideband_resample_plan")
+    out = (WidebandResamplePlan * max(n, 1))()
+    n = L.amps_recc_wideband_resample_plan(rate_hz, out, n)
+    return [(int(p.interp), int(p.decim), int(p.channels), int(p.bank_decim), int(p.samples_per_symbol), int(p.ntaps_per_phase),
+             int(p.bin_hz), int(p.channel_stride), int(p.usable_hz)) for p in out[:n]]
 
 
 def resample_plan(rate_hz, width_hz=0.0):

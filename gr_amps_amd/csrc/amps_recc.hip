@@ -428,7 +428,8 @@ int amps_recc_push_wideband_dist(amps_recc_t *h, const float *iq, size_t nsamp, 
     if (npushed) *npushed = 0;
     if (!h) return -EINVAL;
     if (h->rccl.dead) return -ENOTCONN;
-    if (!h->chz.enabled || !h->rccl.comm) return -ENOSYS;
+    if (!h->chz.enabled || h->chz.rs.enabled) return -ENOSYS;  // behind a resampler: the blocks RCCL carries are at the bank's rate, whatever the communicator
+    if (!h->rccl.comm) return -ENOSYS;
     HIP_TRY(hipSetDevice(h->device));
     const float2 *blk = nullptr;
     int slot = 0;
@@ -669,6 +670,66 @@ int amps_recc_wideband_shift(const amps_recc_t *h, double *shift_hz)
     if (!h || !shift_hz) return -EINVAL;
     if (!h->chz.has(CHZ_HAS_SHIFT)) return -ENOSYS;
     *shift_hz = h->chz.shift.hz;
+    return 0;
+}
+
+// The resampler in front of the bank: admitted by wbr_admit, which the plan below asks too.  Nothing behind the resampler is touched.
+int amps_recc_set_wideband_resample(amps_recc_t *h, const amps_recc_wideband_resample_cfg_t *r)
+{
+    if (!h || !r || r->struct_size != sizeof(amps_recc_wideband_resample_cfg_t)) return -EINVAL;
+    ChannelizerState &z = h->chz;
+    if (!z.enabled) return -ENOSYS;
+    if (z.started) return -EBUSY;
+    HIP_TRY(hipSetDevice(h->device));
+    if (r->decim == 0) { z.rs = WbResampleState{}; return 0; }
+    WbrFilter f;
+    if (int rc = wbr_admit(*z.bank, r->interp, r->decim, r->rate_hz, r->cutoff_hz, r->width_hz, &f)) return rc;
+    return wb_resample_create(z.rs, r->interp, r->decim, r->rate_hz, f,
+                              xlate_design_taps((double)r->interp, r->interp * r->rate_hz, f.cutoff_hz, f.width_hz), h->stream.get());
+}
+
+int amps_recc_wideband_resample_plan(double rate_hz, amps_recc_wideband_resample_plan_t *out, size_t cap)
+{
+    if (!(rate_hz > 0.0) || std::isinf(rate_hz) || (cap && !out)) return -EINVAL;
+    int n = 0;
+    for (uint32_t interp = 1; interp <= WBR_MAX_LM; interp++)
+        for (uint32_t decim = 1; decim <= WBR_MAX_LM; decim++)
+            for (const ChzBank &b : CHZ_BANKS) {
+                WbrFilter f;
+                if (wbr_admit(b, interp, decim, rate_hz, 0.0, 0.0, &f)) continue;
+                for (uint32_t D : b.decim) {
+                    if (!D) continue;
+                    if ((size_t)n < cap)
+                        out[n] = amps_recc_wideband_resample_plan_t{ interp, decim, b.M, D, b.samples_per_symbol(D), f.npp, b.bin_hz, b.stride, (uint32_t)std::nearbyint(f.usable_hz), 0u };
+                    n++;
+                }
+            }
+    return n;
+}
+
+// test tap: the resampler alone, continuing its stream
+int amps_recc_debug_wideband_resample(amps_recc_t *h, const void *iq, size_t nsamp, int format, int mem, float *out, size_t cap, size_t *nout)
+{
+    if (!h || !iq || !out || !nout || !chz_sample_bytes(format)) return -EINVAL;
+    ChannelizerState &z = h->chz;
+    if (!z.enabled || !z.rs.enabled) return -ENOSYS;
+    if (wb_resample_count(z.rs, nsamp) > cap) return -E2BIG;
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = h->stream.get();
+    const void *d = iq;
+    if (mem == AMPS_MEM_HOST) {                                // (never armed: the call ends with the stream idle)
+        const size_t bytes = chz_sample_bytes(format) * nsamp;
+        const uint8_t *staged = nullptr;
+        uint64_t pitch = 0;
+        if (int rc = z.stage.stage((const uint8_t *)iq, bytes, bytes, 1, bytes, &staged, &pitch)) return rc;
+        d = staged;
+    }
+    uint32_t n = 0;
+    if (int rc = wb_resample_run(z.rs, d, nsamp, format, s, &n)) return rc;
+    z.started = true;
+    if (n) HIP_TRY(hipMemcpyAsync(out, z.rs.out.get(), sizeof(float2) * n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *nout = n;
     return 0;
 }
 

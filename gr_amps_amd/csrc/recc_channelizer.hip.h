@@ -44,6 +44,7 @@
 #include "recc_chz_narrow.hip.h"  // the banks of 512, 256 and 128 branches: a kernel of their own behind the same state, carry and host code
 #include "recc_wideband_shift.h"  // WidebandShift: the tuner correction of the banks below 1024 branches
 #include "recc_chz_grid10.hip.h"  // the banks of 2500, 2000, 1000 and 500 branches of 10 kHz (25, 20, 10 and 5 Msps): likewise
+#include "recc_wideband_resample.hip.h"   // WbResampleState: the L / M resampler in front of a bank, for the rates that are no bank's
 
 namespace amps {
 
@@ -181,6 +182,8 @@ struct ChannelizerState {
     HostStage stage;                // host-resident wideband input as the caller's samples (fc32, sc16, sc8 or cu8), sized in bytes: the largest block so far
     DevBuf<float2> cvt;             // an integer block expanded to fc32, the fused family only: sc16 in the checking modes and the pre-pass experiment, sc8 / cu8 always
     bool short_prepass = false;     // AMPS_RECC_SHORT_PREPASS=1 at create: sc16 blocks go through chz_short_to_float_kernel + the fc32 kernel
+    WbResampleState rs;             // amps_recc_set_wideband_resample: blocks arrive at rs.rate_hz and reach the bank through the resampler.  Kept over a reset
+    bool started = false;           // the seam has taken a block since create or reset: the resampler can no longer be set or removed
 };
 
 inline double bessel_i0(double x)
@@ -222,7 +225,8 @@ inline int channelizer_reset(ChannelizerState &z, hipStream_t s)
     z.carry_cur = 0;
     z.carry_len = z.bank->hist(z.D);                 // all-zero history, no leftover
     z.frames_done = 0;
-    return 0;
+    z.started = false;
+    return wb_resample_reset(z.rs, s);
 }
 
 inline void channelizer_destroy(ChannelizerState &z) { z = ChannelizerState(); }
@@ -357,13 +361,17 @@ inline int channelizer_run(ChannelizerState &z, const ChzRunIn &in, hipStream_t 
     const ChzBank &bank = *z.bank;
     const bool chz12 = bank.family == ChzFamily::FUSED1024;       // chz12_kernel; the other families: the two-kernel form whatever was asked, every sample format read in place
     const bool fused = in.fused && bank.has(CHZ_HAS_FUSED);
-    const size_t nsamp = in.nsamp;
+    // behind a resampler the bank sees the resampler's outputs: their number is host arithmetic, so that a push that is too large is
+    // refused below before anything moves
+    const uint64_t nsamp64 = z.rs.enabled ? wb_resample_count(z.rs, in.nsamp) : in.nsamp;
+    if (z.rs.enabled && nsamp64 > 0xffffffffull) return -E2BIG;
+    const size_t nsamp = (size_t)nsamp64;
     int format = in.format;
     if (!chz_sample_bytes(format)) return -EINVAL;
     if (!fused && z.groups > 1) return -ENOSYS;                   // channel groups exist in the fused form only
     const void *d = in.iq;
     if (in.mem == AMPS_MEM_HOST) {                                // one row of bytes, as the caller's samples
-        const size_t bytes = chz_sample_bytes(format) * nsamp;
+        const size_t bytes = chz_sample_bytes(format) * in.nsamp;
         const uint8_t *staged = nullptr;
         uint64_t pitch = 0;
         if (int rc = z.stage.stage((const uint8_t *)in.iq, bytes, bytes, 1, bytes, &staged, &pitch)) return rc;
@@ -377,6 +385,13 @@ inline int channelizer_run(ChannelizerState &z, const ChzRunIn &in, hipStream_t 
     // D = M / 2, frame phase 0 of 4 at D = 3 M / 4 and at D = M / 4), and in the fused form a multiple of 64 (whole words of the RECC bit ring); the rest waits in the carry
     const uint32_t nframes = (uint32_t)(avail / z.D) & bank.frame_mask(z.D, fused);
     if (nframes > z.max_frames) return -E2BIG;
+    if (z.rs.enabled) {
+        // the block at the delivered rate -> fc32 at the bank's rate in a buffer of the resampler's, then everything as for a device fc32 block
+        uint32_t n = 0;
+        if (int rc = wb_resample_run(z.rs, d, in.nsamp, format, s, &n)) return rc;
+        d = z.rs.out.get();
+        format = AMPS_RECC_SAMPLES_FC32;
+    }
     if (chz12 && format != AMPS_RECC_SAMPLES_FC32 && (format != AMPS_RECC_SAMPLES_SC16 || !fused || z.short_prepass)) {
         // the block as fc32 in a buffer of its own, then everything as for an fc32 block.  Stream order keeps the buffer safe: the
         // kernels of the previous push that read it run before this conversion
@@ -453,6 +468,7 @@ inline int channelizer_run(ChannelizerState &z, const ChzRunIn &in, hipStream_t 
     z.carry_cur ^= 1;
     z.carry_len = hist + new_left;
     z.frames_done += nframes;
+    z.started = true;
     if (chan_iq) *chan_iq = z.out.get();
     if (ld) *ld = z.ld;
     *nframes_out = nframes;

@@ -54,6 +54,7 @@
 #include "recc_chz_common.hip.h"    // cf2, cmul, chz_sc16
 #include "recc_devmem.hip.h"
 #include "recc_xlate_steps.h"
+#include "recc_firdes.h"            // xlate_ntaps, xlate_design_taps
 
 namespace amps {
 
@@ -447,32 +448,7 @@ struct XlateState {
     HostStage stage;                 // host-resident blocks: [rows][D * max_out / L]
 };
 
-// firdes.low_pass(gain, fs, cutoff, width, WIN_BLACKMAN) as the flow graph calls it (grc/recctest.grc:115-155):
-// ntaps = int(74 fs / (22 width)) made odd; windowed sinc normalised to DC gain `gain`
-inline int xlate_ntaps(double fs, double width)
-{
-    const double want = 74.0 * fs / (22.0 * width);
-    int n = want < 1e9 ? (int)want : 1000000000;                 // far beyond every kernel's limit
-    if (!(n & 1)) n++;
-    return n;
-}
-inline std::vector<float> xlate_design_taps(double gain, double fs, double cutoff, double width)
-{
-    const int n = xlate_ntaps(fs, width);
-    const int m = (n - 1) / 2;
-    std::vector<double> t((size_t)n);
-    const double w0 = 2.0 * M_PI * cutoff / fs;
-    double sum = 0.0;
-    for (int i = 0; i < n; i++) {
-        const int k = i - m;
-        const double win = 0.42 - 0.5 * std::cos(2.0 * M_PI * i / (n - 1)) + 0.08 * std::cos(4.0 * M_PI * i / (n - 1));
-        t[(size_t)i] = (k == 0 ? w0 / M_PI : std::sin(k * w0) / (k * M_PI)) * win;
-        sum += t[(size_t)i];
-    }
-    std::vector<float> out((size_t)n);
-    for (int i = 0; i < n; i++) out[(size_t)i] = (float)(t[(size_t)i] * gain / sum);
-    return out;
-}
+// the filter design, xlate_ntaps and xlate_design_taps: recc_firdes.h (host arithmetic only, shared with the wideband seam's resampler)
 
 // What a form accepts of a stream at rate_hz decimated by D for a handle of sps samples per symbol, in the order the configuration
 // answers: a filter the design formula can make, a kernel for D and the symbol rate met (-EINVAL), the filter's length within that

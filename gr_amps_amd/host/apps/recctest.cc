@@ -18,7 +18,8 @@
 //                                      2000, 1000 or 500: a capture at M x 10 kHz (25, 20, 10, 5 Msps) through the bank of M branches of
 //                                      10 kHz, the M / 3 channels on bins 0, 3, 6 ... at decim = M / 4, which recctest sets itself.  An argument
 //                                      `shift=<hz>` anywhere behind the file, with channels=<M>, corrects a tuner that delivered everything <hz>
-//                                      too high inside the bank (recc_wideband::make(..., shift_hz))
+//                                      too high inside the bank (recc_wideband::make(..., shift_hz)); `resample=<rate_hz>:<L>/<M>` likewise reads a file at
+//                                      rate_hz and resamples it by L / M into the bank (recc_wideband::make(..., rate_hz, interp, decim_in))
 //   recctest widerank <file.fc32> <chunk> <idfile> <nranks> <rank> [mode]   ONE rank of the same band over `nranks` processes (2, 4 or 8; one per GPU of a
 //                                      node): gr::amps::recc_wideband::make(832, 96, -1, nranks, rank) + set_rccl -- rank 0 owns the capture and the
 //                                      library distributes it (mode 0 = ncclBroadcast, 1 = scatter + all-gather); the other ranks' items only pace
@@ -162,10 +163,14 @@ int main(int argc, char **argv)
     // wide: `channels=<M>` anywhere behind the file selects a narrow bank; the positional arguments are what is left
     // and `shift=<hz>` the tuner correction of such a bank
     int wide_channels = 1024;
-    double wide_shift = 0.0;
+    double wide_shift = 0.0, wide_rate = 0.0;                   // resample=<rate_hz>:<L>/<M>: the file is at rate_hz, resampled by L / M into the bank
+    int wide_interp = 1, wide_decim_in = 1;
     for (int i = 3; mode == "wide" && i < argc;) {
         if (std::strncmp(argv[i], "channels=", 9) == 0) wide_channels = std::atoi(argv[i] + 9);
         else if (std::strncmp(argv[i], "shift=", 6) == 0) wide_shift = std::atof(argv[i] + 6);
+        else if (std::strncmp(argv[i], "resample=", 9) == 0) {
+            if (std::sscanf(argv[i] + 9, "%lf:%d/%d", &wide_rate, &wide_interp, &wide_decim_in) != 3 || !(wide_rate > 0.0)) { std::fprintf(stderr, "resample=<rate_hz>:<L>/<M>\n"); return 2; }
+        }
         else { i++; continue; }
         for (int j = i; j + 1 < argc; j++) argv[j] = argv[j + 1];
         argc--;
@@ -224,9 +229,9 @@ int main(int argc, char **argv)
             for (int i = 6; !ranks && i < argc && i < 9; i++) power = power || std::string(argv[i]) == "power";
             const bool grid10 = wide_channels == 2500 || wide_channels == 2000 || wide_channels == 1000 || wide_channels == 500;   // bins of 10 kHz
             auto src = ranks ? gr::amps::recc_wideband::make(832, 96, -1, nranks, rank)
-                             : grid10 ? gr::amps::recc_wideband::make(wide_channels / 3, 0, argc > 4 ? std::atoi(argv[4]) : -1, 0, 0, wide_channels / 4, false, power, wide_channels, format, wide_shift)
-                             : wide_channels != 1024 ? gr::amps::recc_wideband::make(wide_channels, 0, argc > 4 ? std::atoi(argv[4]) : -1, 0, 0, argc > 5 ? std::atoi(argv[5]) : 0, false, power, wide_channels, format, wide_shift)
-                             : gr::amps::recc_wideband::make(832, 96, argc > 4 ? std::atoi(argv[4]) : -1, 0, 0, argc > 5 ? std::atoi(argv[5]) : 0, false, power, 1024, format, wide_shift);
+                             : grid10 ? gr::amps::recc_wideband::make(wide_channels / 3, 0, argc > 4 ? std::atoi(argv[4]) : -1, 0, 0, wide_channels / 4, false, power, wide_channels, format, wide_shift, wide_rate, wide_interp, wide_decim_in)
+                             : wide_channels != 1024 ? gr::amps::recc_wideband::make(wide_channels, 0, argc > 4 ? std::atoi(argv[4]) : -1, 0, 0, argc > 5 ? std::atoi(argv[5]) : 0, false, power, wide_channels, format, wide_shift, wide_rate, wide_interp, wide_decim_in)
+                             : gr::amps::recc_wideband::make(832, 96, argc > 4 ? std::atoi(argv[4]) : -1, 0, 0, argc > 5 ? std::atoi(argv[5]) : 0, false, power, 1024, format, wide_shift, wide_rate, wide_interp, wide_decim_in);
             if (ranks) {
                 // the control plane is the application's: here, a file
                 std::string id;

@@ -53,8 +53,13 @@ public:
     // shift_hz: the tuner's frequency error, corrected inside the filter bank (amps_recc_set_wideband_shift: every bank but the 1024
     //         one): the frequency in the delivered stream of what shall land on bin 0's centre, +e for a radio that delivers
     //         everything e hertz too high.  0 = none.  A non-zero shift on a 1024 bank, or beyond +- fs / 2, throws.
+    // rate_hz, interp, decim_in: a stream at a rate that is no bank's (amps_recc_set_wideband_resample): the items arrive at rate_hz and are
+    //         resampled by interp / decim_in to the bank's rate on the device -- a HackRF's 8 Msps x 5/4 into channels = 1000, 12.5 Msps x 2/1
+    //         into 2500; amps_recc_wideband_resample_plan lists what a rate admits.  rate_hz = 0: none.  A ratio or rate the library refuses
+    //         throws.  Not with set_rccl, which throws on such a block: the library has no distributed push behind a resampler (-ENOSYS).
     static sptr make(int n_channels = 832, int first_bin = 96, int slicer = -1, int groups = 0, int group = 0, int decim = 0, bool short_input = false,
-                     bool channel_power = false, int channels = 1024, int input_format = 0, double shift_hz = 0.0);
+                     bool channel_power = false, int channels = 1024, int input_format = 0, double shift_hz = 0.0,
+                     double rate_hz = 0.0, int interp = 1, int decim_in = 1);
     // Replace the shift in mid-stream: in force from the next work() call on, nothing reset, and from then on the bank delivers what a
     // block made with this shift would.  Throws where the library refuses (NaN, beyond +- fs / 2, a 1024 bank).
     virtual void set_shift(double shift_hz) = 0;

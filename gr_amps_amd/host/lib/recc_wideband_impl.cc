@@ -22,6 +22,7 @@ class recc_wideband_impl : public recc_wideband {
     unsigned long long d_stream_samples = 0, d_paced_items = 0;   // non-root ranks: samples the root has distributed / items this rank's pacing input has offered
     bool d_ended = false;                          // the root's end of stream has been sent (root) / seen (the others)
     int d_format = AMPS_RECC_SAMPLES_FC32;         // AMPS_RECC_SAMPLES_* of the items: one gr_complex, two shorts ("sc16") or two bytes ("sc8", "cu8")
+    bool d_resample = false;                       // the items arrive at a rate of their own and reach the bank through the L / M resampler: no set_rccl
     bool d_power = false;                          // AMPS_RECC_FLAG_CHANNEL_POWER: every record's burst power goes out on "power"
     std::vector<float> d_pow;
     std::vector<uint32_t> d_nsnap;
@@ -42,7 +43,8 @@ public:
         return short_input ? AMPS_RECC_SAMPLES_SC16 : input_format;
     }
 
-    recc_wideband_impl(int C, int first_bin, int slicer, int groups, int group, int decim, bool short_input, bool channel_power, int channels, int input_format, double shift_hz)
+    recc_wideband_impl(int C, int first_bin, int slicer, int groups, int group, int decim, bool short_input, bool channel_power, int channels, int input_format, double shift_hz,
+                       double rate_hz, int interp, int decim_in)
         : gr::sync_block("recc_wideband", gr::io_signature::make(1, 1, (int)item_size(checked_format(short_input, input_format))), gr::io_signature::make(0, 0, 0)),
           d_handle(nullptr), d_recs(kMaxRecs), d_bursts((size_t)kMaxRecs * AMPS_RECC_CAPTURE_SYMS), d_format(checked_format(short_input, input_format)), d_power(channel_power),
           d_pow(channel_power ? kMaxRecs : 0), d_nsnap(channel_power ? kMaxRecs : 0)
@@ -53,7 +55,10 @@ public:
         cfg.samples_per_symbol = 0;                // what goes with the decimation: 3 (60 ksps per channel, D = 512) or 2 (40 ksps, D = 768)
         const bool narrow = channels > 0 && channels != 1024;      // every bank but the 1024 one is the two-kernel form: received power is the IQ seam's
         const int dmin = narrow ? (decim > 0 ? decim : 3 * channels / 4) : 512;   // fewest input samples a frame takes
-        cfg.max_samples_per_push = (uint32_t)(kMaxPush / dmin + 72);
+        const bool resample = rate_hz != 0.0;                      // the input arrives at rate_hz and reaches the bank through the L / M resampler
+        if (resample && (interp < 1 || decim_in < 1)) throw std::runtime_error("amps::recc_wideband: resample: interp and decim_in are 1 ... 8");
+        // frames of the largest push: behind a resampler kMaxPush items are up to interp / decim_in times as many samples at the bank
+        cfg.max_samples_per_push = (uint32_t)((resample ? ((uint64_t)kMaxPush * (uint64_t)interp + decim_in - 1) / decim_in : (uint64_t)kMaxPush) / dmin + 72);
         cfg.max_bursts = kMaxRecs;
         cfg.device = -1;
         cfg.flags = AMPS_RECC_FLAG_KEEP_BURSTS | (slicer == 0 ? AMPS_RECC_FLAG_SLICER_ATAN : slicer == 1 ? AMPS_RECC_FLAG_SLICER_PRODUCT
@@ -69,6 +74,13 @@ public:
         if (rc != 0) throw std::runtime_error(std::string("amps::recc_wideband: ") + amps_recc_strerror(rc));
         if (shift_hz != 0.0) {
             try { set_shift(shift_hz); } catch (...) { amps_recc_destroy(d_handle); throw; }
+        }
+        if (resample) {
+            amps_recc_wideband_resample_cfg_t r = {};
+            r.struct_size = sizeof(r); r.interp = (uint32_t)interp; r.decim = (uint32_t)decim_in; r.rate_hz = rate_hz;
+            rc = amps_recc_set_wideband_resample(d_handle, &r);
+            if (rc != 0) { amps_recc_destroy(d_handle); throw std::runtime_error(std::string("amps::recc_wideband: resample: ") + amps_recc_strerror(rc)); }
+            d_resample = true;
         }
         message_port_register_out(pmt::mp("bursts"));
         message_port_register_out(pmt::mp("records"));
@@ -86,6 +98,8 @@ public:
     {
         // (the blocks RCCL carries are fc32: amps_recc_push_wideband_dist has no integer form)
         if (d_format != AMPS_RECC_SAMPLES_FC32) throw std::runtime_error("amps::recc_wideband: set_rccl is not available on a block with 16-bit or 8-bit input; distribute an fc32 stream");
+        // (... and at the bank's rate: the library answers the distributed push of a resampling handle with -ENOSYS)
+        if (d_resample) throw std::runtime_error("amps::recc_wideband: set_rccl is not available on a block with a resampler (rate_hz); distribute a stream at the bank's rate");
         if (id.size() != AMPS_RECC_RCCL_ID_BYTES) throw std::runtime_error("amps::recc_wideband: the RCCL id is 128 bytes");
         if (mode != AMPS_RECC_DIST_BROADCAST && mode != AMPS_RECC_DIST_SCATTER_ALLGATHER) throw std::runtime_error("amps::recc_wideband: unknown distribution mode");
         int rc = amps_recc_rccl_init(d_handle, (const uint8_t *)id.data(), nranks, rank);
@@ -157,9 +171,10 @@ public:
     }
 };
 
-recc_wideband::sptr recc_wideband::make(int n_channels, int first_bin, int slicer, int groups, int group, int decim, bool short_input, bool channel_power, int channels, int input_format, double shift_hz)
+recc_wideband::sptr recc_wideband::make(int n_channels, int first_bin, int slicer, int groups, int group, int decim, bool short_input, bool channel_power, int channels, int input_format, double shift_hz,
+                                        double rate_hz, int interp, int decim_in)
 {
-    return gnuradio::get_initial_sptr(new recc_wideband_impl(n_channels, first_bin, slicer, groups, group, decim, short_input, channel_power, channels, input_format, shift_hz));
+    return gnuradio::get_initial_sptr(new recc_wideband_impl(n_channels, first_bin, slicer, groups, group, decim, short_input, channel_power, channels, input_format, shift_hz, rate_hz, interp, decim_in));
 }
 
 std::string recc_wideband::rccl_unique_id()

@@ -67,7 +67,10 @@ extern "C" {
                                      still 4, one entry point added and nothing changed: amps_recc_wideband_grid_plan, with cfg.wideband_channels =
                                      2500, 2000, 1000 and 500 at wideband_decim = M / 4, the wideband seam at 25, 20, 10 and 5 Msps;
                                      still 4, two entry points added and nothing changed: amps_recc_set_wideband_shift / amps_recc_wideband_shift,
-                                     a tuner's frequency error corrected inside the banks below 1024 branches) */
+                                     a tuner's frequency error corrected inside the banks below 1024 branches;
+                                     still 4, three entry points added and nothing changed: amps_recc_set_wideband_resample /
+                                     amps_recc_wideband_resample_plan / amps_recc_debug_wideband_resample, an L / M resampler in front of the
+                                     banks for the rates that are no bank's: 8, 12.5, 16, 6, 4 and 3.2 Msps) */
 
 /* protocol constants of the reference */
 #define AMPS_RECC_TRIGGER_SYMS 74   /* lib/recc_impl.cc:76-77: 37 bits x 2 Manchester symbols   */
@@ -543,6 +546,61 @@ int amps_recc_debug_channelize_as(amps_recc_t *h, const void *iq, size_t nsamp, 
  * NULL argument, -ENOSYS as above). */
 int amps_recc_set_wideband_shift(amps_recc_t *h, double shift_hz);
 int amps_recc_wideband_shift(const amps_recc_t *h, double *shift_hz);
+
+/* wideband seam behind a rational resampler: the rates SDRs deliver that are no bank's rate -- a HackRF's 8 Msps * 5/4 = 10 Msps, its
+ * 12.5 Msps * 2/1 = 25 and 16 Msps * 5/4 = 20, an Airspy Mini's or SDRplay's 6 Msps * 5/3 = 10, 4 Msps * 5/4 = 5, 3.2 Msps * 6/5 = 3.84;
+ * amps_recc_wideband_resample_plan lists what a rate admits.  Resampling UP to the next bank rate keeps the whole delivered band, and
+ * frequencies in hertz do not move: a tuner on a multiple of the bank's bin width still has every channel centre on a bin, and
+ * amps_recc_set_wideband_shift corrects what is left.
+ * DEFINITION.  The stream at rate_hz is resampled by interp / decim = L / M to the bank's rate, wideband_channels times its bin width,
+ * by the textbook polyphase resampler.  With f_low = min(rate_hz, the bank's rate), width_hz = 0 selects f_low / 16 and cutoff_hz = 0
+ * selects f_low / 2 - width_hz / 2: the stop band then begins at f_low / 2 and the pass band is flat to f_low / 2 - width_hz.  The
+ * prototype g = firdes.low_pass(L, L * rate_hz, cutoff_hz, width_hz) (Blackman), the design of amps_recc_set_xlate_resampled at the
+ * up-sampled rate with gain L for the zero stuffing, has N_g = int(74 L rate_hz / (22 width_hz)) made odd taps.  Phase p has the taps
+ * h_p[i] = g[L i + p], zero beyond N_g: Np = ceil(N_g / L) taps per phase, zero padded to a multiple of 8 (ntp) -- 54 (56) with the
+ * defaults when resampling up, 107 (112) at 1/2.  For output k write k M = L q_k + p_k, 0 <= p_k < L; then
+ *     y[k] = sum_{i = 0}^{ntp - 1} h_{p_k}[i] x[q_k - i],
+ * each component one fp32 fma chain in ascending i, x the block converted by the plain AMPS_RECC_SAMPLES_* conversion, samples before
+ * the stream's start zero, k and q absolute indices since create or amps_recc_reset in 64-bit arithmetic.  After N input samples in
+ * all the stream has delivered ceil(L N / M) outputs; a push delivers the difference to what was delivered before.  The result does
+ * not depend on push boundaries or on the sample format.
+ * The bank behind it sees y exactly as it would see a device fc32 block: the carry, the frame masks, max_samples_per_push in frames,
+ * positions, the power and offset rings and the records are what they are without a resampler, and the n of
+ * amps_recc_set_wideband_shift counts the resampler's outputs.
+ * interp, decim: 1 ... 8 with no factor in common, interp != decim, 1/2 <= interp / decim <= 4; decim = 0 removes the stage.
+ * rate_hz * interp / decim must lie within 1e-6 (relative) of the bank's rate.
+ * While a resampler is configured, amps_recc_push_wideband, _short, _as, amps_recc_debug_channelize and _as take blocks at rate_hz, in
+ * any format, through the resampler; a push whose frames would exceed max_samples_per_push answers -E2BIG with nothing consumed; the
+ * distributed pushes amps_recc_push_wideband_dist / _bcast answer -ENOSYS.  amps_recc_reset keeps the configuration and restarts k
+ * and q at 0 with zero history.
+ * Errors: -EINVAL (null handle or cfg, wrong struct_size); -ENOSYS (a handle without the wideband seam); -EBUSY (the seam has taken
+ * a block since create or reset: set or remove the stage before the first push, or after amps_recc_reset); -EINVAL (interp or decim
+ * outside 1 ... 8, a common factor, interp == decim, a ratio outside 1/2 ... 4, a rate mismatch, numbers that are not finite or are
+ * negative, a width_hz that gives fewer than 3 taps, a cutoff_hz above interp * rate_hz / 2); -E2BIG (more than 512 padded taps per
+ * phase, or the tap sets and a tile's window beyond 64 KB of LDS).  A call that is refused leaves the handle as it was. */
+typedef struct amps_recc_wideband_resample_cfg {
+    uint32_t struct_size, interp, decim, _pad;   /* L, M; decim = 0 removes the stage */
+    double   rate_hz;                            /* the delivered rate; rate_hz * L / M == the bank's rate */
+    double   cutoff_hz, width_hz;                /* 0 = the defaults above */
+} amps_recc_wideband_resample_cfg_t;
+int amps_recc_set_wideband_resample(amps_recc_t *h, const amps_recc_wideband_resample_cfg_t *r);
+/* "Which ratio into which bank?"  The (interp, decim, channels, bank_decim) combinations a stream at rate_hz admits with the default
+ * filter, ascending by (interp, decim) and, within one bank, by its decimations in the order of amps_recc_wideband_grid_plan:
+ * 8e6: (5, 2, 2000, 500), (5, 4, 1000, 250), (5, 8, 500, 125); 12.5e6: (2, 1, 2500, 625), (4, 5, 1000, 250), (8, 5, 2000, 500);
+ * 3.2e6: (6, 5, 128, 96), (6, 5, 128, 64); nothing for 56 Msps.  A bank's own rate lists only true resamplings.  An entry adds what
+ * amps_recc_create wants beside channels and bank_decim (samples_per_symbol), ntaps_per_phase = ceil(N_g / interp), the bank's bin
+ * width and channel stride, and usable_hz = 2 (f_low / 2 - width_hz), the band the filter keeps flat.  Give the handle the channels
+ * inside that band only (wideband_first_channel, n_channels): when resampling up, the bank's bins beyond the delivered band hold the
+ * stop band's images of the band, signal and noise alike some 74 dB down, and an FM receiver decodes an image as it does the mobile.
+ * Return value, cap and errors
+ * as amps_recc_wideband_grid_plan.  Host arithmetic only, and it asks the same function the configuration asks. */
+typedef struct amps_recc_wideband_resample_plan {
+    uint32_t interp, decim, channels, bank_decim, samples_per_symbol, ntaps_per_phase, bin_hz, channel_stride, usable_hz, _pad;
+} amps_recc_wideband_resample_plan_t;
+int amps_recc_wideband_resample_plan(double rate_hz, amps_recc_wideband_resample_plan_t *out, size_t cap);
+/* test tap: run only the resampler on a block in `format` (AMPS_RECC_SAMPLES_*), continuing its stream; out is host fc32 [cap] and
+ * *nout the outputs this block delivered (-E2BIG beyond cap, with nothing consumed).  -ENOSYS without a configured resampler. */
+int amps_recc_debug_wideband_resample(amps_recc_t *h, const void *iq, size_t nsamp, int format, int mem, float *out, size_t cap, size_t *nout);
 
 /* Retune: replace the centres of the translate form configured last (amps_recc_set_xlate, _set_xlate_shared or _set_xlate_resampled)
  * in mid-stream.  Taps, carry, absolute positions, the decimation or L / M and everything behind the stage are kept; nothing is
