@@ -148,42 +148,88 @@ class Reply(C.Structure):
     ]
 
 
-EXPORTS = (
-    "amps_recc_abi_version", "amps_recc_strerror", "amps_recc_burst_size", "amps_recc_create",
-    "amps_recc_destroy", "amps_recc_reset", "amps_recc_push_symbols", "amps_recc_decode_bursts",
-    "amps_recc_push_iq", "amps_recc_push_wideband", "amps_recc_drain", "amps_recc_debug_demod",
-    "amps_recc_get_timing", "amps_recc_reply_words", "amps_recc_debug_channelize",
-    "amps_bch_encode_words", "amps_bch_decode_words",
-    "amps_recc_set_xlate", "amps_recc_push_raw", "amps_recc_debug_xlate", "amps_recc_set_timing",
-    "amps_recc_drain_begin", "amps_recc_drain_end", "amps_recc_set_origin",
-    "amps_recc_wait_event", "amps_recc_record_event", "amps_recc_refchain_symbols", "amps_recc_refchain_tables",
-    "amps_recc_drain_bursts", "amps_recc_default_slicer", "amps_recc_default_wideband_decim", "amps_recc_debug_exact_slice",
-    "amps_recc_rccl_unique_id", "amps_recc_rccl_init", "amps_recc_push_wideband_bcast", "amps_recc_drain_gather",
-    "amps_recc_push_wideband_dist", "amps_recc_rccl_info", "amps_recc_rccl_abort", "amps_recc_rccl_set_timeout",
-    "amps_recc_debug_slicer_bits", "amps_recc_push_wideband_short",
-    "amps_recc_channel_power", "amps_recc_burst_power", "amps_recc_power_ring_snaps",
-    "amps_recc_set_xlate_shared", "amps_recc_push_raw_shared", "amps_recc_debug_xlate_shared",
-    "amps_recc_push_raw_shared_as", "amps_recc_push_raw_as", "amps_recc_debug_xlate_shared_as", "amps_recc_debug_xlate_as",
-    "amps_recc_xlate_shared_plan",
-    "amps_recc_set_xlate_resampled", "amps_recc_xlate_resample_plan",
-    "amps_recc_channel_autocorr", "amps_recc_burst_autocorr", "amps_recc_burst_offset",
-    "amps_recc_retune_xlate",
-    "amps_recc_wideband_plan", "amps_recc_wideband_grid_plan",
-    "amps_recc_push_wideband_as", "amps_recc_debug_channelize_as",
-    "amps_recc_set_wideband_shift", "amps_recc_wideband_shift",
-    "amps_recc_set_wideband_resample", "amps_recc_wideband_resample_plan", "amps_recc_debug_wideband_resample",
-)
+def _prototypes():
+    """Every entry point of include/amps_recc.h, in the header's order: name -> (restype, argtypes).  A new entry point is one row
+    here and one method body below; tests/test_cpu_capi_prototypes.py holds the rows to the header's declarations."""
+    vp, i, sz, u32, u64, dbl = C.c_void_p, C.c_int, C.c_size_t, C.c_uint32, C.c_uint64, C.c_double
+    psz, pu32, pu64, pdbl = C.POINTER(sz), C.POINTER(u32), C.POINTER(u64), C.POINTER(dbl)
+    ring_rows = [vp, u64, sz, vp, sz, pu32, pu64]          # (h, first, n, out, out_ld, &rows, &produced)
+    ring_bursts = [vp, vp, sz, vp, vp]                     # (h, records, n, value out, count out)
+    return {
+        "amps_recc_abi_version": (i, []),
+        "amps_recc_default_slicer": (i, []),
+        "amps_recc_default_wideband_decim": (u32, []),
+        "amps_recc_strerror": (C.c_char_p, [i]),
+        "amps_recc_burst_size": (sz, []),
+        "amps_recc_create": (i, [C.POINTER(vp), C.POINTER(Cfg)]),
+        "amps_recc_destroy": (None, [vp]),
+        "amps_recc_reset": (i, [vp]),
+        "amps_recc_set_origin": (i, [vp, u64]),
+        "amps_recc_push_symbols": (i, [vp, vp, sz, i, i, vp, vp, sz, psz]),
+        "amps_recc_decode_bursts": (i, [vp, vp, sz, i, vp, vp]),
+        "amps_recc_push_iq": (i, [vp, vp, sz, sz, i]),
+        "amps_recc_push_wideband": (i, [vp, vp, sz, i]),
+        "amps_recc_push_wideband_short": (i, [vp, vp, sz, i]),
+        "amps_recc_set_xlate": (i, [vp, C.POINTER(XlateCfg)]),
+        "amps_recc_push_raw": (i, [vp, vp, sz, sz, i]),
+        "amps_recc_debug_xlate": (i, [vp, vp, sz, sz, i, vp, sz, psz]),
+        "amps_recc_set_xlate_shared": (i, [vp, C.POINTER(XlateSharedCfg)]),
+        "amps_recc_xlate_shared_plan": (i, [dbl, dbl, C.POINTER(XlatePlan), sz]),
+        "amps_recc_wideband_plan": (i, [dbl, C.POINTER(WidebandPlan), sz]),
+        "amps_recc_wideband_grid_plan": (i, [dbl, C.POINTER(WidebandGridPlan), sz]),
+        "amps_recc_push_raw_shared": (i, [vp, vp, sz, i]),
+        "amps_recc_debug_xlate_shared": (i, [vp, vp, sz, i, vp, sz, psz]),
+        "amps_recc_set_xlate_resampled": (i, [vp, C.POINTER(XlateResampleCfg)]),
+        "amps_recc_xlate_resample_plan": (i, [dbl, dbl, C.POINTER(ResamplePlan), sz]),
+        "amps_recc_push_raw_shared_as": (i, [vp, vp, sz, i, i]),
+        "amps_recc_push_raw_as": (i, [vp, vp, sz, sz, i, i]),
+        "amps_recc_debug_xlate_shared_as": (i, [vp, vp, sz, i, i, vp, sz, psz]),
+        "amps_recc_debug_xlate_as": (i, [vp, vp, sz, sz, i, i, vp, sz, psz]),
+        "amps_recc_push_wideband_as": (i, [vp, vp, sz, i, i]),
+        "amps_recc_debug_channelize_as": (i, [vp, vp, sz, i, i, vp, sz, psz]),
+        "amps_recc_set_wideband_shift": (i, [vp, dbl]),
+        "amps_recc_wideband_shift": (i, [vp, pdbl]),
+        "amps_recc_set_wideband_resample": (i, [vp, C.POINTER(WidebandResampleCfg)]),
+        "amps_recc_wideband_resample_plan": (i, [dbl, C.POINTER(WidebandResamplePlan), sz]),
+        "amps_recc_debug_wideband_resample": (i, [vp, vp, sz, i, i, vp, sz, psz]),
+        "amps_recc_retune_xlate": (i, [vp, pdbl, sz]),
+        "amps_recc_refchain_symbols": (i, [vp, vp, sz, sz, i, vp, sz, vp]),
+        "amps_recc_refchain_tables": (i, [vp, vp, vp]),
+        "amps_recc_wait_event": (i, [vp, vp]),
+        "amps_recc_record_event": (i, [vp, vp]),
+        "amps_recc_drain": (i, [vp, vp, sz, psz]),
+        "amps_recc_drain_begin": (i, [vp]),
+        "amps_recc_drain_end": (i, [vp, vp, sz, psz]),
+        "amps_recc_drain_bursts": (i, [vp, vp, vp, sz, psz]),
+        "amps_recc_debug_demod": (i, [vp, vp, sz, i, vp, vp, vp]),
+        "amps_recc_debug_slicer_bits": (i, ring_rows),
+        "amps_recc_channel_power": (i, ring_rows),
+        "amps_recc_burst_power": (i, ring_bursts),
+        "amps_recc_power_ring_snaps": (u32, [vp]),
+        "amps_recc_channel_autocorr": (i, ring_rows),
+        "amps_recc_burst_autocorr": (i, ring_bursts),
+        "amps_recc_burst_offset": (i, ring_bursts),
+        "amps_recc_rccl_unique_id": (i, [vp]),
+        "amps_recc_rccl_init": (i, [vp, vp, i, i]),
+        "amps_recc_rccl_set_timeout": (i, [vp, u32]),
+        "amps_recc_rccl_abort": (i, [vp]),
+        "amps_recc_push_wideband_dist": (i, [vp, vp, sz, i, i, i, psz]),
+        "amps_recc_push_wideband_bcast": (i, [vp, vp, sz, i, i]),
+        "amps_recc_drain_gather": (i, [vp, vp, sz, psz, i]),
+        "amps_recc_rccl_info": (i, [vp, C.POINTER(RcclInfo)]),
+        "amps_recc_debug_exact_slice": (i, [i, i, pu32, pu32]),
+        "amps_recc_debug_channelize": (i, [vp, vp, sz, i, vp, sz, psz]),
+        "amps_recc_get_timing": (i, [vp, C.POINTER(Timing), i]),
+        "amps_recc_set_timing": (i, [vp, i]),
+        "amps_recc_reply_words": (i, [vp, C.POINTER(Reply)]),
+        "amps_bch_encode_words": (i, [vp, vp, sz, i, i, vp]),
+        "amps_bch_decode_words": (i, [vp, vp, sz, i, i, vp, vp, vp]),
+    }
+
+
+PROTOTYPES = _prototypes()
+EXPORTS = tuple(PROTOTYPES)
 GRID10_CHANNELS = (2500, 2000, 1000, 500)   # branches of the wideband seam's banks of 10 kHz bins: 25, 20, 10 and 5 Msps
-_WIDEBAND_AS = ("amps_recc_push_wideband_as", "amps_recc_debug_channelize_as")
-_WIDEBAND_SHIFT = ("amps_recc_set_wideband_shift", "amps_recc_wideband_shift")
-_WIDEBAND_RESAMPLE = ("amps_recc_set_wideband_resample", "amps_recc_wideband_resample_plan", "amps_recc_debug_wideband_resample")
-_XLATE_RESAMPLED = ("amps_recc_set_xlate_resampled", "amps_recc_xlate_resample_plan")
-_XLATE_AS = ("amps_recc_push_raw_shared_as", "amps_recc_push_raw_as", "amps_recc_debug_xlate_shared_as", "amps_recc_debug_xlate_as")
-_XLATE_SHARED = ("amps_recc_set_xlate_shared", "amps_recc_push_raw_shared", "amps_recc_debug_xlate_shared")
-_POWER = ("amps_recc_channel_power", "amps_recc_burst_power", "amps_recc_power_ring_snaps")
-_OFFSET = ("amps_recc_channel_autocorr", "amps_recc_burst_autocorr", "amps_recc_burst_offset")
-_RETUNE = ("amps_recc_retune_xlate",)
-_NEW_IN_ABI4 = ("amps_recc_push_wideband_dist", "amps_recc_rccl_info", "amps_recc_rccl_abort", "amps_recc_rccl_set_timeout")
 DIST_BROADCAST, DIST_SCATTER_ALLGATHER = 0, 1
 # sample formats of the translate seams' _as entry points (AMPS_RECC_SAMPLES_*): the element dtype of a block, two per sample
 SAMPLES_FC32, SAMPLES_SC16, SAMPLES_SC8, SAMPLES_CU8 = 0, 1, 2, 3
@@ -209,110 +255,59 @@ def load():
         raise ImportError(f"{LIB_PATH} not built -- run `python -c 'import __graft_entry__ as g; g.build()'`; "
                           "there is no CPU fallback for the RECC path")
     L = C.CDLL(LIB_PATH)
-    vp = C.c_void_p
-    L.amps_recc_abi_version.restype = C.c_int
-    if hasattr(L, "amps_recc_default_slicer"):      # absent only from A/B builds of earlier revisions (AMPS_RECC_LIB)
-        L.amps_recc_default_slicer.restype = C.c_int
-    if hasattr(L, "amps_recc_default_wideband_decim"):
-        L.amps_recc_default_wideband_decim.restype = C.c_uint32
-    L.amps_recc_strerror.argtypes = [C.c_int]
-    L.amps_recc_strerror.restype = C.c_char_p
-    L.amps_recc_burst_size.restype = C.c_size_t
-    L.amps_recc_create.argtypes = [C.POINTER(vp), C.POINTER(Cfg)]
-    L.amps_recc_destroy.argtypes = [vp]
-    L.amps_recc_destroy.restype = None
-    L.amps_recc_reset.argtypes = [vp]
-    L.amps_recc_set_origin.argtypes = [vp, C.c_uint64]
-    L.amps_recc_push_symbols.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.amps_recc_decode_bursts.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, vp]
-    L.amps_recc_push_iq.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int]
-    L.amps_recc_push_wideband.argtypes = [vp, vp, C.c_size_t, C.c_int]
-    if hasattr(L, "amps_recc_push_wideband_short"):   # absent only from A/B builds of earlier revisions (AMPS_RECC_LIB)
-        L.amps_recc_push_wideband_short.argtypes = [vp, vp, C.c_size_t, C.c_int]
-    if hasattr(L, "amps_recc_push_wideband_bcast"):   # absent only from A/B builds of earlier revisions (AMPS_RECC_LIB)
-        L.amps_recc_rccl_unique_id.argtypes = [vp]
-        L.amps_recc_rccl_init.argtypes = [vp, vp, C.c_int, C.c_int]
-        L.amps_recc_push_wideband_bcast.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int]
-    if hasattr(L, "amps_recc_drain_gather"):
-        L.amps_recc_drain_gather.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
-    if hasattr(L, "amps_recc_push_wideband_dist"):
-        L.amps_recc_push_wideband_dist.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
-        L.amps_recc_rccl_info.argtypes = [vp, C.POINTER(RcclInfo)]
-        L.amps_recc_rccl_abort.argtypes = [vp]
-        L.amps_recc_rccl_set_timeout.argtypes = [vp, C.c_uint32]
-    L.amps_recc_drain.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.amps_recc_refchain_symbols.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_size_t, vp]
-    L.amps_recc_refchain_tables.argtypes = [vp, vp, vp]
-    L.amps_recc_wait_event.argtypes = [vp, vp]
-    L.amps_recc_record_event.argtypes = [vp, vp]
-    L.amps_recc_drain_bursts.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.amps_recc_drain_begin.argtypes = [vp]
-    L.amps_recc_drain_end.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.amps_recc_debug_demod.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, vp, vp]
-    L.amps_recc_get_timing.argtypes = [vp, C.POINTER(Timing), C.c_int]
-    L.amps_recc_set_timing.argtypes = [vp, C.c_int]
-    L.amps_recc_debug_channelize.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
-    if hasattr(L, "amps_recc_debug_slicer_bits"):
-        L.amps_recc_debug_slicer_bits.argtypes = [vp, C.c_uint64, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
-    if hasattr(L, "amps_recc_channel_power"):         # absent only from A/B builds of earlier revisions (AMPS_RECC_LIB)
-        L.amps_recc_channel_power.argtypes = [vp, C.c_uint64, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
-        L.amps_recc_burst_power.argtypes = [vp, vp, C.c_size_t, vp, vp]
-        L.amps_recc_power_ring_snaps.argtypes = [vp]
-    if hasattr(L, "amps_recc_channel_autocorr"):      # likewise
-        L.amps_recc_channel_autocorr.argtypes = [vp, C.c_uint64, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
-        L.amps_recc_burst_autocorr.argtypes = [vp, vp, C.c_size_t, vp, vp]
-        L.amps_recc_burst_offset.argtypes = [vp, vp, C.c_size_t, vp, vp]
-    if hasattr(L, "amps_recc_retune_xlate"):          # likewise
-        L.amps_recc_retune_xlate.argtypes = [vp, C.POINTER(C.c_double), C.c_size_t]
-    L.amps_recc_reply_words.argtypes = [vp, C.POINTER(Reply)]
-    L.amps_recc_set_xlate.argtypes = [vp, C.POINTER(XlateCfg)]
-    L.amps_recc_push_raw.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int]
-    L.amps_recc_debug_xlate.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
-    if hasattr(L, "amps_recc_set_xlate_shared"):      # absent only from A/B builds of earlier revisions (AMPS_RECC_LIB)
-        L.amps_recc_set_xlate_shared.argtypes = [vp, C.POINTER(XlateSharedCfg)]
-        L.amps_recc_push_raw_shared.argtypes = [vp, vp, C.c_size_t, C.c_int]
-        L.amps_recc_debug_xlate_shared.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
-    if hasattr(L, "amps_recc_push_raw_shared_as"):    # absent only from A/B builds of earlier revisions (AMPS_RECC_LIB)
-        L.amps_recc_push_raw_shared_as.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int]
-        L.amps_recc_push_raw_as.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int]
-        L.amps_recc_debug_xlate_shared_as.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
-        L.amps_recc_debug_xlate_as.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
-    if hasattr(L, "amps_recc_xlate_shared_plan"):     # absent only from A/B builds of earlier revisions (AMPS_RECC_LIB)
-        L.amps_recc_xlate_shared_plan.argtypes = [C.c_double, C.c_double, C.POINTER(XlatePlan), C.c_size_t]
-    if hasattr(L, "amps_recc_set_xlate_resampled"):   # absent only from A/B builds of earlier revisions (AMPS_RECC_LIB)
-        L.amps_recc_set_xlate_resampled.argtypes = [vp, C.POINTER(XlateResampleCfg)]
-        L.amps_recc_xlate_resample_plan.argtypes = [C.c_double, C.c_double, C.POINTER(ResamplePlan), C.c_size_t]
-    if hasattr(L, "amps_recc_wideband_plan"):         # absent only from A/B builds of earlier revisions (AMPS_RECC_LIB)
-        L.amps_recc_wideband_plan.argtypes = [C.c_double, C.POINTER(WidebandPlan), C.c_size_t]
-    if hasattr(L, "amps_recc_wideband_grid_plan"):    # likewise
-        L.amps_recc_wideband_grid_plan.argtypes = [C.c_double, C.POINTER(WidebandGridPlan), C.c_size_t]
-    if hasattr(L, "amps_recc_push_wideband_as"):      # absent only from A/B builds of earlier revisions (AMPS_RECC_LIB)
-        L.amps_recc_push_wideband_as.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int]
-        L.amps_recc_debug_channelize_as.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
-    if hasattr(L, "amps_recc_set_wideband_shift"):    # likewise
-        L.amps_recc_set_wideband_shift.argtypes = [vp, C.c_double]
-        L.amps_recc_wideband_shift.argtypes = [vp, C.POINTER(C.c_double)]
-    if hasattr(L, "amps_recc_set_wideband_resample"):   # likewise
-        L.amps_recc_set_wideband_resample.argtypes = [vp, C.POINTER(WidebandResampleCfg)]
-        L.amps_recc_wideband_resample_plan.argtypes = [C.c_double, C.POINTER(WidebandResamplePlan), C.c_size_t]
-        L.amps_recc_debug_wideband_resample.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.amps_bch_encode_words.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp]
-    L.amps_bch_decode_words.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, vp, vp]
-    for name in EXPORTS:
-        if name in ("amps_recc_default_slicer", "amps_recc_default_wideband_decim", "amps_recc_debug_exact_slice", "amps_recc_rccl_unique_id", "amps_recc_rccl_init",
-                    "amps_recc_push_wideband_bcast", "amps_recc_drain_gather", "amps_recc_debug_slicer_bits",
-                    "amps_recc_push_wideband_short", "amps_recc_xlate_shared_plan", "amps_recc_wideband_plan", "amps_recc_wideband_grid_plan") + _NEW_IN_ABI4 + _POWER + _OFFSET + _RETUNE + _XLATE_SHARED + _XLATE_AS + _XLATE_RESAMPLED + _WIDEBAND_AS + _WIDEBAND_SHIFT + _WIDEBAND_RESAMPLE and not hasattr(L, name):
+    missing = []
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(L, name, None)
+        if fn is None:
+            missing.append(name)
             continue
-        if name not in ("amps_recc_strerror", "amps_recc_burst_size", "amps_recc_destroy"):   # every other entry point returns int
-            getattr(L, name).restype = C.c_uint32 if name == "amps_recc_power_ring_snaps" else C.c_int
+        fn.restype = restype
+        fn.argtypes = argtypes
+    # the tree's own library has every entry point; an A/B library of another revision (AMPS_RECC_LIB) may lack some, and calling
+    # one of those is an AttributeError
+    if missing and not os.environ.get("AMPS_RECC_LIB"):
+        raise ImportError(f"{LIB_PATH} lacks {', '.join(missing)} -- rebuild it")
     if L.amps_recc_burst_size() != BURST_DTYPE.itemsize:
         raise ImportError("amps_recc_burst_t layout mismatch between binding and library")
     _lib = L
     return L
 
 
+def _call(name, *args):
+    """entry point `name` of the library; a non-zero result is an AmpsError that carries the name"""
+    rc = getattr(load(), name)(*args)
+    if rc:
+        raise AmpsError(rc, name)
+
+
+def _plan(name, struct, *rate):
+    """a *_plan entry point: ask how many entries (rate..., NULL, 0) answers, fetch them, one tuple of the struct's fields each"""
+    fn = getattr(load(), name)
+    n = fn(*rate, None, 0)
+    if n < 0:
+        raise AmpsError(n, name)
+    out = (struct * max(n, 1))()
+    n = fn(*rate, out, n)
+    fields = [f for f, _ in struct._fields_ if f != "_pad"]
+    return [tuple(int(getattr(p, f)) for f in fields) for p in out[:n]]
+
+
 def _hostptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def _fc32_rows(iq, rows):
+    """fc32 rows [rows][ld] -> (block, ld): a numpy array is cast to complex64 and reshaped, a tensor is taken as it is"""
+    if isinstance(iq, np.ndarray):
+        iq = np.ascontiguousarray(iq, np.complex64).reshape(rows, -1)
+    return iq, iq.shape[1]
+
+
+def _fc32_row(iq):
+    """one fc32 row -> (block, n): a numpy array is cast to complex64 and flattened, a tensor is taken as it is"""
+    if isinstance(iq, np.ndarray):
+        iq = np.ascontiguousarray(iq, np.complex64).reshape(-1)
+    return iq, iq.shape[0]
 
 
 def _as_ptr(x, sync_torch=True):
@@ -402,7 +397,7 @@ class Recc:
             raise ValueError("stream_offset must be False, True or 'unit'")
         if isinstance(slicer, bool) or slicer not in _SLICER_FLAGS:        # a typo must not run a different numeric spec silently
             raise ValueError("slicer must be one of %r" % sorted(map(str, _SLICER_FLAGS)))
-        self.slicer = SLICER_NAMES[L.amps_recc_default_slicer() if hasattr(L, "amps_recc_default_slicer") else 0] if _SLICER_FLAGS[slicer] == 0 else \
+        self.slicer = SLICER_NAMES[L.amps_recc_default_slicer()] if _SLICER_FLAGS[slicer] == 0 else \
             {FLAG_SLICER_ATAN: "atan", FLAG_SLICER_PRODUCT: "product", FLAG_SLICER_SINE: "sine", FLAG_SLICER_EXACT: "exact"}[_SLICER_FLAGS[slicer]]
         self.sync_torch = sync_torch
         if wideband:
@@ -419,7 +414,7 @@ class Recc:
                 if int(wideband["channels"]) < 1024:
                     wideband["decim"] = 3 * int(wideband["channels"]) // 4
                 else:
-                    wideband["decim"] = int(L.amps_recc_default_wideband_decim()) if hasattr(L, "amps_recc_default_wideband_decim") else 512
+                    wideband["decim"] = int(L.amps_recc_default_wideband_decim())
             if sps is None:
                 sps = 3 * int(wideband["channels"]) // (2 * int(wideband["decim"]))
         elif sps is None:
@@ -476,10 +471,29 @@ class Recc:
         self.close()
 
     def reset(self):
-        rc = load().amps_recc_reset(self._h)
-        if rc:
-            raise AmpsError(rc, "amps_recc_reset")
+        _call("amps_recc_reset", self._h)
         self._origin = 0
+
+    def _tap(self, name, rows, cap, *args):
+        """a test tap: entry point `name`(handle, *args, out, cap, &nout) fills complex64 [rows][cap] ([cap] with rows = None) -> the
+        nout it delivered of every row"""
+        out = np.zeros(cap if rows is None else (rows, cap), np.complex64)
+        nout = C.c_size_t(0)
+        _call(name, self._h, *args, _hostptr(out), cap, C.byref(nout))
+        return out[..., :nout.value].copy()
+
+    def _records(self, name, cap, *tail, symbols=None, shared=False, copy=True):
+        """a drain: entry point `name`(handle, out, [symbols,] cap, &nout, *tail) -> the nout records.  shared: into the handle's
+        own buffer, which copy=False hands out as a view; otherwise into a fresh one"""
+        if shared:
+            out = getattr(self, "_drain_buf", None)
+            if out is None or out.shape[0] < cap:
+                out = self._drain_buf = np.empty(cap, BURST_DTYPE)
+        else:
+            out = np.empty(cap, BURST_DTYPE)
+        nout = C.c_size_t(0)
+        _call(name, self._h, _hostptr(out), *(() if symbols is None else (_hostptr(symbols),)), cap, C.byref(nout), *tail)
+        return out[:nout.value].copy() if copy else out[:nout.value]
 
     # ---- seam (i): recc::work ----
     def push_symbols(self, syms, n=None):
@@ -494,9 +508,7 @@ class Recc:
         out = np.zeros((self.max_bursts, CAPTURE), np.uint8)
         ch = np.zeros(self.max_bursts, np.uint32)
         nout = C.c_size_t(0)
-        rc = load().amps_recc_push_symbols(self._h, ptr, ld, n, mem, _hostptr(out), _hostptr(ch), self.max_bursts, C.byref(nout))
-        if rc:
-            raise AmpsError(rc, "amps_recc_push_symbols")
+        _call("amps_recc_push_symbols", self._h, ptr, ld, n, mem, _hostptr(out), _hostptr(ch), self.max_bursts, C.byref(nout))
         return out[:nout.value].copy(), ch[:nout.value].copy()
 
     def decode_bursts(self, bursts, channels=None):
@@ -511,57 +523,33 @@ class Recc:
         if channels is not None:
             channels = np.ascontiguousarray(channels, np.uint32)
             chp = _hostptr(channels)
-        rc = load().amps_recc_decode_bursts(self._h, ptr, nb, mem, chp, _hostptr(out))
-        if rc:
-            raise AmpsError(rc, "amps_recc_decode_bursts")
+        _call("amps_recc_decode_bursts", self._h, ptr, nb, mem, chp, _hostptr(out))
         return out
 
     # ---- seam (ii): fused IQ ----
     def push_iq(self, iq, nsamp=None):
         """iq: complex64 [C][ld] numpy array, or torch cuda tensor (complex64 [C][ld] or float32 [C][ld][2])."""
-        if isinstance(iq, np.ndarray):
-            iq = np.ascontiguousarray(iq, np.complex64).reshape(self.n_channels, -1)
-            ld = iq.shape[1]
-        else:
-            ld = iq.shape[1]
-        nsamp = ld if nsamp is None else nsamp
+        iq, ld = _fc32_rows(iq, self.n_channels)
         ptr, mem, keep = _as_ptr(iq, self.sync_torch)
-        rc = load().amps_recc_push_iq(self._h, ptr, ld, nsamp, mem)
-        if rc:
-            raise AmpsError(rc, "amps_recc_push_iq")
+        _call("amps_recc_push_iq", self._h, ptr, ld, ld if nsamp is None else nsamp, mem)
 
     def set_xlate(self, rate_hz=400e3, center_hz=160e3, decim=2, gain=0.0, cutoff_hz=0.0, width_hz=0.0):
         """Put the reference flow graph's channel filter (freq_xlating_fir_filter_ccc, grc/recctest.grc:889-937)
         in front of the IQ seam; zeros select the flow graph's gain / cutoff / transition width."""
         x = XlateCfg(C.sizeof(XlateCfg), decim, rate_hz, center_hz, gain, cutoff_hz, width_hz)
-        rc = load().amps_recc_set_xlate(self._h, C.byref(x))
-        if rc:
-            raise AmpsError(rc, "amps_recc_set_xlate")
+        _call("amps_recc_set_xlate", self._h, C.byref(x))
 
     def push_raw(self, iq, nsamp=None):
         """like push_iq, at the translate stage's input rate (e.g. the 400 ksps .raw captures of recctest.grc)."""
-        if isinstance(iq, np.ndarray):
-            iq = np.ascontiguousarray(iq, np.complex64).reshape(self.n_channels, -1)
-        ld = iq.shape[1]
-        nsamp = ld if nsamp is None else nsamp
+        iq, ld = _fc32_rows(iq, self.n_channels)
         ptr, mem, keep = _as_ptr(iq, self.sync_torch)
-        rc = load().amps_recc_push_raw(self._h, ptr, ld, nsamp, mem)
-        if rc:
-            raise AmpsError(rc, "amps_recc_push_raw")
+        _call("amps_recc_push_raw", self._h, ptr, ld, ld if nsamp is None else nsamp, mem)
 
     def debug_xlate(self, iq):
         """Translate stage only (test tap): complex64 [C][n] -> complex64 [C][nout]."""
-        if isinstance(iq, np.ndarray):
-            iq = np.ascontiguousarray(iq, np.complex64).reshape(self.n_channels, -1)
-        n = iq.shape[1]
+        iq, n = _fc32_rows(iq, self.n_channels)
         ptr, mem, keep = _as_ptr(iq)
-        cap = n + 8
-        out = np.zeros((self.n_channels, cap), np.complex64)
-        no = C.c_size_t(0)
-        rc = load().amps_recc_debug_xlate(self._h, ptr, n, n, mem, _hostptr(out), cap, C.byref(no))
-        if rc:
-            raise AmpsError(rc, "amps_recc_debug_xlate")
-        return out[:, :no.value].copy()
+        return self._tap("amps_recc_debug_xlate", self.n_channels, n + 8, ptr, n, n, mem)
 
     # ---- translate seam, shared form: many channels of one narrowband stream
     def set_xlate_shared(self, rate_hz, centers_hz, decim, gain=0.0, cutoff_hz=0.0, width_hz=0.0):
@@ -573,35 +561,27 @@ class Recc:
         cen = np.ascontiguousarray(centers_hz, np.float64).reshape(-1)
         x = XlateSharedCfg(C.sizeof(XlateSharedCfg), int(decim), cen.size, 0, rate_hz, gain, cutoff_hz, width_hz,
                            cen.ctypes.data_as(C.POINTER(C.c_double)))
-        rc = load().amps_recc_set_xlate_shared(self._h, C.byref(x))
-        if rc:
-            raise AmpsError(rc, "amps_recc_set_xlate_shared")
+        _call("amps_recc_set_xlate_shared", self._h, C.byref(x))
 
     def retune_xlate(self, centers_hz):
         """Replace the centres of the configured translate form in mid-stream (amps_recc_retune_xlate): n_channels centres for the
         shared and the resampled form, one for the per-row form.  Takes effect with the next push; from then on the stage delivers,
         bit for bit, what a handle configured with these centres from the start would.  Nothing is reset and the host does not wait."""
         cen = np.ascontiguousarray(centers_hz, np.float64).reshape(-1)
-        rc = load().amps_recc_retune_xlate(self._h, cen.ctypes.data_as(C.POINTER(C.c_double)), cen.size)
-        if rc:
-            raise AmpsError(rc, "amps_recc_retune_xlate")
+        _call("amps_recc_retune_xlate", self._h, cen.ctypes.data_as(C.POINTER(C.c_double)), cen.size)
 
     def set_wideband_shift(self, shift_hz):
         """Correct a tuner's frequency error inside the filter bank (amps_recc_set_wideband_shift; the banks below 1024 branches):
         shift_hz is the frequency in the delivered stream of what shall land on bin 0's centre, so a radio that delivers everything
         e hertz too high gets +e.  Takes effect with the next push; from then on the bank delivers, bit for bit, what a handle with
         this shift from the start would.  Nothing is reset and the host does not wait; 0 runs the unmixed kernels again."""
-        rc = load().amps_recc_set_wideband_shift(self._h, float(shift_hz))
-        if rc:
-            raise AmpsError(rc, "amps_recc_set_wideband_shift")
+        _call("amps_recc_set_wideband_shift", self._h, float(shift_hz))
 
     @property
     def wideband_shift(self):
         """The shift in force in hertz, as quantised to the mixer's step (amps_recc_wideband_shift)."""
         hz = C.c_double(0.0)
-        rc = load().amps_recc_wideband_shift(self._h, C.byref(hz))
-        if rc:
-            raise AmpsError(rc, "amps_recc_wideband_shift")
+        _call("amps_recc_wideband_shift", self._h, C.byref(hz))
         return hz.value
 
     def set_wideband_resample(self, rate_hz, interp, decim, cutoff_hz=0.0, width_hz=0.0):
@@ -611,28 +591,20 @@ class Recc:
         lists what a rate admits.  Every push_wideband* and debug_channelize* then takes blocks at rate_hz; decim 0 removes the stage.
         Before the first push, or after reset()."""
         x = WidebandResampleCfg(C.sizeof(WidebandResampleCfg), int(interp), int(decim), 0, float(rate_hz), float(cutoff_hz), float(width_hz))
-        rc = load().amps_recc_set_wideband_resample(self._h, C.byref(x))
-        if rc:
-            raise AmpsError(rc, "amps_recc_set_wideband_resample")
+        _call("amps_recc_set_wideband_resample", self._h, C.byref(x))
         self.resample = (int(interp), int(decim)) if int(decim) else None
 
     def debug_wideband_resample(self, iq, format=SAMPLES_FC32):
         """The resampler only (test tap), continuing its stream: a block in `format` at the delivered rate -> complex64 [nout] at the
         bank's rate."""
         if format == SAMPLES_FC32 and isinstance(iq, np.ndarray) and iq.dtype == np.complex64:
-            iq, n = np.ascontiguousarray(iq).reshape(-1), iq.size
+            iq, n = _fc32_row(iq)                              # of any shape, flattened
         else:
             iq, n = _typed_block(iq, format, None, "debug_wideband_resample")
         n = n or 0
         ptr, mem, keep = _as_ptr(iq)
         interp, decim = self.resample or (1, 1)
-        cap = n * interp // decim + 2
-        out = np.zeros(cap, np.complex64)
-        no = C.c_size_t(0)
-        rc = load().amps_recc_debug_wideband_resample(self._h, ptr, n, format, mem, _hostptr(out), cap, C.byref(no))
-        if rc:
-            raise AmpsError(rc, "amps_recc_debug_wideband_resample")
-        return out[:no.value].copy()
+        return self._tap("amps_recc_debug_wideband_resample", None, n * interp // decim + 2, ptr, n, format, mem)
 
     def _bank_samples(self, n):
         """samples at the bank's rate that n delivered samples come to at the most"""
@@ -646,38 +618,28 @@ class Recc:
         cen = np.ascontiguousarray(centers_hz, np.float64).reshape(-1)
         x = XlateResampleCfg(C.sizeof(XlateResampleCfg), int(interp), int(decim), cen.size, 0, rate_hz, gain, cutoff_hz, width_hz,
                              cen.ctypes.data_as(C.POINTER(C.c_double)))
-        rc = load().amps_recc_set_xlate_resampled(self._h, C.byref(x))
-        if rc:
-            raise AmpsError(rc, "amps_recc_set_xlate_resampled")
+        _call("amps_recc_set_xlate_resampled", self._h, C.byref(x))
 
     @staticmethod
     def _one_row(iq):
-        if isinstance(iq, np.ndarray):
-            return np.ascontiguousarray(iq, np.complex64).reshape(-1)
-        if iq.dim() != 1 and not (iq.dim() == 2 and iq.shape[-1] == 2 and not iq.is_complex()):
-            raise TypeError("the shared stream is one row: a 1-D complex64 tensor, not shape %r" % (tuple(iq.shape),))
-        return iq.contiguous()
+        """_fc32_row for the shared stream, which refuses a tensor that is not one row"""
+        if not isinstance(iq, np.ndarray):
+            if iq.dim() != 1 and not (iq.dim() == 2 and iq.shape[-1] == 2 and not iq.is_complex()):
+                raise TypeError("the shared stream is one row: a 1-D complex64 tensor, not shape %r" % (tuple(iq.shape),))
+            iq = iq.contiguous()
+        return _fc32_row(iq)
 
     def push_raw_shared(self, iq):
         """one block of the shared stream: a 1-D complex64 numpy array (staged) or torch device tensor (read in place)"""
-        iq = self._one_row(iq)
+        iq, n = self._one_row(iq)
         ptr, mem, keep = _as_ptr(iq, self.sync_torch)
-        rc = load().amps_recc_push_raw_shared(self._h, ptr, iq.shape[0], mem)
-        if rc:
-            raise AmpsError(rc, "amps_recc_push_raw_shared")
+        _call("amps_recc_push_raw_shared", self._h, ptr, n, mem)
 
     def debug_xlate_shared(self, iq):
         """Shared translate stage only (test tap): complex64 [n] -> complex64 [C][nout]."""
-        iq = self._one_row(iq)
-        n = iq.shape[0]
+        iq, n = self._one_row(iq)
         ptr, mem, keep = _as_ptr(iq)
-        cap = n + 8
-        out = np.zeros((self.n_channels, cap), np.complex64)
-        no = C.c_size_t(0)
-        rc = load().amps_recc_debug_xlate_shared(self._h, ptr, n, mem, _hostptr(out), cap, C.byref(no))
-        if rc:
-            raise AmpsError(rc, "amps_recc_debug_xlate_shared")
-        return out[:, :no.value].copy()
+        return self._tap("amps_recc_debug_xlate_shared", self.n_channels, n + 8, ptr, n, mem)
 
     # ---- translate seams on an SDR's integer samples (sc16, sc8, cu8), read in place: include/amps_recc.h, AMPS_RECC_SAMPLES_*
     def push_raw_shared_as(self, iq, format):
@@ -686,22 +648,14 @@ class Recc:
         dtype that does not match the format is a TypeError, never a cast."""
         iq, n = _typed_block(iq, format, None, "push_raw_shared_as")
         ptr, mem, keep = _as_ptr(iq, self.sync_torch)
-        rc = load().amps_recc_push_raw_shared_as(self._h, ptr, n or 0, format, mem)
-        if rc:
-            raise AmpsError(rc, "amps_recc_push_raw_shared_as")
+        _call("amps_recc_push_raw_shared_as", self._h, ptr, n or 0, format, mem)
 
     def debug_xlate_shared_as(self, iq, format):
         """Shared translate stage only (test tap) on a block in `format`: [n, 2] or [2n] -> complex64 [C][nout]."""
         iq, n = _typed_block(iq, format, None, "debug_xlate_shared_as")
         n = n or 0
         ptr, mem, keep = _as_ptr(iq)
-        cap = n + 8
-        out = np.zeros((self.n_channels, cap), np.complex64)
-        no = C.c_size_t(0)
-        rc = load().amps_recc_debug_xlate_shared_as(self._h, ptr, n, format, mem, _hostptr(out), cap, C.byref(no))
-        if rc:
-            raise AmpsError(rc, "amps_recc_debug_xlate_shared_as")
-        return out[:, :no.value].copy()
+        return self._tap("amps_recc_debug_xlate_shared_as", self.n_channels, n + 8, ptr, n, format, mem)
 
     def push_raw_as(self, iq, format, nsamp=None):
         """push_raw on rows in `format`: [C, n, 2] or [C, 2n] of the format's dtype, numpy or torch device tensor; the first nsamp
@@ -710,9 +664,7 @@ class Recc:
         ld = ld or 0
         nsamp = ld if nsamp is None else nsamp
         ptr, mem, keep = _as_ptr(iq, self.sync_torch)
-        rc = load().amps_recc_push_raw_as(self._h, ptr, ld, nsamp, format, mem)
-        if rc:
-            raise AmpsError(rc, "amps_recc_push_raw_as")
+        _call("amps_recc_push_raw_as", self._h, ptr, ld, nsamp, format, mem)
 
     def debug_xlate_as(self, iq, format, nsamp=None):
         """Translate stage only (test tap) on rows in `format`: [C, n, 2] or [C, 2n] -> complex64 [C][nout]."""
@@ -720,47 +672,20 @@ class Recc:
         ld = ld or 0
         nsamp = ld if nsamp is None else nsamp
         ptr, mem, keep = _as_ptr(iq)
-        cap = nsamp + 8
-        out = np.zeros((self.n_channels, cap), np.complex64)
-        no = C.c_size_t(0)
-        rc = load().amps_recc_debug_xlate_as(self._h, ptr, ld, nsamp, format, mem, _hostptr(out), cap, C.byref(no))
-        if rc:
-            raise AmpsError(rc, "amps_recc_debug_xlate_as")
-        return out[:, :no.value].copy()
+        return self._tap("amps_recc_debug_xlate_as", self.n_channels, nsamp + 8, ptr, ld, nsamp, format, mem)
 
     def push_wideband(self, iq):
-        if isinstance(iq, np.ndarray):
-            iq = np.ascontiguousarray(iq, np.complex64).reshape(-1)
-        n = iq.shape[0]
+        iq, n = _fc32_row(iq)
         ptr, mem, keep = _as_ptr(iq, self.sync_torch)
-        rc = load().amps_recc_push_wideband(self._h, ptr, n, mem)
-        if rc:
-            raise AmpsError(rc, "amps_recc_push_wideband")
+        _call("amps_recc_push_wideband", self._h, ptr, n, mem)
 
     def push_wideband_short(self, iq):
         """The wideband block as interleaved 16-bit I/Q (amps_recc_push_wideband_short): a numpy int16 array of shape [n, 2] or [2n], or
         a torch int16 CUDA tensor of the same shapes (read in place, like push_wideband's device blocks).  Nothing else is taken: a
         float array is a TypeError, not a silent cast."""
-        if isinstance(iq, np.ndarray):
-            if iq.dtype != np.int16:
-                raise TypeError("push_wideband_short takes int16 samples, not %s" % iq.dtype)
-            if not (iq.ndim == 1 or (iq.ndim == 2 and iq.shape[1] == 2)) or iq.size % 2:
-                raise TypeError("push_wideband_short takes shape [n, 2] or [2n], not %r" % (iq.shape,))
-            iq = np.ascontiguousarray(iq).reshape(-1)
-        elif hasattr(iq, "data_ptr") and hasattr(iq, "is_cuda"):
-            import torch
-            if iq.dtype != torch.int16 or not iq.is_cuda:
-                raise TypeError("push_wideband_short takes an int16 CUDA tensor, not %s on %s" % (iq.dtype, iq.device))
-            if not (iq.dim() == 1 or (iq.dim() == 2 and iq.shape[1] == 2)) or iq.numel() % 2:
-                raise TypeError("push_wideband_short takes shape [n, 2] or [2n], not %r" % (tuple(iq.shape),))
-            iq = iq.contiguous().reshape(-1)
-        else:
-            raise TypeError(type(iq))
-        n = iq.shape[0] // 2
+        iq, n = _typed_block(iq, SAMPLES_SC16, None, "push_wideband_short")
         ptr, mem, keep = _as_ptr(iq, self.sync_torch)
-        rc = load().amps_recc_push_wideband_short(self._h, ptr, n, mem)
-        if rc:
-            raise AmpsError(rc, "amps_recc_push_wideband_short")
+        _call("amps_recc_push_wideband_short", self._h, ptr, n, mem)
 
     # ---- wideband seam on an SDR's integer samples (sc16, sc8, cu8), read in place: include/amps_recc.h, amps_recc_push_wideband_as
     def push_wideband_as(self, iq, format):
@@ -769,9 +694,7 @@ class Recc:
         push_wideband(convert_samples(iq, format)); a dtype that does not match the format is a TypeError, never a cast."""
         iq, n = _typed_block(iq, format, None, "push_wideband_as")
         ptr, mem, keep = _as_ptr(iq, self.sync_torch)
-        rc = load().amps_recc_push_wideband_as(self._h, ptr, n or 0, format, mem)
-        if rc:
-            raise AmpsError(rc, "amps_recc_push_wideband_as")
+        _call("amps_recc_push_wideband_as", self._h, ptr, n or 0, format, mem)
 
     def debug_channelize_as(self, iq, format):
         """Channelizer only (test tap) on a block in `format`: [n, 2] or [2n] -> complex64 [C][nframes]."""
@@ -779,29 +702,20 @@ class Recc:
         n = n or 0
         ptr, mem, keep = _as_ptr(iq)
         cap = self._bank_samples(n) // min(512, self.decim or 512) + 6          # as debug_channelize
-        out = np.zeros((self.n_channels, cap), np.complex64)
-        nf = C.c_size_t(0)
-        rc = load().amps_recc_debug_channelize_as(self._h, ptr, n, format, mem, _hostptr(out), cap, C.byref(nf))
-        if rc:
-            raise AmpsError(rc, "amps_recc_debug_channelize_as")
-        return out[:, :nf.value].copy()
+        return self._tap("amps_recc_debug_channelize_as", self.n_channels, cap, ptr, n, format, mem)
 
     # ---- one band over the GPUs of a node: RCCL inside the C ABI (include/amps_recc.h, amps_recc_push_wideband_bcast)
     @staticmethod
     def rccl_unique_id():
         """128 bytes from ncclGetUniqueId: one rank makes them, the application carries them to the others"""
         buf = (C.c_uint8 * 128)()
-        rc = load().amps_recc_rccl_unique_id(buf)
-        if rc:
-            raise AmpsError(rc, "amps_recc_rccl_unique_id")
+        _call("amps_recc_rccl_unique_id", buf)
         return bytes(buf)
 
     def rccl_init(self, uid, nranks, rank):
         """collective: returns when all nranks handles (one per GPU / process) have joined"""
         buf = (C.c_uint8 * 128).from_buffer_copy(uid)
-        rc = load().amps_recc_rccl_init(self._h, buf, int(nranks), int(rank))
-        if rc:
-            raise AmpsError(rc, "amps_recc_rccl_init")
+        _call("amps_recc_rccl_init", self._h, buf, int(nranks), int(rank))
 
     def push_wideband_dist(self, iq, nsamp=None, root=0, mode="broadcast"):
         """every rank in step; the root passes its block (a CUDA tensor, used in place, or a numpy array, staged), the others None.
@@ -809,17 +723,14 @@ class Recc:
         The root passing None ends the stream: every rank's call raises AmpsError with code -errno.ENODATA, nothing is pushed."""
         ptr, mem, n = None, MEM_DEVICE, 0
         if iq is not None:
-            if isinstance(iq, np.ndarray):
-                iq = np.ascontiguousarray(iq, np.complex64).reshape(-1)
+            iq, _ = _fc32_row(iq)
             have = int(iq.numel()) if hasattr(iq, "numel") else int(iq.size)      # complex samples
             n = have if nsamp is None else int(nsamp)
             if n > have:                                   # the C side would read past the end of the buffer
                 raise ValueError("nsamp = %d exceeds the %d complex samples of the block" % (n, have))
             ptr, mem, keep = _as_ptr(iq, self.sync_torch)
         pushed = C.c_size_t(0)
-        rc = load().amps_recc_push_wideband_dist(self._h, ptr, n, mem, int(root), DIST_MODES[mode], C.byref(pushed))
-        if rc:
-            raise AmpsError(rc, "amps_recc_push_wideband_dist")
+        _call("amps_recc_push_wideband_dist", self._h, ptr, n, mem, int(root), DIST_MODES[mode], C.byref(pushed))
         return int(pushed.value)
 
     def push_wideband_bcast(self, iq, nsamp=None, root=0):
@@ -828,22 +739,16 @@ class Recc:
 
     def rccl_abort(self):
         """this rank leaves: its communicator is aborted, the peers' bounded waits end with -ETIMEDOUT"""
-        rc = load().amps_recc_rccl_abort(self._h)
-        if rc:
-            raise AmpsError(rc, "amps_recc_rccl_abort")
+        _call("amps_recc_rccl_abort", self._h)
 
     def rccl_set_timeout(self, milliseconds):
-        rc = load().amps_recc_rccl_set_timeout(self._h, int(milliseconds))
-        if rc:
-            raise AmpsError(rc, "amps_recc_rccl_set_timeout")
+        _call("amps_recc_rccl_set_timeout", self._h, int(milliseconds))
 
     def rccl_info(self):
         """the communicator as RCCL reports it + the device it runs on + the timed data collectives, as a dict"""
         info = RcclInfo()
         info.struct_size = C.sizeof(RcclInfo)
-        rc = load().amps_recc_rccl_info(self._h, C.byref(info))
-        if rc:
-            raise AmpsError(rc, "amps_recc_rccl_info")
+        _call("amps_recc_rccl_info", self._h, C.byref(info))
         d = {k: getattr(info, k) for k, _ in RcclInfo._fields_ if k not in ("struct_size", "_pad", "device_uuid", "library")}
         d["device_uuid"] = bytes(info.device_uuid).hex()
         d["library"] = info.library.decode(errors="replace")
@@ -854,34 +759,22 @@ class Recc:
     def drain_gather(self, root=0, cap=None):
         """every rank in step: each drains its own list, the root returns the records of ALL ranks sorted by (channel, position)
         (what one whole-band handle would have drained), the others an empty array"""
-        cap = cap or self.max_bursts
-        out = np.empty(cap, BURST_DTYPE)
-        nout = C.c_size_t(0)
-        rc = load().amps_recc_drain_gather(self._h, _hostptr(out), cap, C.byref(nout), int(root))
-        if rc:
-            raise AmpsError(rc, "amps_recc_drain_gather")
-        return out[:nout.value].copy()
+        return self._records("amps_recc_drain_gather", cap or self.max_bursts, int(root))
 
     def refchain_symbols(self, iq):
         """The flow graph's own sub-chain (quadrature_demod_cf -> clock_recovery_mm_ff -> binary_slicer_fb) on the device:
         complex64 [C][n] at 200 ksps -> list of uint8 symbol arrays, one per channel (continues across calls)."""
-        if isinstance(iq, np.ndarray):
-            iq = np.ascontiguousarray(iq, np.complex64).reshape(self.n_channels, -1)
-        n = iq.shape[1]
+        iq, n = _fc32_rows(iq, self.n_channels)
         ptr, mem, keep = _as_ptr(iq, self.sync_torch)
         cap = n // 9 + 16
         out = np.zeros((self.n_channels, cap), np.uint8)
         ns = np.zeros(self.n_channels, np.uint32)
-        rc = load().amps_recc_refchain_symbols(self._h, ptr, n, n, mem, _hostptr(out), cap, _hostptr(ns))
-        if rc:
-            raise AmpsError(rc, "amps_recc_refchain_symbols")
+        _call("amps_recc_refchain_symbols", self._h, ptr, n, n, mem, _hostptr(out), cap, _hostptr(ns))
         return [out[c, :ns[c]].copy() for c in range(self.n_channels)]
 
     def refchain_tables(self):
         a, m = np.zeros(258, np.float32), np.zeros((129, 8), np.float32)
-        rc = load().amps_recc_refchain_tables(self._h, _hostptr(a), _hostptr(m))
-        if rc:
-            raise AmpsError(rc, "amps_recc_refchain_tables")
+        _call("amps_recc_refchain_tables", self._h, _hostptr(a), _hostptr(m))
         return a, m
 
     def wait_torch(self, stream=None):
@@ -890,9 +783,7 @@ class Recc:
         import torch
         ev = torch.cuda.Event()
         ev.record(stream or torch.cuda.current_stream())
-        rc = load().amps_recc_wait_event(self._h, C.c_void_p(ev.cuda_event))
-        if rc:
-            raise AmpsError(rc, "amps_recc_wait_event")
+        _call("amps_recc_wait_event", self._h, C.c_void_p(ev.cuda_event))
         self._keep_ev = ev
 
     def record_torch_event(self):
@@ -901,9 +792,7 @@ class Recc:
         import torch
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream())          # creates the underlying hipEvent_t
-        rc = load().amps_recc_record_event(self._h, C.c_void_p(ev.cuda_event))
-        if rc:
-            raise AmpsError(rc, "amps_recc_record_event")
+        _call("amps_recc_record_event", self._h, C.c_void_p(ev.cuda_event))
         return ev
 
     def bch_encode(self, msg_bits):
@@ -911,9 +800,7 @@ class Recc:
         m = np.ascontiguousarray(msg_bits, np.uint8)
         n, k = m.shape
         out = np.zeros((n, k + 12), np.uint8)
-        rc = load().amps_bch_encode_words(self._h, _hostptr(m), n, k, MEM_HOST, _hostptr(out))
-        if rc:
-            raise AmpsError(rc, "amps_bch_encode_words")
+        _call("amps_bch_encode_words", self._h, _hostptr(m), n, k, MEM_HOST, _hostptr(out))
         return out
 
     def bch_decode(self, codewords):
@@ -922,97 +809,57 @@ class Recc:
         n, nb = c.shape
         k = nb - 12
         msg, valid, nerr = np.zeros((n, k), np.uint8), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
-        rc = load().amps_bch_decode_words(self._h, _hostptr(c), n, k, MEM_HOST, _hostptr(msg), _hostptr(valid), _hostptr(nerr))
-        if rc:
-            raise AmpsError(rc, "amps_bch_decode_words")
+        _call("amps_bch_decode_words", self._h, _hostptr(c), n, k, MEM_HOST, _hostptr(msg), _hostptr(valid), _hostptr(nerr))
         return msg, valid, nerr
 
     def debug_channelize(self, iq):
         """Channelizer only (test tap): wideband complex64 [n] -> complex64 [C][nframes]."""
-        if isinstance(iq, np.ndarray):
-            iq = np.ascontiguousarray(iq, np.complex64).reshape(-1)
-        n = iq.shape[0]
+        iq, n = _fc32_row(iq)
         ptr, mem, keep = _as_ptr(iq)
         cap = self._bank_samples(n) // min(512, self.decim or 512) + 6          # the frames of the block, and up to four whose samples waited in the carry
-        out = np.zeros((self.n_channels, cap), np.complex64)
-        nf = C.c_size_t(0)
-        rc = load().amps_recc_debug_channelize(self._h, ptr, n, mem, _hostptr(out), cap, C.byref(nf))
-        if rc:
-            raise AmpsError(rc, "amps_recc_debug_channelize")
-        return out[:, :nf.value].copy()
+        return self._tap("amps_recc_debug_channelize", self.n_channels, cap, ptr, n, mem)
 
     def drain(self, cap=None, copy=True):
         """Synchronise and return the decoded bursts since the last drain, sorted by (channel, position).
         copy=False returns a view of a buffer owned by this handle, valid until the next drain()."""
-        cap = cap or self.max_bursts
-        out = getattr(self, "_drain_buf", None)
-        if out is None or out.shape[0] < cap:
-            out = self._drain_buf = np.empty(cap, BURST_DTYPE)
-        nout = C.c_size_t(0)
-        rc = load().amps_recc_drain(self._h, _hostptr(out), cap, C.byref(nout))
-        if rc:
-            raise AmpsError(rc, "amps_recc_drain")
-        return out[:nout.value].copy() if copy else out[:nout.value]
+        return self._records("amps_recc_drain", cap or self.max_bursts, shared=True, copy=copy)
 
     def drain_bursts(self, cap=None):
         """drain() plus the 3374 captured symbol bytes of every record (handle created with keep_bursts=True)"""
         cap = cap or self.max_bursts
-        out = np.empty(cap, BURST_DTYPE)
         sym = np.zeros((cap, CAPTURE), np.uint8)
-        nout = C.c_size_t(0)
-        rc = load().amps_recc_drain_bursts(self._h, _hostptr(out), _hostptr(sym), cap, C.byref(nout))
-        if rc:
-            raise AmpsError(rc, "amps_recc_drain_bursts")
-        return out[:nout.value].copy(), sym[:nout.value].copy()
+        recs = self._records("amps_recc_drain_bursts", cap, symbols=sym)
+        return recs, sym[:len(recs)].copy()
 
     def set_origin(self, first_sample):
         """absolute index of the first sample pushed after create / reset (multiple of 64)"""
-        rc = load().amps_recc_set_origin(self._h, first_sample)
-        if rc:
-            raise AmpsError(rc, "amps_recc_set_origin")
+        _call("amps_recc_set_origin", self._h, first_sample)
         self._origin = int(first_sample)
 
     def drain_begin(self):
         """Close the current record list without waiting; pushes issued after this append to a second list."""
-        rc = load().amps_recc_drain_begin(self._h)
-        if rc:
-            raise AmpsError(rc, "amps_recc_drain_begin")
+        _call("amps_recc_drain_begin", self._h)
 
     def drain_end(self, cap=None, copy=True):
         """Wait for the work enqueued before drain_begin() only, and return its records (sorted)."""
-        cap = cap or self.max_bursts
-        out = getattr(self, "_drain_buf", None)
-        if out is None or out.shape[0] < cap:
-            out = self._drain_buf = np.empty(cap, BURST_DTYPE)
-        nout = C.c_size_t(0)
-        rc = load().amps_recc_drain_end(self._h, _hostptr(out), cap, C.byref(nout))
-        if rc:
-            raise AmpsError(rc, "amps_recc_drain_end")
-        return out[:nout.value].copy() if copy else out[:nout.value]
+        return self._records("amps_recc_drain_end", cap or self.max_bursts, shared=True, copy=copy)
 
     def debug_demod(self, iq):
         iq = np.ascontiguousarray(iq, np.complex64).reshape(-1)
         n = iq.size
         d, s, g = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint8)
-        rc = load().amps_recc_debug_demod(self._h, _hostptr(iq), n, MEM_HOST, _hostptr(d), _hostptr(s), _hostptr(g))
-        if rc:
-            raise AmpsError(rc, "amps_recc_debug_demod")
+        _call("amps_recc_debug_demod", self._h, _hostptr(iq), n, MEM_HOST, _hostptr(d), _hostptr(s), _hostptr(g))
         p = (n // 64) * 64
         return d[:p], s[:p], g[:p]
 
     def debug_slicer_bits(self, first, n):
         """Test tap of the slicer bit ring: (bits uint8 [rows][n], produced) -- the bits of absolute samples [first, first + n) of
         every ring row once the pushes so far have finished, and one past the last sample produced (amps_recc_debug_slicer_bits)."""
-        L = load()
         rows, produced = C.c_uint32(0), C.c_uint64(0)
-        rc = L.amps_recc_debug_slicer_bits(self._h, 0, 0, None, 0, C.byref(rows), C.byref(produced))
-        if rc:
-            raise AmpsError(rc, "amps_recc_debug_slicer_bits")
+        _call("amps_recc_debug_slicer_bits", self._h, 0, 0, None, 0, C.byref(rows), C.byref(produced))
         out = np.zeros((rows.value, n), np.uint8)
         if n:
-            rc = L.amps_recc_debug_slicer_bits(self._h, first, n, _hostptr(out), n, C.byref(rows), C.byref(produced))
-            if rc:
-                raise AmpsError(rc, "amps_recc_debug_slicer_bits")
+            _call("amps_recc_debug_slicer_bits", self._h, first, n, _hostptr(out), n, C.byref(rows), C.byref(produced))
         return out, produced.value
 
     # ---- received power: of the wideband seam (handles created with channel_power=True: one snapshot every 256 frames) and of the IQ
@@ -1033,29 +880,22 @@ class Recc:
 
     def _ring_rows(self, name, ring_slots, dtype, first, n):
         """channel_power / channel_autocorr: ask what is produced, default to the held window, allocate, fetch"""
-        fn = getattr(load(), name)
         rows, prod = C.c_uint32(0), C.c_uint64(0)
-        rc = fn(self._h, 0, 0, None, 0, C.byref(rows), C.byref(prod))
-        if rc:
-            raise AmpsError(rc, name)
+        _call(name, self._h, 0, 0, None, 0, C.byref(rows), C.byref(prod))
         if first is None:
             first = max(-(-self._origin // POWER_STRIDE), prod.value - ring_slots)      # the held window's first entry
         if n is None:
             n = max(0, prod.value - first)
         out = np.zeros((rows.value, n), dtype)
         if n:
-            rc = fn(self._h, first, n, _hostptr(out), n, None, None)
-            if rc:
-                raise AmpsError(rc, name)
+            _call(name, self._h, first, n, _hostptr(out), n, None, None)
         return out, int(first)
 
     def _ring_bursts(self, name, records, dtype):
         """burst_power / burst_autocorr / burst_offset: records in, one value and one count per record out"""
         recs = np.ascontiguousarray(records, BURST_DTYPE).reshape(-1)
         val, cnt = np.zeros(recs.size, dtype), np.zeros(recs.size, np.uint32)
-        rc = getattr(load(), name)(self._h, _hostptr(recs), recs.size, _hostptr(val), _hostptr(cnt))
-        if rc:
-            raise AmpsError(rc, name)
+        _call(name, self._h, _hostptr(recs), recs.size, _hostptr(val), _hostptr(cnt))
         return val, cnt
 
     def burst_power(self, records):
@@ -1096,24 +936,18 @@ class Recc:
     def set_timing(self, mode):
         """mode: "off" | "all" | "dominant" (only the streaming kernel of the seam in use is bracketed by HIP events) |
         "sampled" (the dominant kernel of every eighth push)"""
-        rc = load().amps_recc_set_timing(self._h, {"off": 0, "all": 1, "dominant": 2, "sampled": 3}[mode])
-        if rc:
-            raise AmpsError(rc, "amps_recc_set_timing")
+        _call("amps_recc_set_timing", self._h, {"off": 0, "all": 1, "dominant": 2, "sampled": 3}[mode])
 
     def timing(self, reset=False):
         t = Timing()
-        rc = load().amps_recc_get_timing(self._h, C.byref(t), int(reset))
-        if rc:
-            raise AmpsError(rc, "amps_recc_get_timing")
+        _call("amps_recc_get_timing", self._h, C.byref(t), int(reset))
         return {k: getattr(t, k) for k, _ in Timing._fields_ if k not in ("struct_size", "_pad")}
 
 
 def reply_words(rec):
     rec = np.ascontiguousarray(rec)
     r = Reply()
-    rc = load().amps_recc_reply_words(_hostptr(rec), C.byref(r))
-    if rc:
-        raise AmpsError(rc, "amps_recc_reply_words")
+    _call("amps_recc_reply_words", _hostptr(rec), C.byref(r))
     return r
 
 
@@ -1136,26 +970,14 @@ def subband_plan(rate_hz, width_hz=0.0):
     handle of `sps` samples per symbol, ascending by decim; ntaps is the channel filter's length at transition width width_hz (0 = the
     flow graph's 4.5 kHz).  Empty for a rate no decimation serves (2.048 Msps, or 4 Msps under the default width).  Needs no GPU
     (amps_recc_xlate_shared_plan)."""
-    L = load()
-    n = L.amps_recc_xlate_shared_plan(rate_hz, width_hz, None, 0)
-    if n < 0:
-        raise AmpsError(n, "amps_recc_xlate_shared_plan")
-    out = (XlatePlan * max(n, 1))()
-    n = L.amps_recc_xlate_shared_plan(rate_hz, width_hz, out, n)
-    return [(int(p.decim), int(p.samples_per_symbol), int(p.ntaps)) for p in out[:n]]
+    return _plan("amps_recc_xlate_shared_plan", XlatePlan, rate_hz, width_hz)
 
 
 def wideband_plan(rate_hz):
     """Which filter bank for a wideband stream at rate_hz?  The (channels, decim, sps, taps) Recc(wideband={"channels": .., "decim": ..})
     accepts for that rate, the default decimation first: two for 30.72, 15.36, 7.68 and 3.84 Msps, none for any other rate.  Needs no
     GPU (amps_recc_wideband_plan)."""
-    L = load()
-    n = L.amps_recc_wideband_plan(rate_hz, None, 0)
-    if n < 0:
-        raise AmpsError(n, "amps_recc_wideband_plan")
-    out = (WidebandPlan * max(n, 1))()
-    n = L.amps_recc_wideband_plan(rate_hz, out, n)
-    return [(int(p.channels), int(p.decim), int(p.samples_per_symbol), int(p.taps)) for p in out[:n]]
+    return _plan("amps_recc_wideband_plan", WidebandPlan, rate_hz)
 
 
 def wideband_grid_plan(rate_hz):
@@ -1163,13 +985,7 @@ def wideband_grid_plan(rate_hz):
     entries of wideband_plan with (30000, 1, channels) behind them, and for 25, 20, 10 and 5 Msps the bank of rate / 10 kHz branches:
     10e6 -> [(1000, 250, 2, 3000, 10000, 3, 333)], for Recc(wideband={"channels": 1000, "decim": 250}), a channel on every third
     bin.  Needs no GPU (amps_recc_wideband_grid_plan)."""
-    L = load()
-    n = L.amps_recc_wideband_grid_plan(rate_hz, None, 0)
-    if n < 0:
-        raise AmpsError(n, "amps_recc_wideband_grid_plan")
-    out = (WidebandGridPlan * max(n, 1))()
-    n = L.amps_recc_wideband_grid_plan(rate_hz, out, n)
-    return [(int(p.channels), int(p.decim), int(p.samples_per_symbol), int(p.taps), int(p.bin_hz), int(p.channel_stride), int(p.max_channels)) for p in out[:n]]
+    return _plan("amps_recc_wideband_grid_plan", WidebandGridPlan, rate_hz)
 
 
 def wideband_resample_plan(rate_hz):
@@ -1177,26 +993,13 @@ def wideband_resample_plan(rate_hz):
     bank_decim, sps, ntaps_per_phase, bin_hz, channel_stride, usable_hz) Recc(wideband={"channels": .., "decim": .., "resample":
     (rate_hz, interp, decim)}) accepts: 8e6 -> (5, 2, 2000, 500, ...), (5, 4, 1000, 250, ...), (5, 8, 500, 125, ...).  Needs no GPU
     (amps_recc_wideband_resample_plan)."""
-    L = load()
-    n = L.amps_recc_wideband_resample_plan(rate_hz, None, 0)
-    if n < 0:
-        raise AmpsError(n, "amps_recc_wideband_resample_plan")
-    out = (WidebandResamplePlan * max(n, 1))()
-    n = L.amps_recc_wideband_resample_plan(rate_hz, out, n)
-    return [(int(p.interp), int(p.decim), int(p.channels), int(p.bank_decim), int(p.samples_per_symbol), int(p.ntaps_per_phase),
-             int(p.bin_hz), int(p.channel_stride), int(p.usable_hz)) for p in out[:n]]
+    return _plan("amps_recc_wideband_resample_plan", WidebandResamplePlan, rate_hz)
 
 
 def resample_plan(rate_hz, width_hz=0.0):
     """Which ratio for a stream at rate_hz that subband_plan has no decimation for?  The (interp, decim, sps, ntaps_per_phase)
     Recc.set_xlate_resampled accepts for that rate, ascending by (interp, decim).  Needs no GPU (amps_recc_xlate_resample_plan)."""
-    L = load()
-    n = L.amps_recc_xlate_resample_plan(rate_hz, width_hz, None, 0)
-    if n < 0:
-        raise AmpsError(n, "amps_recc_xlate_resample_plan")
-    out = (ResamplePlan * max(n, 1))()
-    n = L.amps_recc_xlate_resample_plan(rate_hz, width_hz, out, n)
-    return [(int(p.interp), int(p.decim), int(p.samples_per_symbol), int(p.ntaps_per_phase)) for p in out[:n]]
+    return _plan("amps_recc_xlate_resample_plan", ResamplePlan, rate_hz, width_hz)
 
 
 def control_channel_centers(system, tuned_hz):

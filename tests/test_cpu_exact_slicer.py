@@ -109,7 +109,6 @@ def test_streaming_kernels_window_logic_on_the_host(sps):
     import ctypes as C
     from gr_amps_amd import capi
     L = capi.load()
-    L.amps_recc_debug_exact_slice.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     rng = np.random.default_rng(sps)
     for trial in range(300):
         # random sign words, with a bias towards long runs (real signals) in half of the trials
@@ -134,7 +133,6 @@ def test_filter_bank_word_logic_on_the_host(fps):
     import ctypes as C
     from gr_amps_amd import capi
     L = capi.load()
-    L.amps_recc_debug_exact_slice.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     rng = np.random.default_rng(33)
     n = 32 * 40
     sx, st, sc = (rng.integers(0, 2, n) for _ in range(3))

@@ -113,7 +113,6 @@ def test_kernel_word_logic_on_exact_values(exact_rows, sps):
     """exact_slice_word<sps> as the streaming kernel uses it: every 32-sample window, oldest sample at bit 0, bits > sps exact"""
     from gr_amps_amd import capi
     L = capi.load()
-    L.amps_recc_debug_exact_slice.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     weights = (1 << np.arange(32, dtype=np.uint64))
     for key, x in exact_rows.items():
         x = x[:2048]
