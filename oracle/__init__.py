@@ -43,8 +43,25 @@ class Reply(C.Structure):
     ]
 
 
+REFERENCE_DIR = os.environ.get("AMPS_REFERENCE_DIR", "/root/reference")
+REFDRIVER = os.path.join(_HERE, "_ref", "refdriver")
+REFDRIVER_SAN = os.path.join(_HERE, "_ref", "refdriver_san")
+
+
+def build_reference(force=False):
+    """Where the reference's sources are present: compile its integer path in place, with refdriver.cc and the stand-in headers of
+    oracle/refshim/, into oracle/_ref/refdriver and refdriver_san (oracle/Makefile, target _ref).  Nothing happens anywhere else.
+    Returns the driver's path or None."""
+    if not os.path.isfile(os.path.join(REFERENCE_DIR, "lib", "recc_decode_impl.cc")):
+        return None
+    subprocess.check_call(["make", "-C", _HERE, "AMPS_REFERENCE_DIR=" + REFERENCE_DIR] + (["-B"] if force else []) + ["_ref"],
+                          stdout=subprocess.DEVNULL)
+    return REFDRIVER
+
+
 def build(force=False):
     """Compile the C restatement (gcc). Building the checker is not using it."""
+    build_reference(force)
     srcs = [os.path.join(_HERE, f) for f in ("ref_chain.c", "fused_model.c", "amps_oracle.h")]
     srcs += [os.path.join(_HERE, "..", "include", f) for f in ("amps_recc.h", "amps_recc_numerics.h")]
     if not force and os.path.exists(_LIB_PATH):

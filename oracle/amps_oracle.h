@@ -5,11 +5,18 @@
  * cpu_baseline leg of bench.py may load this library; the product (gr_amps_amd/, include/) never
  * includes, links or calls anything in oracle/.
  *
- * PARITY STATUS (see DESIGN.md "Oracle"):  the reference cannot be built in this image -- every
- * source file on the path includes GNU Radio / IT++ / Boost headers that are absent, and writing
- * stand-ins for them is not allowed -- and the reference's own test-suite is empty
- * (lib/qa_amps.cc:9-15): NO reference-produced vector exists, so parity stays "partial".  What pins
- * each row instead (tests/test_cpu_oracle.py, tests/test_cpu_oracle_pins.py, tests/test_gpu_pins.py):
+ * PARITY STATUS (see DESIGN.md "Oracle"):  every source file on the path includes GNU Radio / IT++ /
+ * Boost headers that are absent here.  The INTEGER path (R1, R2, R3, R5-R8, the TX word builders) is
+ * nevertheless held to the reference's own compiled code: oracle/Makefile's target _ref compiles the
+ * reference's recc_impl.cc, recc_decode_impl.cc, amps_packet.cc and utils.cc in place against the
+ * stand-in headers of oracle/refshim/ with oracle/refdriver.cc, tests/golden/make_reference_compiled.py
+ * keeps that program's inputs and outputs (tests/golden/reference_compiled.npz), and
+ * tests/test_cpu_reference_compiled.py / tests/test_gpu_reference_compiled.py compare this library,
+ * the second restatements and the kernels with them, exactly.  The BCH verdict inside that build is a
+ * stand-in (a table decoder held to tests/bchref.py), and the GNU Radio float blocks G1-G4 have NO
+ * reference-produced vector (the reference's own test-suite is empty, lib/qa_amps.cc:9-15): there
+ * parity stays "partial".  What else pins each row
+ * (tests/test_cpu_oracle.py, tests/test_cpu_oracle_pins.py, tests/test_gpu_pins.py):
  *   R1 trigger, R3 Manchester, R6/R7 word + MIN parse, TX word builders
  *        the constants embedded in the reference sources + the known-answer values SURVEY.md 8a
  *        recorded from the reference's compiled code (tests/golden/survey_kats.json)
@@ -32,8 +39,8 @@
  *        a SECOND restatement written apart from this one (tests/refdecode.py: Python over lists, BCH verdict from
  *        tests/bchref.py) agrees with this library and with the HIP kernel on every field of random bursts steered
  *        into all seven message classes, with bit errors and non-Manchester pairs (tests/test_second_restatement.py)
- *        -- two restatements by the same hand, not a reference vector
- *   still unpinned: what only a build of the reference could confirm:
+ *        -- two restatements by the same hand; both equal the compiled reference on what it reveals
+ *   still unpinned: IT++'s own verdict (above), and what only a GNU Radio build could confirm:
  *        G3's loop arithmetic (clock_recovery_mm_ff) and G1's rotator renormalisation period, which
  *        only a GNU Radio build could confirm; word-level equality with the restated chain is
  *        self-consistency, not reference parity.
