@@ -28,6 +28,11 @@ amps.recc -> amps.recc_decode] of grc/recctest.grc.  Needs an MI355X: the librar
                                                   # half is measured as --cfo-unit, every centre is moved by the median of its decoded
                                                   # bursts (Recc.retune_xlate: nothing is reset, the stream goes on) and the second half's
                                                   # residual median is printed -- the mobiles' own offsets are all that is left
+    python examples/decode_subband.py --seizures  # with any of the above: the handle keeps seizure events (Recc(seizure_events=True)), drained
+                                                  # after every push (Recc.drain_seizures), and the stream is pushed in 2 ms blocks; every
+                                                  # burst is printed with found_at - position in milliseconds of stream -- how long after
+                                                  # its trigger the seizure was reported: the block length at most (+ 128 samples), where
+                                                  # its record takes 169 ms more
 """
 import os
 import sys
@@ -41,6 +46,7 @@ RTL2048 = "--rtl2048" in sys.argv[1:]
 RTL = "--rtl" in sys.argv[1:] or RTL2048
 RSSI = "--rssi" in sys.argv[1:]
 AFC = "--afc" in sys.argv[1:]
+SEIZURES = "--seizures" in sys.argv[1:]
 CFO_UNIT = "--cfo-unit" in sys.argv[1:] or AFC
 CFO = "--cfo" in sys.argv[1:] or CFO_UNIT
 TUNER_HZ = 1200.0                                 # --cfo: what every channel is off by; mobile c adds (c % 5 - 2) * 150 Hz of its own
@@ -67,7 +73,7 @@ else:
 
 try:
     rx = capi.Recc(n_channels=len(centres), sps=SPS, max_samples=NSAMP // DECIM if INTERP == 1 else NSAMP * INTERP // DECIM + 1, max_bursts=64,
-                   stream_power=RSSI, stream_offset="unit" if CFO_UNIT else CFO)
+                   stream_power=RSSI, stream_offset="unit" if CFO_UNIT else CFO, seizure_events=SEIZURES)
 except capi.AmpsError as e:
     sys.exit("no MI355X here (%s): the library has no CPU fallback" % e)
 
@@ -75,6 +81,7 @@ rng = np.random.default_rng(7)
 k = np.arange(NSAMP)
 x = np.zeros(NSAMP * HALVES, np.complex128)
 sent, sent_hz, sent2 = {}, {}, {}
+seizures = []                                     # --seizures: the events, as they were drained behind every push
 for c, fc in enumerate(centres):                  # one seizure burst per channel, at its own time
     iq, truth = synth.make_channel_block(NSAMP, 1, seed=7000 + c, sps=RATE / 20e3 if INTERP > 1 else 10 * DECIM, snr_db=40.0, first=FIRST + GAP * c,
                                           **({"cfo_hz": TUNER_HZ + 150.0 * (c % 5 - 2)} if CFO else {}))
@@ -103,11 +110,13 @@ with rx:
         rx.set_xlate_shared(RATE, centres, DECIM, cutoff_hz=CFO_CUTOFF if CFO else 0.0)
     def push_until(end, pos):                     # blocks of any size: samples short of a decimation step wait in the handle
         while pos < end:
-            n = min(int(rng.integers(10_000, 150_000)), end - pos)
+            n = min(int(RATE * 2e-3) if SEIZURES else int(rng.integers(10_000, 150_000)), end - pos)   # --seizures: 2 ms blocks, as a radio delivers
             if SC16 or RTL:
                 rx.push_raw_shared_as(x[pos:pos + n], capi.SAMPLES_SC16 if SC16 else capi.SAMPLES_CU8)
             else:
                 rx.push_raw_shared(x[pos:pos + n])
+            if SEIZURES:
+                seizures.append(rx.drain_seizures())
             pos += n
 
     push_until(NSAMP, 0)
@@ -126,6 +135,16 @@ for r in recs:
     print("  channel %3d (AMPS %d, %.2f MHz)  MIN %s  class %d  words valid %s  %s"
           % (ch, 313 + ch, (TUNED + centres[ch]) / 1e6, got, int(r["msg_class"]), "".join(str(int(v)) for v in r["valid"]),
              "ok" if sent.get(ch) == got else "MISMATCH"))
+if SEIZURES:
+    ev = np.concatenate(seizures)
+    fs = 20e3 * SPS                               # the channel rate: position and found_at count its samples
+    print("seizure events: %d, reported this long after the trigger (found_at - position):" % len(ev))
+    for e in ev:
+        rec = recs[(recs["channel"] == e["channel"]) & (recs["position"] == e["position"])]
+        print("  channel %3d  position %8d  %6.2f ms  coded DCC %s  %s"
+              % (int(e["channel"]), int(e["position"]), 1e3 * (int(e["found_at"]) - int(e["position"])) / fs,
+                 "".join(str(int(b)) for b in e["dcc"]) if int(e["flags"]) & capi.SEIZURE_FLAG_DCC_COMPLETE else "(not in yet)",
+                 "MIN %s" % rec[0]["min"].decode() if len(rec) else "(its record is in the second half)" if AFC else "NO RECORD"))
 if RSSI and len(recs):
     print("burst power, dB relative to the strongest (sent 0, -3, -6, -9, -12 dB in turn):")
     for r, p, nb in zip(recs, power, nblk):

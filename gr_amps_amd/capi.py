@@ -28,6 +28,8 @@ FLAG_CHANNEL_POWER = 512
 FLAG_STREAM_POWER = 0x400                # received power on the IQ and translate seams (block means; channel_power: the wideband seam's snapshots)
 FLAG_STREAM_OFFSET = 0x800               # carrier offset on the IQ and translate seams (lag-one autocorrelation sums per block)
 FLAG_STREAM_OFFSET_UNIT = 0x1000         # the same ring and entry points with the unit-amplitude statistic (the one to use behind a channel filter)
+FLAG_SEIZURE_EVENTS = 0x2000             # one event per seizure after the push in which its trigger was accepted (Recc.drain_seizures)
+SEIZURE_FLAG_DCC_COMPLETE = 1            # amps_recc_seizure_t.flags: dcc / dcc_bad were read (the 14 symbols behind the trigger were in)
 POWER_STRIDE = 256                       # AMPS_RECC_POWER_STRIDE: channel-rate samples between two power snapshots / in one power block
 
 # slicer names accepted by Recc(slicer=...): numeric spec of include/amps_recc_numerics.h -> cfg flag
@@ -53,6 +55,10 @@ BURST_DTYPE = np.dtype([
     ("esn", "<u4"), ("has_esn", "u1"), ("msg_class", "u1"), ("n_called_words", "u1"), ("_pad3", "u1"),
     ("min", "S12"), ("dialed", "S36"), ("_pad4", "<u4"),
 ], align=False)
+
+# mirrors amps_recc_seizure_t of include/amps_recc_seizure.h (32 bytes)
+SEIZURE_DTYPE = np.dtype([("channel", "<u4"), ("flags", "<u4"), ("position", "<u8"), ("dcc", "u1", (7,)), ("dcc_bad", "u1"),
+                          ("found_at", "<u8")], align=False)
 
 
 class Cfg(C.Structure):
@@ -229,6 +235,12 @@ def _prototypes():
 
 PROTOTYPES = _prototypes()
 EXPORTS = tuple(PROTOTYPES)
+# The entry points of the extension headers, in the same form: include/amps_recc_seizure.h (seizure events).  load() sets them up with
+# the table above; tests/test_cpu_seizure_events.py holds the rows to that header's declarations.
+EXTENSION_PROTOTYPES = {
+    "amps_recc_drain_seizures": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+}
+EXTENSION_EXPORTS = tuple(EXTENSION_PROTOTYPES)
 GRID10_CHANNELS = (2500, 2000, 1000, 500)   # branches of the wideband seam's banks of 10 kHz bins: 25, 20, 10 and 5 Msps
 DIST_BROADCAST, DIST_SCATTER_ALLGATHER = 0, 1
 # sample formats of the translate seams' _as entry points (AMPS_RECC_SAMPLES_*): the element dtype of a block, two per sample
@@ -256,7 +268,7 @@ def load():
                           "there is no CPU fallback for the RECC path")
     L = C.CDLL(LIB_PATH)
     missing = []
-    for name, (restype, argtypes) in PROTOTYPES.items():
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(EXTENSION_PROTOTYPES.items()):
         fn = getattr(L, name, None)
         if fn is None:
             missing.append(name)
@@ -391,7 +403,8 @@ class Recc:
 
     def __init__(self, n_channels=1, sps=None, max_samples=0, max_bursts=1024, device=-1, time_kernels=False,
                  stream=None, wideband=None, majority=False, unfused_wideband=False, sync_tolerance=0, slicer="default",
-                 sync_torch=True, keep_bursts=False, fixed_timing=False, channel_power=False, stream_power=False, stream_offset=False):
+                 sync_torch=True, keep_bursts=False, fixed_timing=False, channel_power=False, stream_power=False, stream_offset=False,
+                 seizure_events=False):
         L = load()
         if stream_offset not in (False, True, "unit"):                     # True: the amplitude-weighted sums; "unit": the unit-amplitude ones
             raise ValueError("stream_offset must be False, True or 'unit'")
@@ -431,7 +444,8 @@ class Recc:
                      | _SLICER_FLAGS[slicer]
                      | (FLAG_KEEP_BURSTS if keep_bursts else 0) | (FLAG_FIXED_TIMING if fixed_timing else 0)
                      | (FLAG_CHANNEL_POWER if channel_power else 0) | (FLAG_STREAM_POWER if stream_power else 0)
-                     | (FLAG_STREAM_OFFSET_UNIT if stream_offset == "unit" else FLAG_STREAM_OFFSET if stream_offset else 0))
+                     | (FLAG_STREAM_OFFSET_UNIT if stream_offset == "unit" else FLAG_STREAM_OFFSET if stream_offset else 0)
+                     | (FLAG_SEIZURE_EVENTS if seizure_events else 0))
         cfg.stream = stream
         cfg.sync_tolerance = sync_tolerance
         if wideband:
@@ -830,6 +844,21 @@ class Recc:
         sym = np.zeros((cap, CAPTURE), np.uint8)
         recs = self._records("amps_recc_drain_bursts", cap, symbols=sym)
         return recs, sym[:len(recs)].copy()
+
+    def drain_seizures(self, cap=None):
+        """The seizure events held (handle created with seizure_events=True), oldest first, as a SEIZURE_DTYPE array ordered by
+        (found_at, channel): one per seizure, available after the push in which its trigger was accepted, long before its record
+        (amps_recc_drain_seizures).  At most `cap` (default max_bursts) are taken; the rest stay for the next call.  If events were
+        dropped because the list was full, the AmpsError (-errno.ENOSPC) carries what was delivered as its `seizures` attribute."""
+        cap = self.max_bursts if cap is None else int(cap)
+        out = np.zeros(cap, SEIZURE_DTYPE)
+        nout, nleft = C.c_size_t(0), C.c_size_t(0)
+        try:
+            _call("amps_recc_drain_seizures", self._h, _hostptr(out) if cap else None, cap, C.byref(nout), C.byref(nleft))
+        except AmpsError as e:
+            e.seizures = out[:nout.value].copy()
+            raise
+        return out[:nout.value].copy()
 
     def set_origin(self, first_sample):
         """absolute index of the first sample pushed after create / reset (multiple of 64)"""

@@ -9,6 +9,7 @@
 #include "recc_timing.hip.h"
 #include "recc_stream_power.hip.h"
 #include "recc_stream_offset.hip.h"
+#include "recc_seizure.hip.h"
 
 namespace amps {
 
@@ -244,9 +245,10 @@ inline FrontArgs front_args(const CaptureState &c, RecordLists &L, const FrontGe
 // the fused chain on channel-major device IQ: front -> carry -> resolve -> capture/decode
 // one workgroup per channel; wide groups when a channel spans more wave segments than 256 lanes cover in one batch.
 // pw: the handle keeps received power (AMPS_RECC_FLAG_STREAM_POWER): its block means are taken behind the streaming kernel, from the
-// block and the carry that launch read; ac: likewise its lag-one autocorrelation sums (AMPS_RECC_FLAG_STREAM_OFFSET)
+// block and the carry that launch read; ac: likewise its lag-one autocorrelation sums (AMPS_RECC_FLAG_STREAM_OFFSET); sz: the handle
+// keeps seizure events (AMPS_RECC_FLAG_SEIZURE_EVENTS): their kernel runs behind the resolve, outside its timing span
 inline int capture_run_iq(CaptureState &c, RecordLists &L, TimingState &tm, hipStream_t s, const float2 *iq, uint64_t ld, uint32_t nsamp,
-                          const PowerRing *pw = nullptr, const AutocorrRing *ac = nullptr)
+                          const PowerRing *pw = nullptr, const AutocorrRing *ac = nullptr, const SeizureState *sz = nullptr)
 {
     c.origin_locked = true;
     if (nsamp == 0) return 0;
@@ -284,6 +286,8 @@ inline int capture_run_iq(CaptureState &c, RecordLists &L, TimingState &tm, hipS
     if (P) {
         launch_resolve(c, records_current(L), tm, geom, P, s);
         if (int rc = debug_sync(s, "resolve + capture")) return rc;
+        if (sz) seizure_launch(*sz, c.pending.get(), c.gring.get(), c.ring_words, c.sps, c.n_done + P, s);
+        if (int rc = debug_sync(s, "seizure events")) return rc;
     }
     HIP_TRY(hipGetLastError());
     c.n_done += P;
@@ -293,7 +297,7 @@ inline int capture_run_iq(CaptureState &c, RecordLists &L, TimingState &tm, hipS
 }
 
 // bit-domain tail of the fused wideband seam: the slicer bits of [n_done, n_done + P) are already in the ring
-inline int capture_run_bits(CaptureState &c, RecordLists &L, TimingState &tm, hipStream_t s, uint32_t P)
+inline int capture_run_bits(CaptureState &c, RecordLists &L, TimingState &tm, hipStream_t s, uint32_t P, const SeizureState *sz = nullptr)
 {
     if (P == 0) return 0;
     const FrontGeom geom = front_geometry(c.C, P, c.max_waves_bits);
@@ -318,6 +322,7 @@ inline int capture_run_bits(CaptureState &c, RecordLists &L, TimingState &tm, hi
 #endif
     }
     launch_resolve(c, records_current(L), tm, geom, P, s, in_resolve, zero2);
+    if (sz) seizure_launch(*sz, c.pending.get(), c.gring.get(), c.ring_words, c.sps, c.n_done + P, s);
     HIP_TRY(hipGetLastError());
     c.n_done += P;
     return 0;

@@ -21,6 +21,9 @@
 // xlate_cutoff_hz = 16e3 to steer by it -- or offset_unit = true: with channel_offset = true it selects the
 // unit-amplitude statistic (AMPS_RECC_FLAG_STREAM_OFFSET_UNIT), which reads the offset behind the default filter too (+1500 Hz reads
 // +1495 Hz where the other reads -475 Hz).  The port stays "offset".
+// seizure_events = true keeps seizure events (AMPS_RECC_FLAG_SEIZURE_EVENTS) and adds the port "seizures": pmt::cons(from_long(0),
+// blob(32)), one amps_recc_seizure_t (include/amps_recc_seizure.h) per seizure, published from the work() call whose push accepted its trigger,
+// in front of that call's records -- some 170 ms before the seizure's own record.
 // retune(xlate_center_hz) moves the translate stage's centre in mid-stream (amps_recc_retune_xlate): from the next work() call on the
 // stage delivers what a block made with that centre would; nothing is reset.  Call it from the thread that runs work() (a message
 // handler) or between runs; it throws std::runtime_error where the library refuses (no translate stage, a centre beyond the rate).
@@ -35,7 +38,7 @@ public:
     typedef AMPS_SPTR<recc_fused> sptr;
     static sptr make(int samples_per_symbol = 10, double xlate_rate_hz = 0.0, double xlate_center_hz = 0.0, int xlate_decim = 2,
                      double xlate_cutoff_hz = 0.0, double xlate_width_hz = 0.0, bool channel_power = false, bool channel_offset = false,
-                     bool offset_unit = false);
+                     bool offset_unit = false, bool seizure_events = false);
     virtual void retune(double xlate_center_hz) = 0;
 };
 

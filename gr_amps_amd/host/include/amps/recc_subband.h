@@ -21,6 +21,9 @@
 //                           and the estimate leans the other way; with cutoff_hz = 16e3 it reads about 5 % low.  With
 //                           offset_unit = true the figure is the unit-amplitude statistic's (AMPS_RECC_FLAG_STREAM_OFFSET_UNIT), which
 //                           is usable behind the default filter: within 26 Hz out to +-2.5 kHz (same section);
+//                 "seizures" (blocks made with seizure_events = true only) pmt::cons(from_long(channel), blob(32)): one amps_recc_seizure_t
+//                           (include/amps_recc_seizure.h) per seizure, published from the work() call whose push accepted its trigger, in
+//                           front of that call's records -- some 170 ms before the seizure's own record;
 // as gr::amps::recc_wideband publishes them.  channel c = the channel at centers_hz[c] relative to the stream's centre.
 #pragma once
 #include <amps/api.h>
@@ -46,9 +49,10 @@ public:
     // channel_power: keep per-channel received power (AMPS_RECC_FLAG_STREAM_POWER) and publish every record's burst power on "power"
     // channel_offset: measure the carrier offset (AMPS_RECC_FLAG_STREAM_OFFSET) and publish every record's on "offset"
     // offset_unit: with channel_offset, the unit-amplitude statistic (AMPS_RECC_FLAG_STREAM_OFFSET_UNIT) instead; the port stays "offset"
+    // seizure_events: keep seizure events (AMPS_RECC_FLAG_SEIZURE_EVENTS) and publish them on "seizures"
     static sptr make(double rate_hz, const std::vector<double> &centers_hz, int decim = 4, int samples_per_symbol = 10, int slicer = -1,
                      double cutoff_hz = 0.0, double width_hz = 0.0, int input_format = 0, int interp = 1, bool channel_power = false,
-                     bool channel_offset = false, bool offset_unit = false);
+                     bool channel_offset = false, bool offset_unit = false, bool seizure_events = false);
     // new centres in mid-stream (amps_recc_retune_xlate): as many as the block was made with; from the next work() call on the stage
     // delivers what a block made with these centres would, and nothing is reset.  Call it from the thread that runs work() (a message
     // handler) or between runs; throws std::runtime_error where the library refuses (another number of centres, one beyond the rate)

@@ -11,6 +11,10 @@
 //                           (linear, unscaled: 1.0 for a mobile at full scale of an fc32 stream, the input's own units squared behind an integer format) and
 //                           the number of power snapshots averaged (26 / 27 at decim 768, 39 / 40 at 512; 0 with power 0.0 if the handle no
 //                           longer held them).  The block drains after every push, so every record is covered.
+//                 "seizures" (blocks made with seizure_events = true only) pmt::cons(from_long(channel), blob(32)): one amps_recc_seizure_t
+//                           (include/amps_recc_seizure.h) per seizure, published from the work() call whose push accepted its trigger, in
+//                           front of that call's records -- some 170 ms before the seizure's own record: what an FOCC block needs to
+//                           set its busy-idle bits in time.  Behind set_rccl a rank publishes its own group's events.
 // With channels = 512, 256 or 128 the input is a stream at channels x 30 kHz = 15.36, 7.68 or 3.84 Msps -- what one SDR delivers -- through
 // the bank of that many branches, in the two-kernel form (cfg.wideband_channels of include/amps_recc.h); "power" then carries the stream
 // power of the IQ seam (AMPS_RECC_FLAG_STREAM_POWER: the mean of |y|^2 over the blocks of 256 channel-rate samples inside the capture).
@@ -57,9 +61,10 @@ public:
     //         resampled by interp / decim_in to the bank's rate on the device -- a HackRF's 8 Msps x 5/4 into channels = 1000, 12.5 Msps x 2/1
     //         into 2500; amps_recc_wideband_resample_plan lists what a rate admits.  rate_hz = 0: none.  A ratio or rate the library refuses
     //         throws.  Not with set_rccl, which throws on such a block: the library has no distributed push behind a resampler (-ENOSYS).
+    // seizure_events: keep seizure events (AMPS_RECC_FLAG_SEIZURE_EVENTS) and publish them on "seizures"
     static sptr make(int n_channels = 832, int first_bin = 96, int slicer = -1, int groups = 0, int group = 0, int decim = 0, bool short_input = false,
                      bool channel_power = false, int channels = 1024, int input_format = 0, double shift_hz = 0.0,
-                     double rate_hz = 0.0, int interp = 1, int decim_in = 1);
+                     double rate_hz = 0.0, int interp = 1, int decim_in = 1, bool seizure_events = false);
     // Replace the shift in mid-stream: in force from the next work() call on, nothing reset, and from then on the bank delivers what a
     // block made with this shift would.  Throws where the library refuses (NaN, beyond +- fs / 2, a 1024 bank).
     virtual void set_shift(double shift_hz) = 0;

@@ -1,12 +1,14 @@
 // recc_publish.h -- what recc_wideband, recc_subband and recc_fused do behind every push: drain the records with their bursts, ask for
 // their burst power where the block keeps power and for their carrier offset where it measures that, and publish on "bursts",
-// "records", "power" and "offset".  Internal to lib/.
+// "records", "power" and "offset"; and, on a block made with seizure_events, in front of all that the push's seizure events on
+// "seizures".  Internal to lib/.
 #pragma once
 #include <amps/api.h>
 #include <cerrno>
 #include <cstdint>
 #include <cstdio>
 #include "amps_recc.h"
+#include "amps_recc_seizure.h"
 
 namespace gr {
 namespace amps {
@@ -17,6 +19,23 @@ static_assert(sizeof(recc_power_payload) == 8, "payload of the power port");
 // payload of the "offset" port, behind the record's channel number (amps_recc_burst_offset)
 struct recc_offset_payload { float offset_hz; uint32_t n_blocks; };
 static_assert(sizeof(recc_offset_payload) == 8, "payload of the offset port");
+
+// The seizure events held behind the push just made (AMPS_RECC_FLAG_SEIZURE_EVENTS), oldest first, each as
+// pmt::cons(channel, blob(amps_recc_seizure_t)) on "seizures": called right behind the push and before recc_drain_and_publish, so an
+// event goes out in front of that call's records -- and its own record comes with a later push.  false = stop the flow graph.
+inline bool recc_publish_seizures(gr::basic_block &blk, const char *name, amps_recc_t *h)
+{
+    amps_recc_seizure_t ev[64];
+    size_t n = 0, left = 0;
+    do {
+        const int rc = amps_recc_drain_seizures(h, ev, sizeof(ev) / sizeof(ev[0]), &n, &left);
+        if (rc == -ENOSPC) std::fprintf(stderr, "amps::%s: %s (seizure events dropped, continuing)\n", name, amps_recc_strerror(rc));
+        else if (rc != 0) { std::fprintf(stderr, "amps::%s: seizure events: %s\n", name, amps_recc_strerror(rc)); return false; }
+        for (size_t i = 0; i < n; i++)
+            blk.message_port_pub(pmt::mp("seizures"), pmt::cons(pmt::from_long((long)ev[i].channel), pmt::mp(&ev[i], sizeof(ev[i]))));
+    } while (left);
+    return true;
+}
 
 // What differs between the blocks: the name in the stderr lines, and whether "bursts" and "records" carry (channel, blob) pairs
 // or the bare blob (recc_fused: one channel, and what gr::amps::recc publishes).  recs / bursts hold `cap` records; pow / nsnap hold as
