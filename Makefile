@@ -23,7 +23,7 @@ all: $(PKG)/libamps_recc.so $(PKG)/libgnuradio-amps-mi355x.so $(PKG)/recctest or
 $(PKG)/libamps_recc.so: $(CSRC)/amps_recc.hip $(wildcard $(CSRC)/*.h) $(wildcard $(CSRC)/*.inc) $(wildcard include/*.h)
 	$(HIPCC) $(HIPFLAGS) -Iinclude -I$(CSRC) $(CSRC)/amps_recc.hip -o $@
 
-$(PKG)/libgnuradio-amps-mi355x.so: $(HOSTSRC) $(wildcard $(HOST)/lib/*.h) $(HOST)/gr_min/gnuradio_min.h include/amps_recc.h include/amps_recc_seizure.h $(PKG)/libamps_recc.so
+$(PKG)/libgnuradio-amps-mi355x.so: $(HOSTSRC) $(wildcard $(HOST)/lib/*.h) $(HOST)/gr_min/gnuradio_min.h include/amps_recc.h include/amps_recc_seizure.h include/amps_recc_early.h $(PKG)/libamps_recc.so
 	$(CXX) -std=c++17 -O2 -fPIC -Wall $(HOSTINC) -shared -o $@ $(HOSTSRC) -L$(PKG) -lamps_recc -Wl,-rpath,'$$ORIGIN'
 
 $(PKG)/recctest: $(HOST)/apps/recctest.cc $(PKG)/libgnuradio-amps-mi355x.so

@@ -33,6 +33,11 @@ amps.recc -> amps.recc_decode] of grc/recctest.grc.  Needs an MI355X: the librar
                                                   # burst is printed with found_at - position in milliseconds of stream -- how long after
                                                   # its trigger the seizure was reported: the block length at most (+ 128 samples), where
                                                   # its record takes 169 ms more
+    python examples/decode_subband.py --early     # with any of the above: the handle keeps early messages (Recc(early_messages=True)); the
+                                                  # stream is pushed in 2 ms blocks and the early messages and the records are drained after
+                                                  # every push (Recc.drain_early, Recc.drain).  Per mobile: stream time from its trigger to
+                                                  # its early message -- 24 ms per announced word and at most a block -- and to its record,
+                                                  # 169 ms and at most a block; the early message's MIN is the record's
 """
 import os
 import sys
@@ -47,6 +52,7 @@ RTL = "--rtl" in sys.argv[1:] or RTL2048
 RSSI = "--rssi" in sys.argv[1:]
 AFC = "--afc" in sys.argv[1:]
 SEIZURES = "--seizures" in sys.argv[1:]
+EARLY = "--early" in sys.argv[1:]
 CFO_UNIT = "--cfo-unit" in sys.argv[1:] or AFC
 CFO = "--cfo" in sys.argv[1:] or CFO_UNIT
 TUNER_HZ = 1200.0                                 # --cfo: what every channel is off by; mobile c adds (c % 5 - 2) * 150 Hz of its own
@@ -73,7 +79,7 @@ else:
 
 try:
     rx = capi.Recc(n_channels=len(centres), sps=SPS, max_samples=NSAMP // DECIM if INTERP == 1 else NSAMP * INTERP // DECIM + 1, max_bursts=64,
-                   stream_power=RSSI, stream_offset="unit" if CFO_UNIT else CFO, seizure_events=SEIZURES)
+                   stream_power=RSSI, stream_offset="unit" if CFO_UNIT else CFO, seizure_events=SEIZURES, early_messages=EARLY)
 except capi.AmpsError as e:
     sys.exit("no MI355X here (%s): the library has no CPU fallback" % e)
 
@@ -82,6 +88,7 @@ k = np.arange(NSAMP)
 x = np.zeros(NSAMP * HALVES, np.complex128)
 sent, sent_hz, sent2 = {}, {}, {}
 seizures = []                                     # --seizures: the events, as they were drained behind every push
+early, early_recs, recs_at = [], [], []           # --early: the early messages and the records as they were drained, and the samples processed by then
 for c, fc in enumerate(centres):                  # one seizure burst per channel, at its own time
     iq, truth = synth.make_channel_block(NSAMP, 1, seed=7000 + c, sps=RATE / 20e3 if INTERP > 1 else 10 * DECIM, snr_db=40.0, first=FIRST + GAP * c,
                                           **({"cfo_hz": TUNER_HZ + 150.0 * (c % 5 - 2)} if CFO else {}))
@@ -110,17 +117,21 @@ with rx:
         rx.set_xlate_shared(RATE, centres, DECIM, cutoff_hz=CFO_CUTOFF if CFO else 0.0)
     def push_until(end, pos):                     # blocks of any size: samples short of a decimation step wait in the handle
         while pos < end:
-            n = min(int(RATE * 2e-3) if SEIZURES else int(rng.integers(10_000, 150_000)), end - pos)   # --seizures: 2 ms blocks, as a radio delivers
+            n = min(int(RATE * 2e-3) if SEIZURES or EARLY else int(rng.integers(10_000, 150_000)), end - pos)   # --seizures: 2 ms blocks, as a radio delivers
             if SC16 or RTL:
                 rx.push_raw_shared_as(x[pos:pos + n], capi.SAMPLES_SC16 if SC16 else capi.SAMPLES_CU8)
             else:
                 rx.push_raw_shared(x[pos:pos + n])
             if SEIZURES:
                 seizures.append(rx.drain_seizures())
+            if EARLY:
+                early.append(rx.drain_early())
+                early_recs.append(rx.drain())
+                recs_at.extend([rx.debug_slicer_bits(0, 0)[1]] * len(early_recs[-1]))
             pos += n
 
     push_until(NSAMP, 0)
-    recs = rx.drain()
+    recs = np.concatenate(early_recs + [rx.drain()]) if EARLY else rx.drain()
     power, nblk = rx.burst_power(recs) if RSSI else (None, None)
     read_hz, nblk_hz = rx.burst_offset(recs) if CFO else (None, None)
     if AFC:                                       # steer by the first half, then go on with the stream: nothing is reset
@@ -145,6 +156,17 @@ if SEIZURES:
               % (int(e["channel"]), int(e["position"]), 1e3 * (int(e["found_at"]) - int(e["position"])) / fs,
                  "".join(str(int(b)) for b in e["dcc"]) if int(e["flags"]) & capi.SEIZURE_FLAG_DCC_COMPLETE else "(not in yet)",
                  "MIN %s" % rec[0]["min"].decode() if len(rec) else "(its record is in the second half)" if AFC else "NO RECORD"))
+if EARLY:
+    ev = np.concatenate(early)
+    fs = 20e3 * SPS                               # the channel rate: position, found_at and the samples processed count its samples
+    print("early messages: %d, stream time from the trigger to the message and to its record:" % len(ev))
+    for e in ev:
+        ch, pos = int(e["rec"]["channel"]), int(e["rec"]["position"])
+        i = np.nonzero((recs["channel"] == ch) & (recs["position"] == pos))[0]
+        after = "%6.2f ms" % (1e3 * (recs_at[i[0]] - pos) / fs) if len(i) and i[0] < len(recs_at) else "(not drained in the first half)"
+        print("  channel %3d  position %8d  words %d  MIN %s  message after %6.2f ms, record after %s  %s"
+              % (ch, pos, int(e["n_words"]), e["rec"]["min"].decode(), 1e3 * (int(e["found_at"]) - pos) / fs, after,
+                 "ok" if len(i) and recs[i[0]]["min"] == e["rec"]["min"] else "NO RECORD" if not len(i) else "MISMATCH"))
 if RSSI and len(recs):
     print("burst power, dB relative to the strongest (sent 0, -3, -6, -9, -12 dB in turn):")
     for r, p, nb in zip(recs, power, nblk):

@@ -29,6 +29,7 @@ FLAG_STREAM_POWER = 0x400                # received power on the IQ and translat
 FLAG_STREAM_OFFSET = 0x800               # carrier offset on the IQ and translate seams (lag-one autocorrelation sums per block)
 FLAG_STREAM_OFFSET_UNIT = 0x1000         # the same ring and entry points with the unit-amplitude statistic (the one to use behind a channel filter)
 FLAG_SEIZURE_EVENTS = 0x2000             # one event per seizure after the push in which its trigger was accepted (Recc.drain_seizures)
+FLAG_EARLY_MESSAGES = 0x4000             # a message's announced words after the push in which the last of them arrived (Recc.drain_early)
 SEIZURE_FLAG_DCC_COMPLETE = 1            # amps_recc_seizure_t.flags: dcc / dcc_bad were read (the 14 symbols behind the trigger were in)
 POWER_STRIDE = 256                       # AMPS_RECC_POWER_STRIDE: channel-rate samples between two power snapshots / in one power block
 
@@ -59,6 +60,9 @@ BURST_DTYPE = np.dtype([
 # mirrors amps_recc_seizure_t of include/amps_recc_seizure.h (32 bytes)
 SEIZURE_DTYPE = np.dtype([("channel", "<u4"), ("flags", "<u4"), ("position", "<u8"), ("dcc", "u1", (7,)), ("dcc_bad", "u1"),
                           ("found_at", "<u8")], align=False)
+
+# mirrors amps_recc_early_t of include/amps_recc_early.h (744 bytes)
+EARLY_DTYPE = np.dtype([("rec", BURST_DTYPE), ("found_at", "<u8"), ("n_words", "<u4"), ("_pad", "<u4")], align=False)
 
 
 class Cfg(C.Structure):
@@ -241,6 +245,11 @@ EXTENSION_PROTOTYPES = {
     "amps_recc_drain_seizures": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
 }
 EXTENSION_EXPORTS = tuple(EXTENSION_PROTOTYPES)
+# include/amps_recc_early.h (early messages), a table of its own: tests/test_cpu_early_messages.py holds the rows to that header
+EARLY_PROTOTYPES = {
+    "amps_recc_drain_early": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+}
+EARLY_EXPORTS = tuple(EARLY_PROTOTYPES)
 GRID10_CHANNELS = (2500, 2000, 1000, 500)   # branches of the wideband seam's banks of 10 kHz bins: 25, 20, 10 and 5 Msps
 DIST_BROADCAST, DIST_SCATTER_ALLGATHER = 0, 1
 # sample formats of the translate seams' _as entry points (AMPS_RECC_SAMPLES_*): the element dtype of a block, two per sample
@@ -268,7 +277,7 @@ def load():
                           "there is no CPU fallback for the RECC path")
     L = C.CDLL(LIB_PATH)
     missing = []
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(EXTENSION_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(EXTENSION_PROTOTYPES.items()) + list(EARLY_PROTOTYPES.items()):
         fn = getattr(L, name, None)
         if fn is None:
             missing.append(name)
@@ -404,7 +413,7 @@ class Recc:
     def __init__(self, n_channels=1, sps=None, max_samples=0, max_bursts=1024, device=-1, time_kernels=False,
                  stream=None, wideband=None, majority=False, unfused_wideband=False, sync_tolerance=0, slicer="default",
                  sync_torch=True, keep_bursts=False, fixed_timing=False, channel_power=False, stream_power=False, stream_offset=False,
-                 seizure_events=False):
+                 seizure_events=False, early_messages=False):
         L = load()
         if stream_offset not in (False, True, "unit"):                     # True: the amplitude-weighted sums; "unit": the unit-amplitude ones
             raise ValueError("stream_offset must be False, True or 'unit'")
@@ -445,7 +454,7 @@ class Recc:
                      | (FLAG_KEEP_BURSTS if keep_bursts else 0) | (FLAG_FIXED_TIMING if fixed_timing else 0)
                      | (FLAG_CHANNEL_POWER if channel_power else 0) | (FLAG_STREAM_POWER if stream_power else 0)
                      | (FLAG_STREAM_OFFSET_UNIT if stream_offset == "unit" else FLAG_STREAM_OFFSET if stream_offset else 0)
-                     | (FLAG_SEIZURE_EVENTS if seizure_events else 0))
+                     | (FLAG_SEIZURE_EVENTS if seizure_events else 0) | (FLAG_EARLY_MESSAGES if early_messages else 0))
         cfg.stream = stream
         cfg.sync_tolerance = sync_tolerance
         if wideband:
@@ -857,6 +866,23 @@ class Recc:
             _call("amps_recc_drain_seizures", self._h, _hostptr(out) if cap else None, cap, C.byref(nout), C.byref(nleft))
         except AmpsError as e:
             e.seizures = out[:nout.value].copy()
+            raise
+        return out[:nout.value].copy()
+
+    def drain_early(self, cap=None):
+        """The early messages held (handle created with early_messages=True), oldest first, as an EARLY_DTYPE array ordered by
+        (found_at, channel): per seizure whose word A announced fewer than seven words, the record of those words (`rec`, a
+        BURST_DTYPE: what the later record will carry for them, bit for bit), available after the push in which the last repeat of the
+        last of them arrived (amps_recc_drain_early).  At most `cap` (default max_bursts) are taken; the rest stay for the next call.
+        If events were dropped because the list was full, the AmpsError (-errno.ENOSPC) carries what was delivered as its `early`
+        attribute."""
+        cap = self.max_bursts if cap is None else int(cap)
+        out = np.zeros(cap, EARLY_DTYPE)
+        nout, nleft = C.c_size_t(0), C.c_size_t(0)
+        try:
+            _call("amps_recc_drain_early", self._h, _hostptr(out) if cap else None, cap, C.byref(nout), C.byref(nleft))
+        except AmpsError as e:
+            e.early = out[:nout.value].copy()
             raise
         return out[:nout.value].copy()
 

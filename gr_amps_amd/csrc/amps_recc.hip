@@ -13,6 +13,7 @@
 
 #include "amps_recc.h"
 #include "amps_recc_seizure.h"
+#include "amps_recc_early.h"
 #include "amps_recc_numerics.h"
 #include "recc_timing.hip.h"
 #include "recc_records.hip.h"
@@ -42,6 +43,7 @@ struct amps_recc {
     TimingState tm;
     RecordLists lists;                // where the capture seam's records go, and the split drain
     SeizureState seizures;            // seizure events (AMPS_RECC_FLAG_SEIZURE_EVENTS): what was reported, the event list
+    EarlyState early;                 // early messages (AMPS_RECC_FLAG_EARLY_MESSAGES): how far each pending capture was looked at, the event list
     CaptureState cap;                 // trigger search, resolve, capture and decode behind the IQ seam and the wideband seam
     SymbolsState sym;
     BchScratch bch;                   // amps_bch_*
@@ -80,6 +82,7 @@ bool is_group_handle(const amps_recc *h) { return h->chz.enabled && h->chz.group
 const PowerRing *power_of(const amps_recc *h) { return h->power.ring ? &h->power : nullptr; }
 const AutocorrRing *offset_of(const amps_recc *h) { return h->offset.ring ? &h->offset : nullptr; }
 const SeizureState *seizures_of(const amps_recc *h) { return h->seizures.enabled ? &h->seizures : nullptr; }
+const EarlyState *early_of(const amps_recc *h) { return h->early.enabled ? &h->early : nullptr; }
 
 int reset_state(amps_recc *h)
 {
@@ -89,6 +92,7 @@ int reset_state(amps_recc *h)
     if (int rc = block_ring_reset(h->offset, s)) return rc;
     if (int rc = records_reset(h->lists, s)) return rc;
     if (int rc = seizure_reset(h->seizures, s)) return rc;
+    if (int rc = early_reset(h->early, s)) return rc;
     if (int rc = symbols_reset(h->sym, s)) return rc;
     if (int rc = channelizer_reset(h->chz, s)) return rc;
     if (int rc = xlate_reset(h->xl, s)) return rc;
@@ -181,6 +185,7 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
     constexpr uint32_t OFFSET_FLAGS = AMPS_RECC_FLAG_STREAM_OFFSET | AMPS_RECC_FLAG_STREAM_OFFSET_UNIT;
     if ((cfg->flags & OFFSET_FLAGS) == OFFSET_FLAGS) return -EINVAL;
     if ((cfg->flags & AMPS_RECC_FLAG_SEIZURE_EVENTS) && !cfg->max_samples_per_push) return -EINVAL;   // the symbol seam has no trigger of its own to report
+    if ((cfg->flags & AMPS_RECC_FLAG_EARLY_MESSAGES) && !cfg->max_samples_per_push) return -EINVAL;   // nor a capture that is still coming in
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return -ENODEV;
     int dev = cfg->device;
@@ -214,6 +219,7 @@ int amps_recc_create(amps_recc_t **out, const amps_recc_cfg_t *cfg_in)
     if (!rc && cfg->max_samples_per_push) rc = capture_create(h->cap, *cfg, h->C, h->slicer, cfg->wideband_channels != 0, dev);
     step("IQ seam buffers allocated");
     if (!rc && (cfg->flags & AMPS_RECC_FLAG_SEIZURE_EVENTS)) rc = seizure_create(h->seizures, h->C, cfg->max_bursts);
+    if (!rc && (cfg->flags & AMPS_RECC_FLAG_EARLY_MESSAGES)) rc = early_create(h->early, h->C, cfg->max_bursts);
     if (!rc && (cfg->flags & AMPS_RECC_FLAG_STREAM_POWER)) rc = block_ring_create(h->power, PowerRule::BLOCK, h->C, h->cap.ring_words);
     if (!rc && (cfg->flags & OFFSET_FLAGS)) rc = block_ring_create(h->offset, PowerRule::BLOCK, h->C, h->cap.ring_words, (cfg->flags & AMPS_RECC_FLAG_STREAM_OFFSET_UNIT) != 0);
     if (!rc && cfg->wideband_channels) rc = channelizer_create(h->chz, *cfg);
@@ -307,7 +313,7 @@ int amps_recc_push_iq(amps_recc_t *h, const float *iq, size_t ld, size_t nsamp, 
     if (mem == AMPS_MEM_HOST) {
         if (int rc = h->cap.stage_iq.stage(d, ld, nsamp, h->C, (size_t)h->C * h->cfg.max_samples_per_push, &d, &dld)) return rc;
     }
-    int rc = capture_run_iq(h->cap, h->lists, h->tm, h->stream.get(), d, dld, (uint32_t)nsamp, power_of(h), offset_of(h), seizures_of(h));
+    int rc = capture_run_iq(h->cap, h->lists, h->tm, h->stream.get(), d, dld, (uint32_t)nsamp, power_of(h), offset_of(h), seizures_of(h), early_of(h));
     if (!rc && mem == AMPS_MEM_HOST) rc = h->cap.stage_iq.arm(h->stream.get());
     return rc;
 }
@@ -342,8 +348,8 @@ static int push_wideband_block(amps_recc_t *h, const void *iq, size_t nsamp, int
     }
     if (rc) return rc;
     if (nout > h->cfg.max_samples_per_push) return -E2BIG;
-    if (fused) return capture_run_bits(h->cap, h->lists, h->tm, h->stream.get(), nout, seizures_of(h));
-    return capture_run_iq(h->cap, h->lists, h->tm, h->stream.get(), chan_iq, ld, nout, power_of(h), offset_of(h), seizures_of(h));   // (rings: CHZ_HAS_STREAM_RINGS only)
+    if (fused) return capture_run_bits(h->cap, h->lists, h->tm, h->stream.get(), nout, seizures_of(h), early_of(h));
+    return capture_run_iq(h->cap, h->lists, h->tm, h->stream.get(), chan_iq, ld, nout, power_of(h), offset_of(h), seizures_of(h), early_of(h));   // (rings: CHZ_HAS_STREAM_RINGS only)
 }
 
 int amps_recc_push_wideband(amps_recc_t *h, const float *iq, size_t nsamp, int mem) { return push_wideband_block(h, iq, nsamp, mem, AMPS_RECC_SAMPLES_FC32); }
@@ -526,7 +532,7 @@ static int xlate_push(amps_recc *h, const void *iq, size_t ld, size_t nsamp, int
     if (rc) return rc;
     if (int rc2 = debug_sync(h->stream.get(), what)) return rc2;
     if (nout == 0) return 0;
-    return capture_run_iq(h->cap, h->lists, h->tm, h->stream.get(), f, fld, nout, power_of(h), offset_of(h), seizures_of(h));
+    return capture_run_iq(h->cap, h->lists, h->tm, h->stream.get(), f, fld, nout, power_of(h), offset_of(h), seizures_of(h), early_of(h));
 }
 
 // test tap: run the translate stage alone and copy its rows out
@@ -891,6 +897,21 @@ int amps_recc_drain_seizures(amps_recc_t *h, amps_recc_seizure_t *out, size_t ca
     const int rc = seizure_drain(h->seizures, h->stream.get(), out, cap, nout, nleft);
     if (is_group_handle(h))                                        // rows of a channel group -> channel numbers, as the records
         for (size_t i = 0; i < *nout; i++) out[i].channel = out[i].channel < h->chz.row2chan.size() ? h->chz.row2chan[out[i].channel] : out[i].channel;
+    return rc;
+}
+
+int amps_recc_drain_early(amps_recc_t *h, amps_recc_early_t *out, size_t cap, size_t *nout, size_t *nleft)
+{
+    if (!h || !nout || (!out && cap)) return -EINVAL;
+    *nout = 0;
+    if (nleft) *nleft = 0;
+    if (!h->early.enabled) return -ENOSYS;
+    STALE_CHECK(h);
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = sync_stream(h, h->stream.get())) return rc;
+    const int rc = early_drain(h->early, h->stream.get(), out, cap, nout, nleft);
+    if (is_group_handle(h))                                        // rows of a channel group -> channel numbers, as the records
+        for (size_t i = 0; i < *nout; i++) out[i].rec.channel = out[i].rec.channel < h->chz.row2chan.size() ? h->chz.row2chan[out[i].rec.channel] : out[i].rec.channel;
     return rc;
 }
 

@@ -10,6 +10,7 @@
 #include "recc_stream_power.hip.h"
 #include "recc_stream_offset.hip.h"
 #include "recc_seizure.hip.h"
+#include "recc_early.hip.h"
 
 namespace amps {
 
@@ -246,9 +247,11 @@ inline FrontArgs front_args(const CaptureState &c, RecordLists &L, const FrontGe
 // one workgroup per channel; wide groups when a channel spans more wave segments than 256 lanes cover in one batch.
 // pw: the handle keeps received power (AMPS_RECC_FLAG_STREAM_POWER): its block means are taken behind the streaming kernel, from the
 // block and the carry that launch read; ac: likewise its lag-one autocorrelation sums (AMPS_RECC_FLAG_STREAM_OFFSET); sz: the handle
-// keeps seizure events (AMPS_RECC_FLAG_SEIZURE_EVENTS): their kernel runs behind the resolve, outside its timing span
+// keeps seizure events (AMPS_RECC_FLAG_SEIZURE_EVENTS): their kernel runs behind the resolve, outside its timing span; ez: it keeps
+// early messages (AMPS_RECC_FLAG_EARLY_MESSAGES): their two kernels run behind that one
 inline int capture_run_iq(CaptureState &c, RecordLists &L, TimingState &tm, hipStream_t s, const float2 *iq, uint64_t ld, uint32_t nsamp,
-                          const PowerRing *pw = nullptr, const AutocorrRing *ac = nullptr, const SeizureState *sz = nullptr)
+                          const PowerRing *pw = nullptr, const AutocorrRing *ac = nullptr, const SeizureState *sz = nullptr,
+                          const EarlyState *ez = nullptr)
 {
     c.origin_locked = true;
     if (nsamp == 0) return 0;
@@ -288,6 +291,8 @@ inline int capture_run_iq(CaptureState &c, RecordLists &L, TimingState &tm, hipS
         if (int rc = debug_sync(s, "resolve + capture")) return rc;
         if (sz) seizure_launch(*sz, c.pending.get(), c.gring.get(), c.ring_words, c.sps, c.n_done + P, s);
         if (int rc = debug_sync(s, "seizure events")) return rc;
+        if (ez) early_launch(*ez, c.pending.get(), c.gring.get(), c.ring_words, c.sps, c.track, c.majority, c.n_done + P, s);
+        if (int rc = debug_sync(s, "early messages")) return rc;
     }
     HIP_TRY(hipGetLastError());
     c.n_done += P;
@@ -297,7 +302,8 @@ inline int capture_run_iq(CaptureState &c, RecordLists &L, TimingState &tm, hipS
 }
 
 // bit-domain tail of the fused wideband seam: the slicer bits of [n_done, n_done + P) are already in the ring
-inline int capture_run_bits(CaptureState &c, RecordLists &L, TimingState &tm, hipStream_t s, uint32_t P, const SeizureState *sz = nullptr)
+inline int capture_run_bits(CaptureState &c, RecordLists &L, TimingState &tm, hipStream_t s, uint32_t P, const SeizureState *sz = nullptr,
+                            const EarlyState *ez = nullptr)
 {
     if (P == 0) return 0;
     const FrontGeom geom = front_geometry(c.C, P, c.max_waves_bits);
@@ -323,6 +329,7 @@ inline int capture_run_bits(CaptureState &c, RecordLists &L, TimingState &tm, hi
     }
     launch_resolve(c, records_current(L), tm, geom, P, s, in_resolve, zero2);
     if (sz) seizure_launch(*sz, c.pending.get(), c.gring.get(), c.ring_words, c.sps, c.n_done + P, s);
+    if (ez) early_launch(*ez, c.pending.get(), c.gring.get(), c.ring_words, c.sps, c.track, c.majority, c.n_done + P, s);
     HIP_TRY(hipGetLastError());
     c.n_done += P;
     return 0;

@@ -13,7 +13,8 @@ def build_host(force=False):
     srcs = [os.path.join(_HERE, "lib", f) for f in ("recc_impl.cc", "recc_decode_impl.cc", "recc_fused_impl.cc", "recc_bank_impl.cc", "recc_wideband_impl.cc",
                                                    "recc_subband_impl.cc")]
     hdrs = [os.path.join(_HERE, "lib", "recc_impl.h"), os.path.join(_HERE, "lib", "recc_decode_impl.h"), os.path.join(_HERE, "lib", "recc_publish.h"),
-            os.path.join(_HERE, "gr_min", "gnuradio_min.h"), os.path.join(_ROOT, "include", "amps_recc.h"), os.path.join(_ROOT, "include", "amps_recc_seizure.h")]
+            os.path.join(_HERE, "gr_min", "gnuradio_min.h"), os.path.join(_ROOT, "include", "amps_recc.h"), os.path.join(_ROOT, "include", "amps_recc_seizure.h"),
+            os.path.join(_ROOT, "include", "amps_recc_early.h")]
     app = os.path.join(_HERE, "apps", "recctest.cc")
     deps = srcs + hdrs + [app]
     if not force and all(os.path.exists(p) for p in (BLOCKS_LIB, RECCTEST)) and \

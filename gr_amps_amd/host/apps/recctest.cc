@@ -52,6 +52,9 @@
 // the file) makes the block keep seizure events (make(..., seizure_events = true)): every event of the "seizures" port is printed as
 // `MSG seizure channel <c> position <n_c> found_at <n> dcc <7 bits, or - where the event came without them> bad <pairs>`, in front of
 // the lines of the records that the same push delivered -- and long before the lines of its own record.
+// Likewise an argument `early` makes the block keep early messages (make(..., early_messages = true)): every message of the "early" port
+// is printed as `MSG early channel <c> position <n_c> found_at <n> words <n_words> class <msg_class> min <MIN>`, in front of the lines of
+// the records that the same push delivered -- 120 ms (two words) or 96 ms (three) before the lines of its own record.
 // Every message published on recc_decode's output ports is printed as one text line, which is what
 // tests/test_gpu_host_blocks.py compares with the oracle.
 #include <amps/recc.h>
@@ -61,6 +64,7 @@
 #include <amps/recc_wideband.h>
 #include <amps/recc_subband.h>
 #include "amps_recc_seizure.h"
+#include "amps_recc_early.h"
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -137,11 +141,21 @@ void print_seizure(const pmt::pmt_t &m)
     std::printf("MSG seizure channel %ld position %llu found_at %llu dcc %s bad %u\n", pmt::to_long(pmt::car(m)), (unsigned long long)e.position,
                 (unsigned long long)e.found_at, dcc.c_str(), (unsigned)e.dcc_bad);
 }
-struct power_sink : gr::block {   // the "power", "offset" and "seizures" ports of a block whose other ports go to recc_decode directly
+// a message of a block's "early" port: pmt::cons(channel, blob(amps_recc_early_t)) (include/amps_recc_early.h)
+void print_early(const pmt::pmt_t &m)
+{
+    amps_recc_early_t e;
+    std::memcpy(&e, pmt::blob_data(pmt::cdr(m)), sizeof(e));
+    std::printf("MSG early channel %ld position %llu found_at %llu words %u class %u min %.10s\n", pmt::to_long(pmt::car(m)), (unsigned long long)e.rec.position,
+                (unsigned long long)e.found_at, (unsigned)e.n_words, (unsigned)e.rec.msg_class, e.rec.min);
+}
+struct power_sink : gr::block {   // the "power", "offset", "seizures" and "early" ports of a block whose other ports go to recc_decode directly
     power_sink() : gr::block("power_sink", gr::io_signature::make(0, 0, 0), gr::io_signature::make(0, 0, 0))
     {
         message_port_register_in(pmt::mp("seizures"));
         set_msg_handler(pmt::mp("seizures"), [](pmt::pmt_t m) { print_seizure(m); });
+        message_port_register_in(pmt::mp("early"));
+        set_msg_handler(pmt::mp("early"), [](pmt::pmt_t m) { print_early(m); });
         message_port_register_in(pmt::mp("power"));
         set_msg_handler(pmt::mp("power"), [](pmt::pmt_t m) { print_power(m); });
         message_port_register_in(pmt::mp("offset"));
@@ -159,7 +173,7 @@ int main(int argc, char **argv)
     // and `offset` for the carrier offset; the two may come in either order
     // `offset unit` selects the unit-amplitude statistic (the one that is right behind the default channel filter).  Behind all of
     // them `retune=<sample>:<hz>` moves every centre by <hz> before the first chunk that begins at or beyond input sample <sample>
-    bool power_last = false, offset_last = false, unit_last = false, seizures = false;
+    bool power_last = false, offset_last = false, unit_last = false, seizures = false, early = false;
     long long retune_at = -1;
     double retune_hz = 0.0;
     if ((mode == "sub" || mode == "raw") && argc > 3 && std::strncmp(argv[argc - 1], "retune=", 7) == 0) {
@@ -174,6 +188,7 @@ int main(int argc, char **argv)
         if (last == "power" && !power_last) power_last = true;
         else if (last == "offset" && !offset_last) offset_last = true;
         else if (last == "seizures" && !seizures) seizures = true;
+        else if (last == "early" && !early) early = true;
         else if (last == "unit" && !offset_last && argc > 4 && std::string(argv[argc - 2]) == "offset") { offset_last = unit_last = true; argc--; }
         else break;
         argc--;
@@ -187,6 +202,7 @@ int main(int argc, char **argv)
         if (std::strncmp(argv[i], "channels=", 9) == 0) wide_channels = std::atoi(argv[i] + 9);
         else if (std::strncmp(argv[i], "shift=", 6) == 0) wide_shift = std::atof(argv[i] + 6);
         else if (std::strcmp(argv[i], "seizures") == 0) seizures = true;
+        else if (std::strcmp(argv[i], "early") == 0) early = true;
         else if (std::strncmp(argv[i], "resample=", 9) == 0) {
             if (std::sscanf(argv[i] + 9, "%lf:%d/%d", &wide_rate, &wide_interp, &wide_decim_in) != 3 || !(wide_rate > 0.0)) { std::fprintf(stderr, "resample=<rate_hz>:<L>/<M>\n"); return 2; }
         }
@@ -248,9 +264,9 @@ int main(int argc, char **argv)
             for (int i = 6; !ranks && i < argc && i < 9; i++) power = power || std::string(argv[i]) == "power";
             const bool grid10 = wide_channels == 2500 || wide_channels == 2000 || wide_channels == 1000 || wide_channels == 500;   // bins of 10 kHz
             auto src = ranks ? gr::amps::recc_wideband::make(832, 96, -1, nranks, rank)
-                             : grid10 ? gr::amps::recc_wideband::make(wide_channels / 3, 0, argc > 4 ? std::atoi(argv[4]) : -1, 0, 0, wide_channels / 4, false, power, wide_channels, format, wide_shift, wide_rate, wide_interp, wide_decim_in, seizures)
-                             : wide_channels != 1024 ? gr::amps::recc_wideband::make(wide_channels, 0, argc > 4 ? std::atoi(argv[4]) : -1, 0, 0, argc > 5 ? std::atoi(argv[5]) : 0, false, power, wide_channels, format, wide_shift, wide_rate, wide_interp, wide_decim_in, seizures)
-                             : gr::amps::recc_wideband::make(832, 96, argc > 4 ? std::atoi(argv[4]) : -1, 0, 0, argc > 5 ? std::atoi(argv[5]) : 0, false, power, 1024, format, wide_shift, wide_rate, wide_interp, wide_decim_in, seizures);
+                             : grid10 ? gr::amps::recc_wideband::make(wide_channels / 3, 0, argc > 4 ? std::atoi(argv[4]) : -1, 0, 0, wide_channels / 4, false, power, wide_channels, format, wide_shift, wide_rate, wide_interp, wide_decim_in, seizures, early)
+                             : wide_channels != 1024 ? gr::amps::recc_wideband::make(wide_channels, 0, argc > 4 ? std::atoi(argv[4]) : -1, 0, 0, argc > 5 ? std::atoi(argv[5]) : 0, false, power, wide_channels, format, wide_shift, wide_rate, wide_interp, wide_decim_in, seizures, early)
+                             : gr::amps::recc_wideband::make(832, 96, argc > 4 ? std::atoi(argv[4]) : -1, 0, 0, argc > 5 ? std::atoi(argv[5]) : 0, false, power, 1024, format, wide_shift, wide_rate, wide_interp, wide_decim_in, seizures, early);
             if (ranks) {
                 // the control plane is the application's: here, a file
                 std::string id;
@@ -290,6 +306,7 @@ int main(int argc, char **argv)
             if (power) gr::msg_connect(src, "power", dm, "power");
             auto ss = std::make_shared<power_sink>();
             if (seizures) gr::msg_connect(src, "seizures", ss, "seizures");
+            if (early) gr::msg_connect(src, "early", ss, "early");
             std::vector<char> tail((size_t)64 * 768 * item, 0);       // silence: flushes the frames the fused form holds back (64 frames of at most 768 samples)
             if (format == 3)                                          // cu8 has no zero: (127, 128), (128, 127), ... = -+0.5, half a step either side of it
                 for (size_t i = 0; i < tail.size(); i++) tail[i] = (char)(127 + (((i >> 1) ^ i) & 1));
@@ -323,7 +340,7 @@ int main(int argc, char **argv)
             const int interp = slash ? std::atoi(argv[5]) : 1, decim = std::atoi(slash ? slash + 1 : argv[5]);
             const double rate = std::atof(argv[4]);
             const int sps = decim > 0 && interp > 0 ? (int)std::lround(rate * interp / decim / 20e3) : 10;
-            auto src = gr::amps::recc_subband::make(rate, centers, decim, sps, -1, 0.0, 0.0, format, interp, power_last, offset_last, unit_last, seizures);
+            auto src = gr::amps::recc_subband::make(rate, centers, decim, sps, -1, 0.0, 0.0, format, interp, power_last, offset_last, unit_last, seizures, early);
             struct demux : gr::block {
                 std::shared_ptr<gr::basic_block> dec;
                 demux() : gr::block("demux", gr::io_signature::make(0, 0, 0), gr::io_signature::make(0, 0, 0))
@@ -347,6 +364,7 @@ int main(int argc, char **argv)
             if (offset_last) gr::msg_connect(src, "offset", dm, "offset");
             auto ss = std::make_shared<power_sink>();
             if (seizures) gr::msg_connect(src, "seizures", ss, "seizures");
+            if (early) gr::msg_connect(src, "early", ss, "early");
             const size_t ns = data.size() / item;
             for (size_t off = 0; off < ns; off += (size_t)chunk) {
                 int n = (int)std::min<size_t>((size_t)chunk, ns - off);
@@ -369,12 +387,13 @@ int main(int argc, char **argv)
         } else {
             const double center = argc > 4 ? std::atof(argv[4]) : 160e3;
             const double cutoff = argc > 5 ? std::atof(argv[5]) : 0.0;
-            auto src = mode == "raw" ? gr::amps::recc_fused::make(10, 400e3, center, 2, cutoff, 0.0, power_last, offset_last, unit_last, seizures) : gr::amps::recc_fused::make(10);
+            auto src = mode == "raw" ? gr::amps::recc_fused::make(10, 400e3, center, 2, cutoff, 0.0, power_last, offset_last, unit_last, seizures, early) : gr::amps::recc_fused::make(10);
             if (mode == "iqb") gr::msg_connect(src, "bursts", dec, "bursts"); else gr::msg_connect(src, "records", dec, "records");
             auto ps = std::make_shared<power_sink>();
             if (power_last) gr::msg_connect(src, "power", ps, "power");
             if (offset_last) gr::msg_connect(src, "offset", ps, "offset");
             if (seizures) gr::msg_connect(src, "seizures", ps, "seizures");
+            if (early) gr::msg_connect(src, "early", ps, "early");
             const size_t ns = data.size() / 8;
             for (size_t off = 0; off < ns; off += (size_t)chunk) {
                 int n = (int)std::min<size_t>((size_t)chunk, ns - off);

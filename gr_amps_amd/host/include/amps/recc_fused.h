@@ -24,6 +24,10 @@
 // seizure_events = true keeps seizure events (AMPS_RECC_FLAG_SEIZURE_EVENTS) and adds the port "seizures": pmt::cons(from_long(0),
 // blob(32)), one amps_recc_seizure_t (include/amps_recc_seizure.h) per seizure, published from the work() call whose push accepted its trigger,
 // in front of that call's records -- some 170 ms before the seizure's own record.
+// early_messages = true keeps early messages (AMPS_RECC_FLAG_EARLY_MESSAGES) and adds the port "early": pmt::cons(from_long(0), blob(744)),
+// one amps_recc_early_t (include/amps_recc_early.h: the record of the message's announced words, found_at, n_words) per seizure whose
+// word A announced fewer than seven words, published from the work() call whose push brought the last of them, in front of that call's
+// records -- 120 ms (two words) or 96 ms (three) before the record that repeats it.
 // retune(xlate_center_hz) moves the translate stage's centre in mid-stream (amps_recc_retune_xlate): from the next work() call on the
 // stage delivers what a block made with that centre would; nothing is reset.  Call it from the thread that runs work() (a message
 // handler) or between runs; it throws std::runtime_error where the library refuses (no translate stage, a centre beyond the rate).
@@ -38,7 +42,7 @@ public:
     typedef AMPS_SPTR<recc_fused> sptr;
     static sptr make(int samples_per_symbol = 10, double xlate_rate_hz = 0.0, double xlate_center_hz = 0.0, int xlate_decim = 2,
                      double xlate_cutoff_hz = 0.0, double xlate_width_hz = 0.0, bool channel_power = false, bool channel_offset = false,
-                     bool offset_unit = false, bool seizure_events = false);
+                     bool offset_unit = false, bool seizure_events = false, bool early_messages = false);
     virtual void retune(double xlate_center_hz) = 0;
 };
 

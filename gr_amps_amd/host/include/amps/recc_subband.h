@@ -24,6 +24,10 @@
 //                 "seizures" (blocks made with seizure_events = true only) pmt::cons(from_long(channel), blob(32)): one amps_recc_seizure_t
 //                           (include/amps_recc_seizure.h) per seizure, published from the work() call whose push accepted its trigger, in
 //                           front of that call's records -- some 170 ms before the seizure's own record;
+//                 "early" (blocks made with early_messages = true only) pmt::cons(from_long(channel), blob(744)): one amps_recc_early_t
+//                           (include/amps_recc_early.h: the record of the message's announced words, found_at, n_words) per seizure whose
+//                           word A announced fewer than seven words, published from the work() call whose push brought the last of
+//                           them, in front of that call's records; the record that repeats it has its (channel, position);
 // as gr::amps::recc_wideband publishes them.  channel c = the channel at centers_hz[c] relative to the stream's centre.
 #pragma once
 #include <amps/api.h>
@@ -50,9 +54,10 @@ public:
     // channel_offset: measure the carrier offset (AMPS_RECC_FLAG_STREAM_OFFSET) and publish every record's on "offset"
     // offset_unit: with channel_offset, the unit-amplitude statistic (AMPS_RECC_FLAG_STREAM_OFFSET_UNIT) instead; the port stays "offset"
     // seizure_events: keep seizure events (AMPS_RECC_FLAG_SEIZURE_EVENTS) and publish them on "seizures"
+    // early_messages: keep early messages (AMPS_RECC_FLAG_EARLY_MESSAGES) and publish them on "early"
     static sptr make(double rate_hz, const std::vector<double> &centers_hz, int decim = 4, int samples_per_symbol = 10, int slicer = -1,
                      double cutoff_hz = 0.0, double width_hz = 0.0, int input_format = 0, int interp = 1, bool channel_power = false,
-                     bool channel_offset = false, bool offset_unit = false, bool seizure_events = false);
+                     bool channel_offset = false, bool offset_unit = false, bool seizure_events = false, bool early_messages = false);
     // new centres in mid-stream (amps_recc_retune_xlate): as many as the block was made with; from the next work() call on the stage
     // delivers what a block made with these centres would, and nothing is reset.  Call it from the thread that runs work() (a message
     // handler) or between runs; throws std::runtime_error where the library refuses (another number of centres, one beyond the rate)

@@ -15,6 +15,11 @@
 //                           (include/amps_recc_seizure.h) per seizure, published from the work() call whose push accepted its trigger, in
 //                           front of that call's records -- some 170 ms before the seizure's own record: what an FOCC block needs to
 //                           set its busy-idle bits in time.  Behind set_rccl a rank publishes its own group's events.
+//                 "early" (blocks made with early_messages = true only) pmt::cons(from_long(channel), blob(744)): one amps_recc_early_t
+//                           (include/amps_recc_early.h: the record of the message's announced words, found_at, n_words) per seizure whose
+//                           word A announced fewer than seven words, published from the work() call whose push brought the last of
+//                           them, in front of that call's records: what a base station answers from, 120 or 96 ms before the record
+//                           that repeats it.  Behind set_rccl a rank publishes its own group's messages.
 // With channels = 512, 256 or 128 the input is a stream at channels x 30 kHz = 15.36, 7.68 or 3.84 Msps -- what one SDR delivers -- through
 // the bank of that many branches, in the two-kernel form (cfg.wideband_channels of include/amps_recc.h); "power" then carries the stream
 // power of the IQ seam (AMPS_RECC_FLAG_STREAM_POWER: the mean of |y|^2 over the blocks of 256 channel-rate samples inside the capture).
@@ -62,9 +67,10 @@ public:
     //         into 2500; amps_recc_wideband_resample_plan lists what a rate admits.  rate_hz = 0: none.  A ratio or rate the library refuses
     //         throws.  Not with set_rccl, which throws on such a block: the library has no distributed push behind a resampler (-ENOSYS).
     // seizure_events: keep seizure events (AMPS_RECC_FLAG_SEIZURE_EVENTS) and publish them on "seizures"
+    // early_messages: keep early messages (AMPS_RECC_FLAG_EARLY_MESSAGES) and publish them on "early"
     static sptr make(int n_channels = 832, int first_bin = 96, int slicer = -1, int groups = 0, int group = 0, int decim = 0, bool short_input = false,
                      bool channel_power = false, int channels = 1024, int input_format = 0, double shift_hz = 0.0,
-                     double rate_hz = 0.0, int interp = 1, int decim_in = 1, bool seizure_events = false);
+                     double rate_hz = 0.0, int interp = 1, int decim_in = 1, bool seizure_events = false, bool early_messages = false);
     // Replace the shift in mid-stream: in force from the next work() call on, nothing reset, and from then on the bank delivers what a
     // block made with this shift would.  Throws where the library refuses (NaN, beyond +- fs / 2, a 1024 bank).
     virtual void set_shift(double shift_hz) = 0;

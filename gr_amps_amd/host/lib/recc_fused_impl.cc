@@ -19,15 +19,16 @@ class recc_fused_impl : public recc_fused {
     bool d_power;                                  // AMPS_RECC_FLAG_STREAM_POWER: every record's burst power goes out on "power"
     bool d_offset;                                 // AMPS_RECC_FLAG_STREAM_OFFSET or _OFFSET_UNIT: every record's carrier offset goes out on "offset"
     bool d_seizures;                               // AMPS_RECC_FLAG_SEIZURE_EVENTS: every push's seizure events go out on "seizures"
+    bool d_early;                                  // AMPS_RECC_FLAG_EARLY_MESSAGES: every push's early messages go out on "early"
     std::vector<unsigned char> d_bursts;
     static const int kMaxPush = 1 << 20;
     static const int kMaxRecs = 64;
 
 public:
     recc_fused_impl(int sps, double xlate_rate, double xlate_center, int xlate_decim, double xlate_cutoff, double xlate_width, bool channel_power, bool channel_offset,
-                    bool offset_unit, bool seizure_events)
+                    bool offset_unit, bool seizure_events, bool early_messages)
         : gr::sync_block("recc_fused", gr::io_signature::make(1, 1, 2 * sizeof(float)), gr::io_signature::make(0, 0, 0)), d_handle(nullptr),
-          d_raw(xlate_rate > 0.0), d_power(channel_power), d_offset(channel_offset), d_seizures(seizure_events), d_bursts((size_t)kMaxRecs * AMPS_RECC_CAPTURE_SYMS)
+          d_raw(xlate_rate > 0.0), d_power(channel_power), d_offset(channel_offset), d_seizures(seizure_events), d_early(early_messages), d_bursts((size_t)kMaxRecs * AMPS_RECC_CAPTURE_SYMS)
     {
         amps_recc_cfg_t cfg = {};
         cfg.struct_size = sizeof(cfg);
@@ -37,7 +38,7 @@ public:
         cfg.max_bursts = kMaxRecs;
         cfg.device = -1;
         cfg.flags = AMPS_RECC_FLAG_KEEP_BURSTS | (channel_power ? AMPS_RECC_FLAG_STREAM_POWER : 0u) | (channel_offset ? (offset_unit ? AMPS_RECC_FLAG_STREAM_OFFSET_UNIT : AMPS_RECC_FLAG_STREAM_OFFSET) : 0u)   // the captured symbols travel with the record
-                  | (seizure_events ? AMPS_RECC_FLAG_SEIZURE_EVENTS : 0u);
+                  | (seizure_events ? AMPS_RECC_FLAG_SEIZURE_EVENTS : 0u) | (early_messages ? AMPS_RECC_FLAG_EARLY_MESSAGES : 0u);
         int rc = amps_recc_create(&d_handle, &cfg);
         if (rc != 0) throw std::runtime_error(std::string("amps::recc_fused: ") + amps_recc_strerror(rc));
         if (d_raw) {
@@ -59,6 +60,7 @@ public:
         if (d_power) message_port_register_out(pmt::mp("power"));
         if (d_offset) message_port_register_out(pmt::mp("offset"));
         if (d_seizures) message_port_register_out(pmt::mp("seizures"));
+        if (d_early) message_port_register_out(pmt::mp("early"));
     }
     ~recc_fused_impl() { amps_recc_destroy(d_handle); }
 
@@ -79,6 +81,7 @@ public:
                            : amps_recc_push_iq(d_handle, in + 2 * (size_t)done, (size_t)n, (size_t)n, AMPS_MEM_HOST);
             if (rc != 0) { std::fprintf(stderr, "amps::recc_fused: %s\n", amps_recc_strerror(rc)); return WORK_DONE; }
             if (d_seizures && !recc_publish_seizures(*this, "recc_fused", d_handle)) return WORK_DONE;
+            if (d_early && !recc_publish_early(*this, "recc_fused", d_handle)) return WORK_DONE;
             amps_recc_burst_t recs[kMaxRecs];
             float pow[kMaxRecs];
             uint32_t nsnap[kMaxRecs];
@@ -95,10 +98,10 @@ public:
 };
 
 recc_fused::sptr recc_fused::make(int samples_per_symbol, double xlate_rate_hz, double xlate_center_hz, int xlate_decim, double xlate_cutoff_hz, double xlate_width_hz,
-                                  bool channel_power, bool channel_offset, bool offset_unit, bool seizure_events)
+                                  bool channel_power, bool channel_offset, bool offset_unit, bool seizure_events, bool early_messages)
 {
     return gnuradio::get_initial_sptr(new recc_fused_impl(samples_per_symbol, xlate_rate_hz, xlate_center_hz, xlate_decim, xlate_cutoff_hz, xlate_width_hz,
-                                                          channel_power, channel_offset, offset_unit, seizure_events));
+                                                          channel_power, channel_offset, offset_unit, seizure_events, early_messages));
 }
 
 } // namespace amps

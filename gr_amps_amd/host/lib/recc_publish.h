@@ -1,7 +1,7 @@
 // recc_publish.h -- what recc_wideband, recc_subband and recc_fused do behind every push: drain the records with their bursts, ask for
 // their burst power where the block keeps power and for their carrier offset where it measures that, and publish on "bursts",
 // "records", "power" and "offset"; and, on a block made with seizure_events, in front of all that the push's seizure events on
-// "seizures".  Internal to lib/.
+// "seizures", and on a block made with early_messages the push's early messages on "early".  Internal to lib/.
 #pragma once
 #include <amps/api.h>
 #include <cerrno>
@@ -9,6 +9,7 @@
 #include <cstdio>
 #include "amps_recc.h"
 #include "amps_recc_seizure.h"
+#include "amps_recc_early.h"
 
 namespace gr {
 namespace amps {
@@ -33,6 +34,24 @@ inline bool recc_publish_seizures(gr::basic_block &blk, const char *name, amps_r
         else if (rc != 0) { std::fprintf(stderr, "amps::%s: seizure events: %s\n", name, amps_recc_strerror(rc)); return false; }
         for (size_t i = 0; i < n; i++)
             blk.message_port_pub(pmt::mp("seizures"), pmt::cons(pmt::from_long((long)ev[i].channel), pmt::mp(&ev[i], sizeof(ev[i]))));
+    } while (left);
+    return true;
+}
+
+// The early messages held behind the push just made (AMPS_RECC_FLAG_EARLY_MESSAGES), oldest first, each as
+// pmt::cons(channel, blob(amps_recc_early_t)) on "early" -- the record of the message's announced words, n_words and found_at: called
+// behind recc_publish_seizures and before recc_drain_and_publish, so a message goes out in front of that call's records, and the record
+// that repeats it (same channel, same position) comes with a later push.  false = stop the flow graph.
+inline bool recc_publish_early(gr::basic_block &blk, const char *name, amps_recc_t *h)
+{
+    amps_recc_early_t ev[16];
+    size_t n = 0, left = 0;
+    do {
+        const int rc = amps_recc_drain_early(h, ev, sizeof(ev) / sizeof(ev[0]), &n, &left);
+        if (rc == -ENOSPC) std::fprintf(stderr, "amps::%s: %s (early messages dropped, continuing)\n", name, amps_recc_strerror(rc));
+        else if (rc != 0) { std::fprintf(stderr, "amps::%s: early messages: %s\n", name, amps_recc_strerror(rc)); return false; }
+        for (size_t i = 0; i < n; i++)
+            blk.message_port_pub(pmt::mp("early"), pmt::cons(pmt::from_long((long)ev[i].rec.channel), pmt::mp(&ev[i], sizeof(ev[i]))));
     } while (left);
     return true;
 }

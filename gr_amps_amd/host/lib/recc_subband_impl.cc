@@ -25,6 +25,7 @@ class recc_subband_impl : public recc_subband {
     std::vector<float> d_off;
     std::vector<uint32_t> d_offn;
     bool d_seizures = false;                       // AMPS_RECC_FLAG_SEIZURE_EVENTS: every push's seizure events go out on "seizures"
+    bool d_early = false;                          // AMPS_RECC_FLAG_EARLY_MESSAGES: every push's early messages go out on "early"
     static const int kMaxOut = 1 << 18;            // channel-rate samples per push: 1.3 s at 200 ksps
     static const int kMaxRecs = 1024;
     // bytes of one input item: two floats, two shorts or two bytes; 0 = no such format
@@ -63,12 +64,12 @@ class recc_subband_impl : public recc_subband {
 
 public:
     recc_subband_impl(double rate_hz, const std::vector<double> &centers_hz, int decim, int sps, int slicer, double cutoff_hz, double width_hz, int input_format,
-                      int interp, bool channel_power, bool channel_offset, bool offset_unit, bool seizure_events)
+                      int interp, bool channel_power, bool channel_offset, bool offset_unit, bool seizure_events, bool early_messages)
         : gr::sync_block("recc_subband", gr::io_signature::make(1, 1, (int)std::max<size_t>(item_size(input_format), 1)), gr::io_signature::make(0, 0, 0)),
           d_handle(nullptr), d_decim(decim), d_interp(interp), d_format(input_format), d_recs(kMaxRecs), d_bursts((size_t)kMaxRecs * AMPS_RECC_CAPTURE_SYMS),
           d_power(channel_power), d_pow(channel_power ? kMaxRecs : 0), d_nsnap(channel_power ? kMaxRecs : 0),
           d_offset(channel_offset), d_off(channel_offset ? kMaxRecs : 0), d_offn(channel_offset ? kMaxRecs : 0),
-          d_seizures(seizure_events)
+          d_seizures(seizure_events), d_early(early_messages)
     {
         if (!item_size(input_format)) throw std::runtime_error("amps::recc_subband: input_format must be 0 (fc32), 1 (sc16), 2 (sc8) or 3 (cu8)");
         if (centers_hz.empty()) throw std::runtime_error("amps::recc_subband: no centres");
@@ -82,7 +83,7 @@ public:
         cfg.max_bursts = kMaxRecs;
         cfg.device = -1;
         cfg.flags = AMPS_RECC_FLAG_KEEP_BURSTS | (channel_power ? AMPS_RECC_FLAG_STREAM_POWER : 0u) | (channel_offset ? (offset_unit ? AMPS_RECC_FLAG_STREAM_OFFSET_UNIT : AMPS_RECC_FLAG_STREAM_OFFSET) : 0u)
-                  | (seizure_events ? AMPS_RECC_FLAG_SEIZURE_EVENTS : 0u)
+                  | (seizure_events ? AMPS_RECC_FLAG_SEIZURE_EVENTS : 0u) | (early_messages ? AMPS_RECC_FLAG_EARLY_MESSAGES : 0u)
                   | (slicer == 0 ? AMPS_RECC_FLAG_SLICER_ATAN : slicer == 1 ? AMPS_RECC_FLAG_SLICER_PRODUCT
                                                   : slicer == 2 ? AMPS_RECC_FLAG_SLICER_SINE : slicer == 3 ? AMPS_RECC_FLAG_SLICER_EXACT : 0u);
         int rc = amps_recc_create(&d_handle, &cfg);
@@ -118,6 +119,7 @@ public:
         if (d_power) message_port_register_out(pmt::mp("power"));
         if (d_offset) message_port_register_out(pmt::mp("offset"));
         if (d_seizures) message_port_register_out(pmt::mp("seizures"));
+        if (d_early) message_port_register_out(pmt::mp("early"));
     }
     ~recc_subband_impl() { amps_recc_destroy(d_handle); }
 
@@ -140,6 +142,7 @@ public:
             int rc = amps_recc_push_raw_shared_as(d_handle, in + item * (size_t)done, (size_t)n, d_format, AMPS_MEM_HOST);
             if (rc != 0) { std::fprintf(stderr, "amps::recc_subband: %s\n", amps_recc_strerror(rc)); return WORK_DONE; }
             if (d_seizures && !recc_publish_seizures(*this, "recc_subband", d_handle)) return WORK_DONE;
+            if (d_early && !recc_publish_early(*this, "recc_subband", d_handle)) return WORK_DONE;
             if (!recc_drain_and_publish(*this, "recc_subband", true, d_handle, d_recs.data(), d_bursts.data(), kMaxRecs, d_power ? d_pow.data() : nullptr,
                                         d_power ? d_nsnap.data() : nullptr, d_offset ? d_off.data() : nullptr, d_offset ? d_offn.data() : nullptr))
                 return WORK_DONE;
@@ -152,10 +155,10 @@ public:
 
 recc_subband::sptr recc_subband::make(double rate_hz, const std::vector<double> &centers_hz, int decim, int samples_per_symbol, int slicer,
                                       double cutoff_hz, double width_hz, int input_format, int interp, bool channel_power, bool channel_offset,
-                                      bool offset_unit, bool seizure_events)
+                                      bool offset_unit, bool seizure_events, bool early_messages)
 {
     return gnuradio::get_initial_sptr(new recc_subband_impl(rate_hz, centers_hz, decim, samples_per_symbol, slicer, cutoff_hz, width_hz, input_format, interp,
-                                                            channel_power, channel_offset, offset_unit, seizure_events));
+                                                            channel_power, channel_offset, offset_unit, seizure_events, early_messages));
 }
 
 } // namespace amps

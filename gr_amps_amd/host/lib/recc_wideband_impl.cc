@@ -27,6 +27,7 @@ class recc_wideband_impl : public recc_wideband {
     std::vector<float> d_pow;
     std::vector<uint32_t> d_nsnap;
     bool d_seizures = false;                       // AMPS_RECC_FLAG_SEIZURE_EVENTS: every push's seizure events go out on "seizures"
+    bool d_early = false;                          // AMPS_RECC_FLAG_EARLY_MESSAGES: every push's early messages go out on "early"
 
 public:
     // bytes of one item of a format; 0: no such format
@@ -45,10 +46,10 @@ public:
     }
 
     recc_wideband_impl(int C, int first_bin, int slicer, int groups, int group, int decim, bool short_input, bool channel_power, int channels, int input_format, double shift_hz,
-                       double rate_hz, int interp, int decim_in, bool seizure_events)
+                       double rate_hz, int interp, int decim_in, bool seizure_events, bool early_messages)
         : gr::sync_block("recc_wideband", gr::io_signature::make(1, 1, (int)item_size(checked_format(short_input, input_format))), gr::io_signature::make(0, 0, 0)),
           d_handle(nullptr), d_recs(kMaxRecs), d_bursts((size_t)kMaxRecs * AMPS_RECC_CAPTURE_SYMS), d_format(checked_format(short_input, input_format)), d_power(channel_power),
-          d_pow(channel_power ? kMaxRecs : 0), d_nsnap(channel_power ? kMaxRecs : 0), d_seizures(seizure_events)
+          d_pow(channel_power ? kMaxRecs : 0), d_nsnap(channel_power ? kMaxRecs : 0), d_seizures(seizure_events), d_early(early_messages)
     {
         amps_recc_cfg_t cfg = {};
         cfg.struct_size = sizeof(cfg);
@@ -65,7 +66,7 @@ public:
         cfg.flags = AMPS_RECC_FLAG_KEEP_BURSTS | (slicer == 0 ? AMPS_RECC_FLAG_SLICER_ATAN : slicer == 1 ? AMPS_RECC_FLAG_SLICER_PRODUCT
                                                   : slicer == 2 ? AMPS_RECC_FLAG_SLICER_SINE : slicer == 3 ? AMPS_RECC_FLAG_SLICER_EXACT : 0u)
                     | (channel_power ? (narrow ? AMPS_RECC_FLAG_STREAM_POWER : AMPS_RECC_FLAG_CHANNEL_POWER) : 0u)
-                    | (seizure_events ? AMPS_RECC_FLAG_SEIZURE_EVENTS : 0u);
+                    | (seizure_events ? AMPS_RECC_FLAG_SEIZURE_EVENTS : 0u) | (early_messages ? AMPS_RECC_FLAG_EARLY_MESSAGES : 0u);
         cfg.wideband_groups = (uint32_t)groups;
         cfg.wideband_group = (uint32_t)group;
         cfg.wideband_channels = (uint32_t)channels;
@@ -88,6 +89,7 @@ public:
         message_port_register_out(pmt::mp("records"));
         if (d_power) message_port_register_out(pmt::mp("power"));
         if (d_seizures) message_port_register_out(pmt::mp("seizures"));
+        if (d_early) message_port_register_out(pmt::mp("early"));
     }
     ~recc_wideband_impl() { amps_recc_destroy(d_handle); }
 
@@ -126,6 +128,7 @@ public:
         if (rc == -ENODATA) { d_ended = true; return false; }   // the root's stream has ended: a clean WORK_DONE, the communicator is left alone
         if (rc != 0) { std::fprintf(stderr, "amps::recc_wideband: %s\n", amps_recc_strerror(rc)); return leave(); }
         if (d_seizures && !recc_publish_seizures(*this, "recc_wideband", d_handle)) return leave();
+        if (d_early && !recc_publish_early(*this, "recc_wideband", d_handle)) return leave();
         if (!recc_drain_and_publish(*this, "recc_wideband", true, d_handle, d_recs.data(), d_bursts.data(), kMaxRecs, d_power ? d_pow.data() : nullptr,
                                     d_power ? d_nsnap.data() : nullptr)) return leave();
         return true;
@@ -176,9 +179,9 @@ public:
 };
 
 recc_wideband::sptr recc_wideband::make(int n_channels, int first_bin, int slicer, int groups, int group, int decim, bool short_input, bool channel_power, int channels, int input_format, double shift_hz,
-                                        double rate_hz, int interp, int decim_in, bool seizure_events)
+                                        double rate_hz, int interp, int decim_in, bool seizure_events, bool early_messages)
 {
-    return gnuradio::get_initial_sptr(new recc_wideband_impl(n_channels, first_bin, slicer, groups, group, decim, short_input, channel_power, channels, input_format, shift_hz, rate_hz, interp, decim_in, seizure_events));
+    return gnuradio::get_initial_sptr(new recc_wideband_impl(n_channels, first_bin, slicer, groups, group, decim, short_input, channel_power, channels, input_format, shift_hz, rate_hz, interp, decim_in, seizure_events, early_messages));
 }
 
 std::string recc_wideband::rccl_unique_id()

@@ -72,7 +72,9 @@ extern "C" {
                                      amps_recc_wideband_resample_plan / amps_recc_debug_wideband_resample, an L / M resampler in front of the
                                      banks for the rates that are no bank's: 8, 12.5, 16, 6, 4 and 3.2 Msps;
                                      still 4, nothing changed in this header: a flag and one entry point in a header of their own,
-                                     amps_recc_seizure.h -- one event per seizure after the push in which its trigger was accepted) */
+                                     amps_recc_seizure.h -- one event per seizure after the push in which its trigger was accepted;
+                                     still 4, nothing changed in this header: a flag and one entry point in a header of their own,
+                                     amps_recc_early.h -- a message's announced words as soon as the last of them is in) */
 
 /* protocol constants of the reference */
 #define AMPS_RECC_TRIGGER_SYMS 74   /* lib/recc_impl.cc:76-77: 37 bits x 2 Manchester symbols   */
@@ -133,6 +135,7 @@ extern "C" {
                                                offset flags together are -EINVAL, as is every combination AMPS_RECC_FLAG_STREAM_OFFSET
                                                refuses.  Combines freely with AMPS_RECC_FLAG_STREAM_POWER */
 /* (bit 0x2000u is AMPS_RECC_FLAG_SEIZURE_EVENTS of the extension header amps_recc_seizure.h: seizure events, amps_recc_drain_seizures) */
+/* (bit 0x4000u is AMPS_RECC_FLAG_EARLY_MESSAGES of the extension header amps_recc_early.h: early messages, amps_recc_drain_early) */
 #define AMPS_RECC_FLAG_MAJORITY    0x2u /* decode mode "majority" instead of "reference" (SURVEY.md 8f.2), see below */
 
 /* message classes, the branches of lib/recc_decode_impl.cc:108-168 */
